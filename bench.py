@@ -18,6 +18,11 @@ processes of itself (pool_shard.spawn_ranks), relays rank 0's JSON line and exit
 Default = weak scaling: every rank scores its own `--pool` (100,000) patches of an N*100,000 pool (config 4's sharding).
 `--pool-global G` = strong scaling: ONE pool of G patches (configs[3]: 1,000,000) in contiguous blocks of ceil(G/N).
 Either way the top-B merge and the 8x8 Fisher-sum all-reduce (RCCL) are inside the timed region.  ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`metric`, `value`, `ms_per_step`, ...).  `--full`
+adds what the headline does not need, behind the timed region: the roofline object (its own event-timed pass), engine clock and
+board power, the accuracy passes, the NET-B side figure and the CPU baseline; the other workloads (`--config 0 / 1 / 4 / 5`) run
+only with `--full`.  `--dump-outputs DIR` writes what the timed path returned in its last step as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -111,7 +116,7 @@ def main():
     ap.add_argument('--warmup', type=int, default=1)
     ap.add_argument('--pool', type=int, default=100000, help='patches per GPU (weak scaling)')
     ap.add_argument('--pool-global', type=int, default=0, help='strong scaling: one pool of this many patches over all GPUs')
-    ap.add_argument('--netb-pool', type=int, default=16384, help='patches of the NET-B side measurement at N = 1 (0 = skip)')
+    ap.add_argument('--netb-pool', type=int, default=16384, help='--full: patches of the NET-B side measurement at N = 1 (0 = skip)')
     ap.add_argument('--batch', type=int, default=2047,
                     help='most patches per device pass.  2047 = the most the engines\' unsigned 32-bit tensor offsets address for 32^3 NET-C '
                          '(the library clamps a larger request to it).  fisher_device cuts a pool into an EVEN number of equal passes of at most '
@@ -125,14 +130,14 @@ def main():
     ap.add_argument('--same-gpu', action='store_true',
                     help='functional rehearsal on a one-GPU box: every rank computes on cuda:0 (use with --backend gloo; RCCL '
                          'refuses two ranks on one device); throughput numbers of such a run mean nothing')
-    ap.add_argument('--prof-every', type=int, default=8, help='--lanes 1 only: HIP-event timing on every k-th pass of the timed region')
+    ap.add_argument('--prof-every', type=int, default=8, help='--full --lanes 1 only: HIP-event timing on every k-th pass of the timed region')
     ap.add_argument('--lanes', type=int, default=2,
                     help='scoring pipelines of the timed region (device.DeviceModel.lanes): 2 = device passes alternate between two libalq '
                          'contexts so that one pass\'s tail runs beside the next one\'s first launches (outputs bit-identical to 1, '
                          'test_two_scoring_pipelines_are_bit_identical_to_one).  Per-launch durations then include co-residency, so the '
                          'roofline object always comes from a SEPARATE single-pipeline pass with HIP events on every launch')
-    ap.add_argument('--roofline-passes', type=int, default=12, help='device passes of the separate single-pipeline roofline pass (an even number: they are then cut like the timed region\'s)')
-    ap.add_argument('--cpu-sample', type=int, default=128, help='patches the CPU baseline scores (~15 s on 16 cores)')
+    ap.add_argument('--roofline-passes', type=int, default=12, help='--full: device passes of the separate single-pipeline roofline pass (an even number: they are then cut like the timed region\'s)')
+    ap.add_argument('--cpu-sample', type=int, default=128, help='--full: patches the CPU baseline scores (~15 s on 16 cores)')
     ap.add_argument('--cpu-all-cores', action='store_true',
                     help='also time ONE patch of the CPU baseline with os.cpu_count() threads (BASELINE.md 3 names that thread count; at '
                          'batch 1 it oversubscribes every op: 0.03 patches/s on the 256-thread box, ~35 s)')
@@ -142,7 +147,20 @@ def main():
                          '1000000), 4 the active-learning loop, 5 rounds over 200,000 patches; 5 (not a BASELINE.json config) the VOLUME-level `fi` query the '
                          'reference times (PW_AL.py:848-855): query_multimg over synthetic padded subjects through alq_gather_normalize, '
                          'the reference\'s own (25,25,1) x 2-modality NET-B')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline figure does not need, behind the timed region: roofline (events on every '
+                         'k-th timed pass with --lanes 1, else a separate single-pipeline pass), clocks, accuracy, NET-B, CPU baseline '
+                         '(each still switched off by its own option); required by --config 0, 1, 4 and 5')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last step returned as DIR/<name>.npy (float32 / float64, at most 64 MB; '
+                         'rank 0\'s shard; configs 2 / 3)')
     args = ap.parse_args()
+    if args.steps < 1 and args.config in (2, 3):
+        ap.error('--steps must be at least 1')
+    if args.config in (0, 1, 4, 5) and not args.full:
+        ap.error('--config %d is one of the --full measurements' % args.config)
+    if args.dump_outputs and args.config not in (2, 3):
+        ap.error('--dump-outputs writes the outputs of the Fisher-scoring path (--config 2 / 3)')
     if args.config == 3 and args.pool_global == 0:
         args.pool_global = 1000000
 
@@ -228,29 +246,33 @@ def main():
         step()
     note('timing %d step(s)' % args.steps)
     sess.prof_reset()
-    # one pipeline: HIP events on our stream around the launches of every 8th pass of the timed region (on every launch the
-    # event pairs themselves cost ~6 % of the step); two pipelines: none - a launch's event span would include whatever the
+    # --full, one pipeline: HIP events on our stream around the launches of every 8th pass of the timed region (on every launch
+    # the event pairs themselves cost ~6 % of the step); two pipelines: none - a launch's event span would include whatever the
     # other pipeline runs beside it - and the roofline pass below instead
-    in_region = model.lanes == 1 and not os.environ.get('ALQ_BENCH_NO_EVENTS')
+    in_region = args.full and model.lanes == 1 and not os.environ.get('ALQ_BENCH_NO_EVENTS')
     sess.prof_enable(args.prof_every if in_region else 0)
-    sampler = ClockSampler(torch, local_rank)
+    sampler = ClockSampler(torch, local_rank) if args.full else None
     pool_shard.barrier()
     torch.cuda.synchronize()
-    sampler.start()
+    if sampler:
+        sampler.start()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         out = step()
     torch.cuda.synchronize()
     pool_shard.barrier()
     dt = time.perf_counter() - t0
-    clocks = sampler.stop()
+    clocks = sampler.stop() if sampler else None
     sess.prof_enable(False)
-    prof = sess.prof_read()
     dt = pool_shard.max_over_ranks(dt)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, a0)
     lanes_timed = int(model.lanes)
-    prof_patches = None
-    clocks_roof = clocks if in_region else None
-    if not in_region and not os.environ.get('ALQ_BENCH_NO_EVENTS'):
+    prof, prof_patches, clocks_roof = None, None, None
+    if args.full:
+        prof = sess.prof_read()
+        clocks_roof = clocks if in_region else None
+    if args.full and not in_region and not os.environ.get('ALQ_BENCH_NO_EVENTS'):
         # the roofline pass: the same launches on the first passes of the pool, ONE pipeline, HIP events on every launch
         # (outside the timed region; what rocprofv3 --kernel-trace shows for `--lanes 1`)
         model.lanes = 1
@@ -270,41 +292,6 @@ def main():
     if rank == 0:
         ms_per_step = 1e3 * dt / args.steps
         value = n_global * args.steps / dt
-        # dominant kernel = igemm4_kernel (conv / conv_transpose fwd + bwd-data on the bf16 matrix cores
-        # with the 3-way operand split: 6 bf16 MFMA MACs per fp32-accurate MAC, so the matrix-core bound
-        # on ALGORITHMIC fp32 flops is the dense bf16 peak / 6)
-        # The launches whose input scale is known ahead of time (the conv under the head, forward and backward - the plane-sweep
-        # kernels of csrc/c3d.hip - and every other backward launch) run on fp16 pairs: 3 fp16 MFMA MACs per fp32-accurate MAC,
-        # bound = dense fp16 peak (= the bf16 one) / 3.  The bound of the mix is the flop-weighted harmonic mean of the two.
-        f16 = prof.get('igemm_f16x2', {'ms': 0.0, 'flops': 0.0, 'launches': 0})
-        bf_fl = prof['igemm3_fwd']['flops'] + prof['igemm3_bwd']['flops']
-        ig_ms = prof['igemm3_fwd']['ms'] + prof['igemm3_bwd']['ms'] + f16['ms']
-        ig_fl = bf_fl + f16['flops']
-        ig_n = prof['igemm3_fwd']['launches'] + prof['igemm3_bwd']['launches'] + f16['launches']
-        # patches behind the sampled launches: 12 igemm4 launches per device pass of `batch` patches (the pool divides evenly
-        # at the default sizes; a ragged last pass would be counted at full size, so derive the count from the passes)
-        passes_per_step = len(model.pass_cut(n_local)[1])
-        sampled_passes = ig_n / 12.0
-        if prof_patches is None:
-            prof_patches = sampled_passes * (n_local / float(passes_per_step))
-        achieved = ig_fl / (ig_ms * 1e-3) / 1e12 if ig_ms > 0 else 0.0
-        peak_bf, peak_f16 = PEAK_BF16_MFMA_TFLOPS / SPLIT_PRODUCTS, PEAK_BF16_MFMA_TFLOPS / 3
-        peak = ig_fl / (bf_fl / peak_bf + f16['flops'] / peak_f16) if ig_fl > 0 else peak_bf
-        executed = (bf_fl * SPLIT_PRODUCTS + f16['flops'] * 3) / (ig_ms * 1e-3) / 1e12 if ig_ms > 0 else 0.0
-        conv_ms = ig_ms + sum(prof[k]['ms'] for k in ('igemm_fwd', 'igemm_bwd', 'direct_conv'))
-        conv_fl = ig_fl + sum(prof[k]['flops'] for k in ('igemm_fwd', 'igemm_bwd', 'direct_conv'))
-        traffic, traffic_note = None, None   # PMC passes are separate runs (tools/run_pmc.sh -> profiles/pmc_traffic.json)
-        tp = os.path.join(ROOT, 'profiles', 'pmc_traffic.json')
-        if os.path.exists(tp):
-            try:
-                tj = json.load(open(tp))
-                # measured per launch at tj['batch'] patches; a launch moves bytes in proportion to its patches
-                per_launch = prof_patches / max(ig_n / 12.0, 1.0)      # patches behind one of the launches `avg_launch_ms` averages
-                traffic = tj.get('hbm_bytes_per_launch') * per_launch / float(tj.get('batch', args.batch))
-                traffic_note = ('PMC 2*FETCH_SIZE + WRITE_SIZE per contraction launch, measured at %d patches per launch (%s), scaled to the '
-                                '%.0f patches per launch of the launches timed here' % (tj.get('batch', args.batch), 'profiles/pmc_traffic.json', per_launch))
-            except Exception:
-                traffic = None
         line = {
             'metric': 'patches/sec Fisher-scored (32^3, 2-class)',
             'value': value, 'unit': 'patches/s', 'n_gpus': ws, 'steps': args.steps, 'warmup': args.warmup,
@@ -330,45 +317,12 @@ def main():
                                             'backward_plane_sweep': int(sess.lib.alq_model_engine_info(model._m, 2)),
                                             'flip_list_overflow': int(sess.lib.alq_model_engine_info(model._m, 5))},
                        'parallelism': 'pool sharded over %d GPU(s), top-B merge (all-gather) + 8x8 Fisher all-reduce: %s' % (ws, comm)},
-            'roofline': {'bound': 'mfma', 'achieved': achieved, 'peak': peak, 'unit': 'TFLOP/s',
-                         'frac': achieved / peak, 'traffic': traffic, 'traffic_note': traffic_note,
-                         # the ratio that does not reward redundant products: algorithmic contraction flops against the best
-                         # fp32-faithful split known (3 products per MAC) on the dense 16-bit peak
-                         'useful_frac': achieved / peak_f16,
-                         'useful_frac_definition': 'algorithmic fp32 flops of the 12 contraction launches / their HIP-event time / (%.0f TFLOP/s / 3 '
-                                                   'products): what a launch would reach at most if every one ran the 3-product fp16-pair split'
-                                                   % PEAK_BF16_MFMA_TFLOPS,
-                         'kernel': 'the 12 contraction launches of a pass: c3d_fwd_kernel / c3d_bwd_kernel (the conv under the head: 53 % of the '
-                                   'flops, fp16 pairs), d3d_fwd / d3d_bwd (dec1), t3d_fwd / t3d_bwd (up2), t3d8_fwd / t3d8_bwd (up1), f3d_fwd (enc2 forward + '
-                                   'pool2), e3d_bwd (enc2 backward + both pool backwards) and two igemm4_kernel launches (bott forward / backward); '
-                                   'fp16 pairs in the backward launches and in the dec1 / enc2 forward launches, bf16 triples in the other forward ones',
-                         'peak_note': 'algorithmic fp32 flops; peak = flop-weighted harmonic mean of %.0f dense 16-bit MFMA / %d '
-                                      'products (bf16x3 launches, %.0f %% of the flops) and / 3 (the fp16x2 launches)'
-                                      % (PEAK_BF16_MFMA_TFLOPS, SPLIT_PRODUCTS, 100.0 * bf_fl / max(ig_fl, 1.0)),
-                         'frac_definition': 'executed 16-bit MFMA flops (algorithmic flops x 6 products in the bf16x3 launches, x 3 in '
-                                            'the fp16x2 ones) / igemm4 time / %.0f TFLOP/s = achieved / peak above; recomputed from a '
-                                            'rocprofv3 --kernel-trace --stats run of this command by tools/roofline_from_stats.py'
-                                            % PEAK_BF16_MFMA_TFLOPS,
-                         'executed_16bit_tflops': executed, 'peak_16bit_tflops': PEAK_BF16_MFMA_TFLOPS,
-                         'igemm4_alg_flops_per_patch': {'bf16x3': bf_fl / max(prof_patches, 1), 'f16x2': f16['flops'] / max(prof_patches, 1)},
-                         'hbm_frac': (traffic * ig_n / (ig_ms * 1e-3) / (PEAK_HBM_TBPS * 1e12)) if traffic and ig_ms > 0 else None,
-                         'f16x2_launches': {'tflops': f16['flops'] / (f16['ms'] * 1e-3) / 1e12 if f16['ms'] > 0 else 0.0,
-                                          'avg_launch_ms': f16['ms'] / max(f16['launches'], 1), 'bound_tflops': peak_f16},
-                         'launches': ig_n, 'avg_launch_ms': ig_ms / max(ig_n, 1),
-                         'timed': ('HIP events on every k-th pass of the timed region, k = %d' % args.prof_every) if in_region else
-                                  ('a separate single-pipeline pass over the first %d pool patches behind the timed region, HIP events on '
-                                   'every launch (the timed region ran %d pipelines: its launches overlap each other)' % (int(prof_patches or 0), lanes_timed)),
-                         'all_conv_engines_tflops': conv_fl / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0,
-                         'flops_per_patch_executed': F_EXEC, 'flops_per_patch_survey': F_SURVEY,
-                         'whole_step_tflops_executed': F_EXEC * value / ws / 1e12,
-                         'hbm_algorithmic_GBps': B_ALG * value / ws / 1e9,
-                         'time_share_ms_sampled': {k: v['ms'] for k, v in prof.items()},
-                         'time_share_note': 'event spans; the reduce / fc_small kernels of the backward pass run on the side stream '
-                                            'BESIDE the igemm launches (their spans overlap those, they do not add up to the step)'},
+        }
+        if args.full:
+            line['roofline'] = netc_roofline(args, model, prof, prof_patches, n_local, value, ws, in_region, lanes_timed)
             # engine clock / board power while the timed region ran: the pass sits at the board's power cap, below the boost clock
             # the peaks above are quoted at (`frac` stays against the datasheet peak)
-            'clocks': clocks,
-        }
+            line['clocks'] = clocks
         if clocks_roof:
             r = line['roofline']
             r['clocks'] = clocks_roof
@@ -389,17 +343,118 @@ def main():
                                      'enc2_backward_fused_with_pool_backwards': int(info(model._m, 9)),
                                      'head_conv_backward_k_steps': {7: 7, 8: 9, 4: 9}.get(int(info(model._m, 13)), 0),
                                      'scoring_pipelines': lanes_timed}
-        if ws == 1 and not args.no_accuracy:
+        if args.full and ws == 1 and not args.no_accuracy:
             line['accuracy'] = accuracy_vs_exact_fp32(sess, model, x, min(args.batch, n_local), n64=min(args.batch, n_local))
-        if ws == 1 and args.netb_pool > 0:
+        if args.full and ws == 1 and args.netb_pool > 0:
             line['netb'] = netb_rate(sess, args.netb_pool, x, accuracy=not args.no_accuracy)
-        if not args.no_cpu_baseline and ws == 1:      # reported at N = 1 only (the other ranks would sit in the barrier)
+        if args.full and not args.no_cpu_baseline and ws == 1:      # reported at N = 1 only (the other ranks would sit in the barrier)
             note('timing the CPU baseline')
             line['cpu_baseline'] = cpu_baseline(x[:args.cpu_sample].cpu().numpy(), ld, sk, in_shape, pars, args.cpu_all_cores)
         print(json.dumps(line))
     if ws > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_BYTES = 64 * 10 ** 6       # --dump-outputs: most bytes written, .npy headers included
+DUMP_SEED = 1007                # --dump-outputs: the fixed sample of patches when the per-patch arrays do not fit
+
+
+def dump_outputs(d, out, a0):
+    """--dump-outputs: what the last timed step returned (pool_shard.score_pool: this rank's per-patch outputs, the pool's top-B and
+    sum of A) as d/<name>.npy in the dtype the step produced it in (p1, H float32; the rest float64; `sel` = the global top-B
+    positions, int64 on the device, exact in float64).  If the per-patch arrays do not fit in DUMP_BYTES they are written for one
+    fixed, seeded sample of rows; `patch` holds the global pool positions of the rows written either way."""
+    os.makedirs(d, exist_ok=True)
+    header = 128                                            # bytes of a .npy header of these shapes
+    whole = {k: out[k] for k in ('sel', 'Asum')}
+    rows = {k: out[k] for k in ('p1', 'H', 'g0', 'g1', 'A', 'trace')}
+    n = int(rows['p1'].shape[0])
+    row_bytes = 8 + sum(t[:1].numel() * t.element_size() for t in rows.values())
+    room = DUMP_BYTES - sum(t.numel() * 8 + header for t in whole.values()) - (len(rows) + 1) * header
+    m = min(n, room // row_bytes)
+    pick = np.arange(n) if m == n else np.sort(np.random.RandomState(DUMP_SEED).choice(n, m, replace=False))
+    idx = out['p1'].new_tensor(pick, dtype=out['sel'].dtype)
+    np.save(os.path.join(d, 'patch.npy'), (a0 + pick).astype(np.float64))
+    for k, t in rows.items():
+        np.save(os.path.join(d, k + '.npy'), t.index_select(0, idx).cpu().numpy())
+    for k, t in whole.items():
+        np.save(os.path.join(d, k + '.npy'), t.cpu().numpy().astype(np.float64))
+
+
+def netc_roofline(args, model, prof, prof_patches, n_local, value, ws, in_region, lanes_timed):
+    """--full: the roofline object of the main line from the HIP-event classes of `prof` (the timed region's sampled passes with
+    --lanes 1, else the separate single-pipeline pass over `prof_patches` patches)."""
+    # dominant kernel = igemm4_kernel (conv / conv_transpose fwd + bwd-data on the bf16 matrix cores
+    # with the 3-way operand split: 6 bf16 MFMA MACs per fp32-accurate MAC, so the matrix-core bound
+    # on ALGORITHMIC fp32 flops is the dense bf16 peak / 6)
+    # The launches whose input scale is known ahead of time (the conv under the head, forward and backward - the plane-sweep
+    # kernels of csrc/c3d.hip - and every other backward launch) run on fp16 pairs: 3 fp16 MFMA MACs per fp32-accurate MAC,
+    # bound = dense fp16 peak (= the bf16 one) / 3.  The bound of the mix is the flop-weighted harmonic mean of the two.
+    f16 = prof.get('igemm_f16x2', {'ms': 0.0, 'flops': 0.0, 'launches': 0})
+    bf_fl = prof['igemm3_fwd']['flops'] + prof['igemm3_bwd']['flops']
+    ig_ms = prof['igemm3_fwd']['ms'] + prof['igemm3_bwd']['ms'] + f16['ms']
+    ig_fl = bf_fl + f16['flops']
+    ig_n = prof['igemm3_fwd']['launches'] + prof['igemm3_bwd']['launches'] + f16['launches']
+    # patches behind the sampled launches: 12 igemm4 launches per device pass of `batch` patches (the pool divides evenly
+    # at the default sizes; a ragged last pass would be counted at full size, so derive the count from the passes)
+    passes_per_step = len(model.pass_cut(n_local)[1])
+    sampled_passes = ig_n / 12.0
+    if prof_patches is None:
+        prof_patches = sampled_passes * (n_local / float(passes_per_step))
+    achieved = ig_fl / (ig_ms * 1e-3) / 1e12 if ig_ms > 0 else 0.0
+    peak_bf, peak_f16 = PEAK_BF16_MFMA_TFLOPS / SPLIT_PRODUCTS, PEAK_BF16_MFMA_TFLOPS / 3
+    peak = ig_fl / (bf_fl / peak_bf + f16['flops'] / peak_f16) if ig_fl > 0 else peak_bf
+    executed = (bf_fl * SPLIT_PRODUCTS + f16['flops'] * 3) / (ig_ms * 1e-3) / 1e12 if ig_ms > 0 else 0.0
+    conv_ms = ig_ms + sum(prof[k]['ms'] for k in ('igemm_fwd', 'igemm_bwd', 'direct_conv'))
+    conv_fl = ig_fl + sum(prof[k]['flops'] for k in ('igemm_fwd', 'igemm_bwd', 'direct_conv'))
+    traffic, traffic_note = None, None   # PMC passes are separate runs (tools/run_pmc.sh -> profiles/pmc_traffic.json)
+    tp = os.path.join(ROOT, 'profiles', 'pmc_traffic.json')
+    if os.path.exists(tp):
+        try:
+            tj = json.load(open(tp))
+            # measured per launch at tj['batch'] patches; a launch moves bytes in proportion to its patches
+            per_launch = prof_patches / max(ig_n / 12.0, 1.0)      # patches behind one of the launches `avg_launch_ms` averages
+            traffic = tj.get('hbm_bytes_per_launch') * per_launch / float(tj.get('batch', args.batch))
+            traffic_note = ('PMC 2*FETCH_SIZE + WRITE_SIZE per contraction launch, measured at %d patches per launch (%s), scaled to the '
+                            '%.0f patches per launch of the launches timed here' % (tj.get('batch', args.batch), 'profiles/pmc_traffic.json', per_launch))
+        except Exception:
+            traffic = None
+    return {'bound': 'mfma', 'achieved': achieved, 'peak': peak, 'unit': 'TFLOP/s',
+            'frac': achieved / peak, 'traffic': traffic, 'traffic_note': traffic_note,
+            # the ratio that does not reward redundant products: algorithmic contraction flops against the best
+            # fp32-faithful split known (3 products per MAC) on the dense 16-bit peak
+            'useful_frac': achieved / peak_f16,
+            'useful_frac_definition': 'algorithmic fp32 flops of the 12 contraction launches / their HIP-event time / (%.0f TFLOP/s / 3 '
+                                      'products): what a launch would reach at most if every one ran the 3-product fp16-pair split'
+                                      % PEAK_BF16_MFMA_TFLOPS,
+            'kernel': 'the 12 contraction launches of a pass: c3d_fwd_kernel / c3d_bwd_kernel (the conv under the head: 53 % of the '
+                      'flops, fp16 pairs), d3d_fwd / d3d_bwd (dec1), t3d_fwd / t3d_bwd (up2), t3d8_fwd / t3d8_bwd (up1), f3d_fwd (enc2 forward + '
+                      'pool2), e3d_bwd (enc2 backward + both pool backwards) and two igemm4_kernel launches (bott forward / backward); '
+                      'fp16 pairs in the backward launches and in the dec1 / enc2 forward launches, bf16 triples in the other forward ones',
+            'peak_note': 'algorithmic fp32 flops; peak = flop-weighted harmonic mean of %.0f dense 16-bit MFMA / %d '
+                         'products (bf16x3 launches, %.0f %% of the flops) and / 3 (the fp16x2 launches)'
+                         % (PEAK_BF16_MFMA_TFLOPS, SPLIT_PRODUCTS, 100.0 * bf_fl / max(ig_fl, 1.0)),
+            'frac_definition': 'executed 16-bit MFMA flops (algorithmic flops x 6 products in the bf16x3 launches, x 3 in '
+                               'the fp16x2 ones) / igemm4 time / %.0f TFLOP/s = achieved / peak above; recomputed from a '
+                               'rocprofv3 --kernel-trace --stats run of this command by tools/roofline_from_stats.py'
+                               % PEAK_BF16_MFMA_TFLOPS,
+            'executed_16bit_tflops': executed, 'peak_16bit_tflops': PEAK_BF16_MFMA_TFLOPS,
+            'igemm4_alg_flops_per_patch': {'bf16x3': bf_fl / max(prof_patches, 1), 'f16x2': f16['flops'] / max(prof_patches, 1)},
+            'hbm_frac': (traffic * ig_n / (ig_ms * 1e-3) / (PEAK_HBM_TBPS * 1e12)) if traffic and ig_ms > 0 else None,
+            'f16x2_launches': {'tflops': f16['flops'] / (f16['ms'] * 1e-3) / 1e12 if f16['ms'] > 0 else 0.0,
+                             'avg_launch_ms': f16['ms'] / max(f16['launches'], 1), 'bound_tflops': peak_f16},
+            'launches': ig_n, 'avg_launch_ms': ig_ms / max(ig_n, 1),
+            'timed': ('HIP events on every k-th pass of the timed region, k = %d' % args.prof_every) if in_region else
+                     ('a separate single-pipeline pass over the first %d pool patches behind the timed region, HIP events on '
+                      'every launch (the timed region ran %d pipelines: its launches overlap each other)' % (int(prof_patches or 0), lanes_timed)),
+            'all_conv_engines_tflops': conv_fl / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0,
+            'flops_per_patch_executed': F_EXEC, 'flops_per_patch_survey': F_SURVEY,
+            'whole_step_tflops_executed': F_EXEC * value / ws / 1e12,
+            'hbm_algorithmic_GBps': B_ALG * value / ws / 1e9,
+            'time_share_ms_sampled': {k: v['ms'] for k, v in prof.items()},
+            'time_share_note': 'event spans; the reduce / fc_small kernels of the backward pass run on the side stream '
+                               'BESIDE the igemm launches (their spans overlap those, they do not add up to the step)'}
 
 
 def _conv_roofline(prof, note):

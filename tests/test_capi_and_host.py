@@ -420,6 +420,62 @@ def test_bench_clock_sampler_reads_the_hwmon_files_of_the_device(tmp_path, monke
     assert s3.dir is None
 
 
+def _load_bench():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('bench_for_test', os.path.join(ROOT, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def _score_pool_like(n, seed):
+    """What pool_shard.score_pool returns for a pool of n patches (NET-C: L = 8), filled with seeded numbers, on the CPU."""
+    import torch
+    g = torch.Generator().manual_seed(seed)
+    f64 = dict(dtype=torch.float64, generator=g)
+    return {'p1': torch.rand(n, generator=g), 'H': torch.rand(n, generator=g), 'g0': torch.rand(n, 8, **f64), 'g1': torch.rand(n, 8, **f64),
+            'A': torch.rand(n, 8, 8, **f64), 'trace': torch.rand(n, **f64), 'Asum': torch.rand(8, 8, **f64),
+            'sel': torch.randint(0, n, (4096,), generator=g), 'absdev': None, 'offset': 0}
+
+
+def test_bench_dump_outputs_fit_64_mb_and_name_the_patches_they_hold(tmp_path):
+    """bench.py --dump-outputs: the last step's arrays as float32 / float64 .npy files, at most 64 MB in all.  A pool whose per-patch
+    arrays fit is written whole; the bench's 100,000-patch pool is written for a fixed, seeded sample of rows, the same one every run,
+    and `patch` names the global pool position of every row written."""
+    bench = _load_bench()
+    for n, a0, whole in ((5000, 700, True), (100000, 0, False)):
+        out = _score_pool_like(n, seed=n)
+        runs = []
+        for r in range(2):
+            d = tmp_path / ('%d_%d' % (n, r))
+            bench.dump_outputs(str(d), out, a0)
+            assert sum(f.stat().st_size for f in d.iterdir()) <= 64 * 10 ** 6
+            runs.append({f.stem: np.load(str(f)) for f in d.iterdir()})
+        z = runs[0]
+        assert sorted(z) == ['A', 'Asum', 'H', 'g0', 'g1', 'p1', 'patch', 'sel', 'trace']
+        assert all(v.dtype in (np.float32, np.float64) for v in z.values())
+        assert all(np.array_equal(z[k], runs[1][k]) for k in z)
+        rows = z['patch'].astype(np.int64) - a0
+        assert (len(rows) == n) == whole and len(rows) > 0.9 * n and np.all(np.diff(rows) > 0)
+        for k in ('p1', 'H', 'g0', 'g1', 'A', 'trace'):
+            assert z[k].dtype == out[k].numpy().dtype and np.array_equal(z[k], out[k].numpy()[rows]), k
+        assert np.array_equal(z['sel'], out['sel'].numpy()) and np.array_equal(z['Asum'], out['Asum'].numpy())
+
+
+@pytest.mark.parametrize('argv', [['--config', '0'], ['--config', '4', '--gpus', '2'], ['--steps', '0'],
+                                  ['--full', '--config', '5', '--dump-outputs', 'x']])
+def test_bench_refuses_what_a_plain_run_does_not_do_before_any_gpu_use(argv, monkeypatch):
+    """The other workloads run only with --full, --dump-outputs belongs to the timed Fisher-scoring path, --steps counts timed steps:
+    refused at argument parsing, before a rank is started or torch is imported."""
+    import sys
+    bench = _load_bench()
+    monkeypatch.setattr(pool_shard, 'spawn_ranks', lambda *a, **kw: pytest.fail('ranks started'))
+    monkeypatch.setattr(sys, 'argv', ['bench.py'] + argv)
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert e.value.code == 2
+
+
 def test_pass_cut_is_even_equal_and_independent_of_the_pipelines(monkeypatch):
     """DeviceModel.pass_cut (what fisher_device and bench.py's bookkeeping share): an even number of equal passes of at most max_batch
     patches once a call spans several; one pass otherwise; ALQ_NO_PASS_BALANCE restores max_batch-sized passes with a ragged last one;

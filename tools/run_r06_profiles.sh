@@ -11,10 +11,10 @@ TAG="${1:-r06}"
 ROOT="$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)"
 OUT="$ROOT/gpurun_out"; mkdir -p "$OUT"; export TMPDIR=/tmp
 cd "$ROOT"
-python3 bench.py > "$OUT/${TAG}_bench_default.json" 2> "$OUT/${TAG}_bench_default.err"; echo "plain bench done"
-rocprofv3 --kernel-trace --stats -d "$OUT/${TAG}_default_stats" -o stats --output-format csv -- python3 bench.py --no-cpu-baseline --no-accuracy --netb-pool 0 > "$OUT/${TAG}_bench_default_under_rocprof.json" 2> "$OUT/${TAG}_rp1.err"; echo "rocprof default done"
-rocprofv3 --kernel-trace --stats -d "$OUT/${TAG}_lanes1_stats" -o stats --output-format csv -- python3 bench.py --lanes 1 --no-cpu-baseline --no-accuracy --netb-pool 0 > "$OUT/${TAG}_bench_lanes1_under_rocprof.json" 2> "$OUT/${TAG}_rp2.err"; echo "rocprof lanes 1 done"
-for c in 0 1 3 4 5; do python3 bench.py --config $c > "$OUT/${TAG}_bench_config$c.json" 2> "$OUT/${TAG}_c$c.err"; echo "config $c done"; done
+python3 bench.py --full > "$OUT/${TAG}_bench_default.json" 2> "$OUT/${TAG}_bench_default.err"; echo "full bench done"
+rocprofv3 --kernel-trace --stats -d "$OUT/${TAG}_default_stats" -o stats --output-format csv -- python3 bench.py --full --no-cpu-baseline --no-accuracy --netb-pool 0 > "$OUT/${TAG}_bench_default_under_rocprof.json" 2> "$OUT/${TAG}_rp1.err"; echo "rocprof default done"
+rocprofv3 --kernel-trace --stats -d "$OUT/${TAG}_lanes1_stats" -o stats --output-format csv -- python3 bench.py --full --lanes 1 --no-cpu-baseline --no-accuracy --netb-pool 0 > "$OUT/${TAG}_bench_lanes1_under_rocprof.json" 2> "$OUT/${TAG}_rp2.err"; echo "rocprof lanes 1 done"
+for c in 0 1 3 4 5; do python3 bench.py --full --config $c > "$OUT/${TAG}_bench_config$c.json" 2> "$OUT/${TAG}_c$c.err"; echo "config $c done"; done
 bash tools/run_pmc.sh ${TAG}pmc 8188
 PMC_ARGS="tools/gpu_netb.py 2048" bash tools/run_pmc.sh ${TAG}netb
 # summaries (the raw counter tables are large: only the summaries and the kernel-stats tables travel back)

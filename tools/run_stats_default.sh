@@ -11,7 +11,7 @@ OUT="$ROOT/gpurun_out"
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd "$ROOT"
-python3 bench.py --steps "$STEPS" --warmup 1 > "$OUT/${TAG}_default.json" 2> "$OUT/${TAG}_default.err"
+python3 bench.py --full --steps "$STEPS" --warmup 1 > "$OUT/${TAG}_default.json" 2> "$OUT/${TAG}_default.err"
 echo "plain bench done"
-rocprofv3 --kernel-trace --stats -d "$OUT/${TAG}_default_stats" -o stats --output-format csv -- python3 bench.py --steps "$STEPS" --warmup 1 --no-cpu-baseline --netb-pool 0 > "$OUT/${TAG}_default_under_rocprof.json" 2> "$OUT/${TAG}_default_under_rocprof.err"
+rocprofv3 --kernel-trace --stats -d "$OUT/${TAG}_default_stats" -o stats --output-format csv -- python3 bench.py --full --steps "$STEPS" --warmup 1 --no-cpu-baseline --netb-pool 0 > "$OUT/${TAG}_default_under_rocprof.json" 2> "$OUT/${TAG}_default_under_rocprof.err"
 echo "rocprof bench done"

@@ -2,7 +2,7 @@
 # Small-pass sweep with HIP events on every launch (one pipeline): do intermediates of a small pass stay in the Infinity Cache?
 # (round 6: no - per-patch launch times only grow below ~1000 patches per pass)     bash tools/small_pass_sweep.sh
 for b in 2047 1000 500 250 125; do
-python bench.py --lanes 1 --batch $b --prof-every 1 --no-accuracy --no-cpu-baseline --netb-pool 0 2>/dev/null | python3 -c "
+python bench.py --full --lanes 1 --batch $b --prof-every 1 --no-accuracy --no-cpu-baseline --netb-pool 0 2>/dev/null | python3 -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 ts=r['time_share_ms_sampled']
