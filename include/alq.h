@@ -198,6 +198,17 @@ int alq_param_grads(alq_model *m, const float *d_x, int N, int mode, int cls, co
                     const int32_t *h_drop_layers, int n_drop_layers, int per_sample, float *d_grads,
                     float *d_post, double *d_loss);
 
+/* Replaces: the per-sample, per-class session.run(model.grad_log_posts) and the squared sums of the expected-gradient-length
+ * query (NNAL.py:234-285).  Per-sample squared norms of parameter gradients, never materialising them.  cls = -1:
+ * u = d(z0 - z1)/dtheta (two-class nets only, ALQ_EINVAL otherwise; d log p0 = p1 u, d log p1 = -p0 u); cls in [0, c):
+ * d log posteriors[cls, n] / dtheta; d_cls [N] int32 (optional, entries in [0, c)) overrides cls per sample.
+ * d_sq [N, 2L] double: [n][2t] = ||dW_t||^2, [n][2t+1] = ||db_t||^2, all L parameterised layers in creation order.
+ * d_post [c, N] optional.  keep_prob 1.  Weight norms of conv / conv_transpose layers on the fp32 matrix cores (exact fp32
+ * products, fp32 accumulation in two levels, fp64 squares); fc layers by the rank-one identity ||delta||^2 ||a||^2.
+ * Every row depends on its own sample only: bit-identical whatever the batch and from run to run.                    */
+int alq_grad_sqnorms(alq_model *m, const float *d_x, int N, int cls, const int32_t *d_cls,
+                     float *d_post, double *d_sq);
+
 /* Replaces: tf.train.GradientDescentOptimizer / AdamOptimizer .minimize (NN.py:591-615) on flat device vectors:
  * theta -= lr g;  Adam (TF-1.x defaults are the caller's: beta1 .9, beta2 .999, eps 1e-8), step count t >= 1:
  * lr_t = lr sqrt(1 - beta2^t) / (1 - beta1^t), m = b1 m + (1-b1) g, v = b2 v + (1-b2) g^2,

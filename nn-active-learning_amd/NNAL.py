@@ -1,5 +1,5 @@
-"""Image-level query strategies (reference: NNAL.py): `CNN_query` with the branches `random`, `entropy` and the
-multi-class Fisher-information query `fi` (NNAL.py:312-464) - the image-level twin of PW_NNAL's binary `fi` and the
+"""Image-level query strategies (reference: NNAL.py): `CNN_query` with the branches `random`, `entropy`, the
+expected-gradient-length query `egl` (NNAL.py:234-285) and the multi-class Fisher-information query `fi` (NNAL.py:312-464) - the image-level twin of PW_NNAL's binary `fi` and the
 last strategy of SURVEY.md 8f-3 that reuses the scoring kernels.
 
 What runs where: posteriors, features and the per-class gradients of the log-posteriors run on the device
@@ -49,9 +49,26 @@ def fi_A_matrices(model, session, sel_X, sel_posteriors):
     return [A[i] for i in range(B)]
 
 
+def egl_candidate_scores(model, sel_X, sel_posteriors):
+    """The scoring loop of the `egl` branch (NNAL.py:255-283) on the device: the per-sample, per-variable squared norms
+    ||d log posteriors[j] / d theta_t||^2 come from alq_grad_sqnorms (nothing of the size of theta is formed), one pass
+    per selected class - c passes for c < 20, else ten passes with the class of slot j given per sample - and
+    NNAL_tools.egl_scores weights them like the reference.  sel_posteriors [c, B]; returns float64 [B]."""
+    classes = NNAL_tools.egl_classes(sel_posteriors)
+    t, n = model._as_device_batch(sel_X)
+    c = sel_posteriors.shape[0]
+    sq = []
+    for j in range(classes.shape[1]):
+        if c < 20:
+            sq.append(model.grad_sqnorms_device(t, n, cls=j).cpu().numpy())
+        else:
+            sq.append(model.grad_sqnorms_device(t, n, cls_per_sample=classes[:, j]).cpu().numpy())
+    return NNAL_tools.egl_scores(np.stack(sq, axis=1), sel_posteriors, classes)
+
+
 def CNN_query(model, expr, pool_inds, method_name, session, col=True, extra_feed_dict={}):
-    """NNAL.CNN_query (NNAL.py:188-525), branches `random` (:297-299), `entropy` (:301-313) and `fi` (:315-464).
-    Returns positions into `pool_inds`."""
+    """NNAL.CNN_query (NNAL.py:188-525), branches `random` (:297-299), `entropy` (:301-313), `egl` (:234-285) and
+    `fi` (:315-464).  Returns positions into `pool_inds`."""
     k = expr.pars['k']
     B = expr.pars['B']
     lambda_ = expr.pars['lambda_']
@@ -61,6 +78,19 @@ def CNN_query(model, expr, pool_inds, method_name, session, col=True, extra_feed
     if method_name == 'entropy':
         posteriors = NNAL_tools.idxBatch_posteriors(model, pool_inds, expr, session, col, extra_feed_dict)
         return np.argsort(-NNAL_tools.compute_entropy(posteriors), kind='stable')[:k]
+    if method_name == 'egl':
+        # the reference's branch calls names it never defines (NNAL_tools.batch_posteriors, img_path_list, pool_X,
+        # batch_size); mapped like `fi`: idxBatch_posteriors, uncertainty_filtering, NN.load_winds of the candidates
+        posteriors = NNAL_tools.idxBatch_posteriors(model, pool_inds, expr, session, col, extra_feed_dict)
+        if B < posteriors.shape[1]:
+            sel_inds = NNAL_tools.uncertainty_filtering(posteriors, B)
+            sel_posteriors = posteriors[:, sel_inds]
+        else:
+            sel_posteriors = posteriors
+            sel_inds = np.arange(posteriors.shape[1])
+        sel_X, _ = NN.load_winds(pool_inds[sel_inds], expr.imgs_path_file, expr.pars['target_shape'], expr.pars['mean'])
+        scores = egl_candidate_scores(model, sel_X, sel_posteriors)
+        return sel_inds[np.argsort(-scores, kind='stable')[:k]]             # ties: lower candidate first
     if method_name == 'fi':
         posteriors = NNAL_tools.idxBatch_posteriors(model, pool_inds, expr, session, col, extra_feed_dict)
         if B < posteriors.shape[1]:
@@ -82,4 +112,4 @@ def CNN_query(model, expr, pool_inds, method_name, session, col=True, extra_feed
         q_opt = np.array(soln['x'][:B]).ravel()
         Q_inds = NNAL_tools.sample_query_dstr(q_opt, k, replacement=True)
         return sel_inds[Q_inds]
-    raise NotImplementedError("query method %r: the image-level path has random, entropy and fi" % (method_name,))
+    raise NotImplementedError("query method %r: the image-level path has random, entropy, egl and fi" % (method_name,))

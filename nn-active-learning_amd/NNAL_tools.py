@@ -61,6 +61,46 @@ def shrink_gradient(grad, method, args=None):
     return np.ravel(out)
 
 
+def egl_classes(sel_posteriors):
+    """The classes the expected-gradient-length query scores per candidate (NNAL.py:264-280): all c classes when
+    c < 20, else the ten largest posteriors of the sample (`argsort(-p)[:10]`; the reference's comment says twenty, its
+    code takes ten).  Stable sort: on tied posteriors the lower class index comes first.  sel_posteriors [c, B];
+    returns int64 [B, J]."""
+    p = np.asarray(sel_posteriors)
+    c, B = p.shape
+    if c < 20:
+        return np.tile(np.arange(c, dtype=np.int64), (B, 1))
+    return np.argsort(-p, axis=0, kind='stable')[:10].T.astype(np.int64)
+
+
+def egl_scores(sq, posts, classes):
+    """The EGL scores of NNAL.py:264-283 in closed form.  sq [B, J, T] float64: ||g_{j,t}||^2 of candidate i, slot j
+    (class classes[i, j]) and variable t (W_0, b_0, W_1, b_1, ... of the grad_layers subset); posts [c, B] posteriors;
+    classes [B, J] (egl_classes).  The reference adds `class_score * p` INSIDE its loop over t, with class_score the
+    running sum over t' <= t, so variable t enters with weight (T - t):
+        score_i = sum_j p_{classes[i, j], i} sum_t (T - t) ||g_{j,t}||^2.
+    That weighting is the reference's indentation, mirrored like the other quirks.  Returns float64 [B]."""
+    sq = np.asarray(sq, dtype=np.float64)
+    B, J, T = sq.shape
+    classes = np.asarray(classes, dtype=np.int64).reshape(B, J)
+    w = (T - np.arange(T)).astype(np.float64)
+    W = sq @ w                                                               # [B, J]
+    p = np.asarray(posts, dtype=np.float64)[classes, np.arange(B)[:, None]]     # [B, J]
+    return np.sum(p * W, axis=1)
+
+
+def egl_binary_scores(sq_u, p1):
+    """EGL of a two-class net from the unit-cotangent norms ||u_t||^2, u = d(z0 - z1) / d theta (alq_grad_sqnorms with
+    cls = -1): d log p0 = p1 u and d log p1 = -p0 u, so with W = sum_t (T - t) ||u_t||^2 the reference's sum over both
+    classes is p0 p1^2 W + p1 p0^2 W, evaluated literally.  sq_u [B, T] float64, p1 [B] posterior of class 1."""
+    sq_u = np.asarray(sq_u, dtype=np.float64)
+    T = sq_u.shape[1]
+    W = sq_u @ (T - np.arange(T)).astype(np.float64)
+    p1 = np.asarray(p1, dtype=np.float64)
+    p0 = 1. - p1
+    return p0 * p1 ** 2 * W + p1 * p0 ** 2 * W
+
+
 def append_zero(A):
     """NNAL_tools.py:833-842."""
     d = A.shape[0]

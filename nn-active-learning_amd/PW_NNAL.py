@@ -152,9 +152,18 @@ def fisher_candidates(expr, model, sess, padded_imgs, pool_inds, vols=None):
     return sel_inds, sel_posts, [A[i] for i in range(len(sel_inds))]
 
 
+def egl_scores_device(model, t, n, p1):
+    """EGL scores of n binary candidates (device patches t, posteriors of class 1 p1): ONE alq_grad_sqnorms pass with the
+    unit cotangent gives ||u_t||^2, u = d(z0 - z1) / d theta, for both classes (NNAL_tools.egl_binary_scores).  The
+    columns follow `grad_layers`, like the reference's T = len(grad_log_posts['0'])."""
+    sq = model.grad_sqnorms_device(t, n, cls=-1).cpu().numpy()
+    return NNAL_tools.egl_binary_scores(sq, p1)
+
+
 def CNN_query(expr, model, sess, padded_imgs, pool_inds, tr_inds, method_name):
-    """PW_NNAL.CNN_query (PW_NNAL.py:18-166), branches `entropy` and `fi`.  Returns positions into
-    `pool_inds` (the caller maps them, PW_AL.py:405-408)."""
+    """PW_NNAL.CNN_query (PW_NNAL.py:18-166), branches `entropy` and `fi`, plus `egl`, which the reference has only at
+    image level (NNAL.py:234-285): uncertainty filter to B like `fi`, score, the k largest (stable: ties -> lower
+    candidate first).  Returns positions into `pool_inds` (the caller maps them, PW_AL.py:405-408)."""
     pool_inds = np.asarray(pool_inds)
     if method_name == 'random':
         return np.random.permutation(len(pool_inds))[:expr.pars['k']]
@@ -171,6 +180,16 @@ def CNN_query(expr, model, sess, padded_imgs, pool_inds, tr_inds, method_name):
                                      expr.pars['stats'], 'posteriors', x_feed_dict)[0]
             total_posts = (posts + i * total_posts) / (i + 1)
         return np.argsort(np.abs(total_posts - .5), kind='stable')[:expr.pars['k']]
+    if method_name == 'egl':
+        B = expr.pars['B']
+        vols = patch_utils.DeviceVolumes(sess, padded_imgs)
+        posts = PW_NN.batch_eval(model, sess, padded_imgs, pool_inds, expr.pars['patch_shape'],
+                                 expr.pars['ntb'], expr.pars['stats'], 'posteriors', _vols=vols)[0]
+        sel_inds = binary_uncertainty_filter(posts, B) if B < len(pool_inds) else np.arange(len(pool_inds))
+        t = vols.gather(pool_inds[sel_inds], expr.pars['patch_shape'],
+                        np.asarray(expr.pars['stats'], dtype=np.float64)[:len(padded_imgs)], quirk=1)
+        scores = egl_scores_device(model, t, len(sel_inds), posts[sel_inds])
+        return sel_inds[np.argsort(-scores, kind='stable')[:expr.pars['k']]]
     if method_name == 'fi':
         lambda_ = expr.pars['lambda_']
         vols = patch_utils.DeviceVolumes(sess, padded_imgs)            # one upload for the whole query
@@ -188,7 +207,7 @@ def CNN_query(expr, model, sess, padded_imgs, pool_inds, tr_inds, method_name):
         q_opt = np.array(soln['x'][:len(sel_inds)]).ravel()
         Q_inds = NNAL_tools.sample_query_dstr(q_opt, expr.pars['k'], replacement=True)
         return sel_inds[Q_inds]
-    raise NotImplementedError("query method %r is outside the scored path (entropy, fi)" % (method_name,))
+    raise NotImplementedError("query method %r is outside the scored path (entropy, egl, fi)" % (method_name,))
 
 
 def _features_device(expr, model, sess, padded_mods, inds, stats):
@@ -312,7 +331,9 @@ def core_set_query(expr, model, sess, all_padded_imgs, pool_inds, labeled_inds):
 
 def query_multimg(expr, model, sess, all_padded_imgs, pool_inds, labeled_inds, method_name):
     """PW_NNAL.query_multimg (PW_NNAL.py:169-629), branches `entropy` (:226-230) and `fi`
-    (:547-627).  Returns, per subject, positions into that subject's pool_inds."""
+    (:547-627), plus `egl` (image level only in the reference, NNAL.py:234-285; candidates gathered and sharded like
+    `fi`, the k largest scores over all subjects, ties -> lower candidate first).  Returns, per subject, positions into
+    that subject's pool_inds."""
     k = expr.pars['k']
     B = expr.pars['B']
     sizes = [len(p) for p in pool_inds]
@@ -346,6 +367,31 @@ def query_multimg(expr, model, sess, all_padded_imgs, pool_inds, labeled_inds, m
         return rep_entropy_query(expr, model, sess, all_padded_imgs, pool_inds)
     if method_name == 'core-set':
         return core_set_query(expr, model, sess, all_padded_imgs, pool_inds, labeled_inds)
+    if method_name == 'egl':
+        from . import pool_shard
+        dvols = {}
+        sel_inds, sel_posts = bin_uncertainty_filter_multimg(expr, model, sess, all_padded_imgs, pool_inds, B, _vols=dvols)
+        m = len(all_padded_imgs[0]) - 1
+        stats = np.asarray(expr.train_stats, dtype=np.float64)
+        nsel = [len(s_) for s_ in sel_inds]
+        ncand = int(np.sum(nsel))
+        a, b = pool_shard.work_block(ncand)            # this rank's block of the candidate list (volumes are replicated)
+        rows = []
+        off = 0
+        for i in range(len(pool_inds)):
+            lo, hi = max(a, off) - off, min(b, off + nsel[i]) - off
+            if hi > lo:
+                vols = dvols.get(i) or patch_utils.DeviceVolumes(sess, all_padded_imgs[i][:m])
+                t = vols.gather(np.asarray(pool_inds[i])[np.asarray(sel_inds[i])[lo:hi]], expr.pars['patch_shape'],
+                                stats[i, :2 * m], quirk=0)                 # slab rule, patch_utils.py:1203-1207
+                rows.append(egl_scores_device(model, t, hi - lo, np.asarray(sel_posts[i][lo:hi], dtype=np.float64))[:, None])
+            off += nsel[i]
+        S = np.concatenate(rows) if rows else np.zeros((0, 1))
+        if (a, b) != (0, ncand):
+            S = pool_shard.allgather_rows(ncand, np.arange(a, b), S, sess)
+        order = np.argsort(-S[:, 0], kind='stable')[:k]
+        local = patch_utils.global2local_inds(order, nsel)
+        return [np.array(sel_inds[i])[local[i]] for i in range(len(sel_inds))]
     if method_name == 'fi':
         from . import pool_shard
         dvols = {}                                                       # one upload per subject for the whole query

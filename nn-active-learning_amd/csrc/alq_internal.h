@@ -58,7 +58,8 @@ struct View {
 // igemm_* = the fp32 engines (v1 / v2), igemm3_* = the bf16x3 matrix-core engine, direct = the VALU first-layer conv
 enum ProfClass { PROF_IGEMM_FWD = 0, PROF_IGEMM_BWD = 1, PROF_ELEMWISE = 2, PROF_REDUCE = 3,
                  PROF_FC_SMALL = 4, PROF_IGEMM3_FWD = 5, PROF_IGEMM3_BWD = 6, PROF_DIRECT = 7,
-                 PROF_IGEMM_F16 = 8 /* igemm4 launches on the fp16x2 split (3 products) */, PROF_NUM = 9 };
+                 PROF_IGEMM_F16 = 8 /* igemm4 launches on the fp16x2 split (3 products) */,
+                 PROF_GNORM = 9 /* per-sample weight-gradient norms on fp32 MFMA (gnorm.hip) */, PROF_NUM = 10 };
 
 struct ProfSlot {
     double ms = 0;
@@ -657,5 +658,12 @@ int k_adam(alq_ctx *, float *theta, const float *g, float *m, float *v, long lon
 int k_sq_accum(alq_ctx *, const float *g, long long per, int N, double *acc);
 int k_shrink_sum(alq_ctx *, const float *g, int N, long long P, const long long *off, int L, double *out);
 int k_fisher_classes(alq_ctx *, const double *g, const double *w, const double *diag, int N, int c, int L, double *A);
+
+// ------------------------------------------------------------------ per-sample gradient norms (gnorm.hip)
+long long gnorm_partials(const View &U, const View &V, const int k[3], const int s[3], const int lo[3]);   // doubles per sample
+int k_gnorm_weight(alq_ctx *, const View &U, const View &V, const int k[3], const int s[3], const int lo[3], int N, double *part,
+                   double *d_sq, int ld, int col);
+int k_gnorm_bias(alq_ctx *, const View &delta, int N, double *d_sq, int ld, int col);
+int k_gnorm_fc(alq_ctx *, const float *delta, int nout, const View &a, int N, double *d_sq, int ld, int col);
 
 }  // namespace alq

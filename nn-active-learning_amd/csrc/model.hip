@@ -141,6 +141,8 @@ struct alq_model {
     int nslab_max = 1;
     float *wg_partial = nullptr;   // slab partials of the weight-gradient kernels (grown on demand)
     size_t wg_partial_len = 0;
+    double *gn_partial = nullptr;  // per-(sample, workgroup) partials of the gradient-norm kernels (grown on demand)
+    size_t gn_partial_len = 0;
     float *x_stage = nullptr;      // [max_batch, elems per patch]: rows gathered by the *_rows entry points
     int64_t epp = 0;               // elements per patch
     // Engine-selection knobs, read from the environment ONCE, when this model is created; every call applies the
@@ -1577,6 +1579,43 @@ static int run_param_grads(alq_model *m, const float *d_x, int N, int sum_n, flo
     return ALQ_OK;
 }
 
+// Per-sample squared norms of every parameterised layer's weight and bias gradient from the tensors a general backward pass
+// left behind (the views run_param_grads reads, split-concat inputs included): d_sq [N, 2L], [n][2t] = ||dW_t||^2,
+// [n][2t + 1] = ||db_t||^2.  Nothing of the size of the parameters is written (gnorm.hip).
+static int run_grad_sqnorms(alq_model *m, const float *d_x, int N, double *d_sq) {
+    alq_ctx *ctx = m->ctx;
+    const int one[3] = {1, 1, 1};
+    long long need = 0;
+    for (Layer &ly : m->layers) {
+        if (ly.pidx < 0 || ly.spec.type == ALQ_FC) continue;
+        const bool convt = ly.spec.type == ALQ_CONVT;
+        need = std::max(need, gnorm_partials(convt ? ly.in : ly.dout, convt ? ly.dout : ly.in, ly.spec.k, convt ? ly.spec.s : one,
+                                             ly.lo) * N);
+    }
+    if ((size_t)need > m->gn_partial_len) {
+        ALQ_TRY(m->dalloc(&m->gn_partial, (size_t)need));
+        m->gn_partial_len = (size_t)need;
+    }
+    const int ld = 2 * m->L;
+    for (size_t i = 0; i < m->layers.size(); ++i) {
+        Layer &ly = m->layers[i];
+        if (ly.pidx < 0) continue;
+        View in = ly.in;
+        if (i == 0) in.p = const_cast<float *>(d_x);
+        const int col = 2 * ly.pidx;
+        if (ly.spec.type == ALQ_CONV) {
+            ALQ_TRY(k_gnorm_weight(ctx, ly.dout, in, ly.spec.k, one, ly.lo, N, m->gn_partial, d_sq, ld, col));
+            ALQ_TRY(k_gnorm_bias(ctx, ly.dout, N, d_sq, ld, col + 1));
+        } else if (ly.spec.type == ALQ_CONVT) {
+            ALQ_TRY(k_gnorm_weight(ctx, in, ly.dout, ly.spec.k, ly.spec.s, ly.lo, N, m->gn_partial, d_sq, ld, col));
+            ALQ_TRY(k_gnorm_bias(ctx, ly.dout, N, d_sq, ld, col + 1));
+        } else {
+            ALQ_TRY(k_gnorm_fc(ctx, ly.dout.p, ly.spec.cout, in, N, d_sq, ld, col));
+        }
+    }
+    return ALQ_OK;
+}
+
 static int make_drop(const alq_model *m, float keep_prob, uint64_t seed, int64_t first_sample, const int32_t *h_layers, int n_layers,
                      DropSpec *d) {
     ALQ_REQUIRE(keep_prob > 0.f && keep_prob <= 1.f, ALQ_EINVAL, "keep_prob %g outside (0, 1]", (double)keep_prob);
@@ -1634,6 +1673,25 @@ int alq_param_grads(alq_model *m, const float *d_x, int N, int mode, int cls, co
     ALQ_TRY(k_logit_cotangent(m->ctx, post, m->nclass, N, mode, cls, d_labels, loss_scale, m->dlogits));
     ALQ_TRY(run_backward_general(m, N, &ds));
     return run_param_grads(m, d_x, N, per_sample ? 0 : 1, d_grads, alq_model_num_params(m));
+}
+
+int alq_grad_sqnorms(alq_model *m, const float *d_x, int N, int cls, const int32_t *d_cls, float *d_post, double *d_sq) {
+    ALQ_REQUIRE(m && d_x && d_sq, ALQ_EINVAL, "alq_grad_sqnorms: null argument");
+    ALQ_REQUIRE(N >= 1 && N <= m->max_batch, ALQ_EINVAL, "alq_grad_sqnorms: N=%d outside [1, max_batch=%d]", N, m->max_batch);
+    ALQ_REQUIRE(d_cls || (cls == -1 && m->nclass == 2) || (cls >= 0 && cls < m->nclass), ALQ_EINVAL,
+                "alq_grad_sqnorms: class %d (-1 needs a two-class net, found %d classes)", cls, m->nclass);
+    ALQ_HIP(hipSetDevice(m->ctx->device));
+    DropSpec ds;
+    ALQ_TRY(make_drop(m, 1.f, 0, 0, nullptr, 0, &ds));
+    m->last_call_fisher = false;
+    apply_knobs(m);
+    ALQ_TRY(run_forward(m, d_x, N, false, /*keep_all=*/true, &ds));
+    float *post = d_post ? d_post : m->post;
+    ALQ_TRY(k_softmax(m->ctx, m->logits, m->nclass, N, post, nullptr));
+    const int mode = d_cls ? 3 : (cls < 0 ? 2 : 0);
+    ALQ_TRY(k_logit_cotangent(m->ctx, post, m->nclass, N, mode, cls, d_cls, 1.f, m->dlogits));
+    ALQ_TRY(run_backward_general(m, N, &ds));
+    return run_grad_sqnorms(m, d_x, N, d_sq);
 }
 
 int alq_sgd_step(alq_ctx *ctx, float *d_theta, const float *d_grad, int64_t n, float lr) {
@@ -2267,7 +2325,7 @@ int alq_topk_merge(const double *h_keys, const int64_t *h_idx, int64_t n, int64_
 }
 
 static const char *kProfNames[PROF_NUM] = {"igemm_fwd", "igemm_bwd", "elementwise", "reduce", "fc_small",
-                                           "igemm3_fwd", "igemm3_bwd", "direct_conv", "igemm_f16x2"};
+                                           "igemm3_fwd", "igemm3_bwd", "direct_conv", "igemm_f16x2", "gnorm"};
 
 int alq_prof_enable(alq_ctx *ctx, int on) {
     ALQ_REQUIRE(ctx != nullptr, ALQ_EINVAL, "null ctx");

@@ -82,7 +82,10 @@ int k_dropout(alq_ctx *ctx, const View &t, int N, long long first_sample, unsign
 // ------------------------------------------------------------------------------------------ cotangents at the logits
 // mode 0: d log p_j / dz = e_j - p for class j = cls (NN.py:639-645);
 // mode 1: d mean-CE / dz = (p - y) / N, y = one-hot of labels[n] (tf.nn.softmax_cross_entropy_with_logits + reduce_mean,
-//         NN.py:583-588); a label outside [0, c) gives a zero row (unlabelled sample).
+//         NN.py:583-588); a label outside [0, c) gives a zero row (unlabelled sample);
+// mode 2: the unit cotangent (+1, -1, 0, ...): d(z0 - z1) / dz, whose parameter gradient u gives both classes of a
+//         two-class net (d log p0 = p1 u, d log p1 = -p0 u);
+// mode 3: mode 0 with a class per sample, cls = labels[n].
 __global__ void logit_cotangent_kernel(const float *post_cN, int c, int N, int mode, int cls, const int *labels, float scale,
                                        float *dlogits /*[N, c]*/) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -91,6 +94,8 @@ __global__ void logit_cotangent_kernel(const float *post_cN, int c, int N, int m
     const float p = post_cN[(long long)j * N + n];
     float d;
     if (mode == 0) d = (j == cls ? 1.f : 0.f) - p;
+    else if (mode == 2) d = j == 0 ? 1.f : (j == 1 ? -1.f : 0.f);
+    else if (mode == 3) d = (j == labels[n] ? 1.f : 0.f) - p;
     else {
         const int y = labels[n];
         d = (y >= 0 && y < c) ? (p - (j == y ? 1.f : 0.f)) * scale : 0.f;

@@ -461,6 +461,31 @@ class DeviceModel(object):
             C.c_void_p(post.data_ptr()) if post is not None else None, C.c_void_p(loss.data_ptr()) if loss is not None else None))
         return g, post, loss
 
+    def grad_sqnorms_device(self, t, n, cls=-1, cls_per_sample=None):
+        """alq_grad_sqnorms over device passes of max_batch patches: [n, 2L'] float64 on the device, column 2t' =
+        ||dW||^2 and 2t' + 1 = ||db||^2 of the t'-th layer of `grad_layers` (all layers when empty).  cls = -1: the
+        unit-cotangent gradient u = d(z0 - z1) / d theta of a two-class net; cls in [0, c): d log posteriors[cls] /
+        d theta; cls_per_sample (int array or device int32 tensor [n]) overrides cls per sample.  Rows do not depend
+        on the pass cut."""
+        torch = self.sess.torch
+        self.sess.bind_stream()
+        L = self.L
+        dc = None
+        if cls_per_sample is not None:
+            dc = cls_per_sample if isinstance(cls_per_sample, torch.Tensor) else \
+                self.sess.to_device(np.asarray(cls_per_sample, dtype=np.int32).reshape(n), torch.int32)
+            assert dc.dtype == torch.int32 and dc.is_contiguous() and int(dc.numel()) == n
+        sq = self.sess.empty((n, 2 * L), torch.float64)
+        for a in range(0, n, self.max_batch):
+            b = min(n, a + self.max_batch)
+            check(self.lib.alq_grad_sqnorms(self._m, C.c_void_p(t.data_ptr() + a * self.elems_per_patch * 4), b - a, int(cls),
+                                            C.c_void_p(dc.data_ptr() + a * 4) if dc is not None else None, None,
+                                            C.c_void_p(sq.data_ptr() + a * 2 * L * 8)))
+        if list(self.grad_layer_idx) != list(range(L)):
+            cols = [2 * i + h for i in self.grad_layer_idx for h in (0, 1)]
+            sq = sq[:, cols].contiguous()
+        return sq
+
     def grad_log_post(self, x, j, keep_prob=1.):
         """`sess.run(model.grad_posts[str(j)], {x: batch})`: gradients of log posteriors[j, 0] - sample 0 of the batch,
         like the reference's graph node (NN.py:639-645) - w.r.t. the variables of `grad_layers`, TF shapes."""
