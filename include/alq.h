@@ -128,10 +128,25 @@ int alq_score_entropy(alq_ctx *ctx, const float *d_p1, int64_t n, double *d_absd
 
 /* Replaces: np.argsort(np.abs(posts - .5))[:B] (PW_NNAL.py:64,109-110,671-681,730).
  * Ascending keys, ties -> lower index first (the reference's tie order is unspecified).
+ * Keys compare in numeric order for either sign (a NaN with the sign bit clear after +inf); -0.0 sorts before +0.0,
+ * so a caller whose keys may be zero of either sign writes them as 0.0 - x, which is never -0.0.
  * d_out_idx: int64 [B].  d_work: device scratch of alq_topk_work_bytes(n) bytes.             */
 size_t alq_topk_work_bytes(int64_t n);
 int alq_topk_uncertain(alq_ctx *ctx, const double *d_keys, int64_t n, int64_t B,
                        int64_t *d_out_idx, void *d_work);
+
+/* Replaces: the committee loop of the `ensemble` and `QBC-JS` queries (PW_NNAL.py:453-545), one member per call.
+ * d_p1: float [n] class-1 posteriors of member `member` (0-based; members in order); d_mean_p: double [n] running mean
+ * posterior av = (p + i*av) / (i+1); mode ALQ_COMMITTEE_QBC_JS also keeps d_mean_h: double [n] running mean entropy
+ * avH = (ent(p) + i*avH) / (i+1), ent(x) = -x*log(x) - (1-x)*log(1-x) with an exact 0 in x or in 1-x lifted to 1e-6
+ * first (d_mean_h may be NULL for ALQ_COMMITTEE_ENSEMBLE).  At member 0 the buffers are written, not read.
+ * d_keys (optional, typically at the last member): double [n] keys for alq_topk_uncertain, ensemble |av - .5|,
+ * QBC-JS 0.0 - (ent(av) - avH) (never -0.0).  Every float64 operation is NumPy's in the reference's order (no
+ * contraction): av and the ensemble keys are bit-exact; entropies differ from NumPy's only by the device log.       */
+#define ALQ_COMMITTEE_ENSEMBLE 0
+#define ALQ_COMMITTEE_QBC_JS 1
+int alq_committee_update(alq_ctx *ctx, const float *d_p1, int64_t n, int member, int mode, double *d_mean_p,
+                         double *d_mean_h, double *d_keys);
 
 /* Multi-GPU top-B merge step (no reference counterpart: the reference is one process).
  * Host function: merges the candidate (key, GLOBAL index) pairs gathered from all ranks

@@ -378,12 +378,26 @@ class Experiment_MultiImg(Experiment):
         if iters > 0 and os.path.exists(state.weights_path(iters)):
             init = state.weights_path(iters)                   # resume: the weights the last complete iteration left
         model.perform_assign_ops(init, sess)
+        committee = method_name in ('ensemble', 'QBC-JS')
+        if committee:
+            # (:780-790, :822-843) for both committee methods: the holder the members are built in, and the member list of
+            # pars['pretrained_paths'] (the reference's is a private file-server list)
+            if not self.pars.get('pretrained_paths'):
+                raise ValueError("method %r needs pars['pretrained_paths']: the weight files of the committee members "
+                                 "(their number is the committee size)" % (method_name,))
+            self.pretrained_paths = list(self.pars['pretrained_paths'])
+            self.model_holder = self._create_model(sess)
+            self.model_holder.add_assign_ops()
         nqueries = 0
         log = []
         while nqueries < max_queries:
             self.labeled_paths = self.train_paths               # (:818-821; the core-set bootstrap from a private data set, :806-816, is not mirrored)
             labeled_inds = training_inds
             self.labeled_stats = self.train_stats
+            if committee and int(np.sum([len(t) for t in training_inds])) > 0:
+                # the committee's start: the current model's weights file (the reference never sets it; :834-843); before
+                # the first fine-tune there is none and the query takes the model's weights from memory
+                self.prev_weights_path = state.weights_path(iters) if os.path.exists(state.weights_path(iters)) else None
             t1 = time.time()
             Q_inds = PW_NNAL.query_multimg(self, model, sess, all_padded_imgs, pool_inds, labeled_inds, method_name)
             dt = time.time() - t1

@@ -20,6 +20,51 @@ def mc_dropout_args(model, x_feed_dict):
     return keep_prob, mc, seed
 
 
+def _eval_passes(model, sess, img_dat, inds, patch_shape, batch_size, stats, drop, want_pred, want_feat, _vols, _first_sample):
+    """The device part of batch_eval: gather + normalise (channel-index rule) + forward, one chunk of _CHUNK voxels at a
+    time.  Yields (a, b, post [c, b-a], pred, feat) device tensors of inds[a:b]; `drop` = mc_dropout_args(...)."""
+    keep_prob, mc, seed = drop
+    if not isinstance(img_dat[0], np.ndarray):
+        # PW_NN.py:429-444: paths -> load (NRRD) and zero-pad by the patch radii
+        from . import nrrd_io
+        rads = [int((patch_shape[i] - 1) / 2.) for i in range(3)]
+        img_dat = [np.pad(nrrd_io.read(p)[0], ((rads[0], rads[0]), (rads[1], rads[1]), (rads[2], rads[2])), 'constant')
+                   for p in img_dat]
+    if int(batch_size) < 1:
+        raise ValueError('batch_size must be positive')
+    m = len(img_dat)
+    inds = np.asarray(inds)
+    n = len(inds)
+    # _vols (not a reference argument): volumes a caller of this package has already uploaded for the same query
+    vols = _vols if _vols is not None else patch_utils.DeviceVolumes(sess, img_dat)
+    st = np.asarray(stats, dtype=np.float64)[:m]
+    for a in range(0, n, _CHUNK):
+        b = min(n, a + _CHUNK)
+        t = vols.gather(inds[a:b], patch_shape, st, quirk=1)
+        if mc:
+            post, pred = model.forward_dropout_device(t, b - a, keep_prob, seed=seed, first_sample=_first_sample + a,
+                                                      want_pred=want_pred)
+            feat = None
+        else:
+            post, pred, feat = model.forward_device(t, b - a, want_pred, want_feat)
+        yield a, b, post, pred, feat
+
+
+def posteriors_device(model, sess, img_dat, inds, patch_shape, batch_size, stats, x_feed_dict={}, _vols=None, _first_sample=0,
+                      out=None):
+    """batch_eval(..., 'posteriors') without the host copy: the class-1 posteriors of `inds` as a float32 device tensor
+    [n] (`out`, when given, is filled).  Same gather, statistics, passes and dropout draws as batch_eval, so the float64
+    widening of this tensor is batch_eval's result bit for bit."""
+    drop = mc_dropout_args(model, x_feed_dict)
+    n = len(np.asarray(inds))
+    if out is None:
+        out = sess.empty((n,), sess.torch.float32)
+    for a, b, post, _, _ in _eval_passes(model, sess, img_dat, inds, patch_shape, batch_size, stats, drop, False, False, _vols,
+                                         _first_sample):
+        out[a:b] = post[1]
+    return out
+
+
 def batch_eval(model, sess, img_dat, inds, patch_shape, batch_size, stats, varnames,
                mask=None, x_feed_dict={}, _vols=None, _first_sample=0):
     """PW_NN.batch_eval: evaluates `varnames` ('posteriors', 'prediction', 'feature_layer')
@@ -42,34 +87,14 @@ def batch_eval(model, sess, img_dat, inds, patch_shape, batch_size, stats, varna
     keep_prob, mc, seed = mc_dropout_args(model, x_feed_dict)
     if mc and 'feature_layer' in varnames:
         raise NotImplementedError('feature_layer at keep_prob < 1')
-    if not isinstance(img_dat[0], np.ndarray):
-        # PW_NN.py:429-444: paths -> load (NRRD) and zero-pad by the patch radii
-        from . import nrrd_io
-        rads = [int((patch_shape[i] - 1) / 2.) for i in range(3)]
-        img_dat = [np.pad(nrrd_io.read(p)[0], ((rads[0], rads[0]), (rads[1], rads[1]), (rads[2], rads[2])), 'constant')
-                   for p in img_dat]
-    if int(batch_size) < 1:
-        raise ValueError('batch_size must be positive')
-    m = len(img_dat)
-    inds = np.asarray(inds)
-    n = len(inds)
-    # _vols (not a reference argument): volumes a caller of this package has already uploaded for the same query
-    vols = _vols if _vols is not None else patch_utils.DeviceVolumes(sess, img_dat)
     want_pred = 'prediction' in varnames
     want_feat = 'feature_layer' in varnames
+    n = len(np.asarray(inds))
     posts = np.zeros(n)
     preds = np.zeros(n)
     feats = np.zeros((model.feature_dim, n)) if want_feat else None
-    st = np.asarray(stats, dtype=np.float64)[:m]
-    for a in range(0, n, _CHUNK):
-        b = min(n, a + _CHUNK)
-        t = vols.gather(inds[a:b], patch_shape, st, quirk=1)
-        if mc:
-            post, pred = model.forward_dropout_device(t, b - a, keep_prob, seed=seed, first_sample=_first_sample + a,
-                                                      want_pred=want_pred)
-            feat = None
-        else:
-            post, pred, feat = model.forward_device(t, b - a, want_pred, want_feat)
+    for a, b, post, pred, feat in _eval_passes(model, sess, img_dat, inds, patch_shape, batch_size, stats, (keep_prob, mc, seed),
+                                               want_pred, want_feat, _vols, _first_sample):
         posts[a:b] = post[1].cpu().numpy()
         if want_pred:
             preds[a:b] = pred.cpu().numpy()

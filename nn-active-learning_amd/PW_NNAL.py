@@ -1,6 +1,7 @@
-"""Patch-wise query strategies of the scored path (reference: PW_NNAL.py): `entropy` and `fi`
-branches of CNN_query / query_multimg, the uncertainty filters and gen_A_matrices, with the
-reference's signatures.  `sess` is a device.DeviceSession, `model` a device.DeviceModel."""
+"""Patch-wise query strategies of the scored path (reference: PW_NNAL.py): the branches of CNN_query / query_multimg,
+the uncertainty filters and gen_A_matrices, with the reference's signatures.  `sess` is a device.DeviceSession, `model` a device.DeviceModel."""
+from collections import OrderedDict
+
 import numpy as np
 
 from . import NNAL_tools, PW_NN, patch_utils
@@ -32,23 +33,19 @@ def device_uncertainty_filter(sess, posts, B, with_keys=False):
     return out
 
 
-def bin_uncertainty_filter_multimg(expr, model, sess, all_padded_imgs, pool_inds, B, x_feed_dict={}, _vols=None):
-    """PW_NNAL.py:684-736: posteriors of every subject's pool voxels (per-subject stats from
-    expr.train_stats), then the B most uncertain over the concatenation, split back per subject.
-
-    Under torch.distributed (one process per GPU, volumes replicated) every rank evaluates one contiguous block of the
-    concatenated pool (pool_shard.work_block) and the posterior vector is assembled on every rank by one all-reduce of
-    owner-filled entries (pool_shard.allgather_rows: x + 0.0 is exact), after which this function continues exactly as
-    in one process - per-patch results do not depend on how the pool is cut into device passes."""
+def pool_posteriors_device(expr, model, sess, all_padded_imgs, pool_inds, x_feed_dict={}, _vols=None):
+    """The device sweep of bin_uncertainty_filter_multimg: the class-1 posteriors of THIS rank's block [a, b) of the
+    concatenated pool (pool_shard.work_block; everything in one process) as a float32 device tensor, in concatenated
+    subject order, per-subject stats from expr.train_stats, batch_eval's gather and passes.  Returns (a, b, p1).
+    `_vols`: a dict subject -> patch_utils.DeviceVolumes the caller keeps across calls (filled on first use)."""
     from . import pool_shard
-    s = len(pool_inds)
     sizes = [len(p) for p in pool_inds]
     m = len(all_padded_imgs[0]) - 1
     n = int(np.sum(sizes))
     a, b = pool_shard.work_block(n)
-    allp = np.zeros(n)
+    p1 = sess.empty((b - a,), sess.torch.float32)
     off = 0
-    for i in range(s):
+    for i in range(len(pool_inds)):
         lo, hi = max(a, off) - off, min(b, off + sizes[i]) - off      # this rank's part of subject i, local positions
         if hi > lo:
             stats = [[expr.train_stats[i, 2 * j], expr.train_stats[i, 2 * j + 1]] for j in range(m)]
@@ -57,12 +54,30 @@ def bin_uncertainty_filter_multimg(expr, model, sess, all_padded_imgs, pool_inds
                 if i not in _vols:
                     _vols[i] = patch_utils.DeviceVolumes(sess, all_padded_imgs[i][:-1])
                 v = _vols[i]
-            allp[off + lo:off + hi] = PW_NN.batch_eval(model, sess, all_padded_imgs[i][:-1], np.asarray(pool_inds[i])[lo:hi],
-                                                       expr.pars['patch_shape'], expr.pars['ntb'], stats,
-                                                       'posteriors', None, x_feed_dict, _vols=v, _first_sample=off + lo)[0]
+            PW_NN.posteriors_device(model, sess, all_padded_imgs[i][:-1], np.asarray(pool_inds[i])[lo:hi], expr.pars['patch_shape'],
+                                    expr.pars['ntb'], stats, x_feed_dict, _vols=v, _first_sample=off + lo,
+                                    out=p1[off + lo - a:off + hi - a])
         elif sizes[i] > 0:
             PW_NN.mc_dropout_args(model, x_feed_dict)       # another rank's subject: keep the RNG streams in step
         off += sizes[i]
+    return a, b, p1
+
+
+def bin_uncertainty_filter_multimg(expr, model, sess, all_padded_imgs, pool_inds, B, x_feed_dict={}, _vols=None):
+    """PW_NNAL.py:684-736: posteriors of every subject's pool voxels (per-subject stats from
+    expr.train_stats), then the B most uncertain over the concatenation, split back per subject.
+
+    Under torch.distributed (one process per GPU, volumes replicated) every rank evaluates one contiguous block of the
+    concatenated pool (pool_shard.work_block, pool_posteriors_device) and the posterior vector is assembled on every rank by
+    one all-reduce of owner-filled entries (pool_shard.allgather_rows: x + 0.0 is exact), after which this function
+    continues exactly as in one process - per-patch results do not depend on how the pool is cut into device passes."""
+    from . import pool_shard
+    s = len(pool_inds)
+    sizes = [len(p) for p in pool_inds]
+    n = int(np.sum(sizes))
+    a, b, p1 = pool_posteriors_device(expr, model, sess, all_padded_imgs, pool_inds, x_feed_dict, _vols)
+    allp = np.zeros(n)
+    allp[a:b] = p1.cpu().numpy()
     if (a, b) != (0, n):
         allp = pool_shard.allgather_rows(n, np.arange(a, b), allp[a:b], sess)
     if len(x_feed_dict) > 0:
@@ -329,9 +344,86 @@ def core_set_query(expr, model, sess, all_padded_imgs, pool_inds, labeled_inds):
     return patch_utils.global2local_inds(Q, sizes)
 
 
+def committee_holder(expr, model, sess):
+    """`expr.model_holder` (PW_AL.py:780-790), or - for a caller that has none - a net built once like `model` (layer dict,
+    input shape, skips, dropout, max_batch, optimiser, grad_layers) on the same session and cached on `expr`."""
+    holder = getattr(expr, 'model_holder', None)
+    if holder is None:
+        from .device import DeviceModel
+        drop = [list(model.dropout_layers), model.dropout_rate] if len(model.dropout_layers) else None
+        holder = DeviceModel(sess, model.layer_dict, model.in_shape, model.skips, model.feature_idx, drop, model.max_batch,
+                             name=model.name + '_holder')
+        if model._opt is not None:
+            holder.get_optimizer(model._opt['lr'], model.train_layers, model._opt['name'])
+        if len(model.grad_layers):
+            holder.get_gradients(model.grad_layers)
+        expr.model_holder = holder
+    return holder
+
+
+def committee_query(expr, model, sess, all_padded_imgs, pool_inds, labeled_inds, method_name):
+    """query_multimg 'ensemble' and 'QBC-JS' (PW_NNAL.py:453-545).  M = len(expr.pretrained_paths) members, evaluated in
+    order i = 0 .. M-1 on `expr.model_holder` (the main `model` is not touched): with no labels yet, member i is the weights
+    file pretrained_paths[i]; otherwise every member starts from expr.prev_weights_path and is fine-tuned once by
+    finetune_multimg (members differ through the NumPy stream only).  Each member's class-1 posteriors of the pool
+    (bin_uncertainty_filter_multimg's device sweep at keep_prob 1, no host copy) update the float64 running means on the
+    device (alq_committee_update, one launch per member); the keys of the last member go to the device top-k:
+    ensemble argsort(|av - .5|), QBC-JS argsort(-(ent(av) - avH)), ties -> lower pool position.
+
+    The reference is broken in three places; resolved by its evident intent:
+      1. expr.prev_weights_path is never set: it is the current model (PW_AL.py:834-843), `curr_weights_<iters>` in
+         PW_AL.Experiment_MultiImg.run_method; a caller without one gets `model`'s current weights.
+      2. run_method creates model_holder / pretrained_paths for 'ensemble' only: here both methods have them.
+      3. pretrained_paths is a hard-coded file-server list: it comes from pars['pretrained_paths'] (ValueError without it).
+    Under torch.distributed each rank sweeps its pool_shard.work_block; the keys are assembled exactly
+    (pool_shard.allgather_rows) and every rank runs the same top-k.  Fine-tuning is replicated on every rank."""
+    from . import PW_AL, pool_shard
+    torch = sess.torch
+    if model.nclass != 2:
+        raise ValueError("query method %r: the committee formulas are binary (PW_NNAL.py:453-545), the net has %d classes"
+                         % (method_name, model.nclass))
+    paths = getattr(expr, 'pretrained_paths', None)
+    if paths is None:
+        paths = expr.pars.get('pretrained_paths')
+    if not paths:
+        raise ValueError("query method %r needs the committee's weight files in pars['pretrained_paths'] (their number is "
+                         "the committee size)" % (method_name,))
+    k = expr.pars['k']
+    sizes = [len(p) for p in pool_inds]
+    n = int(np.sum(sizes))
+    n_labels = int(np.sum([len(labeled_inds[i]) for i in range(len(labeled_inds))])) if labeled_inds is not None else 0
+    holder = committee_holder(expr, model, sess)
+    mode = 0 if method_name == 'ensemble' else 1
+    start = None
+    if n_labels > 0 and getattr(expr, 'prev_weights_path', None) is None:
+        start = OrderedDict((nme, [np.array(W), np.array(b)]) for nme, (W, b) in model.var_dict.items())
+    dvols = {}                                                  # one upload per subject for all members
+    a, b = pool_shard.work_block(n)
+    mean_p = sess.empty((b - a,), torch.float64)
+    mean_h = sess.empty((b - a,), torch.float64) if mode == 1 else None
+    keys = sess.empty((b - a,), torch.float64)
+    M = len(paths)
+    for i in range(M):
+        if n_labels == 0:
+            holder.perform_assign_ops(paths[i], sess)
+        else:
+            if start is None:
+                holder.perform_assign_ops(expr.prev_weights_path, sess)
+            else:
+                holder.set_weights(start)
+            PW_AL.finetune_multimg(expr, holder, sess, all_padded_imgs, labeled_inds)
+        _, _, p1 = pool_posteriors_device(expr, holder, sess, all_padded_imgs, pool_inds, {holder.keep_prob: 1.}, dvols)
+        sess.committee_update(p1, i, mode, mean_p, mean_h, keys if i == M - 1 else None)
+    if (a, b) != (0, n):
+        K = pool_shard.allgather_rows(n, np.arange(a, b), keys.cpu().numpy(), sess)
+        keys = sess.to_device(K, torch.float64)
+    order = sess.topk_smallest(keys, min(k, n)).cpu().numpy()
+    return patch_utils.global2local_inds(order, sizes)
+
+
 def query_multimg(expr, model, sess, all_padded_imgs, pool_inds, labeled_inds, method_name):
-    """PW_NNAL.query_multimg (PW_NNAL.py:169-629), branches `entropy` (:226-230) and `fi`
-    (:547-627), plus `egl` (image level only in the reference, NNAL.py:234-285; candidates gathered and sharded like
+    """PW_NNAL.query_multimg (PW_NNAL.py:169-629), branches `entropy` (:226-230), `ensemble` / `QBC-JS` (:453-545,
+    committee_query) and `fi` (:547-627), plus `egl` (image level only in the reference, NNAL.py:234-285; candidates gathered and sharded like
     `fi`, the k largest scores over all subjects, ties -> lower candidate first).  Returns, per subject, positions into
     that subject's pool_inds."""
     k = expr.pars['k']
@@ -363,6 +455,8 @@ def query_multimg(expr, model, sess, all_padded_imgs, pool_inds, labeled_inds, m
         else:
             order = np.argsort(-(bin_entropy(mean_p) - mean_h), kind='stable')
         return patch_utils.global2local_inds(order[:k], sizes)
+    if method_name in ('ensemble', 'QBC-JS'):
+        return committee_query(expr, model, sess, all_padded_imgs, pool_inds, labeled_inds, method_name)
     if method_name == 'rep-entropy':
         return rep_entropy_query(expr, model, sess, all_padded_imgs, pool_inds)
     if method_name == 'core-set':
@@ -427,4 +521,5 @@ def query_multimg(expr, model, sess, all_padded_imgs, pool_inds, labeled_inds, m
         draws = NNAL_tools.sample_query_dstr(q_opt, k, replacement=True)
         local = patch_utils.global2local_inds(draws, [len(s) for s in sel_inds])
         return [np.array(sel_inds[i])[local[i]] for i in range(len(sel_inds))]
-    raise NotImplementedError("query method %r is outside the scored path (entropy, fi)" % (method_name,))
+    raise NotImplementedError("query method %r is outside the scored path (random, entropy, MC-entropy, BALD, ensemble, QBC-JS, "
+                              "rep-entropy, core-set, egl, fi)" % (method_name,))

@@ -52,6 +52,7 @@ _SIGNATURES = {
     'alq_param_grads': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_float, C.c_float, C.c_uint64, C.c_int64,
                                   C.POINTER(C.c_int32), C.c_int, C.c_int, _P, _P, _P]),
     'alq_grad_sqnorms': (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
+    'alq_committee_update': (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, _P, _P, _P]),
     'alq_sgd_step': (C.c_int, [_P, _P, _P, C.c_int64, C.c_float]),
     'alq_adam_step': (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int64]),
     'alq_sq_accum': (C.c_int, [_P, _P, C.c_int64, C.c_int, _P]),

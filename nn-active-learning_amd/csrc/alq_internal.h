@@ -59,7 +59,8 @@ struct View {
 enum ProfClass { PROF_IGEMM_FWD = 0, PROF_IGEMM_BWD = 1, PROF_ELEMWISE = 2, PROF_REDUCE = 3,
                  PROF_FC_SMALL = 4, PROF_IGEMM3_FWD = 5, PROF_IGEMM3_BWD = 6, PROF_DIRECT = 7,
                  PROF_IGEMM_F16 = 8 /* igemm4 launches on the fp16x2 split (3 products) */,
-                 PROF_GNORM = 9 /* per-sample weight-gradient norms on fp32 MFMA (gnorm.hip) */, PROF_NUM = 10 };
+                 PROF_GNORM = 9 /* per-sample weight-gradient norms on fp32 MFMA (gnorm.hip) */,
+                 PROF_COMMITTEE = 10 /* committee running means and keys (committee.hip) */, PROF_NUM = 11 };
 
 struct ProfSlot {
     double ms = 0;
@@ -665,5 +666,9 @@ int k_gnorm_weight(alq_ctx *, const View &U, const View &V, const int k[3], cons
                    double *d_sq, int ld, int col);
 int k_gnorm_bias(alq_ctx *, const View &delta, int N, double *d_sq, int ld, int col);
 int k_gnorm_fc(alq_ctx *, const float *delta, int nout, const View &a, int N, double *d_sq, int ld, int col);
+
+// ------------------------------------------------------------------ committee statistics (committee.hip)
+int committee_update_impl(alq_ctx *, const float *d_p1, int64_t n, int member, int mode, double *d_mean_p, double *d_mean_h,
+                          double *d_keys);
 
 }  // namespace alq

@@ -2241,6 +2241,18 @@ int alq_score_entropy(alq_ctx *ctx, const float *d_p1, int64_t n, double *d_absd
     return score_entropy_impl(ctx, d_p1, n, d_absdev, d_H);
 }
 
+int alq_committee_update(alq_ctx *ctx, const float *d_p1, int64_t n, int member, int mode, double *d_mean_p, double *d_mean_h,
+                         double *d_keys) {
+    ALQ_REQUIRE(ctx && n >= 0 && member >= 0, ALQ_EINVAL, "alq_committee_update: bad argument (n=%lld member=%d)", (long long)n,
+                member);
+    ALQ_REQUIRE(mode == ALQ_COMMITTEE_ENSEMBLE || mode == ALQ_COMMITTEE_QBC_JS, ALQ_EINVAL, "alq_committee_update: mode %d", mode);
+    ALQ_REQUIRE(n == 0 || (d_p1 && d_mean_p && (mode == ALQ_COMMITTEE_ENSEMBLE || d_mean_h)), ALQ_EINVAL,
+                "alq_committee_update: null argument");
+    if (n == 0) return ALQ_OK;
+    ALQ_HIP(hipSetDevice(ctx->device));
+    return committee_update_impl(ctx, d_p1, n, member, mode, d_mean_p, d_mean_h, d_keys);
+}
+
 size_t alq_topk_work_bytes(int64_t n) { return topk_work_bytes_impl(n); }
 
 int alq_topk_uncertain(alq_ctx *ctx, const double *d_keys, int64_t n, int64_t B, int64_t *d_out_idx, void *d_work) {
@@ -2325,7 +2337,8 @@ int alq_topk_merge(const double *h_keys, const int64_t *h_idx, int64_t n, int64_
 }
 
 static const char *kProfNames[PROF_NUM] = {"igemm_fwd", "igemm_bwd", "elementwise", "reduce", "fc_small",
-                                           "igemm3_fwd", "igemm3_bwd", "direct_conv", "igemm_f16x2", "gnorm"};
+                                           "igemm3_fwd", "igemm3_bwd", "direct_conv", "igemm_f16x2", "gnorm",
+                                           "committee"};
 
 int alq_prof_enable(alq_ctx *ctx, int on) {
     ALQ_REQUIRE(ctx != nullptr, ALQ_EINVAL, "null ctx");

@@ -1,4 +1,4 @@
-// Top-B "most uncertain" selection = full ascending sort of (|p-0.5| as fp64 bits, index) pairs
+// Top-B "most uncertain" selection = full ascending sort of (|p-0.5| as order-preserving fp64 bits, index) pairs
 // with a bitonic network (replaces np.argsort(np.abs(posts-.5))[:B], PW_NNAL.py:64,109,730).
 // The index is part of the sort key, so equal scores come out in ascending index order
 // whatever the network does (the tie rule this build defines; numpy's default sort is unstable).
@@ -31,7 +31,10 @@ __global__ void topk_init_kernel(const double *keys, long long n, long long P, K
          i += (long long)gridDim.x * blockDim.x) {
         KeyIdx e;
         if (i < n) {
-            e.key = (unsigned long long)__double_as_longlong(keys[i]);   // keys are >= 0: bits are monotone
+            // numeric order as unsigned bits: a key with the sign bit clear keeps its bits above every negative one
+            // (so keys >= 0 compare exactly as their raw bits did), a negative key has its bits inverted
+            const unsigned long long u = (unsigned long long)__double_as_longlong(keys[i]);
+            e.key = (u >> 63) ? ~u : (u | (1ull << 63));
             e.idx = (unsigned long long)i;
         } else {
             e.key = ~0ull;

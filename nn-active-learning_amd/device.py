@@ -108,8 +108,8 @@ class DeviceSession(object):
         return device_uncertainty_filter(self, posts, B, with_keys)
 
     def topk_smallest(self, keys, B):
-        """Positions of the B smallest entries of a float64 device vector, ascending, ties -> lower position (bit-pattern
-        order: +inf and NaN come last)."""
+        """Positions of the B smallest entries of a float64 device vector, ascending, ties -> lower position (numeric order
+        for either sign, -0.0 before +0.0; +inf and a NaN with the sign bit clear come last)."""
         torch = self.torch
         self.bind_stream()
         n = int(keys.numel())
@@ -118,6 +118,20 @@ class DeviceSession(object):
         check(self.lib.alq_topk_uncertain(self._ctx, C.c_void_p(keys.data_ptr()), n, int(B), C.c_void_p(out.data_ptr()),
                                           C.c_void_p(work.data_ptr())))
         return out
+
+    def committee_update(self, p1, member, mode, mean_p, mean_h=None, keys=None):
+        """alq_committee_update: member `member` (0-based, in order) of the ensemble (mode 0) or QBC-JS (mode 1) committee,
+        p1 = its class-1 posteriors (float32 device [n]); updates the float64 device running means mean_p (and mean_h,
+        QBC-JS) in place and, when `keys` is given, writes the float64 top-k keys for topk_smallest into it."""
+        torch = self.torch
+        self.bind_stream()
+        n = int(p1.numel())
+        for t, dt in ((p1, torch.float32), (mean_p, torch.float64), (mean_h, torch.float64), (keys, torch.float64)):
+            assert t is None or (t.dtype == dt and t.is_contiguous() and int(t.numel()) == n and t.device == self.device)
+
+        def ptr(t):
+            return C.c_void_p(t.data_ptr()) if t is not None else None
+        check(self.lib.alq_committee_update(self._ctx, ptr(p1), n, int(member), int(mode), ptr(mean_p), ptr(mean_h), ptr(keys)))
 
     # -- RCCL communicator of the sharded pool (pool_shard.attach_comm) --------------------
     def comm_unique_id(self):
