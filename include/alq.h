@@ -148,6 +148,25 @@ int alq_topk_uncertain(alq_ctx *ctx, const double *d_keys, int64_t n, int64_t B,
 int alq_committee_update(alq_ctx *ctx, const float *d_p1, int64_t n, int member, int mode, double *d_mean_p,
                          double *d_mean_h, double *d_keys);
 
+/* Replaces: PW_analyze_results.get_preds_stats (PW_analyze_results.py:234-258) on the predictions of one chunk of evaluated
+ * voxels - what Experiment_MultiImg.test_eval (PW_AL.py:653-668), full_model_eval (PW_analyze_results.py:649-651) and
+ * grid_based_F1 (:794-795) call it on after copying every PW_NN.batch_eval(..., 'prediction') vector to the host - and the
+ * scatter `preds[:, :, ind] = slice_evals` / np.uint8(preds) of full_model_eval (:613-625, :663-665).
+ * d_pred: int64 [n] as alq_forward writes it; d_inds: int64 [n] raveled UN-padded voxel indices (those of
+ * alq_gather_normalize) into d_mask, the subject's un-padded mask volume of mask_elems elements, float or double
+ * (mask_is_f64 = 1), resident on the device; it may hold NaN.  The label of sample i is mask[d_inds[i]]; d_inds NULL: d_mask
+ * is already the label vector (n <= mask_elems), as with the labels of gen_multimg_inds (PW_AL.py:921-975).
+ * d_counts: int64 [6] = P, N, TP, FP, TN, FN; the call ADDS to them (the caller zeroes them; they stay on the device over all
+ * chunks and subjects): P += mask > 0, N += mask == 0, TP += pred > 0 && mask > 0, FP += pred > 0 && mask == 0,
+ * TN += pred == 0 && mask == 0, FN += pred == 0 && mask > 0 - a NaN or a negative label counts nowhere, as in NumPy.
+ * d_seg (optional): uint8 un-padded volume, d_seg[d_inds[i]] = pred[i] (d_seg[i] without indices; distinct indices);
+ * other bytes are left alone.  Integer sums: exact and bit-identical whatever the chunking, the grid or the launch order.
+ * An index outside [0, mask_elems) is skipped on the device (nothing read, written or counted for it) and the call returns
+ * ALQ_EINVAL: with d_inds the call therefore synchronises the stream (one 4-byte flag read); without, it does not.
+ * n = 0: nothing is done.                                                                                                   */
+int alq_eval_counts(alq_ctx *ctx, const int64_t *d_pred, const int64_t *d_inds, int64_t n, const void *d_mask,
+                    int mask_is_f64, int64_t mask_elems, int64_t *d_counts, uint8_t *d_seg);
+
 /* Multi-GPU top-B merge step (no reference counterpart: the reference is one process).
  * Host function: merges the candidate (key, GLOBAL index) pairs gathered from all ranks
  * (torch.distributed all_gather over RCCL in pool_shard.merge_topB; entries with index < 0 are padding)

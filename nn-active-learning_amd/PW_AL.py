@@ -319,6 +319,66 @@ class Experiment_MultiImg(Experiment):
         if self.train_stats.ndim == 1:                           # one subject: savetxt dropped the dimension (:626-631)
             self.train_stats = np.expand_dims(self.train_stats, axis=0)
         self.model_factory = None     # callable(expr, input_shape, sess) -> model for nets other than the reference's 'PW'
+        if len(test_paths) > 0:       # the subjects of test_eval (the reference drops the argument and has callers set the attribute)
+            self.test_paths = test_paths
+
+    def test_eval(self, model, sess, test_inds=[], test_labels=[]):
+        """PW_AL.py:639-677: F1 of `model` over the grid voxels of self.test_paths (gen_multimg_inds at
+        pars['grid_spacing'] unless indices and labels are given), per-subject stats self.test_stats[i, 2j], [i, 2j+1] (as the
+        reference's test_eval reads them; get_stats stores at j*m: the two agree for one or two modalities), P / TP / FP
+        summed over the subjects.  Returns (F1, the LAST subject's predictions as a float64 array).
+
+        The predictions of every chunk are counted on the device against the labels (alq_eval_counts, through
+        PW_analyze_results.eval_counts_device): 48 bytes per subject reach the host, plus the last subject's predictions,
+        which the reference returns - taken from the same pass.  Under torch.distributed every rank evaluates its
+        pool_shard.work_block of the concatenated test voxels; the counts are summed over the ranks (integers below 2^53:
+        exact in float64) and the last subject's predictions assembled with pool_shard.allgather_rows of owner-filled
+        entries, so every rank returns the same values.  self.test_counts keeps the per-subject [s, 6] totals (P, N, TP,
+        FP, TN, FN) of the last call."""
+        from . import PW_analyze_results, pool_shard
+        torch = sess.torch
+        m = len(self.test_paths[0]) - 1
+        if len(test_inds) == 0:
+            test_inds, test_labels = gen_multimg_inds(self.test_paths, self.pars['grid_spacing'])
+        s = len(test_inds)
+        sizes = [len(t) for t in test_inds]
+        n = int(np.sum(sizes))
+        _, ws = pool_shard.world()
+        a, b = pool_shard.work_block(n)
+        counts = sess.to_device(np.zeros((s, 6), dtype=np.int64), torch.int64)
+        last = np.zeros(sizes[-1])
+        last_lo, last_hi = 0, 0
+        off = 0
+        for i in range(s):
+            lo, hi = max(a, off) - off, min(b, off + sizes[i]) - off      # this rank's part of subject i, local positions
+            if hi > lo:
+                stats = []
+                for j in range(m):
+                    stats += [[self.test_stats[i, 2 * j], self.test_stats[i, 2 * j + 1]]]
+                preds = sess.empty((hi - lo,), torch.int64) if i == s - 1 else None
+                PW_analyze_results.eval_counts_device(
+                    model, sess, self.test_paths[i][:-1], np.asarray(test_inds[i], dtype=np.int64)[lo:hi], self.pars['patch_shape'],
+                    self.pars['ntb'], stats, np.asarray(test_labels[i], dtype=np.float64)[lo:hi], _counts=counts[i], _preds=preds)
+                if preds is not None:
+                    last[lo:hi] = preds.cpu().numpy()
+                    last_lo, last_hi = lo, hi
+            off += sizes[i]
+        C = counts.cpu().numpy().astype(np.float64)
+        if ws > 1:
+            C = pool_shard.allreduce_sum(C, sess)
+            last = pool_shard.allgather_rows(sizes[-1], np.arange(last_lo, last_hi), last[last_lo:last_hi], sess)
+        self.test_counts = C
+        test_preds = last
+        tP, tTP, tFP = 0, 0, 0
+        for i in range(s):
+            P, N, TP, FP, TN, FN = [float(v) for v in C[i]]
+            tP += P
+            tTP += TP
+            tFP += FP
+        # compute total Pr/Rc and F1; F1 = 0 where the reference's float divisions raise ZeroDivisionError (no predicted
+        # positives, or no positives at all): its own `Pr>0 and Rc>0` fallback - a one-class model must not abort a curve
+        F1 = PW_analyze_results._f1_or_zero(tP, tTP, tFP)
+        return F1, test_preds
 
     def add_method(self, method_name):
         from . import pool_shard

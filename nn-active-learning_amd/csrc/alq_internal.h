@@ -60,7 +60,8 @@ enum ProfClass { PROF_IGEMM_FWD = 0, PROF_IGEMM_BWD = 1, PROF_ELEMWISE = 2, PROF
                  PROF_FC_SMALL = 4, PROF_IGEMM3_FWD = 5, PROF_IGEMM3_BWD = 6, PROF_DIRECT = 7,
                  PROF_IGEMM_F16 = 8 /* igemm4 launches on the fp16x2 split (3 products) */,
                  PROF_GNORM = 9 /* per-sample weight-gradient norms on fp32 MFMA (gnorm.hip) */,
-                 PROF_COMMITTEE = 10 /* committee running means and keys (committee.hip) */, PROF_NUM = 11 };
+                 PROF_COMMITTEE = 10 /* committee running means and keys (committee.hip) */,
+                 PROF_EVAL = 11 /* confusion counts of a test-set evaluation (evalcounts.hip) */, PROF_NUM = 12 };
 
 struct ProfSlot {
     double ms = 0;
@@ -90,6 +91,7 @@ struct ProfSlot {
 #endif
 
 #define ALQ_PARAM_BLOCK_BYTES 512
+#define ALQ_PARAM_FLAG_OFFSET (ALQ_PARAM_BLOCK_BYTES - 8)   // last word of the block: the bad-index flag of alq_eval_counts
 
 struct alq_ctx {
     int device = 0;
@@ -670,5 +672,9 @@ int k_gnorm_fc(alq_ctx *, const float *delta, int nout, const View &a, int N, do
 // ------------------------------------------------------------------ committee statistics (committee.hip)
 int committee_update_impl(alq_ctx *, const float *d_p1, int64_t n, int member, int mode, double *d_mean_p, double *d_mean_h,
                           double *d_keys);
+
+// ------------------------------------------------------------------ confusion counts of an evaluation (evalcounts.hip)
+int eval_counts_impl(alq_ctx *, const int64_t *d_pred, const int64_t *d_inds, int64_t n, const void *d_mask, int mask_is_f64,
+                     int64_t mask_elems, int64_t *d_counts, uint8_t *d_seg, int *d_bad);
 
 }  // namespace alq

@@ -2206,7 +2206,7 @@ int alq_gather_normalize(alq_ctx *ctx, const void *const *d_vols, int mm, int vo
         hb.ptrs[j] = d_vols[j];
         if (h_stats) { hb.stats[2 * j] = h_stats[2 * j]; hb.stats[2 * j + 1] = h_stats[2 * j + 1]; }
     }
-    static_assert(sizeof(Block) <= ALQ_PARAM_BLOCK_BYTES, "parameter block too small");
+    static_assert(sizeof(Block) <= ALQ_PARAM_FLAG_OFFSET, "parameter block too small");
     Block *db = reinterpret_cast<Block *>(ctx->param_block);
     // pageable source: the copy is staged before the call returns, and it is stream-ordered
     // behind any kernel of an earlier call that still reads the block
@@ -2251,6 +2251,28 @@ int alq_committee_update(alq_ctx *ctx, const float *d_p1, int64_t n, int member,
     if (n == 0) return ALQ_OK;
     ALQ_HIP(hipSetDevice(ctx->device));
     return committee_update_impl(ctx, d_p1, n, member, mode, d_mean_p, d_mean_h, d_keys);
+}
+
+int alq_eval_counts(alq_ctx *ctx, const int64_t *d_pred, const int64_t *d_inds, int64_t n, const void *d_mask, int mask_is_f64,
+                    int64_t mask_elems, int64_t *d_counts, uint8_t *d_seg) {
+    ALQ_REQUIRE(ctx && n >= 0 && mask_elems >= 0, ALQ_EINVAL, "alq_eval_counts: bad argument (n=%lld mask_elems=%lld)", (long long)n,
+                (long long)mask_elems);
+    ALQ_REQUIRE(n == 0 || (d_pred && d_mask && d_counts), ALQ_EINVAL, "alq_eval_counts: null argument");
+    ALQ_REQUIRE(d_inds || n <= mask_elems, ALQ_EINVAL, "alq_eval_counts: %lld samples, a label vector of %lld", (long long)n,
+                (long long)mask_elems);
+    if (n == 0) return ALQ_OK;
+    ALQ_HIP(hipSetDevice(ctx->device));
+    int *d_bad = reinterpret_cast<int *>(static_cast<char *>(ctx->param_block) + ALQ_PARAM_FLAG_OFFSET);
+    if (d_inds) ALQ_HIP(hipMemsetAsync(d_bad, 0, sizeof(int), ctx->stream));
+    ALQ_TRY(eval_counts_impl(ctx, d_pred, d_inds, n, d_mask, mask_is_f64, mask_elems, d_counts, d_seg, d_bad));
+    if (d_inds) {
+        // the indices live on the device: the kernel skipped any outside the volume and raised the flag
+        int bad = 0;
+        ALQ_HIP(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        ALQ_HIP(hipStreamSynchronize(ctx->stream));
+        ALQ_REQUIRE(!bad, ALQ_EINVAL, "alq_eval_counts: an index outside [0, %lld)", (long long)mask_elems);
+    }
+    return ALQ_OK;
 }
 
 size_t alq_topk_work_bytes(int64_t n) { return topk_work_bytes_impl(n); }
@@ -2338,7 +2360,7 @@ int alq_topk_merge(const double *h_keys, const int64_t *h_idx, int64_t n, int64_
 
 static const char *kProfNames[PROF_NUM] = {"igemm_fwd", "igemm_bwd", "elementwise", "reduce", "fc_small",
                                            "igemm3_fwd", "igemm3_bwd", "direct_conv", "igemm_f16x2", "gnorm",
-                                           "committee"};
+                                           "committee", "eval"};
 
 int alq_prof_enable(alq_ctx *ctx, int on) {
     ALQ_REQUIRE(ctx != nullptr, ALQ_EINVAL, "null ctx");

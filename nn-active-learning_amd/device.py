@@ -133,6 +133,28 @@ class DeviceSession(object):
             return C.c_void_p(t.data_ptr()) if t is not None else None
         check(self.lib.alq_committee_update(self._ctx, ptr(p1), n, int(member), int(mode), ptr(mean_p), ptr(mean_h), ptr(keys)))
 
+    def eval_counts(self, pred, inds, mask, counts, seg=None):
+        """alq_eval_counts: adds the confusion counts (P, N, TP, FP, TN, FN; get_preds_stats) of the predictions `pred` (int64
+        device [n]) against the labels mask[inds] - `mask` the subject's un-padded mask volume on the device (float32 or
+        float64, NaN = ignored), `inds` int64 device [n] raveled indices into it, or None when `mask` is the label vector
+        itself - to the int64 device totals `counts` [6]; with `seg` (uint8 device, the mask's size) also seg[inds] = pred."""
+        torch = self.torch
+        self.bind_stream()
+        n = int(pred.numel())
+        assert mask.dtype in (torch.float32, torch.float64) and mask.is_contiguous() and mask.device == self.device
+        assert counts.dtype == torch.int64 and counts.is_contiguous() and int(counts.numel()) == 6 and counts.device == self.device
+        for t, dt in ((pred, torch.int64), (inds, torch.int64)):
+            assert t is None or (t.dtype == dt and t.is_contiguous() and int(t.numel()) == n and t.device == self.device)
+        elems = int(mask.numel())
+        assert inds is not None or elems >= n
+        assert seg is None or (seg.dtype == torch.uint8 and seg.is_contiguous() and seg.device == self.device and
+                               int(seg.numel()) >= (elems if inds is not None else n))
+
+        def ptr(t):
+            return C.c_void_p(t.data_ptr()) if t is not None else None
+        check(self.lib.alq_eval_counts(self._ctx, ptr(pred), ptr(inds), n, ptr(mask), 1 if mask.dtype == torch.float64 else 0,
+                                       elems, ptr(counts), ptr(seg)))
+
     # -- RCCL communicator of the sharded pool (pool_shard.attach_comm) --------------------
     def comm_unique_id(self):
         buf = C.create_string_buffer(128)
