@@ -87,6 +87,23 @@ int alq_model_layer_out_elems(const alq_model *m, int layer_idx, int64_t *elems)
  * reference's flatten order (full axis reversal, NN.py:296-301); bias [Co] / [out,1].
  * Synchronises the stream before returning (the host buffers may be reused at once).         */
 int alq_model_set_weights(alq_model *m, int t, const float *h_W, const float *h_b);
+/* Same contract as alq_model_set_weights, but d_W / d_b are DEVICE pointers (TF layouts, fp32, any 4-byte alignment), e.g. slices
+ * of the flat parameter vector that alq_sgd_step / alq_adam_step just updated: the model ends up in the state the host call
+ * would have left with the same values, and every entry point returns the same bits.  Stream-ordered on the context's stream:
+ * the buffers must be ready there (a producer on another stream: order it with an event first).
+ * A wide fully connected layer - forward and backward Gemm both on the streaming GEMM of csrc/fcgemm.hip: inputs and units
+ * multiples of 64, both >= 256 (alq_model_layer_packs_on_device) - is packed by HIP kernels (csrc/wpack.hip): flatten
+ * permutation, bf16 triples and fp16 pairs of both Gemm orientations, the layer's L1 bound.  No weight element of such a layer
+ * crosses to the host; the call reads back 16 bytes (at most 64 by contract) for the host-side scalars - the bound and the
+ * fp16 scale exponent - and synchronises the stream for that.  Its raw fp32 weights stay resident; the forms of the engines
+ * that only the debug knobs select behind the streaming GEMM are packed from them on the host when a call first needs them.
+ * Any other layer (conv / conv_transpose engines, the two-class head, narrow fc layers) is not an error: its slice is copied to
+ * the host and goes through alq_model_set_weights.  Works before any host call (first-call allocations).
+ * ALQ_EINVAL: null pointer, no parameterised layer t.                                                                     */
+int alq_model_set_weights_device(alq_model *m, int t, const float *d_W, const float *d_b);
+/* 1 when alq_model_set_weights_device packs parameterised layer t with the device kernels, 0 when it takes the host packers;
+ * negative error code for a bad t.                                                                                        */
+int alq_model_layer_packs_on_device(const alq_model *m, int t);
 
 /* ---- patch gather + normalisation ------------------------------------------------------- */
 /* Replaces: patch_utils.get_patches (patch_utils.py:1087-1173) + the normalisation loops of
@@ -334,7 +351,9 @@ int alq_prof_read(alq_ctx *ctx, int cls, double *ms, int64_t *launches, double *
  * (after the ReLU mask), 2 = channel-sum field of the layer's INPUT [N, vox_in], 3 = channel-sum
  * field of its masked cotangent [N, vox_out], 4 = the unit-cotangent layer sums S [N, L] (as
  * float; layer_idx ignored), 5 = the fused fc head's logit-difference partials [N, tiles * 4] (one per
- * (tile, wave) of the last conv's launch).  *elems_out receives the element count.  Tests only.  */
+ * (tile, wave) of the last conv's launch); of a wide fc layer (streaming GEMM), as raw bytes in 4-byte words: 6 / 7 = the packed
+ * bf16 triples / fp16 pairs of its forward Gemm, 8 / 9 = of its backward Gemm, 10 = 4 words: the fp16 scale exponents of the
+ * forward and the backward plan and the bits of the layer's fp64 L1 bound (N ignored).  *elems_out receives the element count.  Tests only.  */
 int alq_model_debug_copy(alq_model *m, int layer_idx, int what, int N, float *d_out,
                          int64_t *elems_out);
 
@@ -360,6 +379,8 @@ int alq_debug_set(int key, int value);
  * dec1 on the plane-sweep kernel of csrc/d3d.hip, 11: the same for its backward-data launch, 12: 1 when the last forward pass
  * ran enc2 and the max-pool behind it as one launch (csrc/f3d.hip), 13: which form of the head conv's backward kernel the last backward
  * pass ran (csrc/c3d.hip): 7 = the 27 taps packed into 7 k-steps (default), 8 / 4 = the 9-k-step kernel (ALQ_C3D_BWD_ROWS), 0 = none.
+ * 14: the number of weight elements that went through the HOST packers since the model was created (alq_model_set_weights, the
+ * per-layer fall-back of alq_model_set_weights_device and the lazy forms behind the debug knobs); saturates at 2^31 - 1.
  * Returns the answer or a negative error code.  */
 int alq_model_engine_info(alq_model *m, int what);
 

@@ -37,6 +37,8 @@ _SIGNATURES = {
     'alq_model_param_sizes': (C.c_int, [_P, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'alq_model_layer_out_elems': (C.c_int, [_P, C.c_int, C.POINTER(C.c_int64)]),
     'alq_model_set_weights': (C.c_int, [_P, C.c_int, _P, _P]),
+    'alq_model_set_weights_device': (C.c_int, [_P, C.c_int, _P, _P]),
+    'alq_model_layer_packs_on_device': (C.c_int, [_P, C.c_int]),
     'alq_gather_normalize': (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.POINTER(C.c_int64), _P, C.c_int64,
                                        C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int, C.c_int, _P]),
     'alq_forward': (C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.c_int]),

@@ -574,6 +574,12 @@ void fcgemm_pack_weights_f16(FcGemmPlan *plan, const std::vector<float> &Bmat /*
 int fcgemm_launch(alq_ctx *ctx, const FcGemmPlan &plan, const View &in, const View &out, const float *bias, int relu,
                   int M, int prof_cls, float in_bound = 0.f, unsigned *row_amax = nullptr);
 
+// Device-side packers of a wide fc layer's weights (wpack.hip; alq_model_set_weights_device).  d_scal: 16 bytes, [0, 8) the bits of
+// max_f sum_o |W[o][f]| (fp64), [8, 12) the bits of max |W| (fp32): wpack_stats writes them, wpack_fc reads the second
+int wpack_stats(alq_ctx *ctx, const float *d_W, int Co, long long F, void *d_scal);
+int wpack_permute(alq_ctx *ctx, const float *d_W, float *d_Wp, int Co, int D, int H, int Wd, int C);      // Wp[o][f_mem] = W[o][f_tf]
+int wpack_fc(alq_ctx *ctx, const float *d_Wp, long long ld, int K, int N, int kmajor, void *d_W3, void *d_W16, const void *d_scal);
+
 // one contraction = general plan + (when eligible) pipelined plan / direct first-layer plan
 struct Gemm {
     IgemmPlan p1;

@@ -59,6 +59,11 @@ struct Layer {
     Gemm bwd;
     bool has_bwd = false;
     bool weights_set = false;
+    // wide fc layer packed on the device (alq_model_set_weights_device): the raw fp32 weights stay resident in activation-memory
+    // order [o][f_mem]; the forms only the debug knobs select (igemm / igemm2 / igemm3 behind the streaming GEMM) are packed from
+    // them on the host when a call first needs them (refresh_fallback_forms)
+    float *d_Wres = nullptr;
+    bool fallback_stale = false;
     // workspaces
     uint8_t *argmax = nullptr;
     float *asum = nullptr, *dsum = nullptr;
@@ -175,6 +180,8 @@ struct alq_model {
     int no_t3d = 0;                // ALQ_NO_T3D (A/B): conv_transpose launches on the two-slot engine (igemm4) as in round 4
     int last_t3f = 0, last_t3b = 0;   // conv_transpose launches of the last forward / backward pass that ran on the row-sweep engine
     bool last_f16_derived = false; // the last forward pass ran a launch on the fp16x2 split with derived input bounds
+    int64_t host_pack_elems = 0;   // weight elements that went through the host packers since the model was created (engine info 14)
+    void *d_wscal = nullptr;       // 16 bytes: the scalars of the device packers (wpack.hip)
 
     template <typename T>
     int dalloc(T **p, size_t count) {
@@ -305,9 +312,10 @@ static int set4(alq_model *m, Igemm4Plan *p4, const std::vector<float> &Bmat) {
     return ALQ_OK;
 }
 
-static int gemm_set(alq_model *m, Gemm *g, const std::vector<float> &Bmat) {
-    if (g->p4.ok) ALQ_TRY(set4(m, &g->p4, Bmat));
-    if (g->pfc.ok) {
+// parts: 1 = the streaming GEMM's forms of a wide fc layer (pfc), 2 = every other engine's
+static int gemm_set(alq_model *m, Gemm *g, const std::vector<float> &Bmat, int parts = 3) {
+    if ((parts & 2) && g->p4.ok) ALQ_TRY(set4(m, &g->p4, Bmat));
+    if ((parts & 1) && g->pfc.ok) {
         fcgemm_pack_weights(&g->pfc, Bmat);
         unsigned short *dw = reinterpret_cast<unsigned short *>(g->pfc.d_W);
         if (!dw) ALQ_TRY(m->dalloc(&dw, g->pfc.h_W.size()));
@@ -326,6 +334,7 @@ static int gemm_set(alq_model *m, Gemm *g, const std::vector<float> &Bmat) {
             std::vector<unsigned short>().swap(g->pfc.h_W16);
         }
     }
+    if (!(parts & 2)) return ALQ_OK;
     if (g->pd.ok) {      // direct kernel reads the B matrix [K][Co] as it is
         if (!g->pd.d_W) ALQ_TRY(m->dalloc(&g->pd.d_W, Bmat.size()));
         ALQ_HIP(hipMemcpyAsync(g->pd.d_W, Bmat.data(), Bmat.size() * sizeof(float), hipMemcpyHostToDevice, m->ctx->stream));
@@ -371,6 +380,34 @@ static int gemm_set(alq_model *m, Gemm *g, const std::vector<float> &Bmat) {
     }
     igemm_pack_weights(&g->p1, Bmat);
     return upload1(m, &g->p1);
+}
+
+// A wide fc layer whose weights were last set from the device holds stale forms for the engines behind the streaming GEMM;
+// gemm_launch selects those only under the debug knobs 4 / 5: pack them now, from the resident fp32 copy, with the host's code.
+static int refresh_fallback_forms(alq_model *m) {
+    for (Layer &ly : m->layers) {
+        if (!ly.fallback_stale) continue;
+        const int64_t F = ly.F;
+        const int Co = ly.spec.cout;
+        std::vector<float> Wp((size_t)Co * F);
+        ALQ_HIP(hipMemcpyAsync(Wp.data(), ly.d_Wres, Wp.size() * sizeof(float), hipMemcpyDeviceToHost, m->ctx->stream));
+        ALQ_HIP(hipStreamSynchronize(m->ctx->stream));
+        std::vector<float> B((size_t)F * Co);
+        for (int64_t f = 0; f < F; ++f)
+            for (int o = 0; o < Co; ++o) B[(size_t)f * Co + o] = Wp[(size_t)o * F + f];
+        ALQ_TRY(gemm_set(m, &ly.fwd[0], B, 2));
+        if (ly.has_bwd) ALQ_TRY(gemm_set(m, &ly.bwd, Wp, 2));
+        ALQ_HIP(hipStreamSynchronize(m->ctx->stream));
+        m->host_pack_elems += ly.w_elems;
+        ly.fallback_stale = false;
+    }
+    return ALQ_OK;
+}
+
+static int prepare_call(alq_model *m) {
+    apply_knobs(m);
+    if (g_dbg_knobs[4] || g_dbg_knobs[5]) ALQ_TRY(refresh_fallback_forms(m));
+    return ALQ_OK;
 }
 
 // returns in *fused whether the epilogue fusion request was honoured (only the pipelined kernel can)
@@ -1648,7 +1685,7 @@ int alq_forward_dropout(alq_model *m, const float *d_x, int N, float keep_prob, 
     DropSpec ds;
     ALQ_TRY(make_drop(m, keep_prob, seed, first_sample, h_drop_layers, n_drop_layers, &ds));
     m->last_call_fisher = false;
-    apply_knobs(m);
+    ALQ_TRY(prepare_call(m));
     ALQ_TRY(run_forward(m, d_x, N, false, /*keep_all=*/true, &ds));
     ALQ_TRY(k_softmax(m->ctx, m->logits, m->nclass, N, d_post ? d_post : m->post, d_pred));
     return ALQ_OK;
@@ -1665,7 +1702,7 @@ int alq_param_grads(alq_model *m, const float *d_x, int N, int mode, int cls, co
     DropSpec ds;
     ALQ_TRY(make_drop(m, keep_prob, seed, first_sample, h_drop_layers, n_drop_layers, &ds));
     m->last_call_fisher = false;
-    apply_knobs(m);
+    ALQ_TRY(prepare_call(m));
     ALQ_TRY(run_forward(m, d_x, N, false, /*keep_all=*/true, &ds));
     float *post = d_post ? d_post : m->post;
     ALQ_TRY(k_softmax(m->ctx, m->logits, m->nclass, N, post, nullptr));
@@ -1684,7 +1721,7 @@ int alq_grad_sqnorms(alq_model *m, const float *d_x, int N, int cls, const int32
     DropSpec ds;
     ALQ_TRY(make_drop(m, 1.f, 0, 0, nullptr, 0, &ds));
     m->last_call_fisher = false;
-    apply_knobs(m);
+    ALQ_TRY(prepare_call(m));
     ALQ_TRY(run_forward(m, d_x, N, false, /*keep_all=*/true, &ds));
     float *post = d_post ? d_post : m->post;
     ALQ_TRY(k_softmax(m->ctx, m->logits, m->nclass, N, post, nullptr));
@@ -2182,6 +2219,83 @@ int alq_model_set_weights(alq_model *m, int t, const float *W, const float *b) {
     }
     ALQ_HIP(hipStreamSynchronize(m->ctx->stream));
     ly.weights_set = true;
+    ly.fallback_stale = false;
+    m->host_pack_elems += ly.w_elems;
+    return ALQ_OK;
+}
+
+// the layers alq_model_set_weights_device packs on the device: fc layers whose forward and backward Gemm both run on the
+// streaming GEMM of fcgemm.hip (and on nothing else by default)
+static bool packs_on_device(const Layer &ly) {
+    return ly.spec.type == ALQ_FC && !ly.dense_fc_small && ly.fwd.size() == 1 && ly.fwd[0].pfc.ok && !ly.fwd[0].pd.ok &&
+           (!ly.has_bwd || (ly.bwd.pfc.ok && !ly.bwd.pd.ok)) && ly.spec.cout <= 65535;
+}
+
+int alq_model_layer_packs_on_device(const alq_model *m, int t) {
+    ALQ_REQUIRE(m != nullptr, ALQ_EINVAL, "null model");
+    for (const Layer &ly : m->layers)
+        if (ly.pidx == t) return packs_on_device(ly) ? 1 : 0;
+    set_error("no parameterised layer %d", t);
+    return ALQ_EINVAL;
+}
+
+int alq_model_set_weights_device(alq_model *m, int t, const float *d_W, const float *d_b) {
+    ALQ_REQUIRE(m && d_W && d_b, ALQ_EINVAL, "alq_model_set_weights_device: null argument");
+    ALQ_HIP(hipSetDevice(m->ctx->device));
+    Layer *lyp = nullptr;
+    for (Layer &l : m->layers)
+        if (l.pidx == t) lyp = &l;
+    ALQ_REQUIRE(lyp != nullptr, ALQ_EINVAL, "no parameterised layer %d", t);
+    Layer &ly = *lyp;
+    alq_ctx *ctx = m->ctx;
+    if (!packs_on_device(ly)) {      // no device packers for this layer's engines: its slice goes through the host's
+        std::vector<float> W((size_t)ly.w_elems), b((size_t)ly.b_elems);
+        ALQ_HIP(hipMemcpyAsync(W.data(), d_W, W.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        ALQ_HIP(hipMemcpyAsync(b.data(), d_b, b.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        ALQ_HIP(hipStreamSynchronize(ctx->stream));
+        return alq_model_set_weights(m, t, W.data(), b.data());
+    }
+    for (int tries = 0; tries < 3 && ctx->f16_subnormal_mfma < 0; ++tries) (void)c3d_subnormals_ok(ctx);
+    ALQ_REQUIRE(ctx->f16_subnormal_mfma >= 0, ALQ_EHIP, "alq_model_set_weights_device: the fp16-subnormal probe of the matrix cores could not run (device error)");
+    const int Co = ly.spec.cout;
+    const int64_t F = ly.F;
+    if (!m->d_wscal) { unsigned char *q = nullptr; ALQ_TRY(m->dalloc(&q, 64)); m->d_wscal = q; }
+    if (!ly.d_Wres) ALQ_TRY(m->dalloc(&ly.d_Wres, (size_t)ly.w_elems));
+    ALQ_HIP(hipMemcpyAsync(ly.d_bias, d_b, ly.b_elems * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    ALQ_TRY(wpack_stats(ctx, d_W, Co, F, m->d_wscal));
+    ALQ_TRY(wpack_permute(ctx, d_W, ly.d_Wres, Co, ly.in.D, ly.in.H, ly.in.W, ly.in.C));
+    const bool sub = c3d_subnormals_ok(ctx) != 0;
+    auto pack = [&](Gemm *g, int K, int N, int kmajor) -> int {
+        ALQ_REQUIRE(g->pfc.K == K && g->pfc.N == N, ALQ_EINVAL, "alq_model_set_weights_device: plan %d x %d, layer %d x %d", g->pfc.K, g->pfc.N, K, N);
+        unsigned short *dw = reinterpret_cast<unsigned short *>(g->pfc.d_W);
+        if (!dw) ALQ_TRY(m->dalloc(&dw, (size_t)K * N * 3));
+        g->pfc.d_W = dw;
+        unsigned short *dw16 = nullptr;
+        if (g->pfc_f16 && sub) {
+            dw16 = reinterpret_cast<unsigned short *>(g->pfc.d_W16);
+            if (!dw16) ALQ_TRY(m->dalloc(&dw16, (size_t)K * N * 2));
+            g->pfc.d_W16 = dw16;
+        }
+        return wpack_fc(ctx, ly.d_Wres, F, K, N, kmajor, dw, dw16, m->d_wscal);
+    };
+    ALQ_TRY(pack(&ly.fwd[0], (int)F, Co, 0));              // B[f_mem][o]
+    if (ly.has_bwd) ALQ_TRY(pack(&ly.bwd, Co, (int)F, 1)); // B[o][f_mem]
+    // the host scalars the launches take their power-of-two scales from: 12 bytes device-to-host
+    unsigned long long sc[2] = {0, 0};
+    ALQ_HIP(hipMemcpyAsync(sc, m->d_wscal, 16, hipMemcpyDeviceToHost, ctx->stream));
+    ALQ_HIP(hipStreamSynchronize(ctx->stream));
+    double l1;
+    std::memcpy(&l1, &sc[0], 8);
+    ly.bwd_l1 = l1;
+    float amax;
+    const unsigned ab = (unsigned)(sc[1] & 0xffffffffull);
+    std::memcpy(&amax, &ab, 4);
+    int ex = 0;
+    if (amax > 0.f) (void)std::frexp(amax, &ex);
+    if (ly.fwd[0].pfc_f16 && sub) ly.fwd[0].pfc.w_exp = 14 - ex;
+    if (ly.has_bwd && ly.bwd.pfc_f16 && sub) ly.bwd.pfc.w_exp = 14 - ex;
+    ly.weights_set = true;
+    ly.fallback_stale = true;
     return ALQ_OK;
 }
 
@@ -2222,7 +2336,7 @@ int alq_forward(alq_model *m, const float *d_x, int N, float *d_post, int64_t *d
     if (N == 0) return ALQ_OK;
     ALQ_HIP(hipSetDevice(m->ctx->device));
     m->last_call_fisher = false;
-    apply_knobs(m);
+    ALQ_TRY(prepare_call(m));
     ALQ_TRY(run_forward(m, d_x, N, false, /*keep_all=*/d_feat != nullptr));
     ALQ_TRY(k_softmax(m->ctx, m->logits, m->nclass, N, d_post ? d_post : m->post, d_pred));
     if (d_feat) {
@@ -2298,7 +2412,7 @@ int alq_fisher(alq_model *m, const float *d_x, int N, const float *d_p1_in, doub
         ~SkipGuard() { c->prof_skip = false; }
     } guard(m->ctx);
     m->last_call_fisher = true;
-    apply_knobs(m);
+    ALQ_TRY(prepare_call(m));
     ALQ_TRY(run_forward(m, d_x, N, true));
     ALQ_TRY(k_softmax(m->ctx, m->logits, m->nclass, N, m->post, nullptr));
     ALQ_TRY(run_backward(m, d_x, N));
@@ -2409,6 +2523,26 @@ int alq_model_debug_copy(alq_model *m, int layer_idx, int what, int N, float *d_
     }
     ALQ_REQUIRE(layer_idx >= 0 && layer_idx < (int)m->layers.size(), ALQ_EINVAL, "bad layer index");
     const Layer &ly = m->layers[layer_idx];
+    if (what >= 6 && what <= 10) {
+        // packed weights of a wide fc layer as raw bytes (test hook): 6 / 7 = bf16 triples / fp16 pairs of the forward Gemm, 8 / 9 = of the
+        // backward Gemm; 10 = 4 words: w_exp of the forward and the backward plan, then the bits of bwd_l1 (fp64)
+        ALQ_REQUIRE(ly.spec.type == ALQ_FC && ly.fwd.size() == 1 && ly.fwd[0].pfc.ok && ly.weights_set, ALQ_EUNSUPPORTED, "layer %d has no streaming-GEMM weights", layer_idx);
+        if (what == 10) {
+            int32_t wd[4] = {ly.fwd[0].pfc.w_exp, ly.bwd.pfc.w_exp, 0, 0};
+            std::memcpy(&wd[2], &ly.bwd_l1, 8);
+            if (elems_out) *elems_out = 4;
+            ALQ_HIP(hipMemcpyAsync(d_out, wd, 16, hipMemcpyHostToDevice, m->ctx->stream));
+            ALQ_HIP(hipStreamSynchronize(m->ctx->stream));
+            return ALQ_OK;
+        }
+        const FcGemmPlan &pl = what <= 7 ? ly.fwd[0].pfc : ly.bwd.pfc;
+        const void *src = (what & 1) ? pl.d_W16 : pl.d_W;
+        ALQ_REQUIRE(pl.ok && src, ALQ_EUNSUPPORTED, "layer %d: this form is not packed", layer_idx);
+        const int64_t e = (int64_t)pl.K * pl.N * ((what & 1) ? 2 : 3) / 2;      // 16-bit pieces in 4-byte words
+        if (elems_out) *elems_out = e;
+        ALQ_HIP(hipMemcpyAsync(d_out, src, (size_t)e * 4, hipMemcpyDeviceToDevice, m->ctx->stream));
+        return ALQ_OK;
+    }
     if (what == 0 || what == 1) {
         // the last conv under a fused fc head: a Fisher pass stores neither its output nor the cotangent of it
         const Layer &head = m->layers.back();
@@ -2431,7 +2565,8 @@ int alq_model_debug_copy(alq_model *m, int layer_idx, int what, int N, float *d_
 }
 
 int alq_model_engine_info(alq_model *m, int what) {
-    ALQ_REQUIRE(m && ((what >= 0 && what <= 3) || (what >= 5 && what <= 13)), ALQ_EINVAL, "alq_model_engine_info: bad argument");
+    ALQ_REQUIRE(m && ((what >= 0 && what <= 3) || (what >= 5 && what <= 14)), ALQ_EINVAL, "alq_model_engine_info: bad argument");
+    if (what == 14) return m->host_pack_elems > 0x7fffffffll ? 0x7fffffff : (int)m->host_pack_elems;      // weight elements through the host packers since creation (saturates)
     if (what == 13) return m->last_c3_bwd ? m->c3_bwd_rows : 0;      // form of the head conv's backward kernel: 7 = 27 taps in 7 k-steps, 8 / 4 = the 9-k-step kernel
     if (what == 6) return m->last_f16_derived ? 1 : 0;
     if (what == 7) return m->last_t3f;        // conv_transpose launches of the last forward pass on the row-sweep engine (t3d.hip)

@@ -350,6 +350,61 @@ def tf_param_shapes(layers, in_shape):
     return out
 
 
+class LazyVarDict(OrderedDict):
+    """`model.var_dict`: name -> [W, b] host arrays in TF layouts.  When the weights were last set from device memory
+    (DeviceModel.set_weights_device, every training step) the host copies are stale: `refresh` - a callable that fetches
+    them and stores them with `put` - is armed with `mark_stale` and runs once, on the first access that reads a value.
+    Names, length and membership never need the device."""
+
+    def __init__(self, *args, **kwargs):
+        self._refresh = None
+        OrderedDict.__init__(self, *args, **kwargs)
+
+    def mark_stale(self, refresh):
+        self._refresh = refresh
+
+    def mark_fresh(self):
+        self._refresh = None
+
+    @property
+    def stale(self):
+        return self._refresh is not None
+
+    def put(self, name, value):
+        """Stores a value without touching the stale mark (what the refresh callable uses)."""
+        OrderedDict.__setitem__(self, name, value)
+
+    def _sync(self):
+        fn = self._refresh
+        if fn is not None:
+            self._refresh = None          # first: the callable reads nothing through us, but an error must not loop
+            try:
+                fn()
+            except Exception:
+                self._refresh = fn
+                raise
+
+    def __getitem__(self, name):
+        self._sync()
+        return OrderedDict.__getitem__(self, name)
+
+    def get(self, name, default=None):
+        self._sync()
+        return OrderedDict.get(self, name, default)
+
+    def values(self):
+        self._sync()
+        return OrderedDict.values(self)
+
+    def items(self):
+        self._sync()
+        return OrderedDict.items(self)
+
+    def copy(self):
+        self._sync()
+        return OrderedDict(OrderedDict.items(self))
+
+
 class DeviceModel(object):
     """The reference model protocol (`x, keep_prob, posteriors, prediction, feature_layer,
     grad_posts, var_dict, dropout_rate`) over a libalq model."""
@@ -411,7 +466,13 @@ class DeviceModel(object):
         for h in (self.posteriors, self.prediction, self.feature_layer):
             h.model = self
         # 2L opaque entries per class, so that len(model.grad_posts['1'])/2 == L (PW_NNAL.py:751)
-        self.var_dict = OrderedDict((n, None) for n in self.var_names)
+        self.var_dict = LazyVarDict((n, None) for n in self.var_names)
+        # Weights that are already in device memory are packed there (alq_model_set_weights_device): per parameterised layer,
+        # whether the library has device packers for it (wide fc layers) and the device tensors (W, b) its current weights were
+        # packed from (None: host arrays only).  ALQ_HOST_REPACK=1 at creation (A/B, tests): everything through the host packers.
+        self._host_repack = os.environ.get('ALQ_HOST_REPACK', '0') not in ('', '0')
+        self._dev_pack = [self.lib.alq_model_layer_packs_on_device(self._m, t) == 1 for t in range(self.L)]
+        self._dev_w = [None] * self.L
         self.grad_layers = []
         self._build_grad_handles()
         self.y_ = Handle('y_')
@@ -602,7 +663,13 @@ class DeviceModel(object):
             check(self.lib.alq_adam_step(self.sess.ctx, C.c_void_p(o['theta'].data_ptr()), C.c_void_p(gsum.data_ptr()),
                                          C.c_void_p(o['m'].data_ptr()), C.c_void_p(o['v'].data_ptr()), P, o['lr'],
                                          0.9, 0.999, 1e-8, o['t']))      # a masked-out parameter keeps m = v = 0: its step is 0 / eps = 0
-        self.set_flat_params(o['theta'].cpu().numpy())
+        if self._host_repack:
+            self.set_flat_params(o['theta'].cpu().numpy())
+        else:
+            # the model is fed from the device vector; a layer outside `train_layers` kept its weights (masked gradient: SGD
+            # subtracts 0, Adam's m = v = 0 step is 0 / eps = 0) and its packed forms
+            only = [t for t, nme in enumerate(self.var_names) if nme in self.train_layers] if self.train_layers else None
+            self.set_weights_device(o['theta'], only=only)
         o['version'] = self._weights_version
         return loss
 
@@ -633,15 +700,88 @@ class DeviceModel(object):
         """`pars`: name -> [W, b] in TF layouts (HWIO / DHWIO, transpose [k..,out,in], fc [out,in],
         fc bias [out,1]); the weight interchange of NN.py:390-394 / :508-517 with numpy arrays in
         place of the HDF5 datasets (h5py is not in the image)."""
+        staged = []
         for t, (name, wshape, bshape) in enumerate(self.param_shapes):
             W, b = pars[name]
             W = np.ascontiguousarray(np.asarray(W, dtype=np.float32))
             b = np.ascontiguousarray(np.asarray(b, dtype=np.float32))
             if tuple(W.shape) != tuple(wshape) or b.size != int(np.prod(bshape)):
                 raise ValueError('layer %s: expected W%s b%s, got W%s b%s' % (name, wshape, bshape, W.shape, b.shape))
-            check(self.lib.alq_model_set_weights(self._m, t, W.ctypes.data_as(C.c_void_p),
-                                                 b.ctypes.data_as(C.c_void_p)))
+            staged.append((W, b))
+        torch = self.sess.torch
+        self.var_dict.mark_fresh()
+        self.sess.bind_stream()
+        for t, name in enumerate(self.var_names):
+            W, b = staged[t]
+            if self._dev_pack[t] and not self._host_repack:
+                # a wide fc layer: the raw arrays are uploaded once and packed on the device; the extra pipelines' models are fed
+                # from the same tensors (_extra_lanes)
+                Wd, bd = self.sess.to_device(W, torch.float32), self.sess.to_device(b, torch.float32)
+                check(self.lib.alq_model_set_weights_device(self._m, t, C.c_void_p(Wd.data_ptr()), C.c_void_p(bd.data_ptr())))
+                self._dev_w[t] = (Wd, bd)
+            else:
+                check(self.lib.alq_model_set_weights(self._m, t, W.ctypes.data_as(C.c_void_p),
+                                                     b.ctypes.data_as(C.c_void_p)))
+                self._dev_w[t] = None
             self.var_dict[name] = [W, b]
+        self._weights_version += 1
+
+    def _device_slices(self, src):
+        """[(W, b)] device fp32 tensors per parameterised layer from a flat parameter-order vector [P], a dict
+        name -> (W, b) or a list of (W, b)."""
+        torch = self.sess.torch
+        if isinstance(src, torch.Tensor):
+            if src.dtype != torch.float32 or not src.is_contiguous() or int(src.numel()) != self.num_params or not src.is_cuda:
+                raise ValueError('expected a contiguous device fp32 vector of %d parameters' % self.num_params)
+            flat = src.reshape(-1)
+            pairs = self.unflatten(flat)
+            return [(pairs[2 * t], pairs[2 * t + 1]) for t in range(self.L)]
+        if isinstance(src, dict):
+            src = [src[nme] for nme in self.var_names]
+        if len(src) != self.L:
+            raise ValueError('expected %d (W, b) pairs, got %d' % (self.L, len(src)))
+        out = []
+        for (name, wshape, bshape), (W, b) in zip(self.param_shapes, src):
+            for a, shp in ((W, wshape), (b, bshape)):
+                if not (isinstance(a, torch.Tensor) and a.is_cuda and a.dtype == torch.float32 and a.is_contiguous() and
+                        int(a.numel()) == int(np.prod(shp))):
+                    raise ValueError('layer %s: expected contiguous device fp32 tensors W%s b%s' % (name, wshape, bshape))
+            out.append((W, b))
+        return out
+
+    def set_weights_device(self, theta_or_slices, only=None):
+        """`set_weights` from DEVICE memory (alq_model_set_weights_device): a flat parameter-order fp32 vector [P] (what the
+        optimiser step updates), a dict name -> (W, b) or a list of (W, b) device tensors in TF layouts.  The tensors must be
+        ready on the current stream.  Wide fc layers are packed by device kernels, any other layer's slice takes the host
+        packers; `var_dict` turns stale and is fetched on its next read.  `only`: the layer indices whose values changed
+        (the rest of the model keeps its packed weights); the source still holds every layer.  The model keeps a reference
+        to the tensors (they feed the extra scoring pipelines): the caller may update them in place only together with
+        another call."""
+        torch = self.sess.torch
+        sl = self._device_slices(theta_or_slices)
+        if self._host_repack:
+            pars = OrderedDict((nme, [sl[t][0].cpu().numpy().reshape(self.param_shapes[t][1]),
+                                      sl[t][1].cpu().numpy().reshape(self.param_shapes[t][2])])
+                               for t, nme in enumerate(self.var_names))
+            return self.set_weights(pars)
+        if only is not None and any(v is None for v in OrderedDict.values(self.var_dict)) and not self.var_dict.stale:
+            only = None          # nothing set yet: every layer needs its weights
+        self.sess.bind_stream()
+        for t in (range(self.L) if only is None else only):
+            W, b = sl[t]
+            check(self.lib.alq_model_set_weights_device(self._m, t, C.c_void_p(W.data_ptr()), C.c_void_p(b.data_ptr())))
+        self._dev_w = list(sl)
+        flat = theta_or_slices if isinstance(theta_or_slices, torch.Tensor) else None
+
+        def refresh():
+            if flat is not None:          # one copy of the whole vector, cut like set_flat_params cuts it
+                arrs = self.unflatten(flat.reshape(-1).cpu().numpy())
+            else:
+                arrs = [a.cpu().numpy().reshape(shp) for (W, b), (_, ws, bs) in zip(sl, self.param_shapes)
+                        for a, shp in ((W, ws), (b, bs))]
+            for t, nme in enumerate(self.var_names):
+                self.var_dict.put(nme, [arrs[2 * t], arrs[2 * t + 1]])
+        self.var_dict.mark_stale(refresh)
         self._weights_version += 1
 
     def load_weights(self, path, session=None):
@@ -887,7 +1027,8 @@ class DeviceModel(object):
 
     def _extra_lanes(self, count):
         """`count` extra scoring pipelines of fisher_device: each a libalq context on its own torch stream and a model of the same
-        layers on it; their weights follow `set_weights` (the host copies in var_dict are the single state)."""
+        layers on it; their weights follow `set_weights` / `set_weights_device`: wide fc layers from the device tensors the first
+        model was fed from, the other layers from the host copies in var_dict."""
         torch = self.sess.torch
         while len(self._xlanes) < count:
             stream = torch.cuda.Stream(self.sess.device)
@@ -903,10 +1044,19 @@ class DeviceModel(object):
             self._xlanes.append(dict(sess=sess2, stream=stream, m=m, version=None))
         for ln in self._xlanes[:count]:
             if ln['version'] != self._weights_version:
-                if any(v is None for v in self.var_dict.values()):
+                if not self.var_dict.stale and any(v is None for v in self.var_dict.values()):
                     raise RuntimeError('set_weights() has not been called')
+                # the pipeline's context runs on its own stream: what fills the device tensors (an upload, the optimiser step) is
+                # ordered on the caller's
+                ln['stream'].wait_stream(torch.cuda.current_stream(self.sess.device))
                 with self._creation_env():
                     for ti, name in enumerate(self.var_names):
+                        if self._dev_pack[ti] and self._dev_w[ti] is not None and not self._host_repack:
+                            Wd, bd = self._dev_w[ti]
+                            with torch.cuda.stream(ln['stream']):
+                                ln['sess'].bind_stream()
+                                check(self.lib.alq_model_set_weights_device(ln['m'], ti, C.c_void_p(Wd.data_ptr()), C.c_void_p(bd.data_ptr())))
+                            continue
                         W, b = self.var_dict[name]
                         check(self.lib.alq_model_set_weights(ln['m'], ti, W.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p)))
                 ln['version'] = self._weights_version
