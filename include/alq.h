@@ -277,6 +277,17 @@ int alq_sq_accum(alq_ctx *ctx, const float *d_grads, int64_t per_sample_len, int
  * alq_param_grads(mode 0, per_sample 1) writes them, h_layer_elems [L] = |W_t| + |b_t| (host; their sum must be P);
  * d_out [N, L] double: (sum of layer t's entries) / (|W_t| + |b_t|), fp64 sums in a fixed order.                        */
 int alq_shrink_sum(alq_ctx *ctx, const float *d_grads, int N, int64_t P, const int64_t *h_layer_elems, int L, double *d_out);
+/* Replaces: the same per-sample, per-class gradient lists and their shrink (NNAL.py:381-405), without forming a gradient:
+ * d_g [N, J, L] double, d_g[n][j][t] = (sum of layer t's entries of d log posteriors[d_cls[j][n], n] / d theta) /
+ * (|W_t| + |b_t|), the quotient in fp64 as in alq_shrink_sum.  d_cls [J][N] int32 on the device: the class of slot j for
+ * every sample, 1 <= J <= 64; any class count from 2 to 64; N <= max_batch; keep_prob 1.  One forward pass, one softmax,
+ * one field launch per parameterised layer (the class-independent factor of the sum: box / transposed box of the input's
+ * channel sums + 1, fc: sum of the input + 1), then per slot the logit cotangent e_j - p, the general backward-data sweep
+ * with the fused mask + channel-sum + dot kernel of csrc/lsum.hip per layer, and a fixed-order finish: no weight gradient,
+ * no [N, P] buffer, no weight-gradient workspace.  d_post [c, N] optional.  A class outside [0, c) gives ALQ_EINVAL and
+ * nothing is written (the slots are checked on the device first: one 4-byte flag read, which synchronises the stream).
+ * Every row depends on its own sample only: bit-identical whatever the batch, the slot position and from run to run.   */
+int alq_class_layer_sums(alq_model *m, const float *d_x, int N, int J, const int32_t *d_cls, float *d_post, double *d_g);
 /* Replaces: the accumulation `Ai += np.outer(g_j, g_j) / new_posts[j] + np.eye(A_size) * 1e-5` over the selected classes
  * (NNAL.py:399-409).  d_g [N, c, L] shrunk class gradients, d_w [N, c] = 1 / new_posts for the classes the reference
  * keeps (posterior >= 1e-6; the ten largest when ten or more remain, :381-394) and 0 for the others - host logic on the
@@ -381,6 +392,8 @@ int alq_debug_set(int key, int value);
  * pass ran (csrc/c3d.hip): 7 = the 27 taps packed into 7 k-steps (default), 8 / 4 = the 9-k-step kernel (ALQ_C3D_BWD_ROWS), 0 = none.
  * 14: the number of weight elements that went through the HOST packers since the model was created (alq_model_set_weights, the
  * per-layer fall-back of alq_model_set_weights_device and the lazy forms behind the debug knobs); saturates at 2^31 - 1.
+ * 15: 1 when the last general backward sweep ran the fused layer-sum kernels of csrc/lsum.hip (alq_class_layer_sums), 0 after
+ * alq_param_grads / alq_grad_sqnorms.
  * Returns the answer or a negative error code.  */
 int alq_model_engine_info(alq_model *m, int what);
 

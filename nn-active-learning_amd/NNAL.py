@@ -2,11 +2,14 @@
 expected-gradient-length query `egl` (NNAL.py:234-285) and the multi-class Fisher-information query `fi` (NNAL.py:312-464) - the image-level twin of PW_NNAL's binary `fi` and the
 last strategy of SURVEY.md 8f-3 that reuses the scoring kernels.
 
-What runs where: posteriors, features and the per-class gradients of the log-posteriors run on the device
-(DeviceModel.forward_device, alq_param_grads per class, alq_shrink_sum for `shrink_gradient(..., 'sum')`, alq_fisher_classes
-for the sum of outer products); the reference's per-sample class selection (posteriors below 1e-6 dropped and the rest
-renormalised; the ten largest when ten or more remain), the feature refinement, the SDP and the draws are host NumPy
-like the reference's.  RNG draws (NN.gen_batch_inds in idxBatch_posteriors and extract_features, then
+What runs where: posteriors, features and the shrunk per-class gradients of the log-posteriors run on the device.  For `fi`
+the reference's per-sample class selection (posteriors below 1e-6 dropped and the rest renormalised; the ten largest when
+ten or more remain) is host NumPy and comes first; only the kept classes are differentiated, as per-sample class slots:
+alq_class_layer_sums runs one forward pass per device pass and one backward-data sweep per slot, and takes
+`shrink_gradient(..., 'sum')` of every layer from fused mask + channel-sum + dot kernels (csrc/lsum.hip) - no gradient of the
+size of theta is formed; alq_fisher_classes adds the outer products over the slots.  ALQ_FI_ROWS=1 selects the earlier
+route for A/B runs: alq_param_grads rows for every class and alq_shrink_sum on them.  The feature refinement, the SDP and
+the draws are host NumPy like the reference's.  RNG draws (NN.gen_batch_inds in idxBatch_posteriors and extract_features, then
 sample_query_dstr) happen in the reference's order, so a seeded run picks the same queries."""
 import numpy as np
 
@@ -36,7 +39,10 @@ def class_weights(x_posterior):
 def fi_A_matrices(model, session, sel_X, sel_posteriors):
     """The A-matrix loop of the `fi` branch (NNAL.py:336-413): A_i = sum_{j kept} g_ij g_ij^T / p'_ij + |kept| 1e-5 I with
     g_ij = shrink_gradient(d log posteriors[j] / d theta, 'sum') of sample i.  sel_posteriors [c, B] float64 (modified
-    in place like the reference's view: entries below 1e-6 become 0).  Returns the list of B float64 [L', L'] arrays."""
+    in place like the reference's view: entries below 1e-6 become 0).  Returns the list of B float64 [L', L'] arrays.
+    Host: the class weights and the diagonal (class_weights per sample).  Device (model.fisher_classes): the kept classes
+    as class slots through alq_class_layer_sums - the layer sums straight from the backward sweep - and the weighted outer
+    products (alq_fisher_classes); with ALQ_FI_ROWS=1 per-class gradient rows and alq_shrink_sum instead."""
     c, B = sel_posteriors.shape
     W = np.zeros((B, c))
     diag = np.zeros(B)

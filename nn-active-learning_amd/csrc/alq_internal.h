@@ -675,6 +675,17 @@ int k_gnorm_weight(alq_ctx *, const View &U, const View &V, const int k[3], cons
 int k_gnorm_bias(alq_ctx *, const View &delta, int N, double *d_sq, int ld, int col);
 int k_gnorm_fc(alq_ctx *, const float *delta, int nout, const View &a, int N, double *d_sq, int ld, int col);
 
+// ------------------------------------------------------------------ per-class layer sums (lsum.hip)
+int lsum_slabs(const View &dout, bool isfc, int *slab_out);      // partials per sample of one layer's class sweep
+// F [N, out voxels] (fc: [N]) double: the class-independent field of a layer (type = ALQ_CONV / ALQ_CONVT / ALQ_FC)
+int k_lsum_field(alq_ctx *, const View &in, const View &out, const int k[3], const int s[3], const int lo[3], int type, int N,
+                 double *F);
+// ReLU mask of dout in place (act != null) + per-sample sum of chansum(dout) * F: part[n * nslab_max + slab]
+int k_lsum_sweep(alq_ctx *, const View &dout, const View *act_or_null, bool isfc, const double *F, int N, double *part, int nslab_max);
+int k_lsum_finish(alq_ctx *, const double *part /*[L][max_batch][nslab_max]*/, const int *h_nslab, int nslab_max, int max_batch,
+                  const double *sizes, int N, int L, int J, int j, double *g /*[N, J, L]*/);
+int k_lsum_check_classes(alq_ctx *, const int *d_cls, int count, int c, int *d_flag);
+
 // ------------------------------------------------------------------ committee statistics (committee.hip)
 int committee_update_impl(alq_ctx *, const float *d_p1, int64_t n, int member, int mode, double *d_mean_p, double *d_mean_h,
                           double *d_keys);

@@ -67,6 +67,7 @@ struct Layer {
     // workspaces
     uint8_t *argmax = nullptr;
     float *asum = nullptr, *dsum = nullptr;
+    double *ls_field = nullptr; // [max_batch, out voxels] (fc: [max_batch]): field of alq_class_layer_sums, filled once per call
     float *osum = nullptr;     // channel sums of this layer's OUTPUT (spatial layers): next layers' asum
     bool delta_ready = false;  // backward: the cotangent of our output is already masked and dsum is filled
     bool signs_ready = false;  // Fisher pass: the forward launch wrote the sign field of our output (View::sg)
@@ -148,6 +149,12 @@ struct alq_model {
     size_t wg_partial_len = 0;
     double *gn_partial = nullptr;  // per-(sample, workgroup) partials of the gradient-norm kernels (grown on demand)
     size_t gn_partial_len = 0;
+    // alq_class_layer_sums (lsum.hip), allocated by its first call: the layers' class-independent fields (Layer::ls_field), the
+    // slab partials [L][max_batch][ls_nslab_max] of one class slot and the slabs each layer writes
+    double *ls_part = nullptr;
+    std::vector<int> ls_nslab;
+    int ls_nslab_max = 0;
+    int last_lsum = 0;             // the last general backward sweep ran the fused layer-sum kernels (engine info 15)
     float *x_stage = nullptr;      // [max_batch, elems per patch]: rows gathered by the *_rows entry points
     int64_t epp = 0;               // elements per patch
     // Engine-selection knobs, read from the environment ONCE, when this model is created; every call applies the
@@ -1540,9 +1547,10 @@ static int run_backward_main(alq_model *m, const float *d_x, int N) {
 // them): every layer's masked pre-activation cotangent ends up in its `dout` view (what the weight gradients need), no
 // shortcut of the Fisher pass is taken (no unit cotangent, no sign-byte input, every tensor stored).  The forward pass
 // must have kept every activation (run_forward(..., keep_all = true)).
-static int run_backward_general(alq_model *m, int N, const DropSpec *drop) {
+static int run_backward_general(alq_model *m, int N, const DropSpec *drop, bool layer_sums = false) {
     alq_ctx *ctx = m->ctx;
     const int nl = (int)m->layers.size();
+    m->last_lsum = layer_sums ? 1 : 0;
     for (int i = nl - 1; i >= 0; --i) {
         Layer &ly = m->layers[i];
         const bool isfc = ly.spec.type == ALQ_FC;
@@ -1557,7 +1565,11 @@ static int run_backward_general(alq_model *m, int N, const DropSpec *drop) {
         }
         View dv = isfc ? flat_view(ly.dout) : ly.dout;
         View av = isfc ? flat_view(ly.out) : ly.out;
-        ALQ_TRY(k_mask_chansum(ctx, dv, ly.spec.relu ? &av : nullptr, ly.dsum, N));      // ReLU-grad mask in place (+ sums, unused)
+        if (layer_sums)     // ReLU-grad mask in place + this slot's layer sum against the layer's field (lsum.hip)
+            ALQ_TRY(k_lsum_sweep(ctx, dv, ly.spec.relu ? &av : nullptr, isfc, ly.ls_field, N,
+                                 m->ls_part + (size_t)ly.pidx * m->max_batch * m->ls_nslab_max, m->ls_nslab_max));
+        else
+            ALQ_TRY(k_mask_chansum(ctx, dv, ly.spec.relu ? &av : nullptr, ly.dsum, N));      // ReLU-grad mask in place (+ sums, unused)
         if (ly.pidx == 0) break;      // the first parameterised layer: nothing below needs a cotangent
         const int acc = prev_is_src ? 1 : 0;
         if (isfc) {
@@ -1729,6 +1741,56 @@ int alq_grad_sqnorms(alq_model *m, const float *d_x, int N, int cls, const int32
     ALQ_TRY(k_logit_cotangent(m->ctx, post, m->nclass, N, mode, cls, d_cls, 1.f, m->dlogits));
     ALQ_TRY(run_backward_general(m, N, &ds));
     return run_grad_sqnorms(m, d_x, N, d_sq);
+}
+
+int alq_class_layer_sums(alq_model *m, const float *d_x, int N, int J, const int32_t *d_cls, float *d_post, double *d_g) {
+    ALQ_REQUIRE(m && d_x && d_cls && d_g, ALQ_EINVAL, "alq_class_layer_sums: null argument");
+    ALQ_REQUIRE(N >= 1 && N <= m->max_batch, ALQ_EINVAL, "alq_class_layer_sums: N=%d outside [1, max_batch=%d]", N, m->max_batch);
+    ALQ_REQUIRE(J >= 1 && J <= 64, ALQ_EINVAL, "alq_class_layer_sums: %d class slots outside [1, 64]", J);
+    ALQ_REQUIRE(m->nclass >= 2 && m->nclass <= 64 && m->L <= 64, ALQ_EUNSUPPORTED, "alq_class_layer_sums: %d classes, %d layers",
+                m->nclass, m->L);
+    alq_ctx *ctx = m->ctx;
+    ALQ_HIP(hipSetDevice(ctx->device));
+    // the class slots live on the device: one flag read (a stream synchronisation) before anything is written
+    int *d_bad = reinterpret_cast<int *>(static_cast<char *>(ctx->param_block) + ALQ_PARAM_FLAG_OFFSET);
+    int bad = 0;
+    ALQ_HIP(hipMemsetAsync(d_bad, 0, sizeof(int), ctx->stream));
+    ALQ_TRY(k_lsum_check_classes(ctx, d_cls, J * N, m->nclass, d_bad));
+    ALQ_HIP(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    ALQ_HIP(hipStreamSynchronize(ctx->stream));
+    ALQ_REQUIRE(!bad, ALQ_EINVAL, "alq_class_layer_sums: a class outside [0, %d)", m->nclass);
+    if (!m->ls_part) {
+        m->ls_nslab.assign(m->L, 1);
+        m->ls_nslab_max = 1;
+        for (Layer &ly : m->layers) {
+            if (ly.pidx < 0) continue;
+            const bool isfc = ly.spec.type == ALQ_FC;
+            m->ls_nslab[ly.pidx] = lsum_slabs(ly.dout, isfc, nullptr);
+            m->ls_nslab_max = std::max(m->ls_nslab_max, m->ls_nslab[ly.pidx]);
+            ALQ_TRY(m->dalloc(&ly.ls_field, (size_t)m->max_batch * (isfc ? 1 : (size_t)ly.out.vox())));
+        }
+        ALQ_TRY(m->dalloc(&m->ls_part, (size_t)m->L * m->max_batch * m->ls_nslab_max));
+    }
+    DropSpec ds;
+    ALQ_TRY(make_drop(m, 1.f, 0, 0, nullptr, 0, &ds));
+    m->last_call_fisher = false;
+    ALQ_TRY(prepare_call(m));
+    ALQ_TRY(run_forward(m, d_x, N, false, /*keep_all=*/true, &ds));
+    float *post = d_post ? d_post : m->post;
+    ALQ_TRY(k_softmax(ctx, m->logits, m->nclass, N, post, nullptr));
+    for (size_t i = 0; i < m->layers.size(); ++i) {      // the fields: once per call, whatever J
+        Layer &ly = m->layers[i];
+        if (ly.pidx < 0) continue;
+        View in = ly.in;
+        if (i == 0) in.p = const_cast<float *>(d_x);
+        ALQ_TRY(k_lsum_field(ctx, in, ly.out, ly.spec.k, ly.spec.s, ly.lo, ly.spec.type, N, ly.ls_field));
+    }
+    for (int j = 0; j < J; ++j) {
+        ALQ_TRY(k_logit_cotangent(ctx, post, m->nclass, N, 3, 0, d_cls + (size_t)j * N, 1.f, m->dlogits));
+        ALQ_TRY(run_backward_general(m, N, &ds, /*layer_sums=*/true));
+        ALQ_TRY(k_lsum_finish(ctx, m->ls_part, m->ls_nslab.data(), m->ls_nslab_max, m->max_batch, m->sizes, N, m->L, J, j, d_g));
+    }
+    return ALQ_OK;
 }
 
 int alq_sgd_step(alq_ctx *ctx, float *d_theta, const float *d_grad, int64_t n, float lr) {
@@ -2565,7 +2627,8 @@ int alq_model_debug_copy(alq_model *m, int layer_idx, int what, int N, float *d_
 }
 
 int alq_model_engine_info(alq_model *m, int what) {
-    ALQ_REQUIRE(m && ((what >= 0 && what <= 3) || (what >= 5 && what <= 14)), ALQ_EINVAL, "alq_model_engine_info: bad argument");
+    ALQ_REQUIRE(m && ((what >= 0 && what <= 3) || (what >= 5 && what <= 15)), ALQ_EINVAL, "alq_model_engine_info: bad argument");
+    if (what == 15) return m->last_lsum;      // the last general backward sweep ran the fused layer-sum kernels (lsum.hip)
     if (what == 14) return m->host_pack_elems > 0x7fffffffll ? 0x7fffffff : (int)m->host_pack_elems;      // weight elements through the host packers since creation (saturates)
     if (what == 13) return m->last_c3_bwd ? m->c3_bwd_rows : 0;      // form of the head conv's backward kernel: 7 = 27 taps in 7 k-steps, 8 / 4 = the 9-k-step kernel
     if (what == 6) return m->last_f16_derived ? 1 : 0;

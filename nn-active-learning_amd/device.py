@@ -1075,7 +1075,8 @@ class DeviceModel(object):
         what the reference obtains with one session.run(model.grad_posts[str(j)]) per sample and class plus a host
         reduction (NNAL.py:381-405, NNAL_tools.py:784-796).  Per device pass: alq_param_grads (mode 0, per-sample rows)
         for class j, alq_shrink_sum on the rows; nothing of size |theta| reaches the host.  L' = the layers of
-        `grad_layers` (all when empty).  Also returns the posteriors [c, n] of these passes (device fp32)."""
+        `grad_layers` (all when empty).  Also returns the posteriors [c, n] of these passes (device fp32).
+        The A/B arm of the query since class_layer_sums_device (fisher_classes(..., fused=False), ALQ_FI_ROWS=1)."""
         torch = self.sess.torch
         t, n = self._as_device_batch(x)
         c, L = self.nclass, self.L
@@ -1098,10 +1099,61 @@ class DeviceModel(object):
             g = g[:, :, idx].contiguous()
         return g, post
 
-    def fisher_classes(self, x, W, diag):
-        """A [n, L', L'] float64 = sum_j W[i, j] g_ij g_ij^T + diag[i] I (alq_fisher_classes on shrunk_class_gradients)."""
+    def class_layer_sums_device(self, t, n, classes):
+        """alq_class_layer_sums over device passes of max_batch samples: g [n, J, L'] float64 on the device, g[i, j] =
+        shrink_gradient(d log posteriors[classes[i, j], i] / d theta, 'sum') over the layers of `grad_layers` (all when
+        empty), like shrunk_class_gradients but for the class slots given per sample and with nothing of the size of theta
+        formed: per pass one forward pass, one field launch per layer, then per slot a backward-data sweep with the fused
+        mask + channel-sum + dot kernels (csrc/lsum.hip).  classes: int array [n, J], entries in [0, c); the slots of a pass
+        are uploaded with it.  Rows do not depend on the pass cut."""
         torch = self.sess.torch
-        g, _ = self.shrunk_class_gradients(x)
+        self.sess.bind_stream()
+        classes = np.asarray(classes)
+        if classes.ndim != 2 or classes.shape[0] != n or not 1 <= classes.shape[1] <= 64:
+            raise ValueError('classes must be [n = %d, J] with 1 <= J <= 64, got %r' % (n, classes.shape))
+        J, L = int(classes.shape[1]), self.L
+        g = self.sess.empty((n, J, L), torch.float64)
+        flat = t.reshape(n, -1)
+        for a in range(0, n, self.max_batch):
+            b = min(n, a + self.max_batch)
+            dc = self.sess.to_device(np.ascontiguousarray(classes[a:b].T, dtype=np.int32), torch.int32)      # [J][b - a]
+            check(self.lib.alq_class_layer_sums(self._m, C.c_void_p(flat[a:b].data_ptr()), b - a, J, C.c_void_p(dc.data_ptr()), None,
+                                                C.c_void_p(g.data_ptr() + a * J * L * 8)))
+        idx = list(self.grad_layer_idx)
+        if idx != list(range(L)):
+            g = g[:, :, idx].contiguous()
+        return g
+
+    @staticmethod
+    def class_slots(W):
+        """The slot form of per-sample class weights W [n, c] (0 = class not kept): (classes [n, J] int, weights [n, J]) with
+        J the largest kept-class count over the samples; slot j of sample i is its j-th kept class in ascending class order,
+        spare slots repeat class 0 with weight 0.  sum_j weights[i, j] g(classes[i, j]) g(..)^T = sum_c W[i, c] g(c) g(c)^T."""
+        W = np.asarray(W, dtype=np.float64)
+        n = W.shape[0]
+        kept = [np.flatnonzero(W[i] != 0.) for i in range(n)]
+        J = max(1, max(len(k) for k in kept)) if n else 1
+        classes = np.zeros((n, J), dtype=np.int64)
+        weights = np.zeros((n, J))
+        for i, k in enumerate(kept):
+            classes[i, :len(k)] = k
+            weights[i, :len(k)] = W[i, k]
+        return classes, weights
+
+    def fisher_classes(self, x, W, diag, fused=None):
+        """A [n, L', L'] float64 = sum_j W[i, j] g_ij g_ij^T + diag[i] I (alq_fisher_classes).  fused (default; None = on unless
+        ALQ_FI_ROWS=1): only the classes with a non-zero weight are differentiated, as class slots (class_slots) through
+        class_layer_sums_device, and alq_fisher_classes runs over the J slots.  Otherwise the gradients of all c classes come
+        from shrunk_class_gradients (alq_param_grads rows + alq_shrink_sum per class): the A/B arm."""
+        torch = self.sess.torch
+        if fused is None:
+            fused = os.environ.get('ALQ_FI_ROWS', '0') in ('', '0')
+        if fused:
+            t, n = self._as_device_batch(x)
+            classes, W = self.class_slots(np.asarray(W, dtype=np.float64).reshape(n, self.nclass))
+            g = self.class_layer_sums_device(t, n, classes)
+        else:
+            g, _ = self.shrunk_class_gradients(x)
         n, c, L = [int(v) for v in g.shape]
         Wd = self.sess.to_device(np.asarray(W, dtype=np.float64).reshape(n, c), torch.float64)
         dd = self.sess.to_device(np.asarray(diag, dtype=np.float64).reshape(n), torch.float64)
