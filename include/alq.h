@@ -364,7 +364,11 @@ int alq_prof_read(alq_ctx *ctx, int cls, double *ms, int64_t *launches, double *
  * float; layer_idx ignored), 5 = the fused fc head's logit-difference partials [N, tiles * 4] (one per
  * (tile, wave) of the last conv's launch); of a wide fc layer (streaming GEMM), as raw bytes in 4-byte words: 6 / 7 = the packed
  * bf16 triples / fp16 pairs of its forward Gemm, 8 / 9 = of its backward Gemm, 10 = 4 words: the fp16 scale exponents of the
- * forward and the backward plan and the bits of the layer's fp64 L1 bound (N ignored).  *elems_out receives the element count.  Tests only.  */
+ * forward and the backward plan and the bits of the layer's fp64 L1 bound (N ignored); after a Fisher pass: 11 = channel-sum field of
+ * the layer's OUTPUT [N, vox_out], 12 = the sign field of the rows its output lies in, as raw bytes in 4-byte words ([N, vox_out, cs / 4]
+ * bytes, cs = channels of the allocation: the layer's own bytes are the C / 4 from byte c0 / 4 of a voxel; bit k of a byte = (channel
+ * 4 b + k > 0)), 13 = a pool layer's arg-max field as raw bytes in 4-byte words ([N, vox_out, C] window indices).  *elems_out
+ * receives the element count.  Tests only.  */
 int alq_model_debug_copy(alq_model *m, int layer_idx, int what, int N, float *d_out,
                          int64_t *elems_out);
 
@@ -375,7 +379,9 @@ int alq_debug_set_stamp_buffer(void *d_buf);
 /* Timing-experiment knobs (tests / profiling only; results may be wrong while a knob is set):
  * key 0 = repeat the MFMA phase n extra times, 1 = flag bits (1 no stores, 2 no loads, 4 no sum
  * MFMAs, 8 no sum stores), 2 = no epilogue fusion in backward GEMMs, 3 = none in forward GEMMs,
- * 4 = use the fp32-MFMA GEMM kernel instead of the bf16x3 split kernel.                         */
+ * 4 = use the fp32-MFMA GEMM kernel instead of the bf16x3 split kernel, 7 = first conv and the pool behind
+ * it as separate launches, 8 = the first conv + pool kernel on its narrow tile with per-voxel sum / sign
+ * stores everywhere (same bits; ALQ_DCP_NARROW at model creation).                                */
 int alq_debug_set(int key, int value);
 /* What the last pass of a model ran on (tests / bench reporting).  what = 0: 1 when the matrix cores of the context's device
  * keep fp16 subnormal operands (probed once; the one-accumulator form of the plane-sweep engine needs it), 1: 1 when the last
@@ -394,6 +400,9 @@ int alq_debug_set(int key, int value);
  * per-layer fall-back of alq_model_set_weights_device and the lazy forms behind the debug knobs); saturates at 2^31 - 1.
  * 15: 1 when the last general backward sweep ran the fused layer-sum kernels of csrc/lsum.hip (alq_class_layer_sums), 0 after
  * alq_param_grads / alq_grad_sqnorms.
+ * 16: form of the first conv + pool kernel (csrc/direct.hip) in the last forward pass: 0 = it did not run, 1 / 2 = narrow tile
+ * (8 x 16 x 16 voxels) with scalar / 16-byte row loads, 4 / 5 = the same on the wide tile (8 x 8 x 32), 6 = wide tile on whole-tile
+ * volumes with 16-byte channel-sum and sign-byte stores.
  * Returns the answer or a negative error code.  */
 int alq_model_engine_info(alq_model *m, int what);
 

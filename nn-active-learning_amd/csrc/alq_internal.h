@@ -287,7 +287,9 @@ struct Igemm2Fuse {
 };
 
 extern unsigned long long *g_igemm2_dbg;
-extern int g_dbg_knobs[8];
+constexpr int ALQ_NKNOBS = 9;
+extern int g_dbg_knobs[ALQ_NKNOBS];
+extern int g_dcp_last_form;      // direct.hip: form of the last first conv + pool launch
 extern int g_no_f16x2;        // ALQ_NO_F16X2, read when a model is created: bf16x3 split in every launch
 extern int g_no_fixed;        // ALQ_NO_FIXED (A/B runs, bit-identity test): igemm4 launches use the runtime-constant instantiation only
 extern int g_no_xcd_order;    // ALQ_NO_XCD_ORDER (A/B runs): igemm4 tiles in dispatch order

@@ -117,12 +117,16 @@ struct DirectPoolArgs {
 };
 
 // Schedule: ONE workgroup barrier (after the halo'd input block is in LDS); from there every wave works alone on its
-// slab of 1 x 8 x 8 windows = 2 x 16 x 16 voxels, one z plane (4 voxels x 8 channels per thread) per pass; 33 KB of
-// LDS and <= 128 registers: four workgroups (16 waves) per CU.
+// slab of 1 x TWY x TWX windows (TWX = 16: 2 x 8 x 32 voxels, whole rows of a 32-voxel volume; TWX = 8: 2 x 16 x 16 for
+// narrower volumes), one z plane (4 voxels x 8 channels per thread) per pass; <= 128 registers and 32,384 B (TWX = 16) or
+// 33,664 B (TWX = 8) of LDS; the FULL instantiation (TWX = 16 only) adds the sum / sign planes: 38,528 B.  Four workgroups
+// (16 waves) per CU by registers and by LDS (4 x 38,528 = 154,112 of 163,840 B).  The narrow tile has no FULL form: with it
+// four workgroups would take 159,232 B, and a volume 16 voxels wide runs exactly the kernel it ran before the wide tile.
 // The kernel is VALU-issue bound (PMC: SQ_ACTIVE_INST_VALU 60 % of the SIMD time, 2.4 k vector instructions per wave of
 // which 864 are the packed FMAs), so everything around the FMAs is written for instruction count:
-//  * halo'd block: rows of 16 aligned floats + two edge values -> 3 float4 + 2 scalar loads per thread with one
-//    division per item (13 scalar loads with two divisions and 64-bit addresses each were 690 instructions, 29 %);
+//  * halo'd block: rows of 2 TWX aligned floats + two edge values -> float4 and scalar loads with one division per item:
+//    3 float4 + 2 scalar per thread at TWX = 8, 4 float4 + 1 scalar at TWX = 16 (13 scalar loads with two divisions and
+//    64-bit addresses each were 690 instructions, 29 %);
 //  * v_pk_fma_f32 takes the broadcast input straight from one half of an aligned register pair (op_sel), so the
 //    64 inputs live in 32 pairs instead of 64 duplicated pairs (no copies, 64 registers less);
 //  * channel sums and the patch maximum come from the registers that hold the results, not from the store loop;
@@ -131,7 +135,11 @@ struct DirectPoolArgs {
 //    q ^ ((q >> 3) & 3): ds_write_b128 serves 8 consecutive lanes per cycle over 32 banks, and the 8 windows of a row
 //    (64 B apart) then hit 8 different 16-byte bank groups instead of 2 (4-way conflicts: SQ_LDS_BANK_CONFLICT was
 //    40 % of the LDS cycles); the reading lanes take consecutive positions, and since the XOR only permutes chunks
-//    inside a 64-byte segment a store instruction still covers a contiguous 1 KB.
+//    inside a 64-byte segment a store instruction still covers a contiguous run: 512 B per row at TWX = 8, and at
+//    TWX = 16 one whole, aligned 1 KB row of a 32-voxel volume (no row is shared with another workgroup);
+//  * channel sums and sign bytes of a full tile take the same road (`vec`): a plane of them (2 TWY rows) is collected
+//    in 1.5 KB of wave-private LDS and leaves as ONE 16-byte store per lane (sums; at TWX = 16 a contiguous 1 KB) and one
+//    per lane of the lower half wave (sign bytes, 512 B) instead of eight 4-byte and eight 2-byte stores per lane.
 // Accumulation order per output is unchanged (bias, then taps z, y, x ascending, one fma each): same bits.
 // the weight pair is a scalar register pair: the weights come through the scalar cache (s_load), not through LDS
 // broadcasts (108 ds_read_b128 per wave were a quarter of the LDS cycles) and hold no vector registers
@@ -142,16 +150,35 @@ static __device__ __forceinline__ void dcp_fma_hi(f32x2 &acc, const f32x2 x, con
     asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,0,0] op_sel_hi:[1,1,1]" : "+v"(acc) : "v"(x), "s"(w));
 }
 typedef const __attribute__((address_space(4))) f32x4 *dcp_cw4;
+// the lane id as a value the compiler does not tie to earlier copies of it
+static __device__ __forceinline__ int dcp_lane() {
+    int l = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    asm volatile("" : "+v"(l));
+    return l;
+}
 
-template <bool ALIGNED>      // ALIGNED: the row length is a multiple of 4 voxels (float4 loads of the block's rows)
+// halo'd block + a half plane of activations per wave; the FULL instantiations add a plane of sums and sign bytes per wave
+constexpr int dcp_lds_floats(int TWX, bool FULL) { return (2 * 4 + 2) * (2 * (64 / TWX) + 2) * (2 * TWX + 8) + 4 * (1024 + (FULL ? 384 : 0)); }
+
+int g_dcp_last_form = 0;      // form of the last launch: 1 + (TWX == 16 ? 3 : 0) + (FULL ? 2 : ALIGNED ? 1 : 0); 3 does not exist   (engine info 16)
+
+// ALIGNED: the row length is a multiple of 4 voxels (float4 loads of the block's rows); TWX: windows per workgroup along x;
+// FULL (needs ALIGNED and TWX = 16): every tile of the volume is whole and sums / sign bytes may leave as 16-byte runs (checked at launch) -
+// the partial-tile code and its registers are not in that instantiation
+template <bool ALIGNED, int TWX, bool FULL>
 __global__ __launch_bounds__(256, 4) void direct_conv_pool_kernel(const DirectPoolArgs a) {
-    constexpr int TWZ = 4, TWY = 8, TWX = 8;                 // windows per workgroup
+    static_assert(!FULL || (ALIGNED && TWX == 16), "the FULL form exists for the wide tile only");
+    constexpr int TWZ = 4, TWY = 64 / TWX;                   // windows per workgroup: a wave owns one z layer of them
     constexpr int HZ = 2 * TWZ + 2, HY = 2 * TWY + 2, HX = 2 * TWX + 2;
-    constexpr int AX = 24;                                   // LDS row: x = -1 at column 3, the 16 aligned voxels from column 4
+    constexpr int AX = 2 * TWX + 8;                          // LDS row: x = -1 at column 3, the 2 TWX aligned voxels from column 4
+    constexpr int P4 = TWX / 2;                              // float4 parts of a block row
     extern __shared__ __attribute__((aligned(16))) float dcp_lds[];
     float *Al = dcp_lds;                                   // HZ * HY rows of AX
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    float *Ol = dcp_lds + HZ * HY * AX + wv * 1024;  // this wave's half plane: 8 x 16 voxels x 8 channels
+    const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    float *Ol = dcp_lds + HZ * HY * AX + wv * 1024;  // this wave's half plane: TWY x 2 TWX voxels x 8 channels
+    // (FULL only: the other instantiations allocate and touch neither)
+    float *Sw = dcp_lds + HZ * HY * AX + 4 * 1024 + wv * 384;      // this wave's plane of channel sums (2 TWY x 2 TWX floats) ...
+    unsigned *Gl = reinterpret_cast<unsigned *>(Sw + 256);          // ... and of sign bytes (two per voxel)
     const dcp_cw4 Wc = (dcp_cw4)(a.W);          // [27][8], read-only for the launch: constant address space -> s_load
     int t = blockIdx.x;
     const int tx = t % a.tilesX; t /= a.tilesX;
@@ -163,19 +190,20 @@ __global__ __launch_bounds__(256, 4) void direct_conv_pool_kernel(const DirectPo
     const float *src = a.in + pv0;
     if constexpr (ALIGNED) {
         // all loads first, then the LDS writes: one memory latency per workgroup
-        f32x4 mid[3];
-        float edge[2];
+        constexpr int NM = (HZ * HY * P4 + 255) / 256, NE = (HZ * HY * 2 + 255) / 256;
+        f32x4 mid[NM];
+        float edge[NE];
 #pragma unroll
-        for (int it = 0; it < 3; ++it) {
-            const int k = tid + it * 256, row = k >> 2, part = k & 3;
+        for (int it = 0; it < NM; ++it) {
+            const int k = tid + it * 256, row = k / P4, part = k % P4;
             const int hz = row / HY, hy = row - hz * HY;
             const int iz = z0 + hz - 1, iy = y0 + hy - 1, ix = x0 + 4 * part;
             mid[it] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (k < HZ * HY * 4 && (unsigned)iz < (unsigned)a.D && (unsigned)iy < (unsigned)a.H && ix < a.Wd)
+            if (k < HZ * HY * P4 && (unsigned)iz < (unsigned)a.D && (unsigned)iy < (unsigned)a.H && ix < a.Wd)
                 mid[it] = *reinterpret_cast<const f32x4 *>(src + (iz * a.H + iy) * a.Wd + ix);
         }
 #pragma unroll
-        for (int it = 0; it < 2; ++it) {
+        for (int it = 0; it < NE; ++it) {
             const int k = tid + it * 256, row = k >> 1, side = k & 1;
             const int hz = row / HY, hy = row - hz * HY;
             const int iz = z0 + hz - 1, iy = y0 + hy - 1, ix = x0 + (side ? HX - 2 : -1);
@@ -184,12 +212,12 @@ __global__ __launch_bounds__(256, 4) void direct_conv_pool_kernel(const DirectPo
                 edge[it] = src[(iz * a.H + iy) * a.Wd + ix];
         }
 #pragma unroll
-        for (int it = 0; it < 3; ++it) {
+        for (int it = 0; it < NM; ++it) {
             const int k = tid + it * 256;
-            if (k < HZ * HY * 4) *reinterpret_cast<f32x4 *>(Al + (k >> 2) * AX + 4 + 4 * (k & 3)) = mid[it];
+            if (k < HZ * HY * P4) *reinterpret_cast<f32x4 *>(Al + (k / P4) * AX + 4 + 4 * (k % P4)) = mid[it];
         }
 #pragma unroll
-        for (int it = 0; it < 2; ++it) {
+        for (int it = 0; it < NE; ++it) {
             const int k = tid + it * 256;
             if (k < HZ * HY * 2) Al[(k >> 1) * AX + ((k & 1) ? HX + 2 : 3)] = edge[it];
         }
@@ -219,7 +247,7 @@ __global__ __launch_bounds__(256, 4) void direct_conv_pool_kernel(const DirectPo
     const int wx = lane % TWX, wy = lane / TWX, wz = wv;
     const int pz = tz * TWZ + wz, py = ty * TWY + wy, px = tx * TWX + wx;      // pooled coordinates
     const int PD = a.D / 2, PH = a.H / 2, PW = a.Wd / 2;
-    const bool wlive = pz < PD && py < PH && px < PW;
+    const bool wlive = FULL || (pz < PD && py < PH && px < PW);
     // 4x4x4 input block of the thread's window in 32 register pairs
     f32x2 in[4][4][2];
 #pragma unroll
@@ -230,7 +258,6 @@ __global__ __launch_bounds__(256, 4) void direct_conv_pool_kernel(const DirectPo
             in[p][q][0] = f32x2{row[0], row[1]};
             in[p][q][1] = f32x2{row[2], row[3]};
         }
-    const unsigned pvox = (unsigned)((pz * PH + py) * PW + px);                // pooled voxel inside the patch
     const long long pp0 = n * (long long)PD * PH * PW;
     char *pbase = reinterpret_cast<char *>(a.pout + pp0 * a.po_cs + a.po_c0);    // uniform bases, 32-bit lane offsets
     char *abase = reinterpret_cast<char *>(a.argmax + pp0 * 2);
@@ -245,13 +272,18 @@ __global__ __launch_bounds__(256, 4) void direct_conv_pool_kernel(const DirectPo
     char *obase = reinterpret_cast<char *>(a.out + pv0 * a.out_cs + a.out_c0);
     char *sbase = a.osum ? reinterpret_cast<char *>(a.osum + pv0) : nullptr;
     unsigned char *gbase = a.sg ? a.sg + ((pv0 * a.out_cs + a.out_c0) >> 2) : nullptr;       // out_cs, out_c0 multiples of 4 (launch)
-    const bool full = z0 + 2 * TWZ <= a.D && y0 + 2 * TWY <= a.H && x0 + 2 * TWX <= a.Wd;      // uniform
+    const bool full = FULL || (z0 + 2 * TWZ <= a.D && y0 + 2 * TWY <= a.H && x0 + 2 * TWX <= a.Wd);      // uniform
     const int vox00 = (((z0 + 2 * wz) * a.H + y0 + 2 * wy) * a.Wd + x0 + 2 * wx);      // first voxel of the window, inside the patch
     const int sw = (wx >> 1) & 3;               // chunk swizzle: position = chunk ^ ((chunk >> 3) & 3), chunk >> 2 == wx
-    // store loop: lane -> chunk position lp of the half plane's row 2 * it + lb (every other row of the plane); the
-    // chunk there is lq
-    const int lp = lane & 31, lb = lane >> 5, lq = lp ^ ((lp >> 3) & 3);
+    // store loop: a row of the half plane is CPR 16-byte chunks, a store instruction covers RPI rows; lane -> chunk
+    // position lp of the half plane's row RPI * it + lb (every other row of the plane); the chunk there is lq
+    constexpr int CPR = 4 * TWX, RPI = 64 / CPR;
+    const int lp = lane % CPR, lb = lane / CPR, lq = lp ^ ((lp >> 3) & 3);
     const int voff = (2 * lb * a.Wd + (lq >> 1)) * a.out_cs + (lq & 1) * 4;
+    constexpr bool vec = FULL;                      // sums and sign bytes of the plane leave through Sw / Gl
+    // the lane's voxel (row 2 wy, x 2 wx) of the plane there; the other three of a plane at constant offsets
+    float *Sl = Sw + 2 * wy * (2 * TWX) + 2 * wx;
+    unsigned short *Gl16 = reinterpret_cast<unsigned short *>(Gl) + 2 * wy * (2 * TWX) + 2 * wx;
 #pragma unroll
     for (int vz = 0; vz < 2; ++vz) {
         f32x2 acc[4][4];
@@ -291,11 +323,21 @@ __global__ __launch_bounds__(256, 4) void direct_conv_pool_kernel(const DirectPo
                     o[2 * c + 1] = a.relu ? fmaxf(acc[v][c].y, 0.f) : acc[v][c].y;
                 }
                 const int ly = 2 * wy + vy, lx = 2 * wx + vx, q0 = 2 * lx;
-                float *orow = Ol + wy * 128;
+                float *orow = Ol + wy * (TWX * 16);
                 *reinterpret_cast<f32x4 *>(orow + ((q0 ^ sw) << 2)) = f32x4{o[0], o[1], o[2], o[3]};
                 *reinterpret_cast<f32x4 *>(orow + (((q0 + 1) ^ sw) << 2)) = f32x4{o[4], o[5], o[6], o[7]};
                 const bool vin = full || (z < a.D && y0 + ly < a.H && x0 + lx < a.Wd);
-                if (vin) {
+                if (vec) {          // (full tile: every voxel is inside) the lane's two voxels of this row, side by side
+                    if (gbase) {
+                        const unsigned lo4 = (o[0] > 0.f ? 1u : 0u) | (o[1] > 0.f ? 2u : 0u) | (o[2] > 0.f ? 4u : 0u) | (o[3] > 0.f ? 8u : 0u);
+                        const unsigned hi4 = (o[4] > 0.f ? 1u : 0u) | (o[5] > 0.f ? 2u : 0u) | (o[6] > 0.f ? 4u : 0u) | (o[7] > 0.f ? 8u : 0u);
+                        Gl16[(vy * (2 * TWX) + vx)] = (unsigned short)(lo4 | (hi4 << 8));
+                    }
+                    if (sbase) Sl[vy * (2 * TWX) + vx] = ((o[0] + o[1]) + (o[2] + o[3])) + ((o[4] + o[5]) + (o[6] + o[7]));
+                    if (!a.relu)
+                        amx = fmaxf(amx, fmaxf(fmaxf(fmaxf(__builtin_fabsf(o[0]), __builtin_fabsf(o[1])), fmaxf(__builtin_fabsf(o[2]), __builtin_fabsf(o[3]))),
+                                               fmaxf(fmaxf(__builtin_fabsf(o[4]), __builtin_fabsf(o[5])), fmaxf(__builtin_fabsf(o[6]), __builtin_fabsf(o[7])))));
+                } else if (vin) {
                     if (gbase) {      // 8 channels = two sign bytes, written as one 16-bit store
                         const unsigned lo4 = (o[0] > 0.f ? 1u : 0u) | (o[1] > 0.f ? 2u : 0u) | (o[2] > 0.f ? 4u : 0u) | (o[3] > 0.f ? 8u : 0u);
                         const unsigned hi4 = (o[4] > 0.f ? 1u : 0u) | (o[5] > 0.f ? 2u : 0u) | (o[6] > 0.f ? 4u : 0u) | (o[7] > 0.f ? 8u : 0u);
@@ -326,13 +368,13 @@ __global__ __launch_bounds__(256, 4) void direct_conv_pool_kernel(const DirectPo
 #pragma unroll
                 for (int it = 0; it < 4; ++it)
                     __builtin_nontemporal_store(*reinterpret_cast<const f32x4 *>(Ol + (it * 64 + lane) * 4),
-                                                reinterpret_cast<f32x4 *>(obase + (unsigned)(orow0 + 4 * it * a.Wd * a.out_cs + voff) * 4u));
+                                                reinterpret_cast<f32x4 *>(obase + (unsigned)(orow0 + 2 * RPI * it * a.Wd * a.out_cs + voff) * 4u));
             } else {
 #pragma unroll
                 for (int it = 0; it < 4; ++it) {
-                    const int row = 2 * (2 * it + lb) + vy;
+                    const int row = 2 * (RPI * it + lb) + vy;
                     if (z < a.D && y0 + row < a.H && x0 + (lq >> 1) < a.Wd)
-                        *reinterpret_cast<f32x4 *>(obase + (unsigned)(orow0 + 4 * it * a.Wd * a.out_cs + voff) * 4u) =
+                        *reinterpret_cast<f32x4 *>(obase + (unsigned)(orow0 + 2 * RPI * it * a.Wd * a.out_cs + voff) * 4u) =
                             *reinterpret_cast<const f32x4 *>(Ol + (it * 64 + lane) * 4);
                 }
             }
@@ -340,8 +382,23 @@ __global__ __launch_bounds__(256, 4) void direct_conv_pool_kernel(const DirectPo
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         }
+        if (vec) {      // the plane's sums: lane -> 4 voxels of row lane / (TWX / 2); its sign bytes: lane < 32 -> 8 voxels (out_cs = 8: 2 B each)
+            const int vrow = (z * a.H + y0) * a.Wd + x0;
+            const int sl = dcp_lane();      // (derived afresh: offsets held across the FMA blocks would be spilled)
+            if (sbase)
+                *reinterpret_cast<f32x4 *>(sbase + (unsigned)(vrow + (sl / (TWX / 2)) * a.Wd + 4 * (sl % (TWX / 2))) * 4u) =
+                    *reinterpret_cast<const f32x4 *>(Sw + sl * 4);
+            if (gbase && sl < 32)
+                *reinterpret_cast<uint4 *>(gbase + (unsigned)(vrow + (sl / (TWX / 4)) * a.Wd + 8 * (sl % (TWX / 4))) * 2u) =
+                    *reinterpret_cast<const uint4 *>(Gl + sl * 4);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        }
     }
     if (wlive) {
+        const int el = dcp_lane();
+        const unsigned pvox = (unsigned)(((tz * TWZ + wv) * PH + ty * TWY + el / TWX) * PW + tx * TWX + el % TWX);      // pooled voxel inside the patch
         char *prow = pbase + pvox * (unsigned)a.po_cs * 4u;
         *reinterpret_cast<f32x4 *>(prow) = f32x4{best[0], best[1], best[2], best[3]};
         *reinterpret_cast<f32x4 *>(prow + 16) = f32x4{best[4], best[5], best[6], best[7]};
@@ -379,32 +436,35 @@ int direct_conv_pool_launch(alq_ctx *ctx, const float *d_W, const View &in, cons
     a.osum = osum; a.posum = posum; a.W = d_W; a.bias = bias; a.amax = amax; a.sg = sg; a.psg = psg;
     a.out_cs = out.cs; a.out_c0 = out.c0; a.po_cs = pout.cs; a.po_c0 = pout.c0;
     a.D = in.D; a.H = in.H; a.Wd = in.W; a.N = N; a.relu = relu;
-    a.tilesZ = (pout.D + 3) / 4; a.tilesY = (pout.H + 7) / 8; a.tilesX = (pout.W + 7) / 8;
+    // a workgroup covers 8 x 8 x 32 voxels (whole rows of a 32-voxel volume: every output row is one aligned run of one wave)
+    // where that leaves no more idle lanes along x than 8 x 16 x 16 does; knob 8 (ALQ_DCP_NARROW=1 at model creation or
+    // alq_debug_set(8, 1): A/B runs, bit-identity test): the narrow tile with per-voxel sum / sign stores everywhere
+    const bool narrow_only = g_dbg_knobs[8] != 0;
+    const bool wide = !narrow_only && (in.W + 31) / 32 * 32 <= (in.W + 15) / 16 * 16;
+    const int twx = wide ? 16 : 8, twy = 64 / twx;
+    a.tilesZ = (pout.D + 3) / 4; a.tilesY = (pout.H + twy - 1) / twy; a.tilesX = (pout.W + twx - 1) / twx;
+    const bool aligned = in.W % 4 == 0 && (reinterpret_cast<uintptr_t>(in.p) & 15) == 0;
+    // whole tiles only, sums and sign bytes of a voxel row contiguous and 16-byte aligned: the FULL instantiation
+    const bool fullv = wide && aligned && in.D % 8 == 0 && in.H % (2 * twy) == 0 && in.W % (2 * twx) == 0 && out.cs == 8 && out.c0 == 0 &&
+                       (reinterpret_cast<uintptr_t>(osum) & 15) == 0 && (reinterpret_cast<uintptr_t>(sg) & 15) == 0;
     ProfScope ps(ctx, PROF_DIRECT, flops_per_patch * N);
-    const size_t lds = (10 * 18 * 24 + 4 * 1024) * sizeof(float);
     // in-patch offsets are 32-bit in the kernel
     ALQ_REQUIRE((long long)in.D * in.H * in.W * std::max(std::max(out.cs, pout.cs), 1) < (1LL << 29), ALQ_EUNSUPPORTED,
                 "direct conv+pool: volume too large");
     const dim3 grid((unsigned)((long long)N * a.tilesZ * a.tilesY * a.tilesX));
-    const bool aligned = in.W % 4 == 0 && (reinterpret_cast<uintptr_t>(in.p) & 15) == 0;
-    if (aligned) {
-        static bool attr_a = false;
-        if (!attr_a) {
-            ALQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(direct_conv_pool_kernel<true>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            attr_a = true;
-        }
-        hipLaunchKernelGGL(direct_conv_pool_kernel<true>, grid, dim3(256), lds, ctx->stream, a);
-    } else {
-        static bool attr_u = false;
-        if (!attr_u) {
-            ALQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(direct_conv_pool_kernel<false>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            attr_u = true;
-        }
-        hipLaunchKernelGGL(direct_conv_pool_kernel<false>, grid, dim3(256), lds, ctx->stream, a);
+    const size_t lds = (size_t)dcp_lds_floats(twx, fullv) * sizeof(float);
+    void (*kern)(const DirectPoolArgs) =
+        wide ? (fullv ? direct_conv_pool_kernel<true, 16, true> : aligned ? direct_conv_pool_kernel<true, 16, false> : direct_conv_pool_kernel<false, 16, false>)
+             : (aligned ? direct_conv_pool_kernel<true, 8, false> : direct_conv_pool_kernel<false, 8, false>);
+    static bool attr_set[6] = {false, false, false, false, false, false};
+    const int ki = (wide ? 3 : 0) + (fullv ? 2 : aligned ? 1 : 0);
+    if (!attr_set[ki]) {
+        ALQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        attr_set[ki] = true;
     }
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, ctx->stream, a);
     ALQ_HIP(hipGetLastError());
+    g_dcp_last_form = ki + 1;
     return ALQ_OK;
 }
 

@@ -159,7 +159,7 @@ struct alq_model {
     int64_t epp = 0;               // elements per patch
     // Engine-selection knobs, read from the environment ONCE, when this model is created; every call applies the
     // model's own snapshot (alq_debug_set overrides a key for all models until it is set back to -1 / re-set).
-    int knobs[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int knobs[ALQ_NKNOBS] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     int no_f16x2 = 0;
     int no_xcd_order = 0;
     int requested_batch = 0;      // what alq_model_create was asked for (max_batch may be lower: 32-bit tensor offsets)
@@ -185,6 +185,7 @@ struct alq_model {
     int no_f3d = 0, last_f3f = 0;  // ALQ_NO_F3D (A/B): enc2's forward on the two-slot engine + the pool as its own launch; the last forward pass ran them fused (f3d.hip)
     int no_d3b = 0, last_d3b = 0;  // ALQ_NO_D3D_BWD (A/B): only the backward launch on the two-slot engine; the last backward pass ran it on d3d.hip
     int no_t3d = 0;                // ALQ_NO_T3D (A/B): conv_transpose launches on the two-slot engine (igemm4) as in round 4
+    int last_dcp = 0;              // form of the first conv + pool kernel the last forward pass ran, 0 = it did not run (direct.hip: g_dcp_last_form)
     int last_t3f = 0, last_t3b = 0;   // conv_transpose launches of the last forward / backward pass that ran on the row-sweep engine
     bool last_f16_derived = false; // the last forward pass ran a launch on the fp16x2 split with derived input bounds
     int64_t host_pack_elems = 0;   // weight elements that went through the host packers since the model was created (engine info 14)
@@ -259,12 +260,12 @@ static int upload1(alq_model *m, IgemmPlan *p) {
 }
 
 static bool g_use_v2 = true;
-static int g_knob_override[8] = {-1, -1, -1, -1, -1, -1, -1, -1};   // alq_debug_set: >= 0 overrides every model's snapshot
+static int g_knob_override[ALQ_NKNOBS] = {-1, -1, -1, -1, -1, -1, -1, -1, -1};   // alq_debug_set: >= 0 overrides every model's snapshot
 
 // The kernels' launch helpers read the process-wide g_dbg_knobs / g_no_f16x2; each entry point loads them from the
 // model it was called on, so creating another model (or its environment) never changes a live one.
 static void apply_knobs(const alq_model *m) {
-    for (int k = 0; k < 8; ++k) g_dbg_knobs[k] = g_knob_override[k] >= 0 ? g_knob_override[k] : m->knobs[k];
+    for (int k = 0; k < ALQ_NKNOBS; ++k) g_dbg_knobs[k] = g_knob_override[k] >= 0 ? g_knob_override[k] : m->knobs[k];
     g_no_f16x2 = m->no_f16x2;
     g_no_xcd_order = m->no_xcd_order;
     g_no_fixed = m->no_fixed;
@@ -903,6 +904,7 @@ static int run_forward(alq_model *m, const float *d_x, int N, bool with_sums, bo
     m->last_t3f = 0;
     m->last_d3f = 0;
     m->last_f3f = 0;
+    m->last_dcp = 0;
     // A conv / conv_transpose launch contracts with the fp16x2 split if it knows max |x| per patch of (every part of)
     // its input ahead of time: the launches that produce those tensors report them (`prod`), the consumers (`cons`)
     // read one scale per tile.  Producers: the first conv + pool kernel and one-patch-per-tile igemm4 launches.
@@ -1047,6 +1049,7 @@ static int run_forward(alq_model *m, const float *d_x, int N, bool with_sums, bo
                                                     with_sums ? ly.osum : nullptr, with_sums ? nx->osum : nullptr, N,
                                                     ly.fwd[0].pd.flops_per_patch, prod[i] ? ly.amax_fwd : nullptr,
                                                     sg_here ? ly.out.sg : nullptr, (sg_here && nx->out.sg) ? nx->out.sg : nullptr));
+                    m->last_dcp = g_dcp_last_form;
                     ly.signs_ready = sg_here;
                     nx->signs_ready = sg_here && nx->out.sg != nullptr;      // (the pool's output: sign of the window maximum)
                     if (any_derived) {      // per-patch bounds on every later layer's output from this layer's measured maximum
@@ -1950,9 +1953,10 @@ int alq_model_create(alq_ctx *ctx, const alq_layer_t *layers, int n_layers, cons
             const char *e = getenv("ALQ_F16_DERIVED"), *n = getenv("ALQ_NO_F16_DERIVED");
             m->no_f16_derived = ((e && atoi(e) == 0) || (n && atoi(n) == 1)) ? 1 : 0;
         }
-        static const char *names[8] = {"ALQ_DEBUG_REPEAT", "ALQ_DEBUG_FLAGS", "ALQ_NO_BWD_FUSE", "ALQ_NO_FWD_FUSE", "ALQ_NO_V3", "ALQ_NO_V4",
-                                       "ALQ_NO_POOL_FIRST", "ALQ_NO_CONV_POOL"};
-        for (int k = 0; k < 8; ++k) {
+        // (ALQ_DCP_NARROW: the first conv + pool kernel on its narrow tile with per-voxel sum / sign stores everywhere, direct.hip)
+        static const char *names[ALQ_NKNOBS] = {"ALQ_DEBUG_REPEAT", "ALQ_DEBUG_FLAGS", "ALQ_NO_BWD_FUSE", "ALQ_NO_FWD_FUSE", "ALQ_NO_V3", "ALQ_NO_V4",
+                                                "ALQ_NO_POOL_FIRST", "ALQ_NO_CONV_POOL", "ALQ_DCP_NARROW"};
+        for (int k = 0; k < ALQ_NKNOBS; ++k) {
             const char *v = getenv(names[k]);
             if (v) m->knobs[k] = atoi(v);
         }
@@ -2605,6 +2609,28 @@ int alq_model_debug_copy(alq_model *m, int layer_idx, int what, int N, float *d_
         ALQ_HIP(hipMemcpyAsync(d_out, src, (size_t)e * 4, hipMemcpyDeviceToDevice, m->ctx->stream));
         return ALQ_OK;
     }
+    if (what >= 11 && what <= 13) {
+        // test hooks for the kernels that write these next to the activation: 11 = channel sums of the layer's output (floats),
+        // 12 = the sign field (View::sg) of the rows its output lies in, 13 = a pool layer's arg-max bytes; 12 / 13 as raw bytes
+        if (what == 11) {
+            ALQ_REQUIRE(ly.osum && m->last_call_fisher, ALQ_EUNSUPPORTED, "layer %d: no channel sums of its output in the last pass", layer_idx);
+            if (elems_out) *elems_out = (int64_t)N * ly.out.vox();
+            ALQ_HIP(hipMemcpyAsync(d_out, ly.osum, (size_t)N * ly.out.vox() * sizeof(float), hipMemcpyDeviceToDevice, m->ctx->stream));
+            return ALQ_OK;
+        }
+        if (what == 12) {      // cs / 4 bytes per voxel as they lie in memory: the layer's own are the C / 4 from byte c0 / 4 of each
+            const View &v = ly.out;
+            ALQ_REQUIRE(v.sg && ly.signs_ready && ((v.C | v.cs | v.c0) & 3) == 0 && ((int64_t)N * v.vox() * v.cs) % 16 == 0, ALQ_EUNSUPPORTED,
+                        "layer %d: no sign field of its output in the last pass", layer_idx);
+            if (elems_out) *elems_out = (int64_t)N * v.vox() * v.cs / 16;
+            ALQ_HIP(hipMemcpyAsync(d_out, v.sg, (size_t)N * v.vox() * v.cs / 4, hipMemcpyDeviceToDevice, m->ctx->stream));
+            return ALQ_OK;
+        }
+        ALQ_REQUIRE(ly.spec.type == ALQ_POOL && ly.argmax && ((int64_t)N * ly.out.vox() * ly.out.C) % 4 == 0, ALQ_EUNSUPPORTED, "layer %d has no arg-max field", layer_idx);
+        if (elems_out) *elems_out = (int64_t)N * ly.out.vox() * ly.out.C / 4;
+        ALQ_HIP(hipMemcpyAsync(d_out, ly.argmax, (size_t)N * ly.out.vox() * ly.out.C, hipMemcpyDeviceToDevice, m->ctx->stream));
+        return ALQ_OK;
+    }
     if (what == 0 || what == 1) {
         // the last conv under a fused fc head: a Fisher pass stores neither its output nor the cotangent of it
         const Layer &head = m->layers.back();
@@ -2627,7 +2653,8 @@ int alq_model_debug_copy(alq_model *m, int layer_idx, int what, int N, float *d_
 }
 
 int alq_model_engine_info(alq_model *m, int what) {
-    ALQ_REQUIRE(m && ((what >= 0 && what <= 3) || (what >= 5 && what <= 15)), ALQ_EINVAL, "alq_model_engine_info: bad argument");
+    ALQ_REQUIRE(m && ((what >= 0 && what <= 3) || (what >= 5 && what <= 16)), ALQ_EINVAL, "alq_model_engine_info: bad argument");
+    if (what == 16) return m->last_dcp;       // form of the first conv + pool kernel in the last forward pass: 0 none, 1 / 2 narrow tile (unaligned / aligned rows), 4 / 5 wide tile, 6 wide tile with 16-byte sum / sign stores
     if (what == 15) return m->last_lsum;      // the last general backward sweep ran the fused layer-sum kernels (lsum.hip)
     if (what == 14) return m->host_pack_elems > 0x7fffffffll ? 0x7fffffff : (int)m->host_pack_elems;      // weight elements through the host packers since creation (saturates)
     if (what == 13) return m->last_c3_bwd ? m->c3_bwd_rows : 0;      // form of the head conv's backward kernel: 7 = 27 taps in 7 k-steps, 8 / 4 = the 9-k-step kernel
@@ -2655,7 +2682,7 @@ int alq_model_engine_info(alq_model *m, int what) {
 }
 
 int alq_debug_set(int key, int value) {
-    ALQ_REQUIRE(key >= 0 && key < 8, ALQ_EINVAL, "alq_debug_set: bad key");
+    ALQ_REQUIRE(key >= 0 && key < ALQ_NKNOBS, ALQ_EINVAL, "alq_debug_set: bad key");
     // an explicit override of every model's snapshot; 0 restores "whatever the model was created with" for the keys
     // whose environment default is 0 (all of them unless the ALQ_* diagnostics variables were set at creation)
     g_knob_override[key] = value > 0 ? value : -1;

@@ -316,7 +316,10 @@ __global__ __launch_bounds__(256, 2) void t3d_bwd_kernel(const T3BwdArgs a) {
     const unsigned ld_off = (unsigned)lane * 16u;
     const unsigned st_off = (unsigned)n * 64u + (unsigned)kg * 16u;       // cell n, channels 4 kg .. + 3 inside a 1 KB row of d_in
     const unsigned mk_off = (unsigned)n * 4u + (unsigned)kg;
-    const unsigned sm_off = kg == 0 ? (unsigned)n * 4u : T3_OOB;
+    // channel sums leave once per PAIR of tiles (rows iy odd, iy - 1: one aligned 128-byte line of d_sum): lanes kg = 0 carry the
+    // even row's 16 sums, lanes kg = 1 the odd row's (every lane holds its cell's sum after the butterfly)
+    static_assert(T3B_PF == 2, "the sum store pairs the two tiles of a pass over the body");
+    const unsigned sm_off = kg < 2 ? (unsigned)n * 4u + (unsigned)kg * 64u : T3_OOB;
     const float sc = a.scale;
     const int total = t3_total_tiles(a.N);
 
@@ -364,6 +367,7 @@ __global__ __launch_bounds__(256, 2) void t3d_bwd_kernel(const T3BwdArgs a) {
     for (int T0 = -T3B_PF; T0 < total; T0 += T3B_PF) {
         const bool live = T0 >= 0;
         const unsigned st_o = live ? st_off : T3_OOB, sm_o = live ? sm_off : T3_OOB;
+        float s_odd = 0.f;      // the sums of the pass's first tile (odd iy)
 #pragma unroll
         for (int k = 0; k < T3B_PF; ++k) {
             const int T = T0 + k;
@@ -425,7 +429,9 @@ __global__ __launch_bounds__(256, 2) void t3d_bwd_kernel(const T3BwdArgs a) {
                 float s = (v.x + v.y) + (v.z + v.w);
                 s += __shfl_xor(s, 16, 64);
                 s += __shfl_xor(s, 32, 64);
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, s), sum_rsrc, (int)sm_o, (int)(crow * 64u), 0);
+                if (k == 0) s_odd = s;      // (tiles come in pairs: T0 is even, so k = 0 is sweep position s even, iy = 15 - s odd)
+                else
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, kg == 1 ? s_odd : s), sum_rsrc, (int)sm_o, (int)(crow * 64u), 0);
             }
             // (the store's data registers stay alive for a while: see the forward kernel's epilogue)
             __builtin_amdgcn_sched_barrier(0);
