@@ -260,6 +260,32 @@ int alq_param_grads(alq_model *m, const float *d_x, int N, int mode, int cls, co
 int alq_grad_sqnorms(alq_model *m, const float *d_x, int N, int cls, const int32_t *d_cls,
                      float *d_post, double *d_sq);
 
+/* Replaces: the Hessian-vector product behind the reference's influence functions - Influence.get_hess_vec_product /
+ * hessian_vector_product (Influence.py:64-166: tf.gradients of <grad L, stop_gradient(v)>, the Pearlmutter double-backward),
+ * what sess.run(model.hess_vecp) and PW_NN.batch_eval(..., 'hess_vecp') (PW_NN.py:467, :532-533) return and
+ * PW_sample_influence (Influence.py:369-453) feeds to scipy's Newton-CG.  d_hv [P] double = H v, H = the Hessian of
+ * loss_scale * sum_n CE(softmax(z_n), label_n) with respect to the flat parameter vector [W_0, b_0, W_1, b_1, ...] (order and
+ * layouts of alq_param_grads; d_v [P] float on the device in the same order; d_labels int32 [N], a label outside [0, c)
+ * contributes nothing; keep_prob 1).  The EXACT R-operator, not a Gauss-Newton product.  The ordinary forward pass with
+ * everything kept fixes the ReLU signs and the max-pool arg-max; on those decisions the call re-evaluates, in fp64 tensors of
+ * its own (csrc/hvp.hip): the activations, the posteriors and the first-order cotangents; the tangent forward pass (Rz_l =
+ * op(a_{l-1}; V_l) + c_l + op(Ra_{l-1}; W_l), ReLU by the stored sign, max-pool at the stored arg-max, 'con' skips
+ * concatenated); Rdelta = loss_scale (diag(p) - p p^T) Rz at the logits; one backward sweep of the tangent cotangent; and the
+ * two-term weight products.  Sums in a fixed order, no [N, P] buffer, no atomics - bit-identical from run to run, and exactly
+ * linear in v and in loss_scale under powers of two.
+ * h_layer_on (host, [L] bytes, or NULL = every layer; the reference's Hess_layers): a layer that is switched off is held
+ * constant - its entries of d_v are never read, its entries of d_hv are written as zeros (left alone when accumulate is set).
+ * accumulate = 1: d_hv += H v, so a set larger than max_batch is a sequence of calls with loss_scale = 1 / n_total.
+ * d_loss (optional): the scaled loss of the call.  The workspaces - four fp64 tensors per layer output (activation, cotangent
+ * and their two tangents, sized for max_batch), the slab partials of the conv weight products (at most 32 MiB), the fp64
+ * posteriors and an fp32 copy of the weights in the TF layout - are allocated on the device by the first call.  Until a call
+ * has uploaded them, a model keeps on the host the weight arrays alq_model_set_weights was given for conv / conv_transpose and
+ * wide fc layers (their engines hold split forms only); skinny fc layers and layers set by alq_model_set_weights_device are
+ * read from their resident fp32 copies.  Stream-ordered; synchronises only to upload weights set since the last call.
+ * ALQ_EINVAL: null d_x / d_labels / d_v / d_hv, N outside [1, max_batch], weights not set.                               */
+int alq_hess_vecp(alq_model *m, const float *d_x, int N, const int32_t *d_labels, float loss_scale, const float *d_v,
+                  const uint8_t *h_layer_on, int accumulate, double *d_hv, double *d_loss);
+
 /* Replaces: tf.train.GradientDescentOptimizer / AdamOptimizer .minimize (NN.py:591-615) on flat device vectors:
  * theta -= lr g;  Adam (TF-1.x defaults are the caller's: beta1 .9, beta2 .999, eps 1e-8), step count t >= 1:
  * lr_t = lr sqrt(1 - beta2^t) / (1 - beta1^t), m = b1 m + (1-b1) g, v = b2 v + (1-b2) g^2,

@@ -47,6 +47,16 @@ def load_winds(inds, imgs_path_file, target_shape, mean=None, labels_file=None):
     return np.stack(imgs), labels
 
 
+def add_loss_grad(model, pars=[]):
+    """NN.add_loss_grad (NN.py:862-871): `model.loss_grad`, the gradient of the mean cross-entropy `model.loss` with respect
+    to `pars` - layer names here, where the reference passes TF variables; [] = every variable.  Fetched with
+    `sess.run(model.loss_grad, {x, y_})` (alq_param_grads mode 1)."""
+    from .device import Handle
+    model.loss_grad = Handle('loss_grad')
+    model.loss_grad.model = model
+    model.loss_grad.layers = list(pars) if len(pars) else 'all'
+
+
 class CNN(DeviceModel):
     """NN.CNN(x, layer_dict, name, feature_layer, dropout, probes): same layer-dict schema
     ``{name: [depth,'conv',[kh,kw]] | [depth,'fc'] | [[window,stride],'pool']}``; `x` is replaced

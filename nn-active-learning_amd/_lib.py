@@ -54,6 +54,7 @@ _SIGNATURES = {
     'alq_param_grads': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_float, C.c_float, C.c_uint64, C.c_int64,
                                   C.POINTER(C.c_int32), C.c_int, C.c_int, _P, _P, _P]),
     'alq_grad_sqnorms': (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
+    'alq_hess_vecp': (C.c_int, [_P, _P, C.c_int, _P, C.c_float, _P, _P, C.c_int, _P, _P]),
     'alq_class_layer_sums': (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
     'alq_committee_update': (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, _P, _P, _P]),
     'alq_eval_counts': (C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_int, C.c_int64, _P, _P]),

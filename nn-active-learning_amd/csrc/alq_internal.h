@@ -688,6 +688,55 @@ int k_lsum_finish(alq_ctx *, const double *part /*[L][max_batch][nslab_max]*/, c
                   const double *sizes, int N, int L, int J, int j, double *g /*[N, J, L]*/);
 int k_lsum_check_classes(alq_ctx *, const int *d_cls, int count, int c, int *d_flag);
 
+// ------------------------------------------------------------------ Hessian-vector products (hvp.hip)
+// A read-only [rows, Ca + Cb] tensor in up to two channel groups (a View with its split concat, or the dense tangent tensors of
+// the two producers of a 'con' skip, skip channels in front); pa == null: no tensor (the term it feeds is skipped)
+struct HSrc {
+    const float *pa = nullptr;       // fp32 tensors of the scoring engines (the network input, stored activations as ReLU masks) ...
+    const double *da = nullptr;      // ... or the call's own fp64 tensors
+    int csa = 0, c0a = 0, Ca = 0;
+    const float *pb = nullptr;
+    const double *db = nullptr;
+    int csb = 0, c0b = 0, Cb = 0;
+};
+// The dense fp64 tensors a step writes its two channel groups to; acc: add to what a skip consumer has already written
+struct HDst {
+    double *pa = nullptr;
+    int Ca = 0, acca = 0;
+    double *pb = nullptr;
+    int Cb = 0, accb = 0;
+};
+struct HGeo {
+    int ID, IH, IW, OD, OH, OW, kz, ky, kx;
+    int a[3], b[3], c[3], d[3];      // source position = (p a + b t + c) / d per dimension
+    int Ci, Cj;                      // contracted / produced channels
+    long long wt, wi, wj;            // filter strides of (tap, contracted channel, produced channel)
+};
+HSrc hsrc_view(const View &v);
+HSrc hsrc_dense(const double *pa, int Ca, const double *pb = nullptr, int Cb = 0);
+int hvp_geometry(int type, int backward, const View &in, const View &out, const int k[3], const int s[3], const int lo[3], HGeo *g);
+int k_hvp_contract(alq_ctx *, const HSrc &s1, const float *W1, const HSrc &s2, const float *W2, const float *cb, const HSrc &mask,
+                   const HDst &dst, const HGeo &g, int N);
+int k_hvp_fc_fwd(alq_ctx *, const HSrc &a, const float *V, const HSrc &Ra, const float *W, const float *cb, const HSrc &mask, double *out,
+                 const View &in, int nout, int N);
+int k_hvp_fc_bwd(alq_ctx *, const double *delta, const float *V, const double *Rdelta, const float *W, const HDst &dst, const View &in, int nout,
+                 int N);
+int k_hvp_fc_wgrad(alq_ctx *, const double *Rdelta, const HSrc &a, const double *delta, const HSrc &Ra, const View &in, int nout, int N,
+                   int accumulate, double *hv);
+long long hvp_wgrad_partial_doubles(long long M);
+int k_hvp_wgrad(alq_ctx *, const HSrc &U1, const HSrc &V1, const HSrc &U2, const HSrc &V2, int UC, int VC, const View &Ug, const View &Vg,
+                const int k[3], const int s[3], const int lo[3], int N, double *partial, int accumulate, double *hv);
+int k_hvp_bias(alq_ctx *, const double *Rd, int C, long long rows, int accumulate, double *hv);
+int k_hvp_mask(alq_ctx *, double *Rd, int C, const HSrc &act, long long rows);
+int k_hvp_pool_fwd(alq_ctx *, const double *Rin, const uint8_t *argmax, double *Rout, const View &in, const View &out, const int w[3],
+                   const int lo[3], int N);
+int k_hvp_pool_bwd(alq_ctx *, const double *Rdout, const uint8_t *argmax, double *Rdin, int accumulate, const View &in, const View &out,
+                   const int w[3], const int lo[3], int N);
+int k_hvp_softmax64(alq_ctx *, const double *z64, const int *labels, int c, int N, float scale, float *post_cN, double *p64, double *delta);
+int k_hvp_softmax2(alq_ctx *, const double *p64, const double *Rz, const int *labels, int c, int N, float scale, double *Rdelta);
+int k_hvp_loss(alq_ctx *, const float *post_cN, int c, int N, const int *labels, float scale, double *d_out);
+int k_hvp_unpermute(alq_ctx *, const float *Wres, float *Wtf, int Co, const View &in);
+
 // ------------------------------------------------------------------ committee statistics (committee.hip)
 int committee_update_impl(alq_ctx *, const float *d_p1, int64_t n, int member, int mode, double *d_mean_p, double *d_mean_h,
                           double *d_keys);

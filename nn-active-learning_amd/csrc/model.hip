@@ -114,6 +114,16 @@ struct Layer {
     bool out_is_skip_src = false;
     // convT class tap lists (indices into the k^3 tap enumeration)
     std::vector<std::vector<int>> class_taps;
+    // alq_hess_vecp (hvp.hip): the plain fp32 weights in the TF layout.  The host keeps the copy alq_model_set_weights was given
+    // (hv_src = 1) or notes that the layer holds them resident in fp32 (hv_src = 2: a device-packed wide fc layer's d_Wres;
+    // hv_src = 3: a skinny fc layer's d_Wp); the device copy
+    // hv_W and the call's fp64 tensors of this layer's output - activation hv_A, its cotangent hv_D, their tangents hv_Ra / hv_Rd,
+    // dense [max_batch, vox, C] - are allocated and filled by the first product.  hv_stale: hv_W is older than the weights.
+    std::vector<float> hv_hW;
+    int hv_src = 0;
+    bool hv_stale = false;
+    float *hv_W = nullptr;
+    double *hv_A = nullptr, *hv_D = nullptr, *hv_Ra = nullptr, *hv_Rd = nullptr;
 };
 
 }  // namespace alq
@@ -190,6 +200,9 @@ struct alq_model {
     bool last_f16_derived = false; // the last forward pass ran a launch on the fp16x2 split with derived input bounds
     int64_t host_pack_elems = 0;   // weight elements that went through the host packers since the model was created (engine info 14)
     void *d_wscal = nullptr;       // 16 bytes: the scalars of the device packers (wpack.hip)
+    bool hv_ready = false;         // alq_hess_vecp has allocated its workspaces (first call)
+    double *hv_part = nullptr;     // slab partials of the weight products (hvp_wgrad_partial_doubles)
+    double *hv_p64 = nullptr;      // [max_batch, c]: the posteriors of the call in fp64
 
     template <typename T>
     int dalloc(T **p, size_t count) {
@@ -1680,6 +1693,178 @@ static int make_drop(const alq_model *m, float keep_prob, uint64_t seed, int64_t
     return ALQ_OK;
 }
 
+// ------------------------------------------------------------------------------------------ Hessian-vector product (hvp.hip)
+// First call: the tangent tensors of every layer, the slab partials of the weight products and the TF-layout fp32 weights;
+// later calls: only the weights of layers that were set since.
+static int hvp_prepare(alq_model *m) {
+    alq_ctx *ctx = m->ctx;
+    const size_t NB = (size_t)m->max_batch;
+    if (!m->hv_ready) {
+        long long Mmax = 1;
+        for (Layer &ly : m->layers) {
+            ALQ_REQUIRE(ly.spec.type != ALQ_POOL || (ly.spec.skip_src < 0 && &ly != &m->layers[0]), ALQ_EUNSUPPORTED,
+                        "alq_hess_vecp: pool layer first or behind a concat");
+            const size_t el = NB * (size_t)ly.out.vox() * ly.out.C;
+            ALQ_TRY(m->dalloc(&ly.hv_A, el));
+            ALQ_TRY(m->dalloc(&ly.hv_D, el));
+            ALQ_TRY(m->dalloc(&ly.hv_Ra, el));
+            ALQ_TRY(m->dalloc(&ly.hv_Rd, el));
+            if (ly.pidx >= 0) {
+                ALQ_TRY(m->dalloc(&ly.hv_W, (size_t)ly.w_elems));
+                if (ly.spec.type != ALQ_FC) Mmax = std::max<long long>(Mmax, ly.w_elems);
+            }
+        }
+        ALQ_TRY(m->dalloc(&m->hv_part, (size_t)hvp_wgrad_partial_doubles(Mmax)));
+        ALQ_TRY(m->dalloc(&m->hv_p64, NB * (size_t)m->nclass));
+        m->hv_ready = true;
+    }
+    for (Layer &ly : m->layers) {
+        if (ly.pidx < 0) continue;
+        ALQ_REQUIRE(ly.weights_set && ly.hv_src != 0, ALQ_EINVAL, "alq_hess_vecp: weights of parameterised layer %d not set", ly.pidx);
+        if (!ly.hv_stale) continue;
+        if (ly.hv_src == 1) {
+            ALQ_HIP(hipMemcpyAsync(ly.hv_W, ly.hv_hW.data(), (size_t)ly.w_elems * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+            ALQ_HIP(hipStreamSynchronize(ctx->stream));
+            std::vector<float>().swap(ly.hv_hW);      // hv_W holds them until the next set_weights
+        } else {
+            const float *res = ly.hv_src == 2 ? ly.d_Wres : ly.d_Wp;      // both [o][f_mem]
+            ALQ_REQUIRE(res != nullptr, ALQ_EINVAL, "alq_hess_vecp: layer %d has no resident weights", ly.pidx);
+            ALQ_TRY(k_hvp_unpermute(ctx, res, ly.hv_W, ly.spec.cout, ly.in));
+        }
+        ly.hv_stale = false;
+    }
+    return ALQ_OK;
+}
+
+// Everything behind the forward pass (which fixed the ReLU and pool decisions: Layer::out's signs, the arg-max fields), in fp64 on
+// the call's own tensors: activations, posteriors and first-order cotangents, the tangent pass, the second-order term at the
+// logits, the sweep of the tangent cotangent and the products (hvp.hip).
+static int run_hess_vecp(alq_model *m, const float *d_x, int N, const int32_t *d_labels, float loss_scale, const float *d_v,
+                         const uint8_t *h_layer_on, int accumulate, double *d_hv, double *d_loss) {
+    alq_ctx *ctx = m->ctx;
+    const int nl = (int)m->layers.size();
+    const int one[3] = {1, 1, 1};
+    std::vector<long long> off(nl, 0);
+    {
+        long long o = 0;
+        for (int i = 0; i < nl; ++i) {
+            off[i] = o;
+            if (m->layers[i].pidx >= 0) o += m->layers[i].w_elems + m->layers[i].b_elems;
+        }
+    }
+    auto on = [&](const Layer &ly) { return !h_layer_on || h_layer_on[ly.pidx] != 0; };
+    // the input of layer i out of the per-layer tensors `which`: the network input itself (fp32) for the first layer's
+    // activations and none for its tangent, two producers behind a 'con' skip
+    auto src_in = [&](int i, double *Layer::*which, bool tangent) {
+        const Layer &ly = m->layers[i];
+        if (i == 0) {
+            if (tangent) return HSrc();
+            View in = ly.in;
+            in.p = const_cast<float *>(d_x);
+            return hsrc_view(in);
+        }
+        if (ly.spec.skip_src >= 0) {
+            const Layer &sl = m->layers[ly.spec.skip_src], &pl = m->layers[i - 1];
+            return hsrc_dense(sl.*which, sl.out.C, pl.*which, pl.out.C);
+        }
+        return hsrc_dense(m->layers[i - 1].*which, ly.in.C);
+    };
+    // one forward walk: tangent = false: activations (bias, no v); true: tangents (the v term of switched-on layers)
+    auto forward = [&](bool tangent) -> int {
+        double *Layer::*out = tangent ? &Layer::hv_Ra : &Layer::hv_A;
+        for (int i = 0; i < nl; ++i) {
+            Layer &ly = m->layers[i];
+            if (ly.spec.type == ALQ_POOL) {
+                ALQ_TRY(k_hvp_pool_fwd(ctx, m->layers[i - 1].*out, ly.argmax, ly.*out, ly.in, ly.out, ly.spec.k, ly.lo, N));
+                continue;
+            }
+            const bool lon = tangent && on(ly);
+            const float *V = lon ? d_v + off[i] : nullptr;
+            const float *cb = tangent ? (lon ? d_v + off[i] + ly.w_elems : nullptr) : ly.d_bias;
+            const HSrc a = lon ? src_in(i, &Layer::hv_A, false) : HSrc(), x = src_in(i, out, tangent);
+            if (ly.spec.type == ALQ_FC) {
+                ALQ_TRY(k_hvp_fc_fwd(ctx, a, V, x, ly.hv_W, cb, ly.spec.relu ? hsrc_view(ly.out) : HSrc(), ly.*out, ly.in, ly.spec.cout, N));
+            } else {
+                HGeo g;
+                ALQ_TRY(hvp_geometry(ly.spec.type, 0, ly.in, ly.out, ly.spec.k, ly.spec.s, ly.lo, &g));
+                HDst dst;
+                dst.pa = ly.*out; dst.Ca = ly.out.C;
+                ALQ_TRY(k_hvp_contract(ctx, a, V, x, ly.hv_W, cb, ly.spec.relu ? hsrc_view(ly.out) : HSrc(), dst, g, N));
+            }
+        }
+        return ALQ_OK;
+    };
+    // one backward walk over the tensors `X` (the layers' output cotangents; the head's is filled): second = false: the
+    // first-order cotangents hv_D; true: their tangents hv_Rd (+ the delta . V term of switched-on layers) and the products
+    auto backward = [&](bool second) -> int {
+        double *Layer::*X = second ? &Layer::hv_Rd : &Layer::hv_D;
+        std::vector<char> written(nl, 0);
+        written[nl - 1] = 1;
+        for (int i = nl - 1; i >= 0; --i) {
+            Layer &ly = m->layers[i];
+            ALQ_REQUIRE(written[i], ALQ_EUNSUPPORTED, "alq_hess_vecp: layer %d has no consumer", i);
+            if (ly.spec.type == ALQ_POOL) {
+                ALQ_TRY(k_hvp_pool_bwd(ctx, ly.*X, ly.argmax, m->layers[i - 1].*X, written[i - 1], ly.in, ly.out, ly.spec.k, ly.lo, N));
+                written[i - 1] = 1;
+                continue;
+            }
+            const bool isfc = ly.spec.type == ALQ_FC;
+            const long long orows = (long long)N * ly.out.vox();
+            if (ly.spec.relu) ALQ_TRY(k_hvp_mask(ctx, ly.*X, ly.out.C, hsrc_view(ly.out), orows));
+            const bool lon = second && on(ly);
+            if (second) {
+                double *hv = d_hv + off[i];
+                if (lon) {
+                    const HSrc a = src_in(i, &Layer::hv_A, false), Ra = src_in(i, &Layer::hv_Ra, true);
+                    const HSrc Rd = hsrc_dense(ly.hv_Rd, ly.out.C), dl = i > 0 ? hsrc_dense(ly.hv_D, ly.out.C) : HSrc();
+                    if (isfc) {
+                        ALQ_TRY(k_hvp_fc_wgrad(ctx, ly.hv_Rd, a, ly.hv_D, Ra, ly.in, ly.spec.cout, N, accumulate, hv));
+                    } else if (ly.spec.type == ALQ_CONV) {
+                        ALQ_TRY(k_hvp_wgrad(ctx, Rd, a, dl, Ra, ly.out.C, ly.in.C, ly.out, ly.in, ly.spec.k, one, ly.lo, N, m->hv_part, accumulate,
+                                            hv));
+                    } else {
+                        ALQ_TRY(k_hvp_wgrad(ctx, a, Rd, Ra, dl, ly.in.C, ly.out.C, ly.in, ly.out, ly.spec.k, ly.spec.s, ly.lo, N, m->hv_part,
+                                            accumulate, hv));
+                    }
+                    ALQ_TRY(k_hvp_bias(ctx, ly.hv_Rd, ly.out.C, orows, accumulate, hv + ly.w_elems));
+                } else if (!accumulate) {
+                    ALQ_HIP(hipMemsetAsync(hv, 0, (size_t)(ly.w_elems + ly.b_elems) * sizeof(double), ctx->stream));
+                }
+            }
+            if (i == 0) break;
+            HDst dst;      // the input's cotangent, routed to the producer(s) of the input
+            if (ly.spec.skip_src >= 0) {
+                const int s = ly.spec.skip_src;
+                dst.pa = m->layers[s].*X; dst.Ca = m->layers[s].out.C; dst.acca = written[s];
+                dst.pb = m->layers[i - 1].*X; dst.Cb = m->layers[i - 1].out.C; dst.accb = written[i - 1];
+                written[s] = 1;
+            } else {
+                dst.pa = m->layers[i - 1].*X; dst.Ca = ly.in.C; dst.acca = written[i - 1];
+            }
+            written[i - 1] = 1;
+            const float *V = lon ? d_v + off[i] : nullptr;
+            if (isfc) {
+                ALQ_TRY(k_hvp_fc_bwd(ctx, ly.hv_D, V, ly.*X, ly.hv_W, dst, ly.in, ly.spec.cout, N));
+            } else {
+                HGeo g;
+                ALQ_TRY(hvp_geometry(ly.spec.type, 1, ly.in, ly.out, ly.spec.k, ly.spec.s, ly.lo, &g));
+                ALQ_TRY(k_hvp_contract(ctx, lon ? hsrc_dense(ly.hv_D, ly.out.C) : HSrc(), V, hsrc_dense(ly.*X, ly.out.C), ly.hv_W, nullptr, HSrc(),
+                                       dst, g, N));
+            }
+        }
+        return ALQ_OK;
+    };
+    Layer &head = m->layers[nl - 1];
+    ALQ_REQUIRE(!head.spec.relu, ALQ_EUNSUPPORTED, "alq_hess_vecp: ReLU on the head");
+    ALQ_TRY(forward(false));
+    ALQ_TRY(k_hvp_softmax64(ctx, head.hv_A, d_labels, m->nclass, N, loss_scale, m->post, m->hv_p64, head.hv_D));
+    if (d_loss) ALQ_TRY(k_hvp_loss(ctx, m->post, m->nclass, N, d_labels, loss_scale, d_loss));
+    ALQ_TRY(backward(false));
+    ALQ_TRY(forward(true));
+    ALQ_TRY(k_hvp_softmax2(ctx, m->hv_p64, head.hv_Ra, d_labels, m->nclass, N, loss_scale, head.hv_Rd));
+    return backward(true);
+}
+
 // =========================================================================================== C ABI
 extern "C" {
 
@@ -1794,6 +1979,20 @@ int alq_class_layer_sums(alq_model *m, const float *d_x, int N, int J, const int
         ALQ_TRY(k_lsum_finish(ctx, m->ls_part, m->ls_nslab.data(), m->ls_nslab_max, m->max_batch, m->sizes, N, m->L, J, j, d_g));
     }
     return ALQ_OK;
+}
+
+int alq_hess_vecp(alq_model *m, const float *d_x, int N, const int32_t *d_labels, float loss_scale, const float *d_v,
+                  const uint8_t *h_layer_on, int accumulate, double *d_hv, double *d_loss) {
+    ALQ_REQUIRE(m && d_x && d_labels && d_v && d_hv, ALQ_EINVAL, "alq_hess_vecp: null argument");
+    ALQ_REQUIRE(N >= 1 && N <= m->max_batch, ALQ_EINVAL, "alq_hess_vecp: N=%d outside [1, max_batch=%d]", N, m->max_batch);
+    ALQ_HIP(hipSetDevice(m->ctx->device));
+    ALQ_TRY(hvp_prepare(m));
+    DropSpec ds;
+    ALQ_TRY(make_drop(m, 1.f, 0, 0, nullptr, 0, &ds));
+    m->last_call_fisher = false;
+    ALQ_TRY(prepare_call(m));
+    ALQ_TRY(run_forward(m, d_x, N, false, /*keep_all=*/true, &ds));
+    return run_hess_vecp(m, d_x, N, d_labels, loss_scale, d_v, h_layer_on, accumulate, d_hv, d_loss);
 }
 
 int alq_sgd_step(alq_ctx *ctx, float *d_theta, const float *d_grad, int64_t n, float lr) {
@@ -2287,6 +2486,16 @@ int alq_model_set_weights(alq_model *m, int t, const float *W, const float *b) {
     ly.weights_set = true;
     ly.fallback_stale = false;
     m->host_pack_elems += ly.w_elems;
+    // what alq_hess_vecp contracts with (its next call fills hv_W): a skinny fc layer's exact fp32 weights are already
+    // resident (d_Wp, activation-memory order); any other layer's engines hold split forms only, so the host keeps the array
+    if (ly.spec.type == ALQ_FC && ly.dense_fc_small && ly.d_Wp) {
+        std::vector<float>().swap(ly.hv_hW);
+        ly.hv_src = 3;
+    } else {
+        ly.hv_hW.assign(W, W + ly.w_elems);
+        ly.hv_src = 1;
+    }
+    ly.hv_stale = true;
     return ALQ_OK;
 }
 
@@ -2362,6 +2571,9 @@ int alq_model_set_weights_device(alq_model *m, int t, const float *d_W, const fl
     if (ly.has_bwd && ly.bwd.pfc_f16 && sub) ly.bwd.pfc.w_exp = 14 - ex;
     ly.weights_set = true;
     ly.fallback_stale = true;
+    std::vector<float>().swap(ly.hv_hW);
+    ly.hv_src = 2;
+    ly.hv_stale = true;
     return ALQ_OK;
 }
 

@@ -36,6 +36,14 @@ class Handle(object):
         return '<device handle %s>' % self.name
 
 
+class MethodHandle(Handle):
+    """A fetch that shares its name with a method of the model (`model.hess_vecp`: Influence.get_hess_vec_product stores the
+    fetch under the name DeviceModel's own product method has): calling it is calling that method."""
+
+    def __call__(self, *args, **kwargs):
+        return getattr(type(self.model), self.name)(self.model, *args, **kwargs)
+
+
 _default_session = None
 _live = None   # weak set of sessions / models, closed at interpreter exit BEFORE the HIP runtime unloads
 
@@ -205,7 +213,9 @@ class DeviceSession(object):
         """`sess.run(fetch, feed_dict={model.x: batch, model.keep_prob: p, model.y_: labels})` for the fetches the
         reference's query / fine-tune code uses: `model.posteriors`, `.prediction`, `.feature_layer` (PW_NN.py:522),
         `model.grad_posts[str(j)]` (PW_NNAL.py:773-807: list of 2L' gradient arrays of log posteriors[j, 0]) and
-        `model.train_step` (PW_AL.py:1075-1080, :1140-1146)."""
+        `model.train_step` (PW_AL.py:1075-1080, :1140-1146); of the influence functions (Influence.py): `model.loss` (scalar
+        mean cross-entropy, needs `model.y_`), `model.loss_grad` (NN.add_loss_grad) and `model.hess_vecp` with the entries of
+        `model.v_placeholder` in the feed (Influence.get_hess_vec_product)."""
         model = getattr(fetch, 'model', None)
         if isinstance(fetch, list):
             model = getattr(fetch[0], 'model', None) if fetch else None
@@ -221,6 +231,17 @@ class DeviceSession(object):
         kp = float(feed_dict.get(model.keep_prob, 1.))
         if fetch.name == 'train_step':
             return model.train_on_batch(x, feed_dict[model.y_], keep_prob=kp)
+        if fetch.name in ('loss', 'loss_grad', 'hess_vecp'):
+            # the training-time graph nodes of the influence functions (NN.py:583-588, :862-871; Influence.py:126-166)
+            if kp != 1.:
+                raise NotImplementedError('%s at keep_prob < 1' % fetch.name)
+            lab = onehot_to_labels(feed_dict[model.y_], model.nclass)
+            if fetch.name == 'loss':
+                return model.mean_loss(x, lab)
+            if fetch.name == 'loss_grad':
+                return model.mean_loss_grad(x, lab, fetch.layers)
+            v = [feed_dict[h] for h in model.v_placeholder]
+            return DeviceModel.hess_vecp(model, x, lab, v, layers=model.Hess_layers)
         res = model.forward(x, want=(fetch.name,), keep_prob=kp)
         return res[fetch.name]
 
@@ -242,6 +263,15 @@ class DeviceSession(object):
 
 
 # ------------------------------------------------------------------------------------------
+def onehot_to_labels(y_onehot, nclass):
+    """[c, n] one-hot columns (the reference's hot_labels, PW_NN.py:494-496) -> int32 labels; an all-zero column (a mask
+    value that is no class) -> -1: the sample adds nothing to the loss, as its zero row does in the reference's sum."""
+    y = np.asarray(y_onehot)
+    if y.ndim != 2 or y.shape[0] != nclass:
+        raise ValueError('labels must be [%d, n] one-hot columns, got %r' % (nclass, y.shape))
+    return np.where(y.sum(0) > 0, y.argmax(0), -1).astype(np.int32)
+
+
 def _is_extended(layer_dict):
     first = next(iter(layer_dict.values()))
     return isinstance(first[0], str)
@@ -476,6 +506,8 @@ class DeviceModel(object):
         self.grad_layers = []
         self._build_grad_handles()
         self.y_ = Handle('y_')
+        self.loss = Handle('loss')        # mean softmax cross-entropy of a labelled batch (NN.py:583-588)
+        self.loss.model = self
         self.train_step = None            # get_optimizer() creates it (NN.py:557-615)
         self._opt = None
         self._weights_version = 0         # bumped by every set_weights: the optimiser's device copy follows it
@@ -582,6 +614,110 @@ class DeviceModel(object):
             cols = [2 * i + h for i in self.grad_layer_idx for h in (0, 1)]
             sq = sq[:, cols].contiguous()
         return sq
+
+    # -- Hessian-vector products (Influence.py:64-166) ---------------------------------------
+    def hess_layer_idx(self, layers='all'):
+        """Parameterised-layer indices of `layers`: 'all' / None, layer names (the reference's Hess_layers) or indices."""
+        if layers is None or (isinstance(layers, str) and layers == 'all'):
+            return list(range(self.L))
+        idx = [self.var_names.index(l) if isinstance(l, str) else int(l) for l in layers]
+        if len(idx) == 0 or len(set(idx)) != len(idx) or min(idx) < 0 or max(idx) >= self.L:
+            raise KeyError('Hessian layers %r' % (layers,))
+        return idx
+
+    def _param_offsets(self):
+        off, out = 0, []
+        for _, wshape, bshape in self.param_shapes:
+            nw, nb = int(np.prod(wshape)), int(np.prod(bshape))
+            out.append((off, nw, nb))
+            off += nw + nb
+        return out
+
+    def ravel_for_layers(self, v, idx):
+        """`v` - a flat vector over all parameters, a flat vector over the layers `idx` (in that order) or a list
+        [VW, Vb, ...] of arrays for them - as a flat float32 vector [P] in parameter order (zero outside `idx`)."""
+        offs = self._param_offsets()
+        if isinstance(v, (list, tuple)):
+            if len(v) != 2 * len(idx):
+                raise ValueError('expected %d arrays (W, b per layer), got %d' % (2 * len(idx), len(v)))
+            v = np.concatenate([np.asarray(a, dtype=np.float32).ravel() for a in v])
+        v = np.asarray(v, dtype=np.float32).ravel()
+        if v.size == self.num_params:
+            return np.ascontiguousarray(v)
+        if v.size != sum(offs[t][1] + offs[t][2] for t in idx):
+            raise ValueError('vector of %d entries fits neither all %d parameters nor the chosen layers' % (v.size, self.num_params))
+        full = np.zeros(self.num_params, dtype=np.float32)
+        c = 0
+        for t in idx:
+            o, nw, nb = offs[t]
+            full[o:o + nw + nb] = v[c:c + nw + nb]
+            c += nw + nb
+        return full
+
+    def hess_vecp_device(self, t, n, labels, v, idx=None, loss_scale=1., out=None, want_loss=False):
+        """alq_hess_vecp on n device patches (any n: passes of max_batch with the same loss_scale): `out` (float64 device
+        [P]; created and overwritten when None) += H v, H the Hessian of loss_scale * sum CE over the layers `idx` (indices;
+        None = all).  labels / v: int32 [n] / float32 [P] device tensors.  Returns (out, scaled loss of the passes or None)."""
+        torch = self.sess.torch
+        self.sess.bind_stream()
+        assert labels.dtype == torch.int32 and labels.is_contiguous() and int(labels.numel()) == n
+        assert v.dtype == torch.float32 and v.is_contiguous() and int(v.numel()) == self.num_params
+        on = None
+        if idx is not None and sorted(idx) != list(range(self.L)):
+            on = (C.c_uint8 * self.L)(*[1 if q in idx else 0 for q in range(self.L)])
+        acc = out is not None
+        if out is None:
+            out = self.sess.empty((self.num_params,), torch.float64)
+        assert out.dtype == torch.float64 and out.is_contiguous() and int(out.numel()) == self.num_params
+        loss = self.sess.empty((1,), torch.float64) if want_loss else None
+        total = torch.zeros((1,), dtype=torch.float64, device=self.sess.device) if want_loss else None
+        for a in range(0, n, self.max_batch):
+            b = min(n, a + self.max_batch)
+            check(self.lib.alq_hess_vecp(self._m, C.c_void_p(t.data_ptr() + a * self.elems_per_patch * 4), b - a,
+                                         C.c_void_p(labels.data_ptr() + a * 4), float(loss_scale), C.c_void_p(v.data_ptr()), on,
+                                         1 if (acc or a > 0) else 0, C.c_void_p(out.data_ptr()),
+                                         C.c_void_p(loss.data_ptr()) if want_loss else None))
+            if want_loss:
+                total += loss
+        return out, total
+
+    def hess_vecp(self, x, labels, v, layers='all', loss_scale=None, out=None):
+        """H v for the Hessian of loss_scale * sum_n CE(softmax(z_n), labels[n]) (loss_scale None: 1 / n, the mean loss of
+        NN.py:583-588) over the parameters of `layers` ('all', names or indices; the others are held constant).  `v`: see
+        ravel_for_layers.  Returns the list [HW, Hb, ...] of the chosen layers in TF shapes, float64.  `out`: a float64
+        device vector [P] the product is ADDED to (multi-pass sums); the list then holds the accumulated values."""
+        torch = self.sess.torch
+        t, n = self._as_device_batch(x)
+        idx = self.hess_layer_idx(layers)
+        lab = labels if isinstance(labels, torch.Tensor) else self.sess.to_device(np.asarray(labels, dtype=np.int32).reshape(n), torch.int32)
+        vd = self.sess.to_device(self.ravel_for_layers(v, idx), torch.float32)
+        hv, _ = self.hess_vecp_device(t, n, lab, vd, idx, 1. / n if loss_scale is None else loss_scale, out)
+        return self.unflatten(hv.cpu().numpy(), idx)
+
+    def mean_loss(self, x, labels):
+        """`sess.run(model.loss, {x, y_})`: the mean softmax cross-entropy of the batch (unlabelled samples add 0 to the sum)."""
+        torch = self.sess.torch
+        t, n = self._as_device_batch(x)
+        lab = self.sess.to_device(np.asarray(labels, dtype=np.int32).reshape(n), torch.int32)
+        loss = 0.
+        for a in range(0, n, self.max_batch):
+            b = min(n, a + self.max_batch)
+            _, _, l = self.param_grads_device(t[a:b], b - a, 1, labels=lab[a:b], loss_scale=1. / n, per_sample=False, want_loss=True)
+            loss += float(l.item()) * (b - a) / n
+        return loss
+
+    def mean_loss_grad(self, x, labels, layers='all'):
+        """`sess.run(model.loss_grad, {x, y_})` (NN.add_loss_grad, NN.py:862-871): gradient of the mean cross-entropy with
+        respect to the variables of `layers`, TF shapes (alq_param_grads mode 1)."""
+        torch = self.sess.torch
+        t, n = self._as_device_batch(x)
+        lab = self.sess.to_device(np.asarray(labels, dtype=np.int32).reshape(n), torch.int32)
+        g = torch.zeros((self.num_params,), dtype=torch.float64, device=self.sess.device)
+        for a in range(0, n, self.max_batch):
+            b = min(n, a + self.max_batch)
+            gp, _, _ = self.param_grads_device(t[a:b], b - a, 1, labels=lab[a:b], loss_scale=1. / n, per_sample=False)
+            g += gp
+        return self.unflatten(g.cpu().numpy().astype(np.float32), self.hess_layer_idx(layers))
 
     def grad_log_post(self, x, j, keep_prob=1.):
         """`sess.run(model.grad_posts[str(j)], {x: batch})`: gradients of log posteriors[j, 0] - sample 0 of the batch,
