@@ -314,6 +314,30 @@ int alq_shrink_sum(alq_ctx *ctx, const float *d_grads, int N, int64_t P, const i
  * nothing is written (the slots are checked on the device first: one 4-byte flag read, which synchronises the stream).
  * Every row depends on its own sample only: bit-identical whatever the batch, the slot position and from run to run.   */
 int alq_class_layer_sums(alq_model *m, const float *d_x, int N, int J, const int32_t *d_cls, float *d_post, double *d_g);
+
+/* Replaces: model_utils.diagonal_Fisher (model_utils.py:294-330) without per-sample gradient rows:
+ * d_acc[i] += sum_n (d log posteriors[d_cls[n], n] / d theta_i)^2, theta the flat vector [W_0, b_0, W_1, b_1, ...] in the order
+ * and TF layouts of alq_param_grads.  d_cls [N] int32 on the device, entries in [0, c): checked on the device before anything
+ * is written (one 4-byte flag read, which synchronises the stream); a class outside the range gives ALQ_EINVAL and d_acc is
+ * left alone.  d_acc [P] double: the call always ADDS, the caller zeroes it; a set larger than max_batch is a sequence of calls.
+ * keep_prob 1.  Conv / conv_transpose weights: every 16 x 16 tile of a sample's weight gradient is held in registers on the
+ * fp32 matrix cores for the sample's voxel sweep (exact fp32 products, fp32 accumulation in two levels), squared in fp64 and
+ * added to fp64 accumulators that leave the workgroup after its last sample; biases from fp64 channel sums; fc layers as
+ * sum_n delta[n, o]^2 a[n, f]^2 in fp64.  No [N, P] buffer and no atomics: every sum has a fixed order, the result is
+ * bit-identical from run to run.  Scratch (allocated by the first call): the largest of one conv layer's sample-group
+ * partials and max_batch x (widest layer) doubles.  ALQ_EINVAL: null argument, N outside [1, max_batch].                   */
+int alq_diag_fisher(alq_model *m, const float *d_x, int N, const int32_t *d_cls, double *d_acc);
+
+/* Replaces: model_utils.keep_k_largest_from_LoV / threshold_LoV (model_utils.py:54-96) on a flat device vector.
+ * alq_topk_mask: d_mask [n] float = 1 on exactly k entries, the k largest of d_v [n] double, 0 elsewhere; entries equal to the
+ * k-th largest value are taken in ascending index order (the reference's argsort leaves tie order open).  Numeric order for
+ * any finite double, -0.0 equal to +0.0.  k = 0: all zeros; k = n: all ones; k < 0 or k > n: ALQ_EINVAL.  A radix select
+ * on the bit patterns (8 histogram passes over d_v) and one ordered pass; nothing is sorted.  d_work: device scratch of
+ * alq_topk_mask_work_bytes(n) bytes (about 1 MiB + n / 512 bytes).  Stream-ordered, no synchronisation.
+ * alq_threshold_mask: d_mask[i] = d_v[i] >= thr ? 1 : 0.                                                                      */
+size_t alq_topk_mask_work_bytes(int64_t n);
+int alq_topk_mask(alq_ctx *ctx, const double *d_v, int64_t n, int64_t k, float *d_mask, void *d_work);
+int alq_threshold_mask(alq_ctx *ctx, const double *d_v, int64_t n, double thr, float *d_mask);
 /* Replaces: the accumulation `Ai += np.outer(g_j, g_j) / new_posts[j] + np.eye(A_size) * 1e-5` over the selected classes
  * (NNAL.py:399-409).  d_g [N, c, L] shrunk class gradients, d_w [N, c] = 1 / new_posts for the classes the reference
  * keeps (posterior >= 1e-6; the ten largest when ten or more remain, :381-394) and 0 for the others - host logic on the

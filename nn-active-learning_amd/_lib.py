@@ -56,6 +56,10 @@ _SIGNATURES = {
     'alq_grad_sqnorms': (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
     'alq_hess_vecp': (C.c_int, [_P, _P, C.c_int, _P, C.c_float, _P, _P, C.c_int, _P, _P]),
     'alq_class_layer_sums': (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
+    'alq_diag_fisher': (C.c_int, [_P, _P, C.c_int, _P, _P]),
+    'alq_topk_mask_work_bytes': (C.c_size_t, [C.c_int64]),
+    'alq_topk_mask': (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P]),
+    'alq_threshold_mask': (C.c_int, [_P, _P, C.c_int64, C.c_double, _P]),
     'alq_committee_update': (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, _P, _P, _P]),
     'alq_eval_counts': (C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_int, C.c_int64, _P, _P]),
     'alq_sgd_step': (C.c_int, [_P, _P, _P, C.c_int64, C.c_float]),

@@ -677,6 +677,19 @@ int k_gnorm_weight(alq_ctx *, const View &U, const View &V, const int k[3], cons
 int k_gnorm_bias(alq_ctx *, const View &delta, int N, double *d_sq, int ld, int col);
 int k_gnorm_fc(alq_ctx *, const float *delta, int nout, const View &a, int N, double *d_sq, int ld, int col);
 
+// ------------------------------------------------------------------ diagonal Fisher and its masks (dfisher.hip)
+// doubles of scratch the weight launch of one conv / conv_transpose layer may need (partials per sample group)
+long long dfisher_weight_scratch(const View &U, const View &V, const int k[3], const int s[3], const int lo[3], int max_batch);
+// d_acc[TF position] += sum_n G_n^2 (U, V as in k_gnorm_weight)
+int k_dfisher_weight(alq_ctx *, const View &U, const View &V, const int k[3], const int s[3], const int lo[3], int N, double *scratch,
+                     double *d_acc);
+int k_dfisher_bias(alq_ctx *, const View &delta, int N, double *scratch /*[N * C]*/, double *d_acc);
+int k_dfisher_fc(alq_ctx *, const float *delta, int nout, const View &a, int N, double *scratch /*[N * nout]*/, double *d_acc_w,
+                 double *d_acc_b);
+size_t topk_mask_work_bytes_impl(int64_t n);
+int topk_mask_impl(alq_ctx *, const double *d_v, int64_t n, int64_t k, float *d_mask, void *d_work);
+int threshold_mask_impl(alq_ctx *, const double *d_v, int64_t n, double thr, float *d_mask);
+
 // ------------------------------------------------------------------ per-class layer sums (lsum.hip)
 int lsum_slabs(const View &dout, bool isfc, int *slab_out);      // partials per sample of one layer's class sweep
 // F [N, out voxels] (fc: [N]) double: the class-independent field of a layer (type = ALQ_CONV / ALQ_CONVT / ALQ_FC)

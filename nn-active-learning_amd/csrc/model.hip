@@ -159,6 +159,8 @@ struct alq_model {
     size_t wg_partial_len = 0;
     double *gn_partial = nullptr;  // per-(sample, workgroup) partials of the gradient-norm kernels (grown on demand)
     size_t gn_partial_len = 0;
+    double *df_scratch = nullptr;  // alq_diag_fisher (dfisher.hip), allocated by its first call: sample-group partials of a conv layer's
+                                   // weights, per-sample channel sums, squared fc cotangents - whichever is largest
     // alq_class_layer_sums (lsum.hip), allocated by its first call: the layers' class-independent fields (Layer::ls_field), the
     // slab partials [L][max_batch][ls_nslab_max] of one class slot and the slabs each layer writes
     double *ls_part = nullptr;
@@ -1681,6 +1683,46 @@ static int run_grad_sqnorms(alq_model *m, const float *d_x, int N, double *d_sq)
     return ALQ_OK;
 }
 
+// Squared per-sample gradients summed over the samples, from the tensors a general backward pass left behind (the views
+// run_param_grads reads): d_acc [P] += in the flat order [W_0, b_0, W_1, b_1, ...] and TF layouts of run_param_grads.  Nothing of
+// the size N x P is written (dfisher.hip).
+static int run_diag_fisher(alq_model *m, const float *d_x, int N, double *d_acc) {
+    alq_ctx *ctx = m->ctx;
+    const int one[3] = {1, 1, 1};
+    if (!m->df_scratch) {
+        long long need = 1;
+        for (Layer &ly : m->layers) {
+            if (ly.pidx < 0) continue;
+            need = std::max(need, (long long)m->max_batch * ly.spec.cout);
+            if (ly.spec.type == ALQ_FC) continue;
+            const bool convt = ly.spec.type == ALQ_CONVT;
+            need = std::max(need, dfisher_weight_scratch(convt ? ly.in : ly.dout, convt ? ly.dout : ly.in, ly.spec.k,
+                                                         convt ? ly.spec.s : one, ly.lo, m->max_batch));
+        }
+        ALQ_TRY(m->dalloc(&m->df_scratch, (size_t)need));
+    }
+    long long off = 0;
+    for (size_t i = 0; i < m->layers.size(); ++i) {
+        Layer &ly = m->layers[i];
+        if (ly.pidx < 0) continue;
+        View in = ly.in;
+        if (i == 0) in.p = const_cast<float *>(d_x);
+        double *aw = d_acc + off, *ab = aw + ly.w_elems;
+        if (ly.spec.type == ALQ_CONV) {
+            ALQ_TRY(k_dfisher_weight(ctx, ly.dout, in, ly.spec.k, one, ly.lo, N, m->df_scratch, aw));
+            ALQ_TRY(k_dfisher_bias(ctx, ly.dout, N, m->df_scratch, ab));
+        } else if (ly.spec.type == ALQ_CONVT) {
+            ALQ_TRY(k_dfisher_weight(ctx, in, ly.dout, ly.spec.k, ly.spec.s, ly.lo, N, m->df_scratch, aw));
+            ALQ_TRY(k_dfisher_bias(ctx, ly.dout, N, m->df_scratch, ab));
+        } else {
+            ALQ_TRY(k_dfisher_fc(ctx, ly.dout.p, ly.spec.cout, in, N, m->df_scratch, aw, ab));
+        }
+        off += ly.w_elems + ly.b_elems;
+    }
+    ALQ_REQUIRE(off == alq_model_num_params(m), ALQ_EINVAL, "parameter count mismatch");
+    return ALQ_OK;
+}
+
 static int make_drop(const alq_model *m, float keep_prob, uint64_t seed, int64_t first_sample, const int32_t *h_layers, int n_layers,
                      DropSpec *d) {
     ALQ_REQUIRE(keep_prob > 0.f && keep_prob <= 1.f, ALQ_EINVAL, "keep_prob %g outside (0, 1]", (double)keep_prob);
@@ -1979,6 +2021,44 @@ int alq_class_layer_sums(alq_model *m, const float *d_x, int N, int J, const int
         ALQ_TRY(k_lsum_finish(ctx, m->ls_part, m->ls_nslab.data(), m->ls_nslab_max, m->max_batch, m->sizes, N, m->L, J, j, d_g));
     }
     return ALQ_OK;
+}
+
+int alq_diag_fisher(alq_model *m, const float *d_x, int N, const int32_t *d_cls, double *d_acc) {
+    ALQ_REQUIRE(m && d_x && d_cls && d_acc, ALQ_EINVAL, "alq_diag_fisher: null argument");
+    ALQ_REQUIRE(N >= 1 && N <= m->max_batch, ALQ_EINVAL, "alq_diag_fisher: N=%d outside [1, max_batch=%d]", N, m->max_batch);
+    alq_ctx *ctx = m->ctx;
+    ALQ_HIP(hipSetDevice(ctx->device));
+    // the classes live on the device: one flag read (a stream synchronisation) before anything is written
+    int *d_bad = reinterpret_cast<int *>(static_cast<char *>(ctx->param_block) + ALQ_PARAM_FLAG_OFFSET);
+    int bad = 0;
+    ALQ_HIP(hipMemsetAsync(d_bad, 0, sizeof(int), ctx->stream));
+    ALQ_TRY(k_lsum_check_classes(ctx, d_cls, N, m->nclass, d_bad));
+    ALQ_HIP(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    ALQ_HIP(hipStreamSynchronize(ctx->stream));
+    ALQ_REQUIRE(!bad, ALQ_EINVAL, "alq_diag_fisher: a class outside [0, %d)", m->nclass);
+    DropSpec ds;
+    ALQ_TRY(make_drop(m, 1.f, 0, 0, nullptr, 0, &ds));
+    m->last_call_fisher = false;
+    ALQ_TRY(prepare_call(m));
+    ALQ_TRY(run_forward(m, d_x, N, false, /*keep_all=*/true, &ds));
+    ALQ_TRY(k_softmax(ctx, m->logits, m->nclass, N, m->post, nullptr));
+    ALQ_TRY(k_logit_cotangent(ctx, m->post, m->nclass, N, 3, 0, d_cls, 1.f, m->dlogits));
+    ALQ_TRY(run_backward_general(m, N, &ds));
+    return run_diag_fisher(m, d_x, N, d_acc);
+}
+
+size_t alq_topk_mask_work_bytes(int64_t n) { return topk_mask_work_bytes_impl(n); }
+
+int alq_topk_mask(alq_ctx *ctx, const double *d_v, int64_t n, int64_t k, float *d_mask, void *d_work) {
+    ALQ_REQUIRE(ctx && (n == 0 || (d_v && d_mask && d_work)), ALQ_EINVAL, "alq_topk_mask: null argument");
+    ALQ_HIP(hipSetDevice(ctx->device));
+    return topk_mask_impl(ctx, d_v, n, k, d_mask, d_work);
+}
+
+int alq_threshold_mask(alq_ctx *ctx, const double *d_v, int64_t n, double thr, float *d_mask) {
+    ALQ_REQUIRE(ctx && n >= 0 && (n == 0 || (d_v && d_mask)), ALQ_EINVAL, "alq_threshold_mask: bad argument");
+    ALQ_HIP(hipSetDevice(ctx->device));
+    return threshold_mask_impl(ctx, d_v, n, thr, d_mask);
 }
 
 int alq_hess_vecp(alq_model *m, const float *d_x, int N, const int32_t *d_labels, float loss_scale, const float *d_v,

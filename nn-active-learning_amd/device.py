@@ -230,6 +230,13 @@ class DeviceSession(object):
         x = feed_dict[model.x]
         kp = float(feed_dict.get(model.keep_prob, 1.))
         if fetch.name == 'train_step':
+            # NN_extended.get_optimizer (NN_extended.py:1441-1449): masks fed under model.par_placeholders hold for this step
+            ph = getattr(model, 'par_placeholders', None)
+            fed = [h in feed_dict for h in ph] if ph else []
+            if any(fed):
+                if not all(fed):
+                    raise KeyError('a PFT step needs a mask for every entry of par_placeholders')
+                return model.train_on_batch(x, feed_dict[model.y_], keep_prob=kp, pft_mask=[feed_dict[h] for h in ph])
             return model.train_on_batch(x, feed_dict[model.y_], keep_prob=kp)
         if fetch.name in ('loss', 'loss_grad', 'hess_vecp'):
             # the training-time graph nodes of the influence functions (NN.py:583-588, :862-871; Influence.py:126-166)
@@ -511,6 +518,9 @@ class DeviceModel(object):
         self.train_step = None            # get_optimizer() creates it (NN.py:557-615)
         self._opt = None
         self._weights_version = 0         # bumped by every set_weights: the optimiser's device copy follows it
+        self.PFT_bflag = False            # set_PFT_mask: the summed gradient is multiplied by a binary mask (NN_extended.py:1441-1449)
+        self._pft_mask = None             # float32 device [P]
+        self._pft_layers = None           # parameterised layers with a non-zero mask entry
         self._drop_calls = 0
         self.num_params = int(self.lib.alq_model_num_params(self._m))
         self._feature_perm = self._feature_permutation()
@@ -752,10 +762,78 @@ class DeviceModel(object):
             off += cnt
         return mask
 
-    def train_on_batch(self, x, y_onehot, keep_prob=1., seed=None):
+    # -- partial fine-tuning (PFT_bflag / par_placeholders, NN_extended.py:1441-1449) ------------
+    def _flat_mask(self, mask):
+        """A PFT mask - list [MW, Mb, ...] in variable shapes (grads_vars order) or a flat vector / device tensor [P] - as
+        (float32 device tensor [P], layers with a non-zero entry)."""
+        torch = self.sess.torch
+        if isinstance(mask, torch.Tensor):
+            if int(mask.numel()) != self.num_params:
+                raise ValueError('mask of %d entries for %d parameters' % (int(mask.numel()), self.num_params))
+            md = mask.to(device=self.sess.device, dtype=torch.float32).reshape(-1).contiguous()
+        else:
+            if isinstance(mask, (list, tuple)):
+                if len(mask) != 2 * self.L:
+                    raise ValueError('expected %d mask arrays (W, b per layer), got %d' % (2 * self.L, len(mask)))
+                for q, (nme, wshape, bshape) in enumerate(self.param_shapes):
+                    for a_, shp in ((mask[2 * q], wshape), (mask[2 * q + 1], bshape)):
+                        if int(np.size(a_)) != int(np.prod(shp)):
+                            raise ValueError('layer %s: mask of %d entries for a variable of shape %s' % (nme, np.size(a_), shp))
+                mask = np.concatenate([np.asarray(a_, dtype=np.float32).ravel() for a_ in mask])
+            mask = np.asarray(mask, dtype=np.float32).ravel()
+            if mask.size != self.num_params:
+                raise ValueError('mask of %d entries for %d parameters' % (mask.size, self.num_params))
+            md = self.sess.to_device(mask, torch.float32)
+        # which layers train: L flags cross to the host, not the mask
+        flags = torch.stack([(md[o:o + nw + nb] != 0).any() for o, nw, nb in self._param_offsets()]).cpu().numpy()
+        return md, [q for q in range(self.L) if flags[q]]
+
+    def set_PFT_mask(self, mask):
+        """Partial fine-tuning: every later train step multiplies the summed gradient by `mask` before the optimiser step (on
+        top of `train_layers`).  `mask`: list in variable shapes, flat vector or flat device tensor [P] (pft_mask_device);
+        None clears it.  Sets `PFT_bflag`.  The mask multiplies the gradient, as in the reference: under SGD a masked-out
+        parameter does not move; under Adam it does not move if the mask held since the optimiser's first step, and otherwise
+        goes on moving on the moments it has (they are not reset), as a TF variable would."""
+        if mask is None:
+            self.PFT_bflag, self._pft_mask, self._pft_layers = False, None, None
+            return
+        self._pft_mask, self._pft_layers = self._flat_mask(mask)
+        self.PFT_bflag = True
+
+    def get_par_placeholders(self):
+        """NN_extended.py:1441-1449: one mask placeholder per variable in grads_vars order (W_0, b_0, W_1, ...); masks fed under
+        them in `sess.run(model.train_step, feed_dict)` hold for that step."""
+        self.par_placeholders = []
+        for nme, wshape, bshape in self.param_shapes:
+            for part, shp in (('W', wshape), ('b', bshape)):
+                self.par_placeholders.append(Handle('par_placeholder_%s_%s' % (nme, part), shp))
+        return self.par_placeholders
+
+    def pft_mask_device(self, diagF_flat, k=None, thr=None):
+        """The binary mask of partial fine-tuning from a flat float64 device vector (diagonal_fisher_device): k given - 1 on
+        the k largest entries, ties at the k-th value to the lower index (alq_topk_mask; keep_k_largest_from_LoV); thr given -
+        1 where the entry >= thr (alq_threshold_mask; threshold_LoV).  float32 device tensor of the same length."""
+        torch = self.sess.torch
+        if (k is None) == (thr is None):
+            raise ValueError('give exactly one of k and thr')
+        v = diagF_flat
+        assert v.dtype == torch.float64 and v.is_contiguous() and v.device == self.sess.device
+        self.sess.bind_stream()
+        n = int(v.numel())
+        mask = self.sess.empty((n,), torch.float32)
+        if k is not None:
+            work = self.sess.empty((self.lib.alq_topk_mask_work_bytes(n),), torch.uint8)
+            check(self.lib.alq_topk_mask(self.sess.ctx, C.c_void_p(v.data_ptr()), n, int(k), C.c_void_p(mask.data_ptr()),
+                                         C.c_void_p(work.data_ptr())))
+        else:
+            check(self.lib.alq_threshold_mask(self.sess.ctx, C.c_void_p(v.data_ptr()), n, float(thr), C.c_void_p(mask.data_ptr())))
+        return mask
+
+    def train_on_batch(self, x, y_onehot, keep_prob=1., seed=None, pft_mask=None):
         """One `sess.run(model.train_step, {x, y_, keep_prob})`: gradient of the batch-mean cross-entropy (summed over
         device passes of max_batch patches), one optimiser step on the device, weights repacked.  y_onehot: [c, n]
         like the reference's hot_labels (PW_AL.py:1064-1067); an all-zero column is an unlabelled sample.
+        A PFT mask (set_PFT_mask, or `pft_mask` for this step only) multiplies the summed gradient before the step.
         Returns the batch-mean loss before the step."""
         if self._opt is None:
             raise RuntimeError('get_optimizer() has not been called (NN.py:1354)')
@@ -790,6 +868,17 @@ class DeviceModel(object):
             o['mask'] = self.sess.to_device(tm, torch.float32) if tm is not None else None
         if o.get('mask') is not None:
             gsum *= o['mask']
+        pmask, players = (self._pft_mask, self._pft_layers) if pft_mask is None else self._flat_mask(pft_mask)
+        if pmask is not None:
+            gsum *= pmask
+            if o['name'] == 'Adam' and len(players) < self.L:
+                # The mask multiplies the gradient only (NN_extended.py:1441-1449): Adam's moments persist, so a layer whose
+                # mask is all zero still moves unless its m and v are all zero BEFORE this step (then m stays 0 and the step is
+                # 0 / eps = 0) - the case when the mask held since the optimiser's first step.  L flags cross to the host.
+                offs = self._param_offsets()
+                still = torch.stack([((o['m'][a_:a_ + nw + nb] == 0).all() & (o['v'][a_:a_ + nw + nb] == 0).all())
+                                     for a_, nw, nb in offs]).cpu().numpy()
+                players = [q for q in range(self.L) if q in players or not still[q]]
         o['t'] += 1
         P = self.num_params
         self.sess.bind_stream()
@@ -798,28 +887,60 @@ class DeviceModel(object):
         else:
             check(self.lib.alq_adam_step(self.sess.ctx, C.c_void_p(o['theta'].data_ptr()), C.c_void_p(gsum.data_ptr()),
                                          C.c_void_p(o['m'].data_ptr()), C.c_void_p(o['v'].data_ptr()), P, o['lr'],
-                                         0.9, 0.999, 1e-8, o['t']))      # a masked-out parameter keeps m = v = 0: its step is 0 / eps = 0
+                                         0.9, 0.999, 1e-8, o['t']))      # a parameter masked out since the first step keeps m = v = 0: its step is 0 / eps = 0
         if self._host_repack:
             self.set_flat_params(o['theta'].cpu().numpy())
         else:
             # the model is fed from the device vector; a layer outside `train_layers` kept its weights (masked gradient: SGD
-            # subtracts 0, Adam's m = v = 0 step is 0 / eps = 0) and its packed forms
+            # subtracts 0, Adam's m = v = 0 step is 0 / eps = 0) and its packed forms.  A layer whose PFT mask is all zero is
+            # left out only where this step provably did not move it: SGD, or Adam with that layer's moments all zero (`players`)
             only = [t for t, nme in enumerate(self.var_names) if nme in self.train_layers] if self.train_layers else None
+            if pmask is not None:
+                only = [t for t in (range(self.L) if only is None else only) if t in players]
             self.set_weights_device(o['theta'], only=only)
         o['version'] = self._weights_version
         return loss
 
-    def diagonal_fisher(self, x, labels=None, batch=None):
+    def diagonal_fisher_device(self, t, n, labels):
+        """alq_diag_fisher over device passes of max_batch patches: the mean over the n samples of the squared gradient of
+        log posteriors[labels[i], i], flat float64 device tensor [P] in parameter order.  No per-sample gradient rows are
+        formed; labels: int array or int32 device tensor [n]."""
+        torch = self.sess.torch
+        self.sess.bind_stream()
+        lab = labels if isinstance(labels, torch.Tensor) else self.sess.to_device(np.asarray(labels, dtype=np.int32).reshape(n), torch.int32)
+        assert lab.dtype == torch.int32 and lab.is_contiguous() and int(lab.numel()) == n
+        acc = torch.zeros((self.num_params,), dtype=torch.float64, device=self.sess.device)
+        for a in range(0, n, self.max_batch):
+            b = min(n, a + self.max_batch)
+            check(self.lib.alq_diag_fisher(self._m, C.c_void_p(t.data_ptr() + a * self.elems_per_patch * 4), b - a,
+                                           C.c_void_p(lab.data_ptr() + a * 4), C.c_void_p(acc.data_ptr())))
+        return acc.div_(max(n, 1))
+
+    def diagonal_fisher(self, x, labels=None, batch=None, fused=None):
         """model_utils.diagonal_Fisher (model_utils.py:294-330): mean over samples of the squared gradient of the
         log-likelihood of the sample's label (labels given) or of the model's own prediction (None), per parameter.
-        Returns the list of arrays in variable shapes."""
+        Returns the list of arrays in variable shapes.  Default: the fused statistic (diagonal_fisher_device); fused=False or
+        ALQ_DIAGF_ROWS=1: per-sample gradient rows squared and folded (alq_param_grads + alq_sq_accum), the A/B arm; `batch`
+        caps the rows of one of its passes (the fused arm forms none and runs passes of max_batch)."""
         torch = self.sess.torch
         t, n = self._as_device_batch(x)
-        acc = torch.zeros((self.num_params,), dtype=torch.float64, device=self.sess.device)
         if labels is None:
             post, pred, _ = self.forward_device(t, n, want_pred=True)
             labels = pred.cpu().numpy()
         labels = np.asarray(labels).astype(np.int64)
+        if fused is None:
+            fused = os.environ.get('ALQ_DIAGF_ROWS', '0') in ('', '0')
+        if fused:
+            return self.unflatten(self.diagonal_fisher_device(t.reshape(n, -1), n, labels.astype(np.int32)).cpu().numpy())
+        return self.unflatten(self.diagonal_fisher_rows_device(t, n, labels, batch).cpu().numpy())
+
+    def diagonal_fisher_rows_device(self, t, n, labels, batch=None):
+        """The rows arm of diagonal_fisher on the device (A/B; tools/gpu_diagfisher.py): per class, the per-sample gradient rows
+        of up to `batch` samples (alq_param_grads) squared and folded (alq_sq_accum).  labels: host int array [n].  Flat
+        float64 device tensor [P], the mean over the n samples."""
+        torch = self.sess.torch
+        labels = np.asarray(labels).astype(np.int64)
+        acc = torch.zeros((self.num_params,), dtype=torch.float64, device=self.sess.device)
         step = min(self.max_batch, batch or self.max_batch)
         for j in range(self.nclass):
             idx = np.nonzero(labels == j)[0]
@@ -829,7 +950,7 @@ class DeviceModel(object):
                 g, _, _ = self.param_grads_device(xs, int(sel.numel()), 0, cls=j)
                 check(self.lib.alq_sq_accum(self.sess.ctx, C.c_void_p(g.data_ptr()), self.num_params, int(sel.numel()),
                                             C.c_void_p(acc.data_ptr())))
-        return self.unflatten((acc / max(n, 1)).cpu().numpy())
+        return acc.div_(max(n, 1))
 
     # -- weights ---------------------------------------------------------------------------
     def set_weights(self, pars):

@@ -1,4 +1,5 @@
-"""The one function of the reference's model_utils.py that reuses the scoring kernels."""
+"""The functions of the reference's model_utils.py behind partial fine-tuning: the diagonal Fisher (which reuses the scoring
+kernels) and the binary masks made from it."""
 import numpy as np
 
 
@@ -6,11 +7,41 @@ def diagonal_Fisher(model, sess, batch_dat):
     """model_utils.diagonal_Fisher (model_utils.py:294-330): per parameter, the mean over the samples of the squared
     gradient of the sample's loss (= the squared gradient of log posteriors[label]); `batch_dat` = (x [N, ...],
     one-hot labels [c, N]).  Returns the arrays in variable order and TF shapes, like the reference's list.
-    The reference runs one sess.run per sample; here the per-sample gradients of a device pass are squared and
-    accumulated on the device (alq_param_grads + alq_sq_accum)."""
+    The reference runs one sess.run per sample; here a device pass squares and sums its samples' gradients without writing
+    them out (alq_diag_fisher).  Masks the model may hold (set_PFT_mask) play no part: the reference feeds ones here
+    (model_utils.py:308-315)."""
     x, y = batch_dat
     y = np.asarray(y)
     labels = np.where(y.sum(0) > 0, y.argmax(0), -1)
     if (labels < 0).any():
         raise ValueError('every sample needs a label (one-hot column)')
     return model.diagonal_fisher(np.asarray(x), labels)
+
+
+def keep_k_largest_from_LoV(LoV, k):
+    """model_utils.keep_k_largest_from_LoV (model_utils.py:54-83): a binary mask with the structure of the list of
+    variables `LoV`, 1 on the k largest values over all of them, and the positions in the list that hold a 1.
+    The reference arg-sorts the negated values and leaves the order of equal values open; here entries equal to the
+    k-th largest value are taken in flat order (variables in list order, each raveled), the rule of alq_topk_mask.
+    Returns (bmask, non_empty_locs)."""
+    LoV = [np.asarray(v) for v in LoV]
+    Ls = [int(v.size) for v in LoV]
+    flat = np.concatenate([v.ravel() for v in LoV]) if LoV else np.zeros(0)
+    k = int(k)
+    if k < 0 or k > flat.size:
+        raise ValueError('k = %d outside [0, %d]' % (k, flat.size))
+    sort_inds = np.argsort(-flat, kind='stable')[:k]
+    fmask = np.zeros(flat.size)
+    fmask[sort_inds] = 1
+    ends = np.cumsum(Ls)
+    bmask = [fmask[e - n:e].reshape(v.shape) for e, n, v in zip(ends, Ls, LoV)]
+    non_empty_locs = np.where(np.array([m.any() for m in bmask], dtype=bool))[0]
+    return bmask, non_empty_locs
+
+
+def threshold_LoV(LoV, thr):
+    """model_utils.threshold_LoV (model_utils.py:85-96): 1 where a variable's value is >= thr, 0 elsewhere."""
+    bmask = [np.zeros(np.shape(v)) for v in LoV]
+    for m, v in zip(bmask, LoV):
+        m[np.asarray(v) >= thr] = 1
+    return bmask
