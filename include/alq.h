@@ -293,6 +293,61 @@ int alq_hess_vecp(alq_model *m, const float *d_x, int N, const int32_t *d_labels
 int alq_sgd_step(alq_ctx *ctx, float *d_theta, const float *d_grad, int64_t n, float lr);
 int alq_adam_step(alq_ctx *ctx, float *d_theta, const float *d_grad, float *d_m, float *d_v, int64_t n, float lr,
                   float beta1, float beta2, float eps, int64_t t);
+/* ---- the training objectives of NN_extended.CNN and the RMSProp step (csrc/loss.hip) ---------------------------------------- */
+/* What differs between the objectives of NN_extended.get_loss is the cotangent at the logits and the reported value; this
+ * struct describes one.  Per sample n with label y, posterior column p (fp32, as the head wrote it) and pt = p[y]:
+ *   ALQ_LOSS_CE       w = [0 <= y < c] * class_w[y] * sample_w[n] * f,  f = (1 - pt)^gamma with focal_gamma > 0 (1 - pt formed in
+ *                     fp32), else 1;  l = -w log pt;  row_j = s [labelled] class_w[y] sample_w[n] (p_j - delta_jy)
+ *                     ((1 - pt)^gamma - gamma (1 - pt)^(gamma - 1) pt log pt): the focal weight is differentiated, as TF does
+ *                     (no stop_gradient); at pt == 1.0f the focal row is exactly zero and w = 0.  With unit weights and no focal
+ *                     term the row has the bits alq_param_grads mode 1 writes.
+ *   ALQ_LOSS_CE_SOFT  targets t [c, N]: l = -sum_j t_j log p_j;  row_j = s (p_j sum_k t_k - t_j).
+ *   ALQ_LOSS_GCE      pc = clip(p, 1e-4, 1 - 1e-4): l = (1 / c) sum_j t_j (1 - pc_j^q) / q;
+ *                     row_k = -(s / c) sum_j t_j [1e-4 <= p_j <= 1 - 1e-4] p_j^q (delta_jk - p_k).
+ *   d_old_logits != NULL adds the learning-without-forgetting term (model_utils.get_LwF): tau = softmax(o / T),
+ *                     pi = softmax(z / T) formed FROM THE FP32 POSTERIORS (pi_j ~ p_j^(1/T), normalised; log p as below), not
+ *                     from the logits: l' = -sum_j tau_j log pi_j, row_j += s' (pi_j - tau_j) / T, unlabelled samples included.
+ *                     (Exact while no posterior underflows fp32, i.e. while the logits of a sample spread by less than 87.)
+ * -log p is log((double)max(p, 1e-38f)) throughout.  s = loss_scale and s' = lwf_scale are the caller's (1 / divisor).
+ * focal_gamma <= 0 (or negative: off) leaves the focal term out.  All pointers are device pointers; NULL = absent.
+ * Statistics d_stats3 (double [3], device): sum_n l_n unscaled; the number of samples whose weight w is not zero (TF's
+ * SUM_BY_NONZERO_WEIGHTS divisor; N for the two soft kinds); sum_n l'_n.  Per-workgroup partials in a fixed tree, summed in
+ * workgroup order by a second launch: no atomics, bit-identical from run to run.                                          */
+enum { ALQ_LOSS_CE = 0, ALQ_LOSS_CE_SOFT = 1, ALQ_LOSS_GCE = 2 };
+typedef struct alq_loss_t {
+    int32_t kind;
+    float focal_gamma;            /* < 0: off */
+    float gce_q;
+    float lwf_T;
+    const float *d_class_w;       /* [c] */
+    const float *d_sample_w;      /* [N] */
+    const float *d_targets;       /* [c, N] */
+    const float *d_old_logits;    /* [c, N] */
+} alq_loss_t;
+
+/* Replaces: sess.run(model.loss, ...) of an NN_extended.CNN whose loss is one of the above (NN_extended.py:1221-1277;
+ * model_utils.py:98-135), given the posteriors [c, N] of a forward pass: the three statistics alone, nothing else written.
+ * d_labels int32 [N] (required for ALQ_LOSS_CE; a label outside [0, c) is an unlabelled sample).  ALQ_EINVAL: null ctx /
+ * d_post / loss / d_stats3, c < 1, N < 1, an unknown kind, CE without labels, CE_SOFT or GCE without targets, GCE with
+ * gce_q == 0, old logits with lwf_T <= 0.                                                                             */
+int alq_loss_stats(alq_ctx *ctx, const float *d_post, int c, int N, const int32_t *d_labels, const alq_loss_t *loss,
+                   double *d_stats3);
+
+/* Replaces: the gradient half of sess.run(model.train_step / model.LwF_train_step, ...) of an NN_extended.CNN
+ * (optimizer.compute_gradients(model.loss), NN_extended.py:1380-1449; model_utils.py:98-135): alq_param_grads mode 1 with the
+ * cotangent of `loss` at the logits - same forward pass, dropout arguments, backward sweep, weight products and [P] layout
+ * (summed over the batch).  d_post [c, N] and d_stats3 optional.  ALQ_EINVAL: as alq_loss_stats, null m / d_x / d_grads,
+ * N outside [1, max_batch].                                                                                              */
+int alq_param_grads_loss(alq_model *m, const float *d_x, int N, const int32_t *d_labels, const alq_loss_t *loss,
+                         float loss_scale, float lwf_scale, float keep_prob, uint64_t seed, int64_t first_sample,
+                         const int32_t *h_drop_layers, int n_drop_layers, float *d_grads, float *d_post, double *d_stats3);
+
+/* Replaces: tf.train.RMSPropOptimizer(lr, decay, momentum, epsilon).apply_gradients (NN_extended.py:1399-1404; not centred)
+ * on flat device vectors: ms = decay ms + (1 - decay) g^2; mom = momentum mom + lr g / sqrt(ms + eps); theta -= mom.
+ * TF 1.x starts the rms slot at ones and the momentum slot at zeros: the caller allocates d_ms / d_mom that way.           */
+int alq_rmsprop_step(alq_ctx *ctx, float *d_theta, const float *d_grad, float *d_ms, float *d_mom, int64_t n, float lr,
+                     float decay, float momentum, float eps);
+
 /* Replaces: the accumulation loop of model_utils.diagonal_Fisher (model_utils.py:294-330):
  * d_acc[i] += sum_n d_grads[n, i]^2 (fp64).                                                                    */
 int alq_sq_accum(alq_ctx *ctx, const float *d_grads, int64_t per_sample_len, int N, double *d_acc);

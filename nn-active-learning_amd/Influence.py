@@ -119,6 +119,8 @@ def PW_sample_influence(model, sess, tr_padded_imgs, tr_mask, tr_inds, tr_stats,
     of the training loss over the voxels `tr_inds` - of their LAST batch of `batch_size` like the reference (see the module
     docstring), of all of them with `whole_set=True`.  Returns scipy's solution vector over `model.Hess_layers`."""
     from scipy.optimize import fmin_ncg
+    if getattr(model, '_obj', None) is not None:      # before anything is evaluated: H exists for NN.py's loss only
+        model._require_default_objective('PW_sample_influence')
     if not hasattr(model, 'v_placeholder'):      # (the reference tests for `hess_vecp`, which is also a method here)
         model.Hess_layers = layers
         get_hess_vec_product(model, layers)

@@ -21,6 +21,12 @@ class LayerT(C.Structure):
                 ('relu', C.c_int32), ('skip_src', C.c_int32)]
 
 
+class LossT(C.Structure):
+    """Mirror of alq_loss_t."""
+    _fields_ = [('kind', C.c_int32), ('focal_gamma', C.c_float), ('gce_q', C.c_float), ('lwf_T', C.c_float),
+                ('d_class_w', C.c_void_p), ('d_sample_w', C.c_void_p), ('d_targets', C.c_void_p), ('d_old_logits', C.c_void_p)]
+
+
 _P = C.c_void_p
 _SIGNATURES = {
     'alq_last_error': (C.c_char_p, []),
@@ -64,6 +70,10 @@ _SIGNATURES = {
     'alq_eval_counts': (C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_int, C.c_int64, _P, _P]),
     'alq_sgd_step': (C.c_int, [_P, _P, _P, C.c_int64, C.c_float]),
     'alq_adam_step': (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int64]),
+    'alq_loss_stats': (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.POINTER(LossT), _P]),
+    'alq_param_grads_loss': (C.c_int, [_P, _P, C.c_int, _P, C.POINTER(LossT), C.c_float, C.c_float, C.c_float, C.c_uint64, C.c_int64,
+                                       C.POINTER(C.c_int32), C.c_int, _P, _P, _P]),
+    'alq_rmsprop_step': (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float]),
     'alq_sq_accum': (C.c_int, [_P, _P, C.c_int64, C.c_int, _P]),
     'alq_shrink_sum': (C.c_int, [_P, _P, C.c_int, C.c_int64, C.POINTER(C.c_int64), C.c_int, _P]),
     'alq_fisher_classes': (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),

@@ -91,6 +91,7 @@ struct ProfSlot {
 #endif
 
 #define ALQ_PARAM_BLOCK_BYTES 512
+#define ALQ_LOSS_MAX_BLOCKS 64      // workgroups of loss_cotangent_kernel (grid-stride beyond 64 * 256 samples)
 #define ALQ_PARAM_FLAG_OFFSET (ALQ_PARAM_BLOCK_BYTES - 8)   // last word of the block: the bad-index flag of alq_eval_counts
 
 struct alq_ctx {
@@ -109,6 +110,7 @@ struct alq_ctx {
     bool side_used = false;
     bool side_off = false;     // alq_ctx_use_side_stream(ctx, 0): statistics kernels stay on the main stream (a caller that overlaps whole passes on two contexts)
     void *param_block = nullptr;   // small device buffer for per-call parameters (gather)
+    double *loss_part = nullptr;   // per-workgroup partials of the loss statistics (loss.hip), allocated by the first call
     void *comm = nullptr;          // RCCL communicator of this rank (comm.hip), or null
     int comm_rank = 0, comm_world = 1;
     int f16_subnormal_mfma = -1;   // c3d_subnormals_ok: -1 not probed yet on this context's device, else 0 / 1
@@ -665,6 +667,11 @@ int k_wgrad(alq_ctx *, const View &U, const View &V, const int k[3], const int s
 int k_bgrad(alq_ctx *, const View &delta, int N, int sum_n, float *d_out, long long out_stride);
 int k_fc_wgrad(alq_ctx *, const float *delta, const View &a, int nout, int N, int sum_n, float *d_out, long long out_stride);
 int k_sgd(alq_ctx *, float *theta, const float *g, long long n, float lr);
+// loss.hip: cotangent rows [N, c] (null: statistics only) and the three loss statistics (null: rows only) of an alq_loss_t
+int k_loss_cotangent(alq_ctx *, const float *post_cN, int c, int N, const int *labels, const alq_loss_t *loss, float loss_scale,
+                     float lwf_scale, float *dlogits, double *d_stats3);
+int k_rmsprop(alq_ctx *, float *theta, const float *g, float *ms, float *mom, long long n, float lr, float decay, float momentum,
+              float eps);
 int k_adam(alq_ctx *, float *theta, const float *g, float *m, float *v, long long n, float lr_t, float b1, float b2, float eps);
 int k_sq_accum(alq_ctx *, const float *g, long long per, int N, double *acc);
 int k_shrink_sum(alq_ctx *, const float *g, int N, long long P, const long long *off, int L, double *out);

@@ -2089,6 +2089,52 @@ int alq_adam_step(alq_ctx *ctx, float *d_theta, const float *d_grad, float *d_m,
     return n ? k_adam(ctx, d_theta, d_grad, d_m, d_v, n, (float)lr_t, beta1, beta2, eps) : ALQ_OK;
 }
 
+static int loss_check(const char *who, const float *d_post_or_x, int c, const int32_t *d_labels, const alq_loss_t *loss) {
+    ALQ_REQUIRE(d_post_or_x && loss, ALQ_EINVAL, "%s: null argument", who);
+    ALQ_REQUIRE(c >= 1, ALQ_EINVAL, "%s: %d classes", who, c);
+    ALQ_REQUIRE(loss->kind == ALQ_LOSS_CE || loss->kind == ALQ_LOSS_CE_SOFT || loss->kind == ALQ_LOSS_GCE, ALQ_EINVAL,
+                "%s: loss kind %d", who, (int)loss->kind);
+    ALQ_REQUIRE(loss->kind != ALQ_LOSS_CE || d_labels, ALQ_EINVAL, "%s: cross-entropy needs labels", who);
+    ALQ_REQUIRE(loss->kind == ALQ_LOSS_CE || loss->d_targets, ALQ_EINVAL, "%s: CE_softclasses / GCE need targets", who);
+    ALQ_REQUIRE(loss->kind != ALQ_LOSS_GCE || loss->gce_q != 0.f, ALQ_EINVAL, "%s: GCE with q = 0", who);
+    ALQ_REQUIRE(!loss->d_old_logits || loss->lwf_T > 0.f, ALQ_EINVAL, "%s: LwF temperature %g", who, (double)loss->lwf_T);
+    return ALQ_OK;
+}
+
+int alq_loss_stats(alq_ctx *ctx, const float *d_post, int c, int N, const int32_t *d_labels, const alq_loss_t *loss, double *d_stats3) {
+    ALQ_REQUIRE(ctx && d_stats3, ALQ_EINVAL, "alq_loss_stats: null argument");
+    ALQ_REQUIRE(N >= 1, ALQ_EINVAL, "alq_loss_stats: N=%d", N);
+    ALQ_TRY(loss_check("alq_loss_stats", d_post, c, d_labels, loss));
+    ALQ_HIP(hipSetDevice(ctx->device));
+    return k_loss_cotangent(ctx, d_post, c, N, d_labels, loss, 1.f, 1.f, nullptr, d_stats3);
+}
+
+int alq_param_grads_loss(alq_model *m, const float *d_x, int N, const int32_t *d_labels, const alq_loss_t *loss, float loss_scale,
+                         float lwf_scale, float keep_prob, uint64_t seed, int64_t first_sample, const int32_t *h_drop_layers,
+                         int n_drop_layers, float *d_grads, float *d_post, double *d_stats3) {
+    ALQ_REQUIRE(m && d_grads, ALQ_EINVAL, "alq_param_grads_loss: null argument");
+    ALQ_REQUIRE(N >= 1 && N <= m->max_batch, ALQ_EINVAL, "alq_param_grads_loss: N=%d outside [1, max_batch=%d]", N, m->max_batch);
+    ALQ_TRY(loss_check("alq_param_grads_loss", d_x, m->nclass, d_labels, loss));
+    ALQ_HIP(hipSetDevice(m->ctx->device));
+    DropSpec ds;
+    ALQ_TRY(make_drop(m, keep_prob, seed, first_sample, h_drop_layers, n_drop_layers, &ds));
+    m->last_call_fisher = false;
+    ALQ_TRY(prepare_call(m));
+    ALQ_TRY(run_forward(m, d_x, N, false, /*keep_all=*/true, &ds));
+    float *post = d_post ? d_post : m->post;
+    ALQ_TRY(k_softmax(m->ctx, m->logits, m->nclass, N, post, nullptr));
+    ALQ_TRY(k_loss_cotangent(m->ctx, post, m->nclass, N, d_labels, loss, loss_scale, lwf_scale, m->dlogits, d_stats3));
+    ALQ_TRY(run_backward_general(m, N, &ds));
+    return run_param_grads(m, d_x, N, 1, d_grads, alq_model_num_params(m));
+}
+
+int alq_rmsprop_step(alq_ctx *ctx, float *d_theta, const float *d_grad, float *d_ms, float *d_mom, int64_t n, float lr, float decay,
+                     float momentum, float eps) {
+    ALQ_REQUIRE(ctx && (n == 0 || (d_theta && d_grad && d_ms && d_mom)) && n >= 0, ALQ_EINVAL, "alq_rmsprop_step: bad argument");
+    ALQ_HIP(hipSetDevice(ctx->device));
+    return n ? k_rmsprop(ctx, d_theta, d_grad, d_ms, d_mom, n, lr, decay, momentum, eps) : ALQ_OK;
+}
+
 int alq_sq_accum(alq_ctx *ctx, const float *d_grads, int64_t per_sample_len, int N, double *d_acc) {
     ALQ_REQUIRE(ctx && d_grads && d_acc && per_sample_len >= 1 && N >= 1, ALQ_EINVAL, "alq_sq_accum: bad argument");
     ALQ_HIP(hipSetDevice(ctx->device));
@@ -2165,6 +2211,7 @@ int alq_ctx_destroy(alq_ctx *ctx) {
         for (auto e : ctx->prof[c].pool) (void)hipEventDestroy(e);
     }
     (void)hipFree(ctx->param_block);
+    if (ctx->loss_part) (void)hipFree(ctx->loss_part);
     delete ctx;
     return ALQ_OK;
 }

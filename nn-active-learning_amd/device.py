@@ -13,7 +13,7 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _lib
-from ._lib import ALQ_CONV, ALQ_CONVT, ALQ_FC, ALQ_POOL, LayerT, check
+from ._lib import ALQ_CONV, ALQ_CONVT, ALQ_FC, ALQ_POOL, LayerT, LossT, check
 
 
 def _torch():
@@ -215,7 +215,11 @@ class DeviceSession(object):
         `model.grad_posts[str(j)]` (PW_NNAL.py:773-807: list of 2L' gradient arrays of log posteriors[j, 0]) and
         `model.train_step` (PW_AL.py:1075-1080, :1140-1146); of the influence functions (Influence.py): `model.loss` (scalar
         mean cross-entropy, needs `model.y_`), `model.loss_grad` (NN.add_loss_grad) and `model.hess_vecp` with the entries of
-        `model.v_placeholder` in the feed (Influence.get_hess_vec_product)."""
+        `model.v_placeholder` in the feed (Influence.get_hess_vec_product).  Per-sample loss weights fed under
+        `model.input_weights` (or an `input_vox_weights` attribute of the model; the reference tests for one name and reads the
+        other, NN_extended.py:1252-1255) multiply the weights of the cross-entropy; `model.LwF_train_step` (model_utils.get_LwF)
+        takes `model.y__`, `model.lambda_o` and `model.T` as well; `model.labels` / `model.pt` are the label vector and the
+        posterior of each sample's label as the two-class focal term reads them (NN_extended.py:1228-1231)."""
         model = getattr(fetch, 'model', None)
         if isinstance(fetch, list):
             model = getattr(fetch[0], 'model', None) if fetch else None
@@ -229,6 +233,22 @@ class DeviceSession(object):
             raise KeyError('unknown fetch %r' % (fetch,))
         x = feed_dict[model.x]
         kp = float(feed_dict.get(model.keep_prob, 1.))
+        iw = None
+        for h in (getattr(model, 'input_weights', None), getattr(model, 'input_vox_weights', None)):
+            if h is not None and h in feed_dict:
+                iw = feed_dict[h]
+        if fetch.name == 'LwF_train_step':
+            lwf = (feed_dict[model.y__], float(feed_dict[model.lambda_o]), float(feed_dict[model.T]))
+            return model.train_on_batch(x, feed_dict[model.y_], keep_prob=kp, input_weights=iw, lwf=lwf)
+        if fetch.name == 'LwF_loss':
+            lwf = (feed_dict[model.y__], float(feed_dict[model.lambda_o]), float(feed_dict[model.T]))
+            return model.lwf_loss(x, feed_dict[model.y_], lwf, keep_prob=kp, input_weights=iw)
+        if fetch.name in ('labels', 'pt'):
+            lab = onehot_to_labels(feed_dict[model.y_], model.nclass)
+            if fetch.name == 'labels':
+                return lab
+            post = model.forward(x, want=('posteriors',), keep_prob=kp)['posteriors']
+            return np.where(lab == 1, post[1], post[0])
         if fetch.name == 'train_step':
             # NN_extended.get_optimizer (NN_extended.py:1441-1449): masks fed under model.par_placeholders hold for this step
             ph = getattr(model, 'par_placeholders', None)
@@ -236,12 +256,20 @@ class DeviceSession(object):
             if any(fed):
                 if not all(fed):
                     raise KeyError('a PFT step needs a mask for every entry of par_placeholders')
-                return model.train_on_batch(x, feed_dict[model.y_], keep_prob=kp, pft_mask=[feed_dict[h] for h in ph])
-            return model.train_on_batch(x, feed_dict[model.y_], keep_prob=kp)
+                return model.train_on_batch(x, feed_dict[model.y_], keep_prob=kp, pft_mask=[feed_dict[h] for h in ph], input_weights=iw)
+            return model.train_on_batch(x, feed_dict[model.y_], keep_prob=kp, input_weights=iw)
         if fetch.name in ('loss', 'loss_grad', 'hess_vecp'):
             # the training-time graph nodes of the influence functions (NN.py:583-588, :862-871; Influence.py:126-166)
             if kp != 1.:
                 raise NotImplementedError('%s at keep_prob < 1' % fetch.name)
+            model._check_input_weights(iw)
+            if model._obj is not None:
+                # an NN_extended objective: soft targets are read as they are fed
+                if fetch.name == 'hess_vecp':
+                    model._require_default_objective('hess_vecp')
+                if fetch.name == 'loss':
+                    return model.mean_loss(x, None, targets=feed_dict[model.y_], input_weights=iw)
+                return model.mean_loss_grad(x, None, fetch.layers, targets=feed_dict[model.y_], input_weights=iw)
             lab = onehot_to_labels(feed_dict[model.y_], model.nclass)
             if fetch.name == 'loss':
                 return model.mean_loss(x, lab)
@@ -517,6 +545,13 @@ class DeviceModel(object):
         self.loss.model = self
         self.train_step = None            # get_optimizer() creates it (NN.py:557-615)
         self._opt = None
+        # NN_extended.set_hypers: None = the batch-mean cross-entropy of NN.py:583-588; else the objective of NN_extended.get_loss
+        self.hypers = None
+        self._obj = None
+        self.input_weights = Handle('input_weights')      # per-sample loss weights [n], fed through feed_dict
+        self.labels = Handle('labels')
+        self.pt = Handle('pt')
+        self.labels.model = self.pt.model = self
         self._weights_version = 0         # bumped by every set_weights: the optimiser's device copy follows it
         self.PFT_bflag = False            # set_PFT_mask: the summed gradient is multiplied by a binary mask (NN_extended.py:1441-1449)
         self._pft_mask = None             # float32 device [P]
@@ -664,10 +699,24 @@ class DeviceModel(object):
             c += nw + nb
         return full
 
+    def _require_default_objective(self, what):
+        """The exact R-operator (csrc/hvp.hip) is that of the batch-mean cross-entropy: a model whose loss set_hypers changed
+        has no Hessian-vector product, whichever way it is asked for."""
+        if self._obj is not None:
+            raise NotImplementedError('%s of a non-default objective (set_hypers): the R-operator covers the batch-mean '
+                                      'cross-entropy only' % what)
+
+    def _check_input_weights(self, input_weights):
+        """Per-sample weights belong to NN_extended.get_loss (NN_extended.py:1252-1255); NN.py's loss has none."""
+        if input_weights is not None and self._obj is None:
+            raise ValueError('input_weights on a model without training hypers: the batch-mean cross-entropy of NN.py:583-588 '
+                             'takes no sample weights (build the NN_extended.CNN with loss_name=\'CE\' for the weighted mean)')
+
     def hess_vecp_device(self, t, n, labels, v, idx=None, loss_scale=1., out=None, want_loss=False):
         """alq_hess_vecp on n device patches (any n: passes of max_batch with the same loss_scale): `out` (float64 device
         [P]; created and overwritten when None) += H v, H the Hessian of loss_scale * sum CE over the layers `idx` (indices;
         None = all).  labels / v: int32 [n] / float32 [P] device tensors.  Returns (out, scaled loss of the passes or None)."""
+        self._require_default_objective('hess_vecp')      # every caller: hess_vecp, sess.run, PW_NN.batch_eval, Influence
         torch = self.sess.torch
         self.sess.bind_stream()
         assert labels.dtype == torch.int32 and labels.is_contiguous() and int(labels.numel()) == n
@@ -696,6 +745,7 @@ class DeviceModel(object):
         NN.py:583-588) over the parameters of `layers` ('all', names or indices; the others are held constant).  `v`: see
         ravel_for_layers.  Returns the list [HW, Hb, ...] of the chosen layers in TF shapes, float64.  `out`: a float64
         device vector [P] the product is ADDED to (multi-pass sums); the list then holds the accumulated values."""
+        self._require_default_objective('hess_vecp')
         torch = self.sess.torch
         t, n = self._as_device_batch(x)
         idx = self.hess_layer_idx(layers)
@@ -704,10 +754,16 @@ class DeviceModel(object):
         hv, _ = self.hess_vecp_device(t, n, lab, vd, idx, 1. / n if loss_scale is None else loss_scale, out)
         return self.unflatten(hv.cpu().numpy(), idx)
 
-    def mean_loss(self, x, labels):
-        """`sess.run(model.loss, {x, y_})`: the mean softmax cross-entropy of the batch (unlabelled samples add 0 to the sum)."""
+    def mean_loss(self, x, labels, targets=None, input_weights=None):
+        """`sess.run(model.loss, {x, y_})`: the mean softmax cross-entropy of the batch (unlabelled samples add 0 to the sum),
+        or the model's own objective once set_hypers gave it one (forward passes + alq_loss_stats; `targets` [c, n]: the
+        soft targets of CE_softclasses / GCE, one-hot columns of `labels` when None; `input_weights` [n])."""
         torch = self.sess.torch
         t, n = self._as_device_batch(x)
+        self._check_input_weights(input_weights)
+        if self._obj is not None:
+            y = self._onehot(labels, n) if targets is None else targets
+            return self._objective_pass(t, n, y, 1., None, input_weights, None, want_grad=False)[1]
         lab = self.sess.to_device(np.asarray(labels, dtype=np.int32).reshape(n), torch.int32)
         loss = 0.
         for a in range(0, n, self.max_batch):
@@ -716,11 +772,17 @@ class DeviceModel(object):
             loss += float(l.item()) * (b - a) / n
         return loss
 
-    def mean_loss_grad(self, x, labels, layers='all'):
+    def mean_loss_grad(self, x, labels, layers='all', targets=None, input_weights=None):
         """`sess.run(model.loss_grad, {x, y_})` (NN.add_loss_grad, NN.py:862-871): gradient of the mean cross-entropy with
-        respect to the variables of `layers`, TF shapes (alq_param_grads mode 1)."""
+        respect to the variables of `layers`, TF shapes (alq_param_grads mode 1) - of the model's own objective once set_hypers
+        gave it one (alq_param_grads_loss; `targets` / `input_weights` as in mean_loss)."""
         torch = self.sess.torch
         t, n = self._as_device_batch(x)
+        self._check_input_weights(input_weights)
+        if self._obj is not None:
+            y = self._onehot(labels, n) if targets is None else targets
+            g, _ = self._objective_pass(t, n, y, 1., None, input_weights, None)
+            return self.unflatten(g.cpu().numpy(), self.hess_layer_idx(layers))
         lab = self.sess.to_device(np.asarray(labels, dtype=np.int32).reshape(n), torch.int32)
         g = torch.zeros((self.num_params,), dtype=torch.float64, device=self.sess.device)
         for a in range(0, n, self.max_batch):
@@ -737,17 +799,55 @@ class DeviceModel(object):
         return self.unflatten(g[0].cpu().numpy(), self.grad_layer_idx)
 
     # -- training step (get_optimizer / train_step, NN.py:557-615) --------------------------
-    def get_optimizer(self, learning_rate, train_layers=[], optimizer_name='SGD'):
-        """Mean softmax cross-entropy + SGD or Adam on all layers or on `train_layers` (NN.py:583-615)."""
-        if optimizer_name not in ('SGD', 'Adam'):
-            raise NotImplementedError('optimizer %r (NN.py:591-615 knows SGD and Adam)' % (optimizer_name,))
+    def set_hypers(self, hypers):
+        """NN_extended.CNN.set_hypers (NN_extended.py:24-63) for the keys a device step reads (NN_extended.CNN.DEFAULT_HYPERS):
+        from here on the model's loss is NN_extended.get_loss's (:1221-1277) and get_optimizer() takes no arguments."""
+        from . import losses
+        torch = self.sess.torch
+        h = dict(hypers)
+        kind = losses.KINDS[h.get('loss_name', 'CE')]
+        bcw, gamma = h.get('bin_class_weights'), h.get('focal_gamma')
+        if (bcw is not None or gamma is not None) and self.nclass != 2:
+            raise ValueError('bin_class_weights / focal_gamma need a two-class net, got %d classes' % self.nclass)
+        if kind == losses.GCE and float(h.get('q', 0.7)) == 0:
+            raise ValueError('q cannot be equal to zero.')
+        self.hypers = h
+        self._obj = dict(kind=kind, divisor='nonzero', q=float(h.get('q', 0.7)),
+                         gamma=float(gamma) if (gamma is not None and kind == losses.CE) else None,
+                         class_w=self.sess.to_device(np.asarray(bcw, dtype=np.float32).reshape(2), torch.float32)
+                         if (bcw is not None and kind == losses.CE) else None)
+
+    def get_optimizer(self, learning_rate=None, train_layers=[], optimizer_name=None):
+        """Mean softmax cross-entropy + SGD or Adam on all layers or on `train_layers` (NN.py:583-615).  Without arguments
+        (NN_extended.get_optimizer, NN_extended.py:1380-1449): the optimiser - SGD, Adam(beta1, beta2) or RMSProp(decay, momentum,
+        epsilon) - and the learning rate (`learning_rate`, else `lr_schedule(step)` evaluated on the host before every step,
+        step = 0 before the first) of the model's hypers; `train_layers` as set on the model before the call, if at all."""
+        h = self.hypers or {}
+        if learning_rate is None and optimizer_name is None and not train_layers:
+            if self.hypers is None:
+                raise TypeError('get_optimizer() without arguments needs the hyper-parameters of an NN_extended.CNN')
+            train_layers = list(getattr(self, 'train_layers', []))
+        if optimizer_name is None:
+            optimizer_name = h.get('optimizer_name', 'SGD')
+        if optimizer_name not in ('SGD', 'Adam', 'RMSProp'):
+            raise NotImplementedError('optimizer %r (SGD, Adam and RMSProp are known)' % (optimizer_name,))
+        schedule = None
+        if learning_rate is None:
+            learning_rate = h.get('learning_rate')
+            if learning_rate is None:
+                schedule = h.get('lr_schedule')
+                if schedule is None:
+                    raise ValueError('neither learning_rate nor lr_schedule is set')
+                learning_rate = schedule(0)
         for nme in train_layers:
             if nme not in self.var_names:
                 raise KeyError('train layer %r' % (nme,))
         self.train_layers = list(train_layers)
         self.train_step = Handle('train_step')
         self.train_step.model = self
-        self._opt = dict(name=optimizer_name, lr=float(learning_rate), t=0, theta=None, m=None, v=None)
+        self._opt = dict(name=optimizer_name, lr=float(learning_rate), schedule=schedule, t=0, theta=None, m=None, v=None,
+                         beta1=float(h.get('beta1', 0.9)), beta2=float(h.get('beta2', 0.999)), decay=float(h.get('decay', 0.9)),
+                         momentum=float(h.get('momentum', 0.)), epsilon=float(h.get('epsilon', 1e-10)))
 
     def _train_mask(self):
         """1 on the parameters of `train_layers` (all when empty), flat order."""
@@ -829,11 +929,127 @@ class DeviceModel(object):
             check(self.lib.alq_threshold_mask(self.sess.ctx, C.c_void_p(v.data_ptr()), n, float(thr), C.c_void_p(mask.data_ptr())))
         return mask
 
-    def train_on_batch(self, x, y_onehot, keep_prob=1., seed=None, pft_mask=None):
+    def _onehot(self, labels, n):
+        lab = np.asarray(labels).astype(np.int64).reshape(n)
+        y = np.zeros((self.nclass, n), dtype=np.float32)
+        ok = (lab >= 0) & (lab < self.nclass)
+        y[lab[ok], np.nonzero(ok)[0]] = 1.
+        return y
+
+    def _objective_pass(self, t, n, y, keep_prob, seed, input_weights, lwf, want_grad=True):
+        """The model's objective (set_hypers; the batch-mean cross-entropy with divisor n when none is set) on n device patches
+        over passes of max_batch: (gradient of the loss, float32 device [P] - None without `want_grad` - and the loss).
+        y [c, n]: one-hot columns (all zero: unlabelled) or, for CE_softclasses / GCE, the soft targets; input_weights [n];
+        lwf = (old logits [c, n], lambda_o, T) adds lambda_o * mean_n l'_n (model_utils.get_LwF).
+        The weighted cross-entropy divides by the number of non-zero weights of the WHOLE batch (TF's SUM_BY_NONZERO_WEIGHTS):
+        without the focal term that count is known on the host from labels and weights; with it the passes run unscaled and
+        the summed gradient is divided by the count on the device (no read in between); focal with LwF - two terms with two
+        divisors - takes the count from forward passes + alq_loss_stats first.  One read of the statistics at the end."""
+        from . import losses
+        torch = self.sess.torch
+        self.sess.bind_stream()
+        obj = self._obj or dict(kind=losses.CE, divisor='N', q=0.7, gamma=None, class_w=None)
+        kind, c = obj['kind'], self.nclass
+        y = np.asarray(y)
+        if y.shape != (c, n):
+            raise ValueError('labels must be [%d, %d] columns, got %r' % (c, n, y.shape))
+        lab = np.where(y.sum(0) > 0, y.argmax(0), -1).astype(np.int32)
+        labd = self.sess.to_device(lab, torch.int32)
+        tgd = self.sess.to_device(y.astype(np.float32), torch.float32) if kind != losses.CE else None
+        sw = None if input_weights is None else np.asarray(input_weights, dtype=np.float32).reshape(n)
+        swd = None if sw is None else self.sess.to_device(sw, torch.float32)
+        cw = obj['class_w']
+        gamma = obj['gamma'] if (obj['gamma'] is not None and obj['gamma'] > 0) else None
+        old, lam, T = None, 0., 1.
+        if lwf is not None:
+            old = self.sess.to_device(np.asarray(lwf[0], dtype=np.float32).reshape(c, n), torch.float32)
+            lam, T = float(lwf[1]), float(lwf[2])
+        kp, arr, nl, seed = self._drop_args(keep_prob, seed)
+        cuts = [(a, min(n, a + self.max_batch)) for a in range(0, n, self.max_batch)]
+
+        def spec(a, b):
+            keep = [None if v is None else v[:, a:b].contiguous() for v in (tgd, old)]
+            L = LossT(kind, -1. if gamma is None else gamma, obj['q'], T, cw.data_ptr() if cw is not None else None,
+                      swd.data_ptr() + a * 4 if swd is not None else None, keep[0].data_ptr() if keep[0] is not None else None,
+                      keep[1].data_ptr() if keep[1] is not None else None)
+            return L, keep
+
+        def stats_only(dst):
+            for k, (a, b) in enumerate(cuts):
+                pb = self.sess.empty((c, b - a), torch.float32)
+                check(self.lib.alq_forward_dropout(self._m, C.c_void_p(t.data_ptr() + a * self.elems_per_patch * 4), b - a, kp, seed, a,
+                                                   arr, nl, C.c_void_p(pb.data_ptr()), None))
+                L, keep = spec(a, b)
+                check(self.lib.alq_loss_stats(self.sess.ctx, C.c_void_p(pb.data_ptr()), c, b - a, C.c_void_p(labd.data_ptr() + a * 4),
+                                              C.byref(L), C.c_void_p(dst.data_ptr() + k * 24)))
+                del keep
+
+        stats = torch.zeros((len(cuts), 3), dtype=torch.float64, device=self.sess.device)
+        post_scale = False
+        if kind == losses.CE_SOFT:
+            s = 1. / n
+        elif kind == losses.GCE:
+            s = 1.           # reduce_mean over the classes leaves a vector over samples: the optimiser differentiates its sum
+        elif obj['divisor'] == 'N':
+            s = 1. / n
+        elif gamma is None:
+            w = (lab >= 0).astype(np.float64)
+            if cw is not None:
+                w = w * np.asarray(self.hypers['bin_class_weights'], dtype=np.float32).reshape(2)[np.where(lab == 1, 1, 0)]
+            if sw is not None:
+                w = w * sw
+            cnt = int(np.count_nonzero(w))
+            s = 1. / cnt if cnt else 0.
+        elif want_grad and lwf is not None:
+            stats_only(stats)
+            cnt = float(stats[:, 1].sum().item())
+            s = 1. / cnt if cnt else 0.
+        else:
+            s, post_scale = 1., True
+        gsum = None
+        if want_grad:
+            gsum = torch.zeros((self.num_params,), dtype=torch.float32, device=self.sess.device)
+            for k, (a, b) in enumerate(cuts):
+                g = self.sess.empty((self.num_params,), torch.float32)
+                L, keep = spec(a, b)
+                check(self.lib.alq_param_grads_loss(self._m, C.c_void_p(t.data_ptr() + a * self.elems_per_patch * 4), b - a,
+                                                    C.c_void_p(labd.data_ptr() + a * 4), C.byref(L), float(s), lam / n, kp, seed, a,
+                                                    arr, nl, C.c_void_p(g.data_ptr()), None, C.c_void_p(stats.data_ptr() + k * 24)))
+                gsum += g
+                del keep
+            if post_scale:
+                cnt_d = stats[:, 1].sum()
+                gsum *= torch.where(cnt_d > 0, 1. / cnt_d.clamp(min=1.), torch.zeros_like(cnt_d)).to(torch.float32)
+        else:
+            stats_only(stats)
+        st = stats.cpu().numpy()
+        if kind == losses.CE and obj['divisor'] == 'N':
+            loss = 0.
+            for (a, b), row in zip(cuts, st):          # the arithmetic of the default step: per-pass means, weighted
+                loss += float(row[0] / (b - a)) * (b - a) / n
+        elif kind == losses.CE:
+            cnt = st[:, 1].sum()
+            loss = float(st[:, 0].sum() / cnt) if cnt else 0.
+        else:
+            loss = float(st[:, 0].sum() / n)      # GCE: the mean of the reference's per-sample loss vector
+        if lwf is not None:
+            loss = loss + lam * float(st[:, 2].sum() / n)
+        return gsum, loss
+
+    def lwf_loss(self, x, y_onehot, lwf, keep_prob=1., seed=None, input_weights=None):
+        """`sess.run(model.LwF_loss, ...)`: the value LwF_train_step minimises, loss + lambda_o * mean_n l'_n, without a step
+        (forward passes + alq_loss_stats).  lwf = (old logits [c, n], lambda_o, T)."""
+        self._check_input_weights(input_weights)
+        t, n = self._as_device_batch(x)
+        return self._objective_pass(t, n, y_onehot, keep_prob, seed, input_weights, lwf, want_grad=False)[1]
+
+    def train_on_batch(self, x, y_onehot, keep_prob=1., seed=None, pft_mask=None, input_weights=None, lwf=None):
         """One `sess.run(model.train_step, {x, y_, keep_prob})`: gradient of the batch-mean cross-entropy (summed over
         device passes of max_batch patches), one optimiser step on the device, weights repacked.  y_onehot: [c, n]
         like the reference's hot_labels (PW_AL.py:1064-1067); an all-zero column is an unlabelled sample.
         A PFT mask (set_PFT_mask, or `pft_mask` for this step only) multiplies the summed gradient before the step.
+        With hypers (set_hypers) or `lwf` = (old logits [c, n], lambda_o, T) the gradient and the loss are those of the model's
+        objective (_objective_pass; alq_param_grads_loss); per-sample `input_weights` [n] need hypers (ValueError without).
         Returns the batch-mean loss before the step."""
         if self._opt is None:
             raise RuntimeError('get_optimizer() has not been called (NN.py:1354)')
@@ -842,17 +1058,21 @@ class DeviceModel(object):
         y = np.asarray(y_onehot)
         if y.shape != (self.nclass, n):
             raise ValueError('labels must be [%d, %d] one-hot columns, got %r' % (self.nclass, n, y.shape))
-        lab = np.where(y.sum(0) > 0, y.argmax(0), -1).astype(np.int32)
-        kp, _, _, seed = self._drop_args(keep_prob, seed)
-        labd = self.sess.to_device(lab, torch.int32)
-        gsum = torch.zeros((self.num_params,), dtype=torch.float32, device=self.sess.device)
-        loss = 0.
-        for a in range(0, n, self.max_batch):
-            b = min(n, a + self.max_batch)
-            g, _, l = self.param_grads_device(t[a:b], b - a, 1, labels=labd[a:b], loss_scale=1. / n, keep_prob=kp,
-                                              seed=seed, first_sample=a, per_sample=False, want_loss=True)
-            gsum += g
-            loss += float(l.item()) * (b - a) / n
+        self._check_input_weights(input_weights)
+        if self._obj is not None or lwf is not None:
+            gsum, loss = self._objective_pass(t, n, y, keep_prob, seed, input_weights, lwf)
+        else:
+            lab = np.where(y.sum(0) > 0, y.argmax(0), -1).astype(np.int32)
+            kp, _, _, seed = self._drop_args(keep_prob, seed)
+            labd = self.sess.to_device(lab, torch.int32)
+            gsum = torch.zeros((self.num_params,), dtype=torch.float32, device=self.sess.device)
+            loss = 0.
+            for a in range(0, n, self.max_batch):
+                b = min(n, a + self.max_batch)
+                g, _, l = self.param_grads_device(t[a:b], b - a, 1, labels=labd[a:b], loss_scale=1. / n, keep_prob=kp,
+                                                  seed=seed, first_sample=a, per_sample=False, want_loss=True)
+                gsum += g
+                loss += float(l.item()) * (b - a) / n
         o = self._opt
         if o['theta'] is None or o.get('version') != self._weights_version:
             # the TF variables are the single state of the reference: weights loaded or assigned since the last step
@@ -864,6 +1084,9 @@ class DeviceModel(object):
         if fresh:
             o['m'] = torch.zeros_like(o['theta'])
             o['v'] = torch.zeros_like(o['theta'])
+            if o['name'] == 'RMSProp':                  # TF 1.x: the rms slot starts at ones, the momentum slot at zeros
+                o['ms'] = torch.ones_like(o['theta'])
+                o['mom'] = torch.zeros_like(o['theta'])
             tm = self._train_mask()
             o['mask'] = self.sess.to_device(tm, torch.float32) if tm is not None else None
         if o.get('mask') is not None:
@@ -879,15 +1102,25 @@ class DeviceModel(object):
                 still = torch.stack([((o['m'][a_:a_ + nw + nb] == 0).all() & (o['v'][a_:a_ + nw + nb] == 0).all())
                                      for a_, nw, nb in offs]).cpu().numpy()
                 players = [q for q in range(self.L) if q in players or not still[q]]
+            if o['name'] == 'RMSProp' and o['momentum'] != 0. and len(players) < self.L:
+                # likewise: a masked layer goes on moving on the momentum it has (momentum 0: mom = lr * 0 / sqrt(.) = 0, it stays)
+                still = torch.stack([(o['mom'][a_:a_ + nw + nb] == 0).all() for a_, nw, nb in self._param_offsets()]).cpu().numpy()
+                players = [q for q in range(self.L) if q in players or not still[q]]
+        if o.get('schedule') is not None:
+            o['lr'] = float(o['schedule'](o['t']))          # the step count before this step: 0 at the first
         o['t'] += 1
         P = self.num_params
         self.sess.bind_stream()
         if o['name'] == 'SGD':
             check(self.lib.alq_sgd_step(self.sess.ctx, C.c_void_p(o['theta'].data_ptr()), C.c_void_p(gsum.data_ptr()), P, o['lr']))
+        elif o['name'] == 'RMSProp':
+            check(self.lib.alq_rmsprop_step(self.sess.ctx, C.c_void_p(o['theta'].data_ptr()), C.c_void_p(gsum.data_ptr()),
+                                            C.c_void_p(o['ms'].data_ptr()), C.c_void_p(o['mom'].data_ptr()), P, o['lr'],
+                                            o['decay'], o['momentum'], o['epsilon']))
         else:
             check(self.lib.alq_adam_step(self.sess.ctx, C.c_void_p(o['theta'].data_ptr()), C.c_void_p(gsum.data_ptr()),
                                          C.c_void_p(o['m'].data_ptr()), C.c_void_p(o['v'].data_ptr()), P, o['lr'],
-                                         0.9, 0.999, 1e-8, o['t']))      # a parameter masked out since the first step keeps m = v = 0: its step is 0 / eps = 0
+                                         o.get('beta1', 0.9), o.get('beta2', 0.999), 1e-8, o['t']))      # a parameter masked out since the first step keeps m = v = 0: its step is 0 / eps = 0
         if self._host_repack:
             self.set_flat_params(o['theta'].cpu().numpy())
         else:

@@ -45,3 +45,22 @@ def threshold_LoV(LoV, thr):
     for m, v in zip(bmask, LoV):
         m[np.asarray(v) >= thr] = 1
     return bmask
+
+
+def get_LwF(model):
+    """model_utils.get_LwF (model_utils.py:98-135): learning without forgetting on top of the loss the model has.  Creates the
+    handles `lambda_o`, `T`, `y__` (the previous model's logits [c, n]), `LwF_loss` and `LwF_train_step`;
+    `sess.run(model.LwF_train_step, {x, y_, y__, lambda_o, T, keep_prob})` takes one optimiser step on
+    loss + lambda_o * mean_n CE(softmax(y__ / T), softmax(output / T)), the mean over all n columns, labelled or not
+    (alq_param_grads_loss with old logits), and returns that loss.  Needs get_optimizer() beforehand, like the reference.
+    Under `train_layers` the reference calls `minimize(model.LwF, ...)`, an AttributeError (the attribute is `LwF_loss`); here
+    the step minimises `LwF_loss` over those layers."""
+    from .device import Handle
+    if getattr(model, '_opt', None) is None:
+        raise RuntimeError('get_LwF needs model.get_optimizer() to be called beforehand')
+    model.lambda_o = Handle('lambda_o')
+    model.T = Handle('T')
+    model.y__ = Handle('y__')
+    model.LwF_loss = Handle('LwF_loss')              # sess.run(model.LwF_loss, ...): the same value, no step
+    model.LwF_train_step = Handle('LwF_train_step')
+    model.LwF_loss.model = model.LwF_train_step.model = model
