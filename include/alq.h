@@ -420,6 +420,34 @@ int alq_colsum_max(alq_ctx *ctx, const double *d_S, int64_t n, int b, const doub
 int alq_take_colmax(alq_ctx *ctx, const double *d_S, int64_t n, int b, int j, int first, double *d_v);
 int alq_fold_rowmax(alq_ctx *ctx, const double *d_S, int t, int64_t n, double *d_v);
 
+/* ---- last-layer closed forms and the stochastic influence recursion (csrc/llfc.hip) -------------------------------- */
+/* Replaces: NN.LLFC_grads / NN.LLFC_hess / NN.PW_LLFC_grads (NN.py:874-1029; duplicated in model_utils.py:137-292) and the
+ * iteration of PW_NNAL.stoch_approx_IF (PW_NNAL.py:851-881).  u [d] = the input of the last fc layer (the model's feature
+ * layer) of a sample, p [c] its posterior; a parameter vector holds W class-major (entry j*d + i) and then the c biases:
+ * P = (d+1) c entries.  Features are taken as the caller hands them: any feature order, as long as pool and training
+ * features share it.  d_feat [n, d] fp32 rows, d_post [c, n] fp32 (alq_forward's layouts), labels int32 [n].
+ *   alq_llfc_grads     d_out [n, P] fp32, row n = (([j == y_n] - p_jn) u_n for j < c, [j == y_n] - p_jn): fp32 arithmetic
+ *   alq_llfc_hess      d_H [P, P] fp64 of ONE sample: A (x) (u~ u~^T), u~ = (u, 1), A_jk = p_j (p_k - [j == k]); symmetric bit
+ *                      for bit.  ALQ_EUNSUPPORTED when P * P * 8 exceeds alq_llfc_hess_max_bytes() (256 MiB): the recursion
+ *                      below never forms the matrix
+ *   alq_llfc_stoch_if  d_V [n_pool, P] fp32: V_0 = G (the gradients at d_pool_labels, each entry the fp64 product rounded
+ *                      once), then for t < T with r = d_draws[t] (int32, clamped to [0, n_tr)):  V <- G + V + H_r V / scale,
+ *                      done per column as c dot products and a rank-c update in fp64, V rounded to fp32 once per iteration.
+ *                      path 1: columns stay in LDS over all T iterations (one launch; needs c <= 4 and c d 4 bytes within
+ *                      the LDS of a CU, else ALQ_EUNSUPPORTED), path 2: V streams through HBM, two launches per iteration,
+ *                      d_work = alq_llfc_if_work_bytes(n_pool, c) bytes (may be NULL on path 1), path 0: what
+ *                      alq_llfc_if_path(d, c) names.  Both paths sum in one fixed order: the same bits, run after run.
+ *                      n and n_pool <= 65535 per call (columns are independent: a larger pool is walked in slices).     */
+int alq_llfc_grads(alq_ctx *ctx, const float *d_feat, const float *d_post, const int32_t *d_labels, int n, int d, int c,
+                   float *d_out);
+size_t alq_llfc_hess_max_bytes(void);
+int alq_llfc_hess(alq_ctx *ctx, const float *d_feat_one, const float *d_post_one, int d, int c, double *d_H);
+int alq_llfc_if_path(int d, int c);
+size_t alq_llfc_if_work_bytes(int n_pool, int c);
+int alq_llfc_stoch_if(alq_ctx *ctx, const float *d_pool_feat, const float *d_pool_post, const int32_t *d_pool_labels, int n_pool,
+                      const float *d_tr_feat, const float *d_tr_post, int n_tr, const int32_t *d_draws, int T, double scale, int d,
+                      int c, int path, float *d_V, void *d_work);
+
 /* ---- fp64 accuracy reference on the device (csrc/ref64.hip; bench.py `accuracy`, tests) ------------------------------- */
 /* One inverted decision of an fp64 evaluation.  layer = model layer index of a ReLU'd conv / conv_transpose / fc layer: the
  * ReLU decision of element `idx` of that layer's pre-activation of ONE sample ([vox, C] flattened; fc: the unit) is

@@ -57,6 +57,54 @@ def add_loss_grad(model, pars=[]):
     model.loss_grad.layers = list(pars) if len(pars) else 'all'
 
 
+def _llfc_forward(model, sess, feed_dict):
+    if float(feed_dict.get(model.keep_prob, 1.)) != 1.:
+        raise NotImplementedError('the last-layer closed forms at keep_prob < 1')
+    model._require_llfc()
+    t, n = model._as_device_batch(feed_dict[model.x])
+    post, pred, feat = model.forward_device(t, n, want_pred=True, want_feat=True)
+    return n, post, pred, feat
+
+
+def LLFC_hess(model, sess, feed_dict):
+    """NN.LLFC_hess (NN.py:874-903): the explicit Hessian of one sample's soft-max loss with respect to the last (fc) layer,
+    float64 [(d+1)c, (d+1)c] in the reference's parameter order (alq_llfc_hess).  ValueError above the library's byte cap
+    (NET-B: 537 MB): PW_NNAL.stoch_approx_IF never forms the matrix."""
+    model._require_llfc_hess_fits()
+    n, post, _, feat = _llfc_forward(model, sess, feed_dict)
+    if n != 1:
+        raise ValueError('LLFC_hess takes one sample, got %d' % n)
+    idx = model.llfc_reference_order()
+    H = model.llfc_hess_device(feat, post).cpu().numpy()
+    return H[np.ix_(idx, idx)]
+
+
+def LLFC_grads(model, sess, feed_dict, labels=None):
+    """NN.LLFC_grads (NN.py:905-955): gradients of the log-likelihood of `labels` (the predictions when None, which are then
+    returned too) with respect to the last (fc) layer, float64 [(d+1)c, n] (alq_llfc_grads)."""
+    n, post, pred, feat = _llfc_forward(model, sess, feed_dict)
+    idx = model.llfc_reference_order()
+    g = model.llfc_grads_device(feat, post, pred if labels is None else np.asarray(labels).reshape(-1))
+    g = np.ascontiguousarray(g.cpu().numpy().astype(np.float64)[:, idx].T)
+    return (g, pred.cpu().numpy()) if labels is None else g
+
+
+def PW_LLFC_grads(model, sess, expr, all_padded_imgs, img_inds, labels):
+    """NN.PW_LLFC_grads (NN.py:957-1029): LLFC_grads of the indexed voxels' patches of several subjects at the given labels (not
+    necessarily those of the masks), float64 [(d+1)c, n] in subject order.  The reference fills the label term from the LAST
+    subject's features only (`a_s`, NN.py:1015); this is the function it documents: every sample's own features."""
+    from . import patch_utils
+    patches, _ = patch_utils.get_patches_multimg(all_padded_imgs, img_inds, expr.pars['patch_shape'], expr.train_stats)
+    labels = np.asarray(labels).reshape(-1)
+    out, cnt = [], 0
+    for i in range(len(img_inds)):
+        ni = len(img_inds[i])
+        if ni:
+            out.append(LLFC_grads(model, sess, {model.x: patches[i], model.keep_prob: 1.}, labels[cnt:cnt + ni]))
+        cnt += ni
+    return np.concatenate(out, axis=1) if out else np.zeros(((model.feature_dim + 1) * model.nclass, 0))
+
+
 class CNN(DeviceModel):
     """NN.CNN(x, layer_dict, name, feature_layer, dropout, probes): same layer-dict schema
     ``{name: [depth,'conv',[kh,kw]] | [depth,'fc'] | [[window,stride],'pool']}``; `x` is replaced

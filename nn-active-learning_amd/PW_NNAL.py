@@ -523,3 +523,22 @@ def query_multimg(expr, model, sess, all_padded_imgs, pool_inds, labeled_inds, m
         return [np.array(sel_inds[i])[local[i]] for i in range(len(sel_inds))]
     raise NotImplementedError("query method %r is outside the scored path (random, entropy, MC-entropy, BALD, ensemble, QBC-JS, "
                               "rep-entropy, core-set, egl, fi)" % (method_name,))
+
+
+def stoch_approx_IF(model, sess, tr_patches, pool_patches, max_iter, scale=50):
+    """PW_NNAL.stoch_approx_IF (PW_NNAL.py:851-881): V_0 = the last-layer gradients of the pool patches at their predicted
+    ("weak") labels, then max_iter times V <- G + V + H_r V / scale with H_r the last-layer Hessian of a uniformly drawn training
+    patch.  Returns (V [(d+1)c, n_pool] float64, weak_labels).  The draws are the reference's, max_iter calls of
+    np.random.randint(ntr) on the global stream, taken up front; the reference forms every H_r with np.kron and multiplies it into V,
+    here each column takes c dot products and a rank-c update on the device (alq_llfc_stoch_if) and only the distinct drawn
+    patches are forwarded."""
+    tr_patches = np.asarray(tr_patches)
+    ntr = tr_patches.shape[0]
+    draws = np.array([np.random.randint(ntr) for _ in range(int(max_iter))], dtype=np.int64)
+    uniq, inv = np.unique(draws, return_inverse=True)
+    pool_t, n_pool = model._as_device_batch(pool_patches)
+    tr_t = model._as_device_batch(tr_patches[uniq])[0] if len(uniq) else None
+    V, weak = model.llfc_stoch_if_device(pool_t, n_pool, tr_t, inv.reshape(-1), scale)
+    idx = sess.to_device(model.llfc_reference_order(), sess.torch.int64)
+    V_t = V.index_select(1, idx).to(sess.torch.float64).t().contiguous()      # the feature permutation, once, on the way out
+    return V_t.cpu().numpy(), weak.cpu().numpy()

@@ -83,6 +83,13 @@ _SIGNATURES = {
     'alq_colsum_max': (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, _P, _P, _P]),
     'alq_take_colmax': (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, _P]),
     'alq_fold_rowmax': (C.c_int, [_P, _P, C.c_int, C.c_int64, _P]),
+    'alq_llfc_grads': (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    'alq_llfc_hess_max_bytes': (C.c_size_t, []),
+    'alq_llfc_hess': (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P]),
+    'alq_llfc_if_path': (C.c_int, [C.c_int, C.c_int]),
+    'alq_llfc_if_work_bytes': (C.c_size_t, [C.c_int, C.c_int]),
+    'alq_llfc_stoch_if': (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, C.c_int, _P, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int,
+                                    _P, _P]),
     'alq_comm_unique_id': (C.c_int, [_P]),
     'alq_comm_init': (C.c_int, [_P, _P, C.c_int, C.c_int]),
     'alq_comm_destroy': (C.c_int, [_P]),

@@ -1185,6 +1185,108 @@ class DeviceModel(object):
                                             C.c_void_p(acc.data_ptr())))
         return acc.div_(max(n, 1))
 
+    # -- last-layer closed forms (NN.py:874-1029, PW_NNAL.py:851-881) -------------------------
+    _LLFC_SLICE = 32768        # samples / columns per launch (alq.h: at most 65535; they are independent)
+
+    def _require_llfc(self):
+        """The closed forms take `feature_layer` as the input u of the last fc layer."""
+        wshape = self.param_shapes[-1][1]
+        if self.feature_idx is None or self.layers[-1]['type'] != ALQ_FC or self.feature_dim * self.nclass != int(np.prod(wshape)):
+            raise ValueError('feature_layer (%r, %d values) is not the input of the last fc layer (weights %r)' %
+                             (self.feature_idx, self.feature_dim, tuple(wshape)))
+
+    def llfc_reference_order(self):
+        """Index vector [P]: entry j*d + i of a reference-ordered last-layer vector (NN.py:296-301 flatten order) is entry
+        idx[j*d + i] of the device's (feature-memory order); the biases keep their places."""
+        d, c = self.feature_dim, self.nclass
+        perm = self._feature_perm if self._feature_perm is not None else np.arange(d)
+        return np.concatenate([(np.arange(c)[:, None] * d + np.asarray(perm)[None, :]).reshape(-1), c * d + np.arange(c)])
+
+    def llfc_grads_device(self, feat, post, labels):
+        """alq_llfc_grads: the gradients of log posteriors[labels[n], n] with respect to the last fc layer, float32 device
+        tensor [n, (d+1)c] (W class-major, then b), from device tensors feat [n, d], post [c, n] (forward_device) and labels
+        (int array or device tensor [n]).  Features in the device's memory order (llfc_reference_order)."""
+        torch = self.sess.torch
+        self._require_llfc()
+        self.sess.bind_stream()
+        n, d, c = int(feat.shape[0]), self.feature_dim, self.nclass
+        lab = labels if isinstance(labels, torch.Tensor) else self.sess.to_device(np.asarray(labels).reshape(n), torch.int32)
+        lab = lab.to(torch.int32).contiguous()
+        assert feat.dtype == torch.float32 and feat.is_contiguous() and tuple(feat.shape) == (n, d)
+        assert post.dtype == torch.float32 and tuple(post.shape) == (c, n) and int(lab.numel()) == n
+        out = self.sess.empty((n, (d + 1) * c), torch.float32)
+        for a in range(0, n, self._LLFC_SLICE):
+            b = min(n, a + self._LLFC_SLICE)
+            pb = post[:, a:b].contiguous()
+            check(self.lib.alq_llfc_grads(self.sess.ctx, C.c_void_p(feat.data_ptr() + a * d * 4), C.c_void_p(pb.data_ptr()),
+                                          C.c_void_p(lab.data_ptr() + a * 4), b - a, d, c, C.c_void_p(out.data_ptr() + a * (d + 1) * c * 4)))
+        return out
+
+    def _require_llfc_hess_fits(self):
+        """Before anything is computed or allocated: the explicit matrix must stay under the library's byte cap."""
+        self._require_llfc()
+        P = (self.feature_dim + 1) * self.nclass
+        cap = int(self.lib.alq_llfc_hess_max_bytes())
+        if P * P * 8 > cap:
+            raise ValueError('the explicit last-layer Hessian of (d+1)c = %d parameters takes %d bytes (cap %d): use the implicit '
+                             'routes, PW_NNAL.stoch_approx_IF / DeviceModel.llfc_stoch_if_device' % (P, P * P * 8, cap))
+
+    def llfc_hess_device(self, feat_one, post_one):
+        """alq_llfc_hess: the explicit [(d+1)c, (d+1)c] float64 Hessian of one sample's loss in the last fc layer."""
+        torch = self.sess.torch
+        self._require_llfc_hess_fits()
+        d, c = self.feature_dim, self.nclass
+        P = (d + 1) * c
+        self.sess.bind_stream()
+        f = feat_one.reshape(-1).contiguous()
+        p = post_one.reshape(-1).contiguous()
+        assert f.dtype == torch.float32 and int(f.numel()) == d and p.dtype == torch.float32 and int(p.numel()) == c
+        H = self.sess.empty((P, P), torch.float64)
+        check(self.lib.alq_llfc_hess(self.sess.ctx, C.c_void_p(f.data_ptr()), C.c_void_p(p.data_ptr()), d, c, C.c_void_p(H.data_ptr())))
+        return H
+
+    def llfc_stoch_if_features_device(self, pool_feat, pool_post, pool_labels, tr_feat, tr_post, draws, scale, path=0):
+        """alq_llfc_stoch_if on features that are already there: pool_feat [n_pool, d], pool_post [c, n_pool], tr_feat [n_tr, d],
+        tr_post [c, n_tr] float32 device tensors, `draws` indices into the training rows.  float32 device tensor [n_pool, (d+1)c]."""
+        torch = self.sess.torch
+        self.sess.bind_stream()
+        d, c = int(pool_feat.shape[1]), int(pool_post.shape[0])
+        n_pool, n_tr = int(pool_feat.shape[0]), int(tr_feat.shape[0]) if tr_feat is not None else 0
+        draws = np.asarray(draws, dtype=np.int64).reshape(-1)
+        T = int(draws.size)
+        if T and (n_tr < 1 or draws.min() < 0 or draws.max() >= n_tr):
+            raise ValueError('draws outside the %d training samples' % n_tr)
+        dr = self.sess.to_device(draws.astype(np.int32), torch.int32) if T else None
+        lab = pool_labels.to(torch.int32).contiguous()
+        for t_ in (pool_feat, tr_feat):
+            assert t_ is None or (t_.dtype == torch.float32 and t_.is_contiguous() and int(t_.shape[1]) == d)
+        tp = tr_post.contiguous() if tr_post is not None else None
+        P = (d + 1) * c
+        V = self.sess.empty((n_pool, P), torch.float32)
+
+        def ptr(t_, off=0):
+            return C.c_void_p(t_.data_ptr() + off) if t_ is not None else None
+        for a in range(0, n_pool, self._LLFC_SLICE):
+            b = min(n_pool, a + self._LLFC_SLICE)
+            pb = pool_post[:, a:b].contiguous()
+            work = self.sess.empty((max(int(self.lib.alq_llfc_if_work_bytes(b - a, c)), 8),), torch.uint8)
+            check(self.lib.alq_llfc_stoch_if(self.sess.ctx, ptr(pool_feat, a * d * 4), ptr(pb), ptr(lab, a * 4), b - a, ptr(tr_feat), ptr(tp),
+                                             n_tr, ptr(dr), T, float(scale), d, c, int(path), ptr(V, a * P * 4), ptr(work)))
+        return V
+
+    def llfc_stoch_if_device(self, pool_t, n_pool, tr_t, draws, scale, path=0):
+        """The recursion of PW_NNAL.stoch_approx_IF on the device: V_0 = the last-layer gradients of the n_pool device patches
+        `pool_t` at their predicted labels, then one step per entry of `draws` (row indices into the device patches `tr_t`).
+        One forward pass over the pool and one over the training patches; nothing leaves the device.  Returns (V float32 device
+        [n_pool, (d+1)c] in the device's feature order - llfc_reference_order - and the predicted labels, int64 device [n_pool])."""
+        self._require_llfc()
+        post, pred, feat = self.forward_device(pool_t, n_pool, want_pred=True, want_feat=True)
+        tpost = tfeat = None
+        if len(draws):
+            n_tr = int(tr_t.numel()) // self.elems_per_patch
+            tpost, _, tfeat = self.forward_device(tr_t, n_tr, want_feat=True)
+        return self.llfc_stoch_if_features_device(feat, post, pred, tfeat, tpost, draws, scale, path), pred
+
     # -- weights ---------------------------------------------------------------------------
     def set_weights(self, pars):
         """`pars`: name -> [W, b] in TF layouts (HWIO / DHWIO, transpose [k..,out,in], fc [out,in],

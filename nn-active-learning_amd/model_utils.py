@@ -2,6 +2,8 @@
 kernels) and the binary masks made from it."""
 import numpy as np
 
+from .NN import LLFC_grads, LLFC_hess, PW_LLFC_grads  # noqa: F401  (the reference keeps a copy of each, model_utils.py:137-292)
+
 
 def diagonal_Fisher(model, sess, batch_dat):
     """model_utils.diagonal_Fisher (model_utils.py:294-330): per parameter, the mean over the samples of the squared
