@@ -514,7 +514,8 @@ int alq_debug_set_stamp_buffer(void *d_buf);
  * MFMAs, 8 no sum stores), 2 = no epilogue fusion in backward GEMMs, 3 = none in forward GEMMs,
  * 4 = use the fp32-MFMA GEMM kernel instead of the bf16x3 split kernel, 7 = first conv and the pool behind
  * it as separate launches, 8 = the first conv + pool kernel on its narrow tile with per-voxel sum / sign
- * stores everywhere (same bits; ALQ_DCP_NARROW at model creation).                                */
+ * stores everywhere (same bits; ALQ_DCP_NARROW at model creation), 9 = at most that many workgroups in
+ * the plane-sweep launch of csrc/e3d.hip (same bits; lets a handful of patches make multi-patch streams). */
 int alq_debug_set(int key, int value);
 /* What the last pass of a model ran on (tests / bench reporting).  what = 0: 1 when the matrix cores of the context's device
  * keep fp16 subnormal operands (probed once; the one-accumulator form of the plane-sweep engine needs it), 1: 1 when the last
@@ -536,6 +537,8 @@ int alq_debug_set(int key, int value);
  * 16: form of the first conv + pool kernel (csrc/direct.hip) in the last forward pass: 0 = it did not run, 1 / 2 = narrow tile
  * (8 x 16 x 16 voxels) with scalar / 16-byte row loads, 4 / 5 = the same on the wide tile (8 x 8 x 32), 6 = wide tile on whole-tile
  * volumes with 16-byte channel-sum and sign-byte stores.
+ * 17: form of the fused enc2 backward launch (csrc/e3d.hip) in the last backward pass: 0 = it did not run, 2 = the z plane sweep
+ * (default), 1 = the row sweep (ALQ_E3D_ROWS=1 at model creation; same bits).
  * Returns the answer or a negative error code.  */
 int alq_model_engine_info(alq_model *m, int what);
 

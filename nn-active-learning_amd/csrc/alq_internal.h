@@ -289,7 +289,7 @@ struct Igemm2Fuse {
 };
 
 extern unsigned long long *g_igemm2_dbg;
-constexpr int ALQ_NKNOBS = 9;
+constexpr int ALQ_NKNOBS = 10;
 extern int g_dbg_knobs[ALQ_NKNOBS];
 extern int g_dcp_last_form;      // direct.hip: form of the last first conv + pool launch
 extern int g_no_f16x2;        // ALQ_NO_F16X2, read when a model is created: bf16x3 split in every launch
@@ -493,7 +493,8 @@ struct E3dPlan {
 int e3d_build(const View &in, const View &out, const int k[3], const int lo[3], const int s[3], E3dPlan *plan);
 void e3d_pack(E3dPlan *plan, const float *W /* TF conv filter [tap][ci 8][co 16] */);
 int e3d_bwd_launch(alq_ctx *ctx, const E3dPlan &plan, int N, const float *skip, const float *dpool, const unsigned char *am2, const unsigned char *sg2,
-                   const unsigned char *am1, const unsigned char *sg1, float *dsum2, float *dsum1, float in_bound);
+                   const unsigned char *am1, const unsigned char *sg1, float *dsum2, float *dsum1, float in_bound,
+                   bool rows /* the row-sweep kernel of rounds 5 - 7 instead of the z plane sweep: same bits */);
 
 // NET-C's dec1 forward (3x3x3 conv 32 -> 16 channels at 16^3 over a split concat, fp16 pairs at per-patch scales): row sweep at one
 // wave per SIMD with all weight fragments in registers (d3d.hip)

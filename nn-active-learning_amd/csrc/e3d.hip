@@ -299,6 +299,225 @@ __global__ __launch_bounds__(256, 2) void e3d_bwd_kernel(const E3Args a) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------- the z plane sweep
+// The same launch with every input row staged ONCE (default since round 8; ALQ_E3D_ROWS=1 keeps the row sweep above, whose
+// workgroups stage six planes for the four they own - every row 1.5 times across the grid - and spend one step in nine on a void
+// one).  A 512-thread workgroup (eight waves, two per SIMD as two row-sweep workgroups per CU gave) takes whole patches b, b + G,
+// ... (G a multiple of 8 in a product launch: patch p then stays on XCD p % 8, the unit order of the other layer kernels) and sweeps z
+// continuously ACROSS patch boundaries: the stream's plane m is plane m & 15 of the workgroup's patch m >> 4, one pipeline fill
+// per workgroup, loop body straight-line.
+//   Step s, behind its one barrier:
+//     * STAGE plane s: 16 rows, two per wave (rows 2 w, 2 w + 1; they share one pooled row, fetched once) - the per-row arithmetic
+//       of the row sweep - into image s & 3 of a ring of four plane images (18 row slots: y = -1 .. 16; rows -1 and 16 and the
+//       voxel slots x = -1 and 16 of every row are zeroed once and never written);
+//     * CONTRACT the wave's tile (rows 2 w, 2 w + 1) of output plane s - 2 from the images s - 3, s - 2, s - 1; per tile the
+//       (dy, dz, K step, product) sequence of the row sweep into the same two accumulators, and its epilogue: both channel-sum
+//       fields come out bit-identical to the row sweep's.
+//   z halo: for output plane 0 the image below (the previous patch's last plane, or nothing) and for plane 15 the one above are
+//   replaced by a fifth, all-zero image.  (The row sweep stages +-0 for rows outside the volume; adding +-0 products to an
+//   accumulator that started at +0 leaves its bits alone either way.)
+//   RING RULE.  The slot staged in step s (s & 3) last held image s - 4, whose last readers were the tiles of step s - 1 (output
+//   plane s - 3: images s - 4, s - 3, s - 2); the barrier at the head of step s separates the two.  The tiles of step s read
+//   slots (s + 1) & 3, (s + 2) & 3, (s + 3) & 3 or the zero image - never s & 3.  The two steps before the stream (prefetch fill)
+//   and the two drain steps behind it (output planes T - 2, T - 1) stage into a sink behind the images that nothing reads, never
+//   into the ring; the first two steps of the stream contract images that hold zeros and store nothing.
+// Loads run two steps ahead in registers (one for the small pooled tensors), every row offset through readfirstlane; all
+// global stores are 4 or 8 bytes wide (no ALQ_STORE_HOLD case).
+constexpr int E3Z_IMG = 18 * E3_SLOT;         // a plane image: rows y = -1 .. 16, pieces h, l
+constexpr int E3Z_ZERO = 4 * E3Z_IMG;         // behind the ring of four: the all-zero image
+constexpr int E3Z_SINK = 5 * E3Z_IMG;         // where the steps outside the stream stage their rows (one row slot)
+constexpr int E3Z_LDS = E3_WLO + E3Z_SINK + E3_SLOT;
+static_assert(E3Z_IMG % 16 == 0 && E3Z_LDS <= 160 * 1024, "e3d plane sweep: LDS layout");
+
+struct E3ZRowB { f32x4 dp; unsigned am; };
+
+__global__ __launch_bounds__(512) void e3d_bwdz_kernel(const E3Args a) {
+    extern __shared__ __attribute__((aligned(16))) char e3lds[];
+    {   // lo weight fragments into LDS, and zeros into the five images and the sink, once
+        const i32x4 *src = reinterpret_cast<const i32x4 *>(a.Wlo);
+        i32x4 *dst = reinterpret_cast<i32x4 *>(e3lds);
+        for (int i = threadIdx.x; i < E3_WLO / 16; i += 512) dst[i] = src[i];
+        for (int i = threadIdx.x; i < (E3Z_LDS - E3_WLO) / 16; i += 512) dst[E3_WLO / 16 + i] = i32x4{0, 0, 0, 0};
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    char *strip = e3lds + E3_WLO;
+    const int n = lane & 15, kg = lane >> 4, ry = n >> 3, j = n & 7;
+    f16x8 wh[9][2];
+#pragma unroll
+    for (int c = 0; c < 9; ++c)
+#pragma unroll
+        for (int s = 0; s < 2; ++s) wh[c][s] = *reinterpret_cast<const f16x8 *>(a.Whi + ((size_t)(c * 2 + s) * 64 + lane) * 8);
+#pragma unroll
+    for (int c = 0; c < 9; ++c)
+#pragma unroll
+        for (int s = 0; s < 2; ++s) asm volatile("" : "+v"(wh[c][s]));      // arrived before the loop (t3d_fwd_kernel)
+    const char *wl = e3lds + lane * 16;
+
+    const __amdgpu_buffer_rsrc_t sk_rsrc = e3_rsrc(a.skip, (unsigned long long)a.N * 4096 * 64);
+    const __amdgpu_buffer_rsrc_t dp_rsrc = e3_rsrc(a.dpool, (unsigned long long)a.N * 512 * 64);
+    const __amdgpu_buffer_rsrc_t a2_rsrc = e3_rsrc(a.am2, (unsigned long long)a.N * 512 * 16);
+    const __amdgpu_buffer_rsrc_t s2_rsrc = e3_rsrc(a.sg2, (unsigned long long)a.N * 4096 * 4);
+    const __amdgpu_buffer_rsrc_t a1_rsrc = e3_rsrc(a.am1, (unsigned long long)a.N * 4096 * 8);
+    const __amdgpu_buffer_rsrc_t s1_rsrc = e3_rsrc(a.sg1, (unsigned long long)a.N * 4096 * 2);
+    const __amdgpu_buffer_rsrc_t d2_rsrc = e3_rsrc(a.dsum2, (unsigned long long)a.N * 4096 * 4);
+    const __amdgpu_buffer_rsrc_t d1_rsrc = e3_rsrc(a.dsum1, (unsigned long long)a.N * 32768 * 4);
+
+    // staging lane roles (as in the row sweep): voxel x = lane >> 2 of a row, channels 4 cq .. + 3
+    const int sx = lane >> 2, cq = lane & 3;
+    const int w_off = (sx + 1) * 32 + cq * 8 + (2 * wave + 1) * E3_SLOT;      // (+ the wave's first row, y = 2 w, of an image)
+    const unsigned ldA = (unsigned)lane * 16u, ldS = (unsigned)lane;
+    const unsigned ldP = (unsigned)(sx >> 1) * 64u + (unsigned)cq * 16u, ldM = (unsigned)(sx >> 1) * 16u + (unsigned)cq * 4u;
+    const unsigned lanepar4 = (unsigned)(sx & 1) * 0x01010101u;
+    const unsigned st2 = cq == 0 ? (unsigned)sx * 4u : E3_OOB;
+    // fragment lane roles: column (ry, j), K step s: window position q = 2 s + (kg >> 1) -> slot 2 j + q, channel half kg & 1; tile row 2 w + ry
+    // reads input rows 2 w + ry + dy - 1 = image rows 2 w + ry + dy
+    const int f_off = (2 * j + (kg >> 1)) * 32 + (kg & 1) * 16 + (2 * wave + ry) * E3_SLOT;
+    // epilogue lane roles: pooled voxel (z, 2 w + ry, x = 2 j + (kg >> 1)) of pool1, channels 4 (kg & 1) .. + 3; window sums shared with lane ^ 16
+    const bool hi = (kg & 1) != 0;
+    const unsigned e_am = (unsigned)(ry * 16 + 2 * j + (kg >> 1)) * 8u + (unsigned)(kg & 1) * 4u;
+    const unsigned e_sg = (unsigned)(ry * 16 + 2 * j + (kg >> 1)) * 2u + (unsigned)(kg & 1);
+    const unsigned e_d1 = (unsigned)(hi ? 32 * 128 : 0) + (unsigned)(2 * ry) * 128u + (unsigned)(2 * (2 * j + (kg >> 1))) * 4u;
+
+    const int G = (int)gridDim.x, b0 = (int)blockIdx.x;
+    const int nunits = a.N > b0 ? (a.N - b0 + G - 1) / G : 0;
+    const int T = nunits * 16;          // planes of the stream; steps s = 0 .. T + 1
+
+    // plane m of the stream (clamped into it) -> patch, z
+    auto plane = [&](int m, int *p, int *z) __attribute__((always_inline)) {
+        const int mc = m < 0 ? 0 : (m < T ? m : T - 1);
+        *p = b0 + (mc >> 4) * G;
+        *z = mc & 15;
+    };
+    auto fetchA = [&](int m, E3RowA *R) __attribute__((always_inline)) {
+        int p, z;
+        plane(m, &p, &z);
+        const unsigned row = ((unsigned)p * 16u + (unsigned)z) * 16u + (unsigned)(2 * wave);      // row index of the 16^3 grid: y = 2 w
+        const int so_sk = e3_s(row * 1024u), so_sg = e3_s(row * 64u);
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            R[r].sk = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(sk_rsrc, (int)(ldA + (unsigned)r * 1024u), so_sk, 0));
+            R[r].sg = (unsigned)(unsigned char)__builtin_amdgcn_raw_buffer_load_b8(s2_rsrc, (int)(ldS + (unsigned)r * 64u), so_sg, 0);
+        }
+    };
+    auto fetchB = [&](int m, E3ZRowB *R) __attribute__((always_inline)) {
+        int p, z;
+        plane(m, &p, &z);
+        const unsigned prow = ((unsigned)p * 8u + (unsigned)(z >> 1)) * 8u + (unsigned)wave;       // row index of the 8^3 grid: rows 2 w, 2 w + 1 -> w
+        R->dp = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(dp_rsrc, (int)ldP, e3_s(prow * 512u), 0));
+        R->am = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(a2_rsrc, (int)ldM, e3_s(prow * 128u), 0);
+    };
+
+    E3RowA RA[2][2];
+    E3ZRowB RB;
+    RB.dp = f32x4{0.f, 0.f, 0.f, 0.f}; RB.am = 0u;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) { RA[b][i].sk = f32x4{0.f, 0.f, 0.f, 0.f}; RA[b][i].sg = 0u; }
+
+    if (T > 0)
+    for (int s0 = -2; s0 < T + 2; s0 += 2) {       // (T is even: the pairs cover the steps -2 .. T + 1 exactly)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            __builtin_amdgcn_sched_barrier(0);
+            const int s = s0 + b;
+            const bool live = s0 >= 0 && s < T;      // plane s exists: stage it
+            const bool tv = s >= 2;                  // output plane s - 2 exists (s <= T + 1): contract it
+            int p, z, po, zo;
+            plane(s, &p, &z);
+            plane(s - 2, &po, &zo);
+            // the rows of step s - 1 are in their image, and the tiles of step s - 1 are done with the slot this step stages into
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            // what the epilogue of this step's tile needs, requested now (see the row sweep)
+            const unsigned trow = ((unsigned)po * 16u + (unsigned)zo) * 16u + (unsigned)(2 * wave);          // first row of the tile in pool1's grid
+            const unsigned am1w = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(a1_rsrc, (int)e_am, e3_s(trow * 128u), 0);
+            const unsigned sg1b = (unsigned)(unsigned char)__builtin_amdgcn_raw_buffer_load_b8(s1_rsrc, (int)e_sg, e3_s(trow * 32u), 0);
+            const unsigned d1row = (unsigned)e3_s((((unsigned)po * 32u + (unsigned)(2 * zo)) * 32u + (unsigned)(4 * wave)) * 128u);     // row (2 z, 2 y0) of enc1's grid, bytes
+            const f32x2 old0 = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(d1_rsrc, (int)e_d1, (int)d1row, 0));
+            const f32x2 old1 = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(d1_rsrc, (int)(e_d1 + 128u), (int)d1row, 0));
+            // ---- stage rows 2 w, 2 w + 1 of plane s into image s & 3
+            const unsigned srow = ((unsigned)p * 16u + (unsigned)z) * 16u + (unsigned)(2 * wave);
+            const int so_d2 = e3_s(srow * 64u);
+            char *img = strip + e3_s(live ? (unsigned)(s & 3) * (unsigned)E3Z_IMG : (unsigned)(E3Z_SINK - (2 * wave + 1) * E3_SLOT)) + w_off;
+            const float scr = a.scale;
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                const E3RowA &ra = RA[b][r];
+                const unsigned x4 = RB.am ^ (lanepar4 ^ ((unsigned)((((z & 1) * 2 + r) * 2)) * 0x01010101u));      // byte c is 0 where channel c's arg-max is this voxel
+                float g0 = ra.sk.x + (((x4 & 0xffu) == 0u) ? RB.dp.x : 0.f);
+                float g1 = ra.sk.y + (((x4 & 0xff00u) == 0u) ? RB.dp.y : 0.f);
+                float g2 = ra.sk.z + (((x4 & 0xff0000u) == 0u) ? RB.dp.z : 0.f);
+                float g3 = ra.sk.w + (((x4 & 0xff000000u) == 0u) ? RB.dp.w : 0.f);
+                unsigned k0 = (unsigned)__builtin_amdgcn_sbfe((int)ra.sg, 0, 1), k1 = (unsigned)__builtin_amdgcn_sbfe((int)ra.sg, 1, 1);
+                unsigned k2 = (unsigned)__builtin_amdgcn_sbfe((int)ra.sg, 2, 1), k3 = (unsigned)__builtin_amdgcn_sbfe((int)ra.sg, 3, 1);
+                asm("" : "+v"(k0), "+v"(k1), "+v"(k2), "+v"(k3));
+                g0 = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, g0) & k0); g1 = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, g1) & k1);
+                g2 = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, g2) & k2); g3 = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, g3) & k3);
+                {   // channel sums of the masked cotangent (four lanes per voxel)
+                    float s_ = (g0 + g1) + (g2 + g3);
+                    s_ += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, s_), 0xB1, 0xf, 0xf, true));      // quad_perm [1, 0, 3, 2]
+                    s_ += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, s_), 0x4E, 0xf, 0xf, true));      // quad_perm [2, 3, 0, 1]
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, s_), d2_rsrc, (int)(live ? st2 + (unsigned)r * 64u : E3_OOB), so_d2, 0);
+                }
+                const float x0 = g0 * scr, x1 = g1 * scr, x2 = g2 * scr, x3 = g3 * scr;
+                const f16x2 h01 = __builtin_convertvector(f32x2{x0, x1}, f16x2), h23 = __builtin_convertvector(f32x2{x2, x3}, f16x2);
+                const float sc11 = scr * 2048.f;
+                const f16x2 l01 = __builtin_convertvector(f32x2{__builtin_fmaf((float)h01.x, -2048.f, g0 * sc11), __builtin_fmaf((float)h01.y, -2048.f, g1 * sc11)}, f16x2);
+                const f16x2 l23 = __builtin_convertvector(f32x2{__builtin_fmaf((float)h23.x, -2048.f, g2 * sc11), __builtin_fmaf((float)h23.y, -2048.f, g3 * sc11)}, f16x2);
+                char *dst = img + (live ? r * E3_SLOT : 0);
+                *reinterpret_cast<i32x2 *>(dst) = i32x2{__builtin_bit_cast(int, h01), __builtin_bit_cast(int, h23)};
+                *reinterpret_cast<i32x2 *>(dst + E3_ROWB) = i32x2{__builtin_bit_cast(int, l01), __builtin_bit_cast(int, l23)};
+            }
+            fetchB(s + 1, &RB);      // (first: the wait for these, one step from now, must not cover the two-step requests behind them - vmcnt retires in order)
+            fetchA(s + 2, RA[b]);
+            // ---- contract the tile (rows 2 w + ry) of output plane s - 2: input planes s - 3 + dz, input rows 2 w + ry + dy - 1
+            const int io[3] = {e3_s(zo == 0 ? (unsigned)E3Z_ZERO : (unsigned)((s + 1) & 3) * (unsigned)E3Z_IMG), e3_s((unsigned)((s + 2) & 3) * (unsigned)E3Z_IMG),
+                               e3_s(zo == 15 ? (unsigned)E3Z_ZERO : (unsigned)((s + 3) & 3) * (unsigned)E3Z_IMG)};
+            f32x4 c = f32x4{0.f, 0.f, 0.f, 0.f}, cl = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int dy = 0; dy < 3; ++dy) {
+#pragma unroll
+                for (int dz = 0; dz < 3; ++dz) {
+                    const char *src = strip + io[dz] + f_off + dy * E3_SLOT;
+#pragma unroll
+                    for (int s2 = 0; s2 < 2; ++s2) {
+                        const f16x8 xh = *reinterpret_cast<const f16x8 *>(src + s2 * 64);
+                        const f16x8 xl = *reinterpret_cast<const f16x8 *>(src + s2 * 64 + E3_ROWB);
+                        const f16x8 wlo = *reinterpret_cast<const f16x8 *>(wl + ((dz * 3 + dy) * 2 + s2) * 1024);
+                        const f16x8 whi = wh[dz * 3 + dy][s2];
+                        cl = __builtin_amdgcn_mfma_f32_16x16x32_f16(wlo, xh, cl, 0, 0, 0);      // (l, h) + (h, l) at 2^11, (h, h)
+                        cl = __builtin_amdgcn_mfma_f32_16x16x32_f16(whi, xl, cl, 0, 0, 0);
+                        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(whi, xh, c, 0, 0, 0);
+                    }
+                }
+            }
+            // ---- epilogue (the row sweep's): this lane holds channels 4 (kg & 1) .. + 3 of pooled voxel (zo, 2 w + ry, x = 2 j + (kg >> 1)) of pool1's output
+            const float r0 = __builtin_fmaf(cl.x, 0x1p-11f, c.x) * a.inv, r1 = __builtin_fmaf(cl.y, 0x1p-11f, c.y) * a.inv;
+            const float r2 = __builtin_fmaf(cl.z, 0x1p-11f, c.z) * a.inv, r3 = __builtin_fmaf(cl.w, 0x1p-11f, c.w) * a.inv;
+            unsigned m0 = (unsigned)__builtin_amdgcn_sbfe((int)sg1b, 0, 1), m1 = (unsigned)__builtin_amdgcn_sbfe((int)sg1b, 1, 1);
+            unsigned m2 = (unsigned)__builtin_amdgcn_sbfe((int)sg1b, 2, 1), m3 = (unsigned)__builtin_amdgcn_sbfe((int)sg1b, 3, 1);
+            asm("" : "+v"(m0), "+v"(m1), "+v"(m2), "+v"(m3));
+            const float v0 = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, r0) & m0), v1 = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, r1) & m1);
+            const float v2 = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, r2) & m2), v3 = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, r3) & m3);
+            float sw[8];
+#pragma unroll
+            for (int w = 0; w < 8; ++w)
+                sw[w] = ((((am1w & 255u) == (unsigned)w) ? v0 : 0.f) + ((((am1w >> 8) & 255u) == (unsigned)w) ? v1 : 0.f)) +
+                        (((((am1w >> 16) & 255u) == (unsigned)w) ? v2 : 0.f) + (((am1w >> 24) == (unsigned)w) ? v3 : 0.f));
+            f32x4 mine;
+            {
+                const float g0 = __shfl_xor(hi ? sw[0] : sw[4], 16, 64), g1 = __shfl_xor(hi ? sw[1] : sw[5], 16, 64);
+                const float g2 = __shfl_xor(hi ? sw[2] : sw[6], 16, 64), g3 = __shfl_xor(hi ? sw[3] : sw[7], 16, 64);
+                mine = f32x4{(hi ? sw[4] : sw[0]) + g0, (hi ? sw[5] : sw[1]) + g1, (hi ? sw[6] : sw[2]) + g2, (hi ? sw[7] : sw[3]) + g3};
+            }
+            const f32x2 n0 = f32x2{old0.x + mine.x, old0.y + mine.y}, n1 = f32x2{old1.x + mine.z, old1.y + mine.w};
+            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(i32x2, n0), d1_rsrc, (int)(tv ? e_d1 : E3_OOB), (int)d1row, 0);
+            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(i32x2, n1), d1_rsrc, (int)(tv ? e_d1 + 128u : E3_OOB), (int)d1row, 0);
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------------------------- host
 int e3d_build(const View &in, const View &out, const int k[3], const int lo[3], const int s[3], E3dPlan *plan) {
     plan->ok = false;
@@ -344,7 +563,7 @@ void e3d_pack(E3dPlan *plan, const float *W) {
 }
 
 int e3d_bwd_launch(alq_ctx *ctx, const E3dPlan &plan, int N, const float *skip, const float *dpool, const unsigned char *am2, const unsigned char *sg2,
-                   const unsigned char *am1, const unsigned char *sg1, float *dsum2, float *dsum1, float in_bound) {
+                   const unsigned char *am1, const unsigned char *sg1, float *dsum2, float *dsum1, float in_bound, bool rows) {
     ALQ_REQUIRE(plan.ok && plan.d_Whi && plan.d_Wlo, ALQ_EINVAL, "e3d: weights not set");
     ALQ_REQUIRE(skip && dpool && am2 && sg2 && am1 && sg1 && dsum2 && dsum1 && in_bound > 0.f, ALQ_EINVAL, "e3d: missing argument");
     ALQ_REQUIRE(N < 4096, ALQ_EUNSUPPORTED, "e3d: 32-bit byte offsets hold fewer than 4096 patches per pass");
@@ -357,6 +576,16 @@ int e3d_bwd_launch(alq_ctx *ctx, const E3dPlan &plan, int N, const float *skip, 
     a.Wlo = reinterpret_cast<const unsigned short *>(plan.d_Wlo); a.am1 = am1; a.sg1 = sg1; a.dsum2 = dsum2; a.dsum1 = dsum1;
     a.scale = std::ldexp(1.f, e_in); a.inv = std::ldexp(1.f, -(e_in + plan.w_exp)); a.N = N;
     const int cus = ctx->num_cus;
+    if (!rows) {      // the z plane sweep: a 512-thread workgroup per CU over whole patches
+        long long g = std::min<long long>(cus, N);
+        g = std::max<long long>(8, (g + 7) / 8 * 8);
+        if (g_dbg_knobs[9] > 0) g = std::min<long long>(g, g_dbg_knobs[9]);      // tests: a few workgroups, so that a handful of patches makes multi-patch streams
+        ALQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(e3d_bwdz_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, E3Z_LDS));
+        ProfScope ps(ctx, PROF_IGEMM_F16, plan.flops_per_patch * N);
+        hipLaunchKernelGGL(e3d_bwdz_kernel, dim3((unsigned)g), dim3(512), (size_t)E3Z_LDS, ctx->stream, a);
+        ALQ_HIP(hipGetLastError());
+        return ALQ_OK;
+    }
     long long g = std::min<long long>(2LL * cus, (long long)N * 4);
     g = std::max<long long>(8, (g + 7) / 8 * 8);
     const size_t lds = E3_WLO + E3_STRIP + E3_SINK;

@@ -171,7 +171,7 @@ struct alq_model {
     int64_t epp = 0;               // elements per patch
     // Engine-selection knobs, read from the environment ONCE, when this model is created; every call applies the
     // model's own snapshot (alq_debug_set overrides a key for all models until it is set back to -1 / re-set).
-    int knobs[ALQ_NKNOBS] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    int knobs[ALQ_NKNOBS] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     int no_f16x2 = 0;
     int no_xcd_order = 0;
     int requested_batch = 0;      // what alq_model_create was asked for (max_batch may be lower: 32-bit tensor offsets)
@@ -192,6 +192,8 @@ struct alq_model {
     bool last_c3_bwd = false;      // ... and the last backward pass its backward
     int no_e3d = 0;                // ALQ_NO_E3D (A/B): pool2 backward, enc2 backward and pool1 backward as three launches as in round 4
     int last_e3b = 0;              // the last backward pass ran them as one launch (e3d.hip)
+    int e3d_rows = 0;              // ALQ_E3D_ROWS=1 (A/B): that launch on the row-sweep kernel of rounds 5 - 7 instead of the z plane sweep (same bits)
+    int last_e3b_form = 0;         // form of that launch in the last backward pass: 0 none, 1 row sweep, 2 z plane sweep
     int no_d3d = 0;                // ALQ_NO_D3D (A/B): dec1's forward on the two-slot engine as in round 4
     int last_d3f = 0;              // the last forward pass ran it on the row-sweep engine (d3d.hip)
     int no_f3d = 0, last_f3f = 0;  // ALQ_NO_F3D (A/B): enc2's forward on the two-slot engine + the pool as its own launch; the last forward pass ran them fused (f3d.hip)
@@ -275,7 +277,7 @@ static int upload1(alq_model *m, IgemmPlan *p) {
 }
 
 static bool g_use_v2 = true;
-static int g_knob_override[ALQ_NKNOBS] = {-1, -1, -1, -1, -1, -1, -1, -1, -1};   // alq_debug_set: >= 0 overrides every model's snapshot
+static int g_knob_override[ALQ_NKNOBS] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // alq_debug_set: >= 0 overrides every model's snapshot
 
 // The kernels' launch helpers read the process-wide g_dbg_knobs / g_no_f16x2; each entry point loads them from the
 // model it was called on, so creating another model (or its environment) never changes a live one.
@@ -1338,6 +1340,7 @@ static int run_backward_main(alq_model *m, const float *d_x, int N) {
     };
     int e3_conv = -1;      // the conv whose backward ran fused with the pool backward steps around it (e3d.hip), or -1
     m->last_e3b = 0;
+    m->last_e3b_form = 0;
     m->last_d3b = 0;
     for (int i = nl - 1; i >= 0; --i) {
         Layer &ly = m->layers[i];
@@ -1353,7 +1356,8 @@ static int run_backward_main(alq_model *m, const float *d_x, int N) {
                              cv.dout.cs == 16 && cv.dout.c0 == 0 && !cv.dout.split && cv.out.cs == 16 && cv.out.c0 == 0 && p1.out.cs == 8 && p1.out.c0 == 0 &&
                              p1.out.C == 8 && c0.out.D == 32 && cv.dout_bound > 0.f && cv.dsum && c0.dsum;
             if (geo) {
-                ALQ_TRY(e3d_bwd_launch(ctx, cv.e3b, N, cv.dout.p, ly.dout.p, ly.argmax, cv.out.sg, p1.argmax, p1.out.sg, cv.dsum, c0.dsum, cv.dout_bound));
+                ALQ_TRY(e3d_bwd_launch(ctx, cv.e3b, N, cv.dout.p, ly.dout.p, ly.argmax, cv.out.sg, p1.argmax, p1.out.sg, cv.dsum, c0.dsum, cv.dout_bound, m->e3d_rows != 0));
+                m->last_e3b_form = m->e3d_rows ? 1 : 2;
                 cv.delta_ready = true;
                 c0.delta_ready = true;
                 e3_conv = i - 1;
@@ -2272,6 +2276,7 @@ int alq_model_create(alq_ctx *ctx, const alq_layer_t *layers, int n_layers, cons
         if (const char *f = getenv("ALQ_F16_FWD_MASK")) m->f16_fwd_mask = atoi(f);
         m->no_t3d = getenv("ALQ_NO_T3D") ? 1 : 0;
         m->no_e3d = getenv("ALQ_NO_E3D") ? 1 : 0;
+        { const char *e = getenv("ALQ_E3D_ROWS"); m->e3d_rows = (e && atoi(e) == 1) ? 1 : 0; }
         m->no_d3d = getenv("ALQ_NO_D3D") ? 1 : 0;
         m->no_f3d = getenv("ALQ_NO_F3D") ? 1 : 0;
         m->no_d3b = getenv("ALQ_NO_D3D_BWD") ? 1 : 0;
@@ -2281,7 +2286,7 @@ int alq_model_create(alq_ctx *ctx, const alq_layer_t *layers, int n_layers, cons
         }
         // (ALQ_DCP_NARROW: the first conv + pool kernel on its narrow tile with per-voxel sum / sign stores everywhere, direct.hip)
         static const char *names[ALQ_NKNOBS] = {"ALQ_DEBUG_REPEAT", "ALQ_DEBUG_FLAGS", "ALQ_NO_BWD_FUSE", "ALQ_NO_FWD_FUSE", "ALQ_NO_V3", "ALQ_NO_V4",
-                                                "ALQ_NO_POOL_FIRST", "ALQ_NO_CONV_POOL", "ALQ_DCP_NARROW"};
+                                                "ALQ_NO_POOL_FIRST", "ALQ_NO_CONV_POOL", "ALQ_DCP_NARROW", "ALQ_E3D_GRID_CAP"};
         for (int k = 0; k < ALQ_NKNOBS; ++k) {
             const char *v = getenv(names[k]);
             if (v) m->knobs[k] = atoi(v);
@@ -2992,7 +2997,8 @@ int alq_model_debug_copy(alq_model *m, int layer_idx, int what, int N, float *d_
 }
 
 int alq_model_engine_info(alq_model *m, int what) {
-    ALQ_REQUIRE(m && ((what >= 0 && what <= 3) || (what >= 5 && what <= 16)), ALQ_EINVAL, "alq_model_engine_info: bad argument");
+    ALQ_REQUIRE(m && ((what >= 0 && what <= 3) || (what >= 5 && what <= 17)), ALQ_EINVAL, "alq_model_engine_info: bad argument");
+    if (what == 17) return m->last_e3b_form;  // form of the fused enc2 backward launch (e3d.hip) in the last backward pass: 0 none, 1 row sweep, 2 z plane sweep
     if (what == 16) return m->last_dcp;       // form of the first conv + pool kernel in the last forward pass: 0 none, 1 / 2 narrow tile (unaligned / aligned rows), 4 / 5 wide tile, 6 wide tile with 16-byte sum / sign stores
     if (what == 15) return m->last_lsum;      // the last general backward sweep ran the fused layer-sum kernels (lsum.hip)
     if (what == 14) return m->host_pack_elems > 0x7fffffffll ? 0x7fffffff : (int)m->host_pack_elems;      // weight elements through the host packers since creation (saturates)

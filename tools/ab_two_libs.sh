@@ -6,7 +6,8 @@
 # 2. <rounds> alternating rounds of the default command at 20 steps; every branch round must beat every parent round and the median
 #    gain must exceed three times the parent arm's own spread (max - min) for the script to call it a gain;
 # 3. one rocprofv3 --kernel-trace --stats run of `bench.py --lanes 1 --no-accuracy` per arm: per-launch times of the first conv and
-#    the up2 kernels.
+#    the up2 kernels, of the fused enc2 backward launch (e3d_bwd_kernel = row sweep, e3d_bwdz_kernel = z plane sweep), and the sum of the
+#    13 main-chain launches of a pass (neighbouring launches trade clock: only the sum counts).
 # Everything lands in $OUT (bench_out by default): <tag>_ab.txt, <tag>_checksums.txt, <tag>_{parent,branch}_lanes1_kernel_stats.csv.
 # Every GPU step has its own time limit and the script stops at the first step that fails.
 set -eo pipefail
@@ -81,7 +82,14 @@ print('per-launch averages, --lanes 1 kernel trace (us): parent -> branch')
 rows = {a: {r['Name']: r for r in csv.DictReader(open(os.path.join(out, '%s_%s_lanes1_kernel_stats.csv' % (tag, a))))} for a in ('parent', 'branch')}
 def pick(a, key):
     return [(n, float(r['AverageNs']) / 1e3, int(r['Calls'])) for n, r in rows[a].items() if key in n]
-for key in ('direct_conv_pool_kernel', 't3d_bwd_kernel', 't3d_fwd_kernel', 'd3d_bwd', 'c3d_fwd', 'c3d_bwd7'):
+for key in ('direct_conv_pool_kernel', 't3d_bwd_kernel', 't3d_fwd_kernel', 'd3d_bwd', 'c3d_fwd', 'c3d_bwd7', 'e3d_bwd'):
     p, b = pick('parent', key), pick('branch', key)
     print('  %-26s %s -> %s' % (key, ' '.join('%.1f (%d calls)' % (t, c) for _, t, c in p), ' '.join('%.1f (%d calls)' % (t, c) for _, t, c in b)))
+# the main chain of a NET-C Fisher pass: the first conv + the twelve contraction launches, once per pass each
+chain = ('direct_conv_pool_kernel', 'f3d_fwd', 'igemm4_kernel', 't3d8_fwd', 'd3d_fwd', 't3d_fwd_kernel', 'c3d_fwd', 'c3d_bwd7', 't3d_bwd_kernel', 'd3d_bwd',
+         't3d8_bwd', 'e3d_bwd')
+tot = {a: sum(t for key in chain for _, t, _ in pick(a, key)) for a in ('parent', 'branch')}
+cnt = {a: sum(1 for key in chain for _ in pick(a, key)) for a in ('parent', 'branch')}
+print('  main chain, sum of %d / %d launches: %.1f -> %.1f us per pass (%+.2f %%)' % (cnt['parent'], cnt['branch'], tot['parent'], tot['branch'],
+                                                                                   100 * (tot['branch'] - tot['parent']) / tot['parent']))
 PY
