@@ -539,6 +539,9 @@ int alq_debug_set(int key, int value);
  * volumes with 16-byte channel-sum and sign-byte stores.
  * 17: form of the fused enc2 backward launch (csrc/e3d.hip) in the last backward pass: 0 = it did not run, 2 = the z plane sweep
  * (default), 1 = the row sweep (ALQ_E3D_ROWS=1 at model creation; same bits).
+ * The backward indices 2, 8, 9, 11, 13 and 17 name launches of the Fisher pass only: all of them are 0 after a general backward
+ * sweep (alq_param_grads, alq_grad_sqnorms, alq_class_layer_sums, alq_diag_fisher, the loss entry points) and after alq_hess_vecp,
+ * whatever an earlier Fisher pass on the same model ran.
  * Returns the answer or a negative error code.  */
 int alq_model_engine_info(alq_model *m, int what);
 

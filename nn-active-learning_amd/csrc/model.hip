@@ -1569,10 +1569,21 @@ static int run_backward_main(alq_model *m, const float *d_x, int N) {
 // them): every layer's masked pre-activation cotangent ends up in its `dout` view (what the weight gradients need), no
 // shortcut of the Fisher pass is taken (no unit cotangent, no sign-byte input, every tensor stored).  The forward pass
 // must have kept every activation (run_forward(..., keep_all = true)).
+// None of the Fisher pass's fused backward launches (c3d / t3d / e3d / d3d) runs in a general sweep or in the fp64 sweep of
+// alq_hess_vecp: engine info 2, 8, 9, 11, 13 and 17 speak of the LAST backward pass, not of the last Fisher pass before it.
+static void clear_fisher_backward_info(alq_model *m) {
+    m->last_c3_bwd = false;
+    m->last_t3b = 0;
+    m->last_e3b = 0;
+    m->last_e3b_form = 0;
+    m->last_d3b = 0;
+}
+
 static int run_backward_general(alq_model *m, int N, const DropSpec *drop, bool layer_sums = false) {
     alq_ctx *ctx = m->ctx;
     const int nl = (int)m->layers.size();
     m->last_lsum = layer_sums ? 1 : 0;
+    clear_fisher_backward_info(m);
     for (int i = nl - 1; i >= 0; --i) {
         Layer &ly = m->layers[i];
         const bool isfc = ly.spec.type == ALQ_FC;
@@ -2076,6 +2087,7 @@ int alq_hess_vecp(alq_model *m, const float *d_x, int N, const int32_t *d_labels
     m->last_call_fisher = false;
     ALQ_TRY(prepare_call(m));
     ALQ_TRY(run_forward(m, d_x, N, false, /*keep_all=*/true, &ds));
+    clear_fisher_backward_info(m);
     return run_hess_vecp(m, d_x, N, d_labels, loss_scale, d_v, h_layer_on, accumulate, d_hv, d_loss);
 }
 
