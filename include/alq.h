@@ -448,6 +448,40 @@ int alq_llfc_stoch_if(alq_ctx *ctx, const float *d_pool_feat, const float *d_poo
                       const float *d_tr_feat, const float *d_tr_post, int n_tr, const int32_t *d_draws, int T, double scale, int d,
                       int c, int path, float *d_V, void *d_work);
 
+/* ---- A-optimal design of the `fi` query: the O(n) side of a Newton step (csrc/aopt.hip) ------------------------------- */
+/* Replaces: the candidate-sized NumPy work of NNAL_tools._aopt_newton, this build's solver of the reference's query SDP at
+ * lambda = 0 (NNAL_tools.py:612-659: min tr((sum_i q_i A_i)^-1) over the simplex).  The loop, the L x L and m x m algebra
+ * (m = L(L+1)/2) and the step-size decisions stay on the host (DeviceSession.aopt_design); per Newton step the four launches
+ * below move O(m^2) doubles and nothing of size n.  All arithmetic is fp64.  d_V [n, m]: the candidates' A_i in the orthonormal
+ * symmetric basis; d_q, d_dq [n].  Supported: 1 <= L <= 8 and 1 <= n < 2^31 / m, else ALQ_EUNSUPPORTED.  h_* arrays must stay
+ * unchanged until the stream has passed the call.  d_work: alq_aopt_work_bytes(n, L) bytes, shared by all launches of one solve.
+ * Every sum is taken in one fixed order (tiles of alq_aopt_tile() candidates, a fixed grid for a given n, per-workgroup
+ * partials folded in workgroup order, no atomics): the same inputs give the same bits on every run.  Candidates beyond n
+ * are never read.  alq_aopt_max_workgroups(): the largest grid; beyond tile * max_workgroups candidates a workgroup walks several tiles.
+ *   alq_aopt_svec        d_V[i, c] = A_i[a, b] for a == b, sqrt(2) A_i[a, b] for a < b; c walks the upper triangle row by row.
+ *                        d_A [n, L, L] as alq_fisher writes it
+ *   alq_aopt_stats       d_i = V_i . kvec,  r_i = (-d_i - mu / q_i) + (obj + n mu),  w_i = q_i^2 / mu,  u_i = R^T V_i (h_R [m, m] row
+ *                        major).  d_out: the upper triangle, row by row, of  sum_i w_i u~_i u~_i^T  with u~_i = (u_i, r_i, 1)
+ *                        [(m+2)(m+3)/2 doubles: G = sum w u u^T, h_r = sum w r u, h_1 = sum w u, s_r = sum w r, s_1 = sum w are
+ *                        its blocks], then max_i d_i:  (m+2)(m+3)/2 + 1 doubles
+ *   alq_aopt_direction   d_dq[i] = -(w_i r_i - sum_k w_i u_ik c_r[k]) + ratio (w_i - sum_k w_i u_ik c_1[k]);
+ *                        d_out = (-sum_i r_i dq_i,  min over dq_i < 0 of -q_i / dq_i (+inf when none),  sum_i dq_i V_i [m])
+ *   alq_aopt_linesearch  d_out[j] = sum_i log(q_i + h_alpha[j] dq_i) for j < J <= 64,  d_out[J] = sum_i log q_i
+ *   alq_aopt_update      q <- q + alpha dq, then q <- q / sum(q);  d_out = (that sum, sum_i q_i V_i [m] of the normalised q)  */
+int alq_aopt_tile(void);
+int alq_aopt_max_workgroups(void);
+size_t alq_aopt_work_bytes(int64_t n, int L);
+int alq_aopt_svec(alq_ctx *ctx, const double *d_A, int64_t n, int L, double *d_V);
+int alq_aopt_stats(alq_ctx *ctx, const double *d_V, const double *d_q, int64_t n, int m, const double *h_kvec,
+                   const double *h_R, double mu, double obj, double *d_out, void *d_work);
+int alq_aopt_direction(alq_ctx *ctx, const double *d_V, const double *d_q, int64_t n, int m, const double *h_kvec,
+                       const double *h_R, const double *h_c_r, const double *h_c_1, double ratio, double mu, double obj,
+                       double *d_dq, double *d_out, void *d_work);
+int alq_aopt_linesearch(alq_ctx *ctx, const double *d_q, const double *d_dq, int64_t n, const double *h_alpha, int J,
+                        double *d_out, void *d_work);
+int alq_aopt_update(alq_ctx *ctx, double *d_q, const double *d_dq, const double *d_V, int64_t n, int m, double alpha,
+                    double *d_out, void *d_work);
+
 /* ---- fp64 accuracy reference on the device (csrc/ref64.hip; bench.py `accuracy`, tests) ------------------------------- */
 /* One inverted decision of an fp64 evaluation.  layer = model layer index of a ReLU'd conv / conv_transpose / fc layer: the
  * ReLU decision of element `idx` of that layer's pre-activation of ONE sample ([vox, C] flattened; fc: the unit) is

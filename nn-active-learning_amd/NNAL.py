@@ -114,7 +114,17 @@ def CNN_query(model, expr, pool_inds, method_name, session, col=True, extra_feed
         if single:
             lambda_ = 0                                                          # :443-445
         F_sel = F_sel - np.mean(F_sel, axis=1, keepdims=True)
-        soln = NNAL_tools.SDP_query_distribution(A, lambda_, F_sel, k)
+        if expr.pars.get('SDP_solver') == 'DEVICE':
+            # this build's value of the key (PW_NNAL.query_multimg): the solve on the device, lambda_ = 0 only; the image-level
+            # A-matrices are a host list, uploaded once
+            if not hasattr(session, 'aopt_design'):
+                raise TypeError("SDP_solver 'DEVICE' needs a device.DeviceSession as `session`, got %s" % type(session).__name__)
+            if lambda_ > 0:
+                raise NotImplementedError("SDP_solver 'DEVICE' has the lambda_ = 0 form only (lambda_ = %r)" % (lambda_,))
+            A_dev = session.to_device(np.asarray(A, dtype=np.float64), session.torch.float64)
+            soln = NNAL_tools.SDP_query_distribution_device(session, A_dev, lambda_, F_sel, k)
+        else:
+            soln = NNAL_tools.SDP_query_distribution(A, lambda_, F_sel, k)
         q_opt = np.array(soln['x'][:B]).ravel()
         Q_inds = NNAL_tools.sample_query_dstr(q_opt, k, replacement=True)
         return sel_inds[Q_inds]

@@ -382,6 +382,18 @@ def SDP_query_distribution(A, lambda_, X_pool, k, tol=1e-7, max_iter=20000, meth
             'primal objective': float(t.sum() + c @ q), 'gap': float(gap), 'iterations': its, 'y': np.asarray(y)}
 
 
+def SDP_query_distribution_device(sess, A_dev, lambda_, X_pool, k, tol=1e-7, max_iter=20000):
+    """`SDP_query_distribution` with the candidates' A-matrices resident on the device (fp64 tensor [n, L, L], as
+    DeviceModel.fisher_device(..., want=('A',)) returns them): the same Newton iteration, its candidate-sized work in the
+    kernels of csrc/aopt.hip (DeviceSession.aopt_design).  Opt-in (expr.pars['SDP_solver'] = 'DEVICE', al_loop.run_rounds(...,
+    sdp='device')); lambda = 0 only - the feature-regularised form stays with the host routine.  Returns the same dict plus
+    'q_device'."""
+    if lambda_ and float(lambda_) > 0:
+        raise NotImplementedError("the device solver has the lambda = 0 form only; lambda_ = %r needs the host routine "
+                                  "(SDP_solver 'CVXOPT')" % (lambda_,))
+    return sess.aopt_design(A_dev, tol=tol, max_iter=max_iter)
+
+
 def solve_FIAL_SDP(A):
     """NNAL_tools.solve_FIAL_SDP (NNAL_tools.py:576-610): same problem through the same solver here;
     returns (q, objective) as PW_NNAL.query_multimg unpacks them (PW_NNAL.py:611-614)."""

@@ -143,10 +143,11 @@ def _entropy_query_single(expr, model, sess, padded_imgs, pool_inds):
     return binary_uncertainty_filter(posts, expr.pars['k'])
 
 
-def fisher_candidates(expr, model, sess, padded_imgs, pool_inds, vols=None):
+def fisher_candidates(expr, model, sess, padded_imgs, pool_inds, vols=None, on_device=False):
     """The device part of CNN_query(...,'fi') (PW_NNAL.py:89-136): posteriors, uncertainty filter
     to B candidates, their patches (channel-index normalisation of :125-129) and A-matrices.
-    Returns (sel_inds, sel_posts, A list).  `vols`: the padded volumes already on the device (uploaded once per query)."""
+    Returns (sel_inds, sel_posts, A list).  `vols`: the padded volumes already on the device (uploaded once per query).
+    on_device: A stays the fp64 device tensor [B, L, L] the Fisher pass wrote (the device SDP solver takes it as it is)."""
     B = expr.pars['B']
     if vols is None:
         vols = patch_utils.DeviceVolumes(sess, padded_imgs)
@@ -163,6 +164,8 @@ def fisher_candidates(expr, model, sess, padded_imgs, pool_inds, vols=None):
                     np.asarray(expr.pars['stats'], dtype=np.float64)[:m], quirk=1)
     p1_in = sess.to_device(sel_posts.astype(np.float32), sess.torch.float32)
     out = model.fisher_device(t, len(sel_inds), p1_in, 1e-5, want=('A',))
+    if on_device:
+        return sel_inds, sel_posts, out['A']
     A = out['A'].cpu().numpy()
     return sel_inds, sel_posts, [A[i] for i in range(len(sel_inds))]
 
@@ -208,7 +211,12 @@ def CNN_query(expr, model, sess, padded_imgs, pool_inds, tr_inds, method_name):
     if method_name == 'fi':
         lambda_ = expr.pars['lambda_']
         vols = patch_utils.DeviceVolumes(sess, padded_imgs)            # one upload for the whole query
-        sel_inds, sel_posts, A = fisher_candidates(expr, model, sess, padded_imgs, pool_inds, vols)
+        # expr.pars['SDP_solver'] = 'DEVICE' (not a value of the reference, whose 'CVXOPT' / 'MOSEK' both mean the host routine
+        # here): the solve runs where the A-matrices are
+        on_device = expr.pars.get('SDP_solver') == 'DEVICE'
+        if on_device and lambda_ > 0:
+            raise NotImplementedError("SDP_solver 'DEVICE' has the lambda_ = 0 form only (lambda_ = %r)" % (lambda_,))
+        sel_inds, sel_posts, A = fisher_candidates(expr, model, sess, padded_imgs, pool_inds, vols, on_device=on_device)
         ref_F = None
         if lambda_ > 0:
             # PW_NNAL.py:138-150: features of the candidates, refined to a well-conditioned full-row-rank subset and
@@ -218,7 +226,10 @@ def CNN_query(expr, model, sess, padded_imgs, pool_inds, tr_inds, method_name):
                                  expr.pars['ntb'], expr.pars['stats'], 'feature_layer', _vols=vols)[0]
             ref_F = refine_feature_matrix(F, expr.pars['B'])
             ref_F = ref_F - np.mean(ref_F, axis=1, keepdims=True)
-        soln = NNAL_tools.SDP_query_distribution(A, lambda_, ref_F, expr.pars['k'])
+        if on_device:
+            soln = NNAL_tools.SDP_query_distribution_device(sess, A, lambda_, ref_F, expr.pars['k'])
+        else:
+            soln = NNAL_tools.SDP_query_distribution(A, lambda_, ref_F, expr.pars['k'])
         q_opt = np.array(soln['x'][:len(sel_inds)]).ravel()
         Q_inds = NNAL_tools.sample_query_dstr(q_opt, expr.pars['k'], replacement=True)
         return sel_inds[Q_inds]
@@ -495,6 +506,11 @@ def query_multimg(expr, model, sess, all_padded_imgs, pool_inds, labeled_inds, m
         nsel = [len(s_) for s_ in sel_inds]
         ncand = int(np.sum(nsel))
         a, b = pool_shard.work_block(ncand)            # this rank's block of the candidate list (volumes are replicated)
+        # expr.pars['SDP_solver'] = 'DEVICE' (this build's value): the A-matrices stay where the Fisher pass wrote them and the
+        # solve runs there (lambda_ = 0 only); one process: no host copy at all, several ranks: the gathered rows go up once
+        on_device = expr.pars.get('SDP_solver') == 'DEVICE'
+        if on_device and expr.pars['lambda_'] > 0:
+            raise NotImplementedError("SDP_solver 'DEVICE' has the lambda_ = 0 form only (lambda_ = %r)" % (expr.pars['lambda_'],))
         rows = []
         off = 0
         for i in range(len(pool_inds)):
@@ -505,19 +521,28 @@ def query_multimg(expr, model, sess, all_padded_imgs, pool_inds, labeled_inds, m
                                 stats[i, :2 * m], quirk=0)                 # slab rule, patch_utils.py:1203-1207
                 p1_in = sess.to_device(np.asarray(sel_posts[i][lo:hi], dtype=np.float32), sess.torch.float32)
                 out = model.fisher_device(t, hi - lo, p1_in, 1e-3, want=('A',))   # diag_load 1e-3, :578
-                rows.append(out['A'].cpu().numpy())
+                rows.append(out['A'] if on_device and (a, b) == (0, ncand) else out['A'].cpu().numpy())
             off += nsel[i]
-        A_rows = np.concatenate(rows) if rows else np.zeros((0, model.L, model.L))
-        if (a, b) != (0, ncand):
-            A_rows = pool_shard.allgather_rows(ncand, np.arange(a, b), A_rows, sess)
-        A = [A_rows[j] for j in range(ncand)]
         # PW_NNAL.py:600-614: 'CVXOPT' -> SDP_query_distribution, 'MOSEK' -> solve_FIAL_SDP; both end in
         # the same A-optimal-design problem, solved here by NNAL_tools' own routine (parity unpinned)
-        if expr.pars.get('SDP_solver', 'CVXOPT') == 'MOSEK':
-            q_opt = np.asarray(NNAL_tools.solve_FIAL_SDP(A)[0]).ravel()
+        if on_device:
+            if (a, b) == (0, ncand):
+                A_dev = sess.torch.cat(rows) if rows else sess.empty((0, model.L, model.L), sess.torch.float64)
+            else:
+                A_rows = np.concatenate(rows) if rows else np.zeros((0, model.L, model.L))
+                A_dev = sess.to_device(pool_shard.allgather_rows(ncand, np.arange(a, b), A_rows, sess), sess.torch.float64)
+            soln = NNAL_tools.SDP_query_distribution_device(sess, A_dev, expr.pars['lambda_'], [], k)
+            q_opt = np.array(soln['x'][:ncand]).ravel()
         else:
-            soln = NNAL_tools.SDP_query_distribution(A, expr.pars['lambda_'], [], k)
-            q_opt = np.array(soln['x'][:len(A)]).ravel()
+            A_rows = np.concatenate(rows) if rows else np.zeros((0, model.L, model.L))
+            if (a, b) != (0, ncand):
+                A_rows = pool_shard.allgather_rows(ncand, np.arange(a, b), A_rows, sess)
+            A = [A_rows[j] for j in range(ncand)]
+            if expr.pars.get('SDP_solver', 'CVXOPT') == 'MOSEK':
+                q_opt = np.asarray(NNAL_tools.solve_FIAL_SDP(A)[0]).ravel()
+            else:
+                soln = NNAL_tools.SDP_query_distribution(A, expr.pars['lambda_'], [], k)
+                q_opt = np.array(soln['x'][:len(A)]).ravel()
         draws = NNAL_tools.sample_query_dstr(q_opt, k, replacement=True)
         local = patch_utils.global2local_inds(draws, [len(s) for s in sel_inds])
         return [np.array(sel_inds[i])[local[i]] for i in range(len(sel_inds))]

@@ -90,6 +90,14 @@ _SIGNATURES = {
     'alq_llfc_if_work_bytes': (C.c_size_t, [C.c_int, C.c_int]),
     'alq_llfc_stoch_if': (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, C.c_int, _P, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int,
                                     _P, _P]),
+    'alq_aopt_tile': (C.c_int, []),
+    'alq_aopt_max_workgroups': (C.c_int, []),
+    'alq_aopt_work_bytes': (C.c_size_t, [C.c_int64, C.c_int]),
+    'alq_aopt_svec': (C.c_int, [_P, _P, C.c_int64, C.c_int, _P]),
+    'alq_aopt_stats': (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P, _P, C.c_double, C.c_double, _P, _P]),
+    'alq_aopt_direction': (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P, _P, _P, _P, C.c_double, C.c_double, C.c_double, _P, _P, _P]),
+    'alq_aopt_linesearch': (C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_int, _P, _P]),
+    'alq_aopt_update': (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int, C.c_double, _P, _P]),
     'alq_comm_unique_id': (C.c_int, [_P]),
     'alq_comm_init': (C.c_int, [_P, _P, C.c_int, C.c_int]),
     'alq_comm_destroy': (C.c_int, [_P]),

@@ -53,7 +53,7 @@ def _finetune(model, sess, x_train, y_train, epochs, b, keep_prob):
 
 
 def run_rounds(model, sess, pool, rounds, B, k, diag_load=1e-3, seed=15, n_global=None, lambda_=0., after_round=None,
-               labels=None, finetune=None, state=None):
+               labels=None, finetune=None, state=None, sdp='host'):
     """pool: this rank's block of the pool, device fp32 tensor [n_local, ...] of normalised patches = global positions
     pool_shard.shard_bounds(n_global, world, rank) (n_global defaults to n_local: one process).  Returns a list with
     one dict per round, identical on every rank except 'seconds': 'queries' (GLOBAL positions, sorted), 'candidates'
@@ -63,7 +63,15 @@ def run_rounds(model, sess, pool, rounds, B, k, diag_load=1e-3, seed=15, n_globa
     labels [n_global] (0 / 1) + finetune = dict(epochs, b) (and the model's get_optimizer): after every round the model
     is fine-tuned on all patches labelled so far - on EVERY rank, on the same batches in the same order, so the
     replicas stay bit-identical without a weight exchange (the queried patches are gathered from their owners).
-    state: a PW_AL.LoopState; rank 0 writes the files, every rank reads them to resume."""
+    state: a PW_AL.LoopState; rank 0 writes the files, every rank reads them to resume.
+    sdp: 'host' (NNAL_tools.SDP_query_distribution) or 'device' (SDP_query_distribution_device, lambda_ = 0 only): with one
+    process the A-matrices go from the Fisher pass to the solver on the device, with several the gathered rows are uploaded
+    once; every rank solves the same gathered problem with the same deterministic launches, so every rank draws from the
+    same q."""
+    if sdp not in ('host', 'device'):
+        raise ValueError("sdp must be 'host' or 'device', got %r" % (sdp,))
+    if sdp == 'device' and lambda_ and float(lambda_) > 0:
+        raise NotImplementedError("sdp='device' has the lambda_ = 0 form only (lambda_ = %r)" % (lambda_,))
     torch = sess.torch
     rank, ws = pool_shard.world()
     n_local = int(pool.shape[0])
@@ -131,15 +139,22 @@ def run_rounds(model, sess, pool, rounds, B, k, diag_load=1e-3, seed=15, n_globa
             rows_dev = sess.to_device(cand[mine] - off, torch.int64)
             p_mine = p_loc.index_select(0, sess.to_device(at, torch.int64)).contiguous()
             res = model.fisher_device(flat, len(mine), p_mine, diag_load, want=('A',), rows=rows_dev)
-            A_mine = res['A'].cpu().numpy()
+            A_mine_dev = res['A']
+            A_mine = A_mine_dev.cpu().numpy()
             posts_mine = p_mine.cpu().numpy().astype(np.float64)
         else:
+            A_mine_dev = None
             A_mine = np.zeros((0, model.L, model.L))
             posts_mine = np.zeros(0)
         A = pool_shard.allgather_rows(len(cand), mine, A_mine, sess)
         posts = pool_shard.allgather_rows(len(cand), mine, posts_mine, sess).astype(np.float32)
         t2 = time.perf_counter()
-        soln = NNAL_tools.SDP_query_distribution(A, lambda_, None, k)
+        if sdp == 'device':
+            # all candidates are ours (one process): the tensor the Fisher pass wrote, else the gathered rows, uploaded once
+            A_dev = A_mine_dev if (A_mine_dev is not None and len(mine) == len(cand)) else sess.to_device(A, torch.float64)
+            soln = NNAL_tools.SDP_query_distribution_device(sess, A_dev, lambda_, None, k)
+        else:
+            soln = NNAL_tools.SDP_query_distribution(A, lambda_, None, k)
         q = np.array(soln['x'][:len(cand)], dtype=np.float64)
         np.random.seed(seed + r)
         draws = NNAL_tools.sample_query_dstr(q, k, replacement=True)
