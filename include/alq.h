@@ -420,6 +420,30 @@ int alq_colsum_max(alq_ctx *ctx, const double *d_S, int64_t n, int b, const doub
 int alq_take_colmax(alq_ctx *ctx, const double *d_S, int64_t n, int b, int j, int first, double *d_v);
 int alq_fold_rowmax(alq_ctx *ctx, const double *d_S, int t, int64_t n, double *d_v);
 
+/* ---- region primitives: local variance maps and per-segment minima (csrc/region.hip) ------------------------------- */
+/* Replaces: patch_utils.get_vars_2d (patch_utils.py:794-826) applied to every slice of a subject, as PW_NNAL.get_HV_inds does
+ * for the `ps-random` queries (PW_NNAL.py:632-669), on a volume that is already resident for alq_gather_normalize.
+ * d_vol: one zero-padded C-order volume, float or double (vol_is_f64 = 1); pad_dims its padded shape, rads the padding radii;
+ * the map is defined on the un-padded box [H, W, S] = pad_dims - 2 rads.  For every slice z and pixel (i, j):
+ * t = trunc(v) as an integer, S1 = sum t and S2 = sum t^2 (64-bit integer sums) over rows [i - d/2, i + (d-1)/2] x columns
+ * [j - d/2, j + (d-1)/2] (integer division) clipped to the slice, var = double(S2) / double(d d) - (double(S1) / double(d d))^2,
+ * every operation rounded on its own.  Bit-identical to the reference's scipy statement whenever all values are finite, >= 0
+ * and trunc(max)^2 d^2 < 2^53 (the caller checks; beyond that the reference itself is inexact).
+ * d_inds NULL: d_out = the whole map, double [H, W, S] in C order (n is ignored).  Otherwise d_out[q], q < n, = the map at
+ * un-padded raveled index d_inds[q] (only those windows are formed; an index outside the box gives NaN and reads nothing).
+ * ALQ_EINVAL: null argument, d outside [1, 65], a radius that leaves no voxel.  Stream-ordered, no synchronisation.          */
+int alq_local_var2d(alq_ctx *ctx, const void *d_vol, int vol_is_f64, const int64_t pad_dims[3], const int32_t rads[3], int d,
+                    const int64_t *d_inds, int64_t n, double *d_out);
+/* Replaces: the regionprops(slice, score_img) 'min_intensity' loop of PW_NNAL.superpix_scoring (PW_NNAL.py:944-1021).
+ * d_labels: int32 over-segmentation [H, W, S] = dims, C order; d_inds: int64 [n] raveled indices into it, d_scores: double [n].
+ * d_table: double [S, n_labels]; the call fills it with +inf, then entry (z, l) becomes the minimum of the scores of the
+ * scored voxels of slice z whose label is l, for 1 <= l < n_labels.  Label 0 (background), a label outside the range and an
+ * index outside the volume are skipped: nothing is stored for them.  The minimum is taken with integer atomics on an
+ * order-preserving key of the double, so the table is bit-identical from run to run (-0.0 orders below +0.0).
+ * NaN scores are outside the contract (their keys order by bit pattern).  Stream-ordered, no synchronisation.                */
+int alq_segment_min(alq_ctx *ctx, const int32_t *d_labels, const int64_t dims[3], int32_t n_labels, const int64_t *d_inds,
+                    const double *d_scores, int64_t n, double *d_table);
+
 /* ---- last-layer closed forms and the stochastic influence recursion (csrc/llfc.hip) -------------------------------- */
 /* Replaces: NN.LLFC_grads / NN.LLFC_hess / NN.PW_LLFC_grads (NN.py:874-1029; duplicated in model_utils.py:137-292) and the
  * iteration of PW_NNAL.stoch_approx_IF (PW_NNAL.py:851-881).  u [d] = the input of the last fc layer (the model's feature

@@ -103,6 +103,22 @@ def finetune_multimg(expr, model, sess, all_padded_imgs, training_inds):
 
 
 # ------------------------------------------------------------------------------------------ experiment state on disk
+def get_SuPix_inds(overseg_img, SuPix_codes):
+    """PW_AL.get_SuPix_inds (PW_AL.py:1168-1231): the voxels of the super-pixels SuPix_codes [2, q] = (slices; labels) of a 3-D
+    over-segmentation, one list of int64 3-D raveled indices per code, in the order of the codes.  The pixels of a super-pixel
+    come in row-major order of its slice, as regionprops(...)['coords'] lists them.  Host NumPy."""
+    seg = np.asarray(overseg_img)
+    codes = np.asarray(SuPix_codes)
+    s = seg.shape
+    out = []
+    for z, label in zip(codes[0], codes[1]):
+        ii, jj = np.nonzero(seg[:, :, int(z)] == label)
+        if len(ii) == 0:
+            raise ValueError('super-pixel %d does not exist in slice %d' % (int(label), int(z)))
+        out.append(list(np.int64(np.ravel_multi_index((ii, jj, np.full(len(ii), int(z))), s))))
+    return out
+
+
 class LoopState(object):
     """The per-method directory of Experiment_MultiImg.run_method (PW_AL.py:690-898): `queries/<iter>` = rows
     [voxel index, subject index] (np.savetxt fmt '%d', :862-884), `AL_running_times/dt_<iter>` (:866-885) and

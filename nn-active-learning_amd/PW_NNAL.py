@@ -178,13 +178,39 @@ def egl_scores_device(model, t, n, p1):
     return NNAL_tools.egl_binary_scores(sq, p1)
 
 
+def get_HV_inds(padded_img, patch_shape, thr, pool_inds, _vols=None):
+    """PW_NNAL.get_HV_inds (PW_NNAL.py:632-669): the positions in `pool_inds` (ascending) of the pool voxels whose local
+    variance is above `thr` - the 2-D variance map of every slice of the un-padded image with the patch RADIUS
+    int((patch_shape[0] - 1) / 2) as the window size (:654-655), evaluated on the device at the pool voxels only
+    (alq_local_var2d, indexed form) where the reference builds the whole map with one scipy convolution pair per slice.
+    `_vols` (not a reference argument): a patch_utils.DeviceVolumes whose first modality is `padded_img`, already resident."""
+    sess = _vols.sess if _vols is not None else None
+    pool_inds = np.asarray(pool_inds, dtype=np.int64)
+    if len(pool_inds) == 0:
+        return np.zeros(0, dtype=np.int64)
+    rads = patch_utils.patch_radii(patch_shape)
+    if _vols is None:
+        from . import device
+        sess = device.default_session()
+        _vols = patch_utils.DeviceVolumes(sess, [padded_img])
+    scores = _vols.local_var(rads[0], 0, pool_inds, rads)
+    return (scores > thr).nonzero().reshape(-1).cpu().numpy()
+
+
 def CNN_query(expr, model, sess, padded_imgs, pool_inds, tr_inds, method_name):
-    """PW_NNAL.CNN_query (PW_NNAL.py:18-166), branches `entropy` and `fi`, plus `egl`, which the reference has only at
+    """PW_NNAL.CNN_query (PW_NNAL.py:18-166), branches `ps-random`, `entropy` and `fi`, plus `egl`, which the reference has only at
     image level (NNAL.py:234-285): uncertainty filter to B like `fi`, score, the k largest (stable: ties -> lower
     candidate first).  Returns positions into `pool_inds` (the caller maps them, PW_AL.py:405-408)."""
     pool_inds = np.asarray(pool_inds)
     if method_name == 'random':
         return np.random.permutation(len(pool_inds))[:expr.pars['k']]
+    if method_name == 'ps-random':
+        # PW_NNAL.py:38-49: random draws among the pool voxels of high local variance (of the first modality).  The reference
+        # reads `exp.pars` there (a NameError); `expr.pars` is meant
+        valid_pool_inds = get_HV_inds(padded_imgs[0], expr.pars['patch_shape'], 2., pool_inds,
+                                      _vols=patch_utils.DeviceVolumes(sess, padded_imgs[:1]))
+        rand_inds = np.random.permutation(len(valid_pool_inds))[:expr.pars['k']]
+        return valid_pool_inds[rand_inds]
     if method_name == 'entropy':
         return _entropy_query_single(expr, model, sess, padded_imgs, pool_inds)
     if method_name == 'MC-entropy':
@@ -233,7 +259,7 @@ def CNN_query(expr, model, sess, padded_imgs, pool_inds, tr_inds, method_name):
         q_opt = np.array(soln['x'][:len(sel_inds)]).ravel()
         Q_inds = NNAL_tools.sample_query_dstr(q_opt, expr.pars['k'], replacement=True)
         return sel_inds[Q_inds]
-    raise NotImplementedError("query method %r is outside the scored path (entropy, egl, fi)" % (method_name,))
+    raise NotImplementedError("query method %r is outside the scored path (random, ps-random, entropy, MC-entropy, egl, fi)" % (method_name,))
 
 
 def _features_device(expr, model, sess, padded_mods, inds, stats):
@@ -433,7 +459,7 @@ def committee_query(expr, model, sess, all_padded_imgs, pool_inds, labeled_inds,
 
 
 def query_multimg(expr, model, sess, all_padded_imgs, pool_inds, labeled_inds, method_name):
-    """PW_NNAL.query_multimg (PW_NNAL.py:169-629), branches `entropy` (:226-230), `ensemble` / `QBC-JS` (:453-545,
+    """PW_NNAL.query_multimg (PW_NNAL.py:169-629), branches `ps-random` (:205-224), `entropy` (:226-230), `ensemble` / `QBC-JS` (:453-545,
     committee_query) and `fi` (:547-627), plus `egl` (image level only in the reference, NNAL.py:234-285; candidates gathered and sharded like
     `fi`, the k largest scores over all subjects, ties -> lower candidate first).  Returns, per subject, positions into
     that subject's pool_inds."""
@@ -443,6 +469,19 @@ def query_multimg(expr, model, sess, all_padded_imgs, pool_inds, labeled_inds, m
     if method_name == 'random':
         inds = np.random.permutation(int(np.sum(sizes)))[:k]
         return patch_utils.global2local_inds(inds, sizes)
+    if method_name == 'ps-random':
+        # PW_NNAL.py:205-224: per subject the pool voxels of high local variance (first modality, threshold 2), then k random
+        # draws over their concatenation; fewer than k qualifying voxels: all of them
+        dvols = {}
+        valid_pool_inds = []
+        for i in range(len(all_padded_imgs)):
+            if len(pool_inds[i]) and i not in dvols:
+                dvols[i] = patch_utils.DeviceVolumes(sess, all_padded_imgs[i][:-1])
+            valid_pool_inds.append(get_HV_inds(all_padded_imgs[i][0], expr.pars['patch_shape'], 2., pool_inds[i], _vols=dvols.get(i)))
+        valid_inds_sizes = [len(v) for v in valid_pool_inds]
+        rand_inds = np.random.permutation(int(np.sum(valid_inds_sizes)))[:k]
+        local_inds = patch_utils.global2local_inds(rand_inds, valid_inds_sizes)
+        return [valid_pool_inds[i][local_inds[i]] for i in range(len(valid_pool_inds))]
     if method_name == 'entropy':
         return bin_uncertainty_filter_multimg(expr, model, sess, all_padded_imgs, pool_inds, k)[0]
     if method_name in ('MC-entropy', 'BALD'):
@@ -546,7 +585,7 @@ def query_multimg(expr, model, sess, all_padded_imgs, pool_inds, labeled_inds, m
         draws = NNAL_tools.sample_query_dstr(q_opt, k, replacement=True)
         local = patch_utils.global2local_inds(draws, [len(s) for s in sel_inds])
         return [np.array(sel_inds[i])[local[i]] for i in range(len(sel_inds))]
-    raise NotImplementedError("query method %r is outside the scored path (random, entropy, MC-entropy, BALD, ensemble, QBC-JS, "
+    raise NotImplementedError("query method %r is outside the scored path (random, ps-random, entropy, MC-entropy, BALD, ensemble, QBC-JS, "
                               "rep-entropy, core-set, egl, fi)" % (method_name,))
 
 
@@ -567,3 +606,86 @@ def stoch_approx_IF(model, sess, tr_patches, pool_patches, max_iter, scale=50):
     idx = sess.to_device(model.llfc_reference_order(), sess.torch.int64)
     V_t = V.index_select(1, idx).to(sess.torch.float64).t().contiguous()      # the feature permutation, once, on the way out
     return V_t.cpu().numpy(), weak.cpu().numpy()
+
+
+def _segment_min_device(sess, overseg_img, inds, scores, n_labels):
+    """alq_segment_min: float64 device table [S, n_labels] of an over-segmentation [H, W, S] (host array), the scored voxels
+    `inds` (host) and their `scores` (float64 device tensor)."""
+    import ctypes as C
+    from ._lib import check
+    torch = sess.torch
+    sess.bind_stream()
+    seg = np.asarray(overseg_img)
+    if seg.ndim != 3:
+        raise ValueError('the over-segmentation must be a 3-D volume')
+    inds = np.ascontiguousarray(np.asarray(inds, dtype=np.int64)).reshape(-1)
+    n = int(inds.shape[0])
+    if int(scores.numel()) != n:
+        raise ValueError('%d scores for %d voxels' % (int(scores.numel()), n))
+    if n and (inds.min() < 0 or inds.max() >= seg.size):
+        raise IndexError('voxel index outside the over-segmentation %r' % (seg.shape,))
+    if len(np.unique(inds)) != n:
+        raise ValueError('superpix_scoring: duplicate voxel indices (the reference keeps an arbitrary one of their scores)')
+    table = sess.empty((int(seg.shape[2]), int(n_labels)), torch.float64)
+    d_lab = sess.to_device(seg.astype(np.int32), torch.int32)
+    d_inds = sess.to_device(inds, torch.int64)
+    dims = (C.c_int64 * 3)(*[int(v) for v in seg.shape])
+    check(sess.lib.alq_segment_min(sess.ctx, C.c_void_p(d_lab.data_ptr()), dims, int(n_labels), C.c_void_p(d_inds.data_ptr()) if n else None,
+                                   C.c_void_p(scores.data_ptr()) if n else None, n, C.c_void_p(table.data_ptr())))
+    return table
+
+
+def superpix_scoring(overseg_img, inds, scores):
+    """PW_NNAL.superpix_scoring (PW_NNAL.py:944-1021): the scores of a set of voxels (raveled indices `inds` into the 3-D
+    over-segmentation, unique) extended to super-pixels: float64 [S, overseg_img.max() + 1], entry (z, l) = the smallest score
+    among the scored voxels of super-pixel l in slice z (regionprops' min_intensity of a score image that is inf elsewhere).
+    inf where a (slice, label) got no scored voxel AND where the label is absent from the slice - the reference's code gives
+    inf in both cases, whatever its docstring says; column 0 (background) stays inf.  Device: alq_segment_min."""
+    from . import device
+    sess = device.default_session()
+    seg = np.asarray(overseg_img)
+    sc = sess.to_device(np.asarray(scores, dtype=np.float64).reshape(-1), sess.torch.float64)
+    return _segment_min_device(sess, seg, inds, sc, int(seg.max()) + 1).cpu().numpy()
+
+
+def SuPix_query(expr, model, sess, padded_imgs, pool_inds, overseg_img, method_name):
+    """PW_NNAL.SuPix_query (PW_NNAL.py:883-941), `entropy`: the k super-pixels (slice, label) whose most uncertain scored
+    voxel is the most uncertain.  Posteriors of the pool voxels as in batch_eval (kept on the device), keys |p - .5|
+    (alq_score_entropy), their minimum per (slice, label) (alq_segment_min), and the k smallest finite entries of the table
+    (alq_topk_uncertain: ties -> lower flat index z * n_labels + label).  Returns (qSuPix int64 [2, k] = slices; labels,
+    PW_AL.get_SuPix_inds(overseg_img, qSuPix)).  Fewer than k scored super-pixels: ValueError (the reference's argsort would
+    hand out unscored ones).  The reference's signature (expr, run, model, pool_lines, train_inds, overseg_img, method_name,
+    sess) belongs to its per-run index-file API; here the pool is given as voxel indices, like CNN_query's.  `random` is not
+    defined by the reference (its `qSuPix` is never assigned there)."""
+    import ctypes as C
+    from . import PW_AL
+    from ._lib import check
+    if method_name != 'entropy':
+        raise NotImplementedError("SuPix_query method %r: only 'entropy' is defined (the reference leaves qSuPix unset for 'random')"
+                                  % (method_name,))
+    torch = sess.torch
+    k = int(expr.pars['k'])
+    seg = np.asarray(overseg_img)
+    pool_inds = np.asarray(pool_inds, dtype=np.int64)
+    vols = patch_utils.DeviceVolumes(sess, padded_imgs)
+    p1 = PW_NN.posteriors_device(model, sess, padded_imgs, pool_inds, expr.pars['patch_shape'], expr.pars['ntb'], expr.pars['stats'],
+                                 _vols=vols)
+    n = int(p1.numel())
+    sess.bind_stream()
+    keys = sess.empty((n,), torch.float64)
+    if n:
+        check(sess.lib.alq_score_entropy(sess.ctx, C.c_void_p(p1.data_ptr()), n, C.c_void_p(keys.data_ptr()), None))
+    n_labels = int(seg.max()) + 1
+    table = _segment_min_device(sess, seg, pool_inds, keys, n_labels)
+    nscored = int(torch.isfinite(table).sum().item())
+    if nscored < k:
+        raise ValueError('SuPix_query: %d super-pixels hold a scored voxel, k = %d' % (nscored, k))
+    order = sess.topk_smallest(table.reshape(-1), k).cpu().numpy()
+    qSuPix = np.array([order // n_labels, order % n_labels], dtype=np.int64)
+    return qSuPix, PW_AL.get_SuPix_inds(seg, qSuPix)
+
+
+def draw_queries(qdist, prior, k, replacement=False):
+    """PW_NNAL.draw_queries (PW_NNAL.py:1023-1039): draws from the query distribution, times a prior when one is given."""
+    pies = qdist if len(prior) == 0 else qdist * prior
+    return NNAL_tools.sample_query_dstr(pies, k, replacement)

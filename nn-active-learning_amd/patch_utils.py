@@ -1,12 +1,13 @@
 """Patch gather / index maps of the scoring path (reference: patch_utils.py).
 
 `get_patches`, `get_patches_multimg` run on the device (alq_gather_normalize); `global2local_inds`
-is host index arithmetic like the reference's."""
+is host index arithmetic like the reference's.  The local-variance map of `get_vars_2d` / `partition_2d_indices` and of
+PW_NNAL.get_HV_inds is DeviceVolumes.local_var (alq_local_var2d)."""
 import ctypes as C
 
 import numpy as np
 
-from . import device
+from . import device, regions
 from ._lib import check
 
 
@@ -30,6 +31,42 @@ class DeviceVolumes(object):
         self.tensors = [sess.to_device(a, dt) for a in arrs]
         self.pad_dims = tuple(int(v) for v in shp)
         self.m = len(arrs)
+        self._host = arrs                    # local_var checks its precondition on the host copy, once per (modality, d)
+        self._var_checked = set()
+
+    def local_var(self, d, modality=0, inds=None, rads=(0, 0, 0)):
+        """The d x d local-variance map of every slice [:, :, z] of one modality (patch_utils.get_vars_2d per slice,
+        PW_NNAL.py:652-656; alq_local_var2d) as a float64 device tensor: [H, W, S] over the un-padded box
+        [r0:D0-r0, r1:D1-r1, r2:D2-r2], or - `inds`: raveled indices into that box - the map at those voxels only, [len(inds)].
+        ValueError when a value is negative or not finite or trunc(max)^2 d^2 >= 2^53 (regions.check_variance_input)."""
+        sess, torch = self.sess, self.sess.torch
+        d = int(d)
+        r = [int(v) for v in rads]
+        box = [self.pad_dims[a] - 2 * r[a] for a in range(3)]
+        if min(r) < 0 or min(box) < 1:
+            raise ValueError('radii %r leave no voxel of a volume of shape %r' % (tuple(r), self.pad_dims))
+        if (modality, d) not in self._var_checked:
+            regions.check_variance_input(self._host[modality], d)
+            self._var_checked.add((modality, d))
+        pd = (C.c_int64 * 3)(*self.pad_dims)
+        rd = (C.c_int32 * 3)(*r)
+        vol = C.c_void_p(self.tensors[modality].data_ptr())
+        sess.bind_stream()
+        if inds is None:
+            out = sess.empty(tuple(box), torch.float64)
+            check(sess.lib.alq_local_var2d(sess.ctx, vol, 1 if self.is_f64 else 0, pd, rd, d, None, 0, C.c_void_p(out.data_ptr())))
+            return out
+        inds = np.ascontiguousarray(np.asarray(inds, dtype=np.int64)).reshape(-1)
+        n = int(inds.shape[0])
+        out = sess.empty((n,), torch.float64)
+        if n == 0:
+            return out
+        if inds.min() < 0 or inds.max() >= box[0] * box[1] * box[2]:
+            raise IndexError('voxel index outside the un-padded volume %r' % (box,))
+        d_inds = sess.to_device(inds, torch.int64)
+        check(sess.lib.alq_local_var2d(sess.ctx, vol, 1 if self.is_f64 else 0, pd, rd, d, C.c_void_p(d_inds.data_ptr()), n,
+                                       C.c_void_p(out.data_ptr())))
+        return out
 
     def gather(self, inds, patch_shape, stats=None, quirk=2, out_f64=False):
         """-> device tensor [n, d1, d2, m*d3]; quirk: 0 slab stats, 1 channel-index stats, 2 none."""
@@ -91,6 +128,34 @@ def get_patches_multimg(all_padded_imgs, img_inds, patch_shape, stats):
         orig = tuple(dv.pad_dims[a] - 2 * r[a] for a in range(3))
         b_labels[j] = np.asarray(all_padded_imgs[j][m])[np.unravel_index(np.asarray(img_inds[j]), orig)]
     return b_patches, b_labels
+
+
+def get_vars_2d(img, d):
+    """patch_utils.get_vars_2d (patch_utils.py:794-826): the variance of the d x d patch around every pixel of a 2-D image,
+    E[x^2] - E[x]^2 of np.uint64(img) with zero fill outside; float64 [H, W], computed on the device (alq_local_var2d)."""
+    a = np.asarray(img)
+    if a.ndim != 2:
+        raise ValueError('get_vars_2d takes a 2-D image')
+    if a.dtype.kind != 'f':
+        regions.check_variance_input(a, d)      # before the cast: a large integer may not survive it
+        a = a.astype(np.float64)
+    dv = DeviceVolumes(device.default_session(), [a[:, :, None]])
+    return dv.local_var(d)[:, :, 0].cpu().numpy()
+
+
+def partition_2d_indices(img, mask):
+    """patch_utils.partition_2d_indices (patch_utils.py:735-791): the raveled indices of a 2-D image split into masked
+    (mask > 0), high-variance and low-variance un-masked pixels - log of the 5 x 5 variance map (zeros lifted by 0.1) above /
+    below 2; a pixel exactly at the threshold is in neither, as in the reference.  Returns (masked, Hvar, Lvar) as arrays
+    SORTED ASCENDING (the reference returns np.array(list(set)), whose order is undefined)."""
+    mask = np.asarray(mask)
+    var_map = get_vars_2d(img, 5)
+    var_map[var_map == 0] += 1e-1
+    var_map = np.log(var_map)
+    var_thr = 2.
+    masked = mask.reshape(-1) > 0
+    flat = var_map.reshape(-1)
+    return (np.nonzero(masked)[0], np.nonzero((flat > var_thr) & ~masked)[0], np.nonzero((flat < var_thr) & ~masked)[0])
 
 
 def global2local_inds(batch_inds, set_sizes):
