@@ -600,7 +600,26 @@ int alq_debug_set(int key, int value);
  * The backward indices 2, 8, 9, 11, 13 and 17 name launches of the Fisher pass only: all of them are 0 after a general backward
  * sweep (alq_param_grads, alq_grad_sqnorms, alq_class_layer_sums, alq_diag_fisher, the loss entry points) and after alq_hess_vecp,
  * whatever an earlier Fisher pass on the same model ran.
- * Returns the answer or a negative error code.  */
+ * Returns the answer or a negative error code (ALQ_EINVAL for 4, which is unused, and for anything outside 0 .. 17).  */
+enum {
+    ALQ_INFO_SUBNORMALS_OK = 0,
+    ALQ_INFO_C3D_FWD = 1,
+    ALQ_INFO_C3D_BWD = 2,
+    ALQ_INFO_C3D_ONE_ACC = 3,
+    ALQ_INFO_FLIP_OVERFLOW = 5,
+    ALQ_INFO_F16_DERIVED = 6,
+    ALQ_INFO_T3D_FWD = 7,
+    ALQ_INFO_T3D_BWD = 8,
+    ALQ_INFO_E3D_BWD = 9,
+    ALQ_INFO_D3D_FWD = 10,
+    ALQ_INFO_D3D_BWD = 11,
+    ALQ_INFO_F3D_FWD = 12,
+    ALQ_INFO_C3D_BWD_FORM = 13,
+    ALQ_INFO_HOST_PACK_ELEMS = 14,
+    ALQ_INFO_LSUM = 15,
+    ALQ_INFO_DCP_FORM = 16,
+    ALQ_INFO_E3D_BWD_FORM = 17
+};
 int alq_model_engine_info(alq_model *m, int what);
 
 /* Synthetic patch generator: counter-based RNG keyed (seed, patch_id, element), standard

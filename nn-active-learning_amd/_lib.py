@@ -1,6 +1,7 @@
 """ctypes binding of libalq.so (include/alq.h).  No fallback: if the HIP library is missing the
 import of any device function raises, so a CPU-only or stale install fails loudly."""
 import ctypes as C
+import enum
 import os
 import subprocess
 
@@ -9,6 +10,28 @@ LIB_PATH = os.path.join(_HERE, os.environ.get('ALQ_LIB', 'libalq.so'))   # ALQ_L
 BUILD_SCRIPT = os.path.join(_HERE, 'csrc', 'build.sh')
 
 ALQ_CONV, ALQ_CONVT, ALQ_POOL, ALQ_FC = 0, 1, 2, 3
+ALQ_EINVAL = -1
+
+
+class EngineInfo(enum.IntEnum):
+    """The `what` of alq_model_engine_info (the ALQ_INFO_* enum of include/alq.h, which documents every index)."""
+    SUBNORMALS_OK = 0
+    C3D_FWD = 1
+    C3D_BWD = 2
+    C3D_ONE_ACC = 3
+    FLIP_OVERFLOW = 5
+    F16_DERIVED = 6
+    T3D_FWD = 7
+    T3D_BWD = 8
+    E3D_BWD = 9
+    D3D_FWD = 10
+    D3D_BWD = 11
+    F3D_FWD = 12
+    C3D_BWD_FORM = 13
+    HOST_PACK_ELEMS = 14
+    LSUM = 15
+    DCP_FORM = 16
+    E3D_BWD_FORM = 17
 
 
 class AlqError(RuntimeError):

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "alq.h"
+#include "engine_switches.h"      // enum Knob, EngineSwitches
 
 namespace alq {
 
@@ -289,8 +290,9 @@ struct Igemm2Fuse {
 };
 
 extern unsigned long long *g_igemm2_dbg;
-constexpr int ALQ_NKNOBS = 10;
-extern int g_dbg_knobs[ALQ_NKNOBS];
+extern int g_dbg_knobs[ALQ_NKNOBS];      // indexed by enum Knob (engine_switches.h)
+// neither knob that takes the two-slot engine (igemm4) away is set
+inline bool two_slot_allowed() { return !g_dbg_knobs[KNOB_NO_V3] && !g_dbg_knobs[KNOB_NO_V4]; }
 extern int g_dcp_last_form;      // direct.hip: form of the last first conv + pool launch
 extern int g_no_f16x2;        // ALQ_NO_F16X2, read when a model is created: bf16x3 split in every launch
 extern int g_no_fixed;        // ALQ_NO_FIXED (A/B runs, bit-identity test): igemm4 launches use the runtime-constant instantiation only

@@ -439,7 +439,7 @@ int direct_conv_pool_launch(alq_ctx *ctx, const float *d_W, const View &in, cons
     // a workgroup covers 8 x 8 x 32 voxels (whole rows of a 32-voxel volume: every output row is one aligned run of one wave)
     // where that leaves no more idle lanes along x than 8 x 16 x 16 does; knob 8 (ALQ_DCP_NARROW=1 at model creation or
     // alq_debug_set(8, 1): A/B runs, bit-identity test): the narrow tile with per-voxel sum / sign stores everywhere
-    const bool narrow_only = g_dbg_knobs[8] != 0;
+    const bool narrow_only = g_dbg_knobs[KNOB_DCP_NARROW] != 0;
     const bool wide = !narrow_only && (in.W + 31) / 32 * 32 <= (in.W + 15) / 16 * 16;
     const int twx = wide ? 16 : 8, twy = 64 / twx;
     a.tilesZ = (pout.D + 3) / 4; a.tilesY = (pout.H + twy - 1) / twy; a.tilesX = (pout.W + twx - 1) / twx;

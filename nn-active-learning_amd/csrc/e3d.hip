@@ -579,7 +579,7 @@ int e3d_bwd_launch(alq_ctx *ctx, const E3dPlan &plan, int N, const float *skip, 
     if (!rows) {      // the z plane sweep: a 512-thread workgroup per CU over whole patches
         long long g = std::min<long long>(cus, N);
         g = std::max<long long>(8, (g + 7) / 8 * 8);
-        if (g_dbg_knobs[9] > 0) g = std::min<long long>(g, g_dbg_knobs[9]);      // tests: a few workgroups, so that a handful of patches makes multi-patch streams
+        if (g_dbg_knobs[KNOB_E3D_GRID_CAP] > 0) g = std::min<long long>(g, g_dbg_knobs[KNOB_E3D_GRID_CAP]);      // tests: a few workgroups, so that a handful of patches makes multi-patch streams
         ALQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(e3d_bwdz_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, E3Z_LDS));
         ProfScope ps(ctx, PROF_IGEMM_F16, plan.flops_per_patch * N);
         hipLaunchKernelGGL(e3d_bwdz_kernel, dim3((unsigned)g), dim3(512), (size_t)E3Z_LDS, ctx->stream, a);

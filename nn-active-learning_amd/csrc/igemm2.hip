@@ -571,7 +571,7 @@ unsigned long long *g_igemm2_dbg = nullptr;
 int g_no_f16x2 = 0;
 int g_no_xcd_order = 0;
 int g_no_fixed = 0;
-int g_dbg_knobs[ALQ_NKNOBS] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // 0 repeat, 1 flags, 2 no-bwd-fuse, 3 no-fwd-fuse ... 8 narrow first-conv tile, 9 grid cap of the e3d plane sweep   // set by alq_debug_set_stamp_buffer (diagnostic build)
+int g_dbg_knobs[ALQ_NKNOBS] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // indexed by enum Knob (engine_switches.h)
 
 template <int NTW, bool WRES, int GEO, bool SUMS>
 static int launch2_s(alq_ctx *ctx, const Igemm2Plan &plan, const Igemm2Args &a, unsigned grid) {
@@ -619,8 +619,8 @@ int igemm2_launch(alq_ctx *ctx, const Igemm2Plan &plan, const View &in, const Vi
         ++ordinal;
     }
     // timing experiments only (alq_debug_set / env): repeat the MFMA phase, drop stores / loads / sums
-    a.dbg_repeat = g_dbg_knobs[0];
-    a.dbg_flags = g_dbg_knobs[1];
+    a.dbg_repeat = g_dbg_knobs[KNOB_REPEAT];
+    a.dbg_flags = g_dbg_knobs[KNOB_FLAGS];
     if (fuse) {
         a.mask = fuse->mask; a.mask_cs = fuse->mask_cs; a.mask_c0 = fuse->mask_c0; a.mask_from = fuse->mask_from;
         a.osumA = fuse->osumA; a.osumB = fuse->osumB;

@@ -646,8 +646,8 @@ int igemm3_launch(alq_ctx *ctx, const Igemm2Plan &p2, const Igemm3Plan &plan, co
         if (want < 0 || ordinal == want) a.dbg = g_igemm2_dbg;
         ++ordinal;
     }
-    a.dbg_repeat = g_dbg_knobs[0];
-    a.dbg_flags = g_dbg_knobs[1];
+    a.dbg_repeat = g_dbg_knobs[KNOB_REPEAT];
+    a.dbg_flags = g_dbg_knobs[KNOB_FLAGS];
     a.split = 1 << 30;
     if (fuse) {
         ALQ_REQUIRE(fuse->split % 4 == 0 && fuse->mask_cs % 4 == 0 && fuse->mask_c0 % 4 == 0 && fuse->mask_from % 4 == 0,
@@ -662,7 +662,7 @@ int igemm3_launch(alq_ctx *ctx, const Igemm2Plan &p2, const Igemm3Plan &plan, co
     a.f16_bound = nullptr; a.f16_wexp = 0;
     // ... or one scale per patch (forward launches): Igemm2Fuse::in_amax = a bound on max |input| of every patch; tiles of one patch
     const bool f16p = fuse && fuse->in_amax && !fuse->in_amax2 && plan.d_W16 && a.PT == 1 && !accumulate && !g_no_f16x2;
-    const bool f16 = f16p || (fuse && fuse->in_bound > 0.f && plan.d_W16 && !accumulate && !g_no_f16x2 && !g_dbg_knobs[2]);
+    const bool f16 = f16p || (fuse && fuse->in_bound > 0.f && plan.d_W16 && !accumulate && !g_no_f16x2 && !g_dbg_knobs[KNOB_NO_BWD_FUSE]);
     if (f16p) {
         a.W = reinterpret_cast<const float *>(plan.d_W16);
         a.f16_bound = fuse->in_amax;

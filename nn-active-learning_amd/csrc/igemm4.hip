@@ -1982,7 +1982,7 @@ static int igemm4_launch_impl(alq_ctx *ctx, const Igemm4Plan &plan, const View &
         if (want < 0 || ordinal == want) a.dbg = g_igemm2_dbg;
         ++ordinal;
     }
-    a.dbg_repeat = g_dbg_knobs[0];
+    a.dbg_repeat = g_dbg_knobs[KNOB_REPEAT];
     a.split = 1 << 30;
     if (fuse) {
         ALQ_REQUIRE(fuse->split % 4 == 0 && fuse->mask_cs % 4 == 0 && fuse->mask_c0 % 4 == 0 && fuse->mask_from % 4 == 0,

@@ -130,11 +130,35 @@ struct Layer {
 
 using namespace alq;
 
+// What the last pass of a model ran (alq_model_engine_info).  run_forward starts from fwd = {}; run_backward_main, run_backward_general
+// and the fp64 sweep of alq_hess_vecp start from bwd = {}: the backward part speaks of the LAST backward pass, whichever kind it was.
+struct PassInfo {
+    struct Fwd {
+        bool head_fused = false;   // the pass did not store the last conv's output (fc head fused into it)
+        bool c3 = false;           // it ran the head conv on the plane-sweep engine (c3d.hip)
+        int t3f = 0;               // conv_transpose launches on the row-sweep engine (t3d.hip)
+        int d3f = 0;               // dec1 ran on the row-sweep engine (d3d.hip)
+        int f3f = 0;               // enc2 and the pool behind it ran fused (f3d.hip)
+        int dcp = 0;               // form of the first conv + pool kernel, 0 = it did not run (direct.hip: g_dcp_last_form)
+        bool f16_derived = false;  // a launch ran on the fp16x2 split with derived input bounds
+    } fwd;
+    struct Bwd {                   // launches of a Fisher pass's backward sweep only
+        bool c3_bwd = false;       // the head conv's backward ran on the plane-sweep engine
+        int t3b = 0;               // conv_transpose launches on the row-sweep engine
+        int e3b = 0;               // pool2 backward, enc2 backward and pool1 backward ran as one launch (e3d.hip)
+        int e3b_form = 0;          // form of that launch: 0 none, 1 row sweep, 2 z plane sweep
+        int d3b = 0;               // dec1's backward-data launch ran on d3d.hip
+    } bwd;
+    int lsum = 0;                  // the last GENERAL backward sweep ran the fused layer-sum kernels (set by run_backward_general only)
+    bool call_fisher = false;      // the last entry point ran a Fisher pass (prepare_call)
+};
+
 struct alq_model {
     alq_ctx *ctx = nullptr;
     int max_batch = 0;
-    bool last_call_fisher = false;   // what alq_model_debug_copy may read
-    bool last_head_fused = false;    // the last forward pass did not store the last conv's output
+    EngineSwitches sw;               // engine-selection switches, read from the environment ONCE, when this model is created
+                                     // (engine_switches.h); every call applies the model's own snapshot
+    PassInfo last;                   // what the last pass ran (alq_model_engine_info, alq_model_debug_copy)
     // per-patch max |x| (float bits) of the two producers of the fused-head conv's input, for its fp16x2 contraction
     unsigned *amax_a = nullptr, *amax_b = nullptr, *amax_tiles = nullptr;
     unsigned *flip_cnt = nullptr, *flip_list = nullptr;     // candidates of the flip-safe fused head (igemm4 FCF + F16)
@@ -143,7 +167,6 @@ struct alq_model {
     unsigned *in_amax = nullptr;            // [max_batch] measured max |x| of every patch of the network input (igemm3's forward fp16 pairs)
     bool v3_fwd_f16 = false;                // some forward conv launch stays on igemm3 and has the fp16-pair twin packed (set at build)
     unsigned *flip_overflow = nullptr;      // marked groups beyond the scan's lists since the model was created: drained by the sweep path of flip_fix_kernel (kernels.hip), none dropped
-    int no_flipfix = 0;                                      // ALQ_NO_FLIPFIX at creation (A/B: the head's sign bits as the fp16x2 contraction leaves them)
     size_t amax_tiles_len = 0;
     int in_dims[4] = {1, 1, 1, 1};
     int nclass = 0;
@@ -166,42 +189,9 @@ struct alq_model {
     double *ls_part = nullptr;
     std::vector<int> ls_nslab;
     int ls_nslab_max = 0;
-    int last_lsum = 0;             // the last general backward sweep ran the fused layer-sum kernels (engine info 15)
     float *x_stage = nullptr;      // [max_batch, elems per patch]: rows gathered by the *_rows entry points
     int64_t epp = 0;               // elements per patch
-    // Engine-selection knobs, read from the environment ONCE, when this model is created; every call applies the
-    // model's own snapshot (alq_debug_set overrides a key for all models until it is set back to -1 / re-set).
-    int knobs[ALQ_NKNOBS] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    int no_f16x2 = 0;
-    int no_xcd_order = 0;
-    int requested_batch = 0;      // what alq_model_create was asked for (max_batch may be lower: 32-bit tensor offsets)
-    int no_bound16 = 0;           // ALQ_NO_BOUND16 at creation: backward launches take their fp16x2 scale from measured per-patch maxima only
-    int no_fixed = 0;             // ALQ_NO_FIXED at creation: runtime-constant igemm4 instantiations only
-    int no_presplit = 0;           // ALQ_NO_PRESPLIT (A/B): split the fc head's weight-difference vector in the staging part again
-    int no_signs = 0;              // ALQ_NO_SIGNS (A/B, bit-identity test): backward launches read ReLU masks from the fp32 activations
-    int no_signs0 = 0;             // ALQ_NO_SIGNS0 (A/B): no sign field from the first conv + pool kernel only
-    int f16_fwd_mask = -1;         // ALQ_F16_FWD_MASK (diagnostics): forward fp16x2 consumers by layer bit, -1 = default rule
     int f16_fwd_derived = 0;       // layers (bits) whose forward launch takes the fp16x2 split with DERIVED input bounds (see run_forward)
-    int no_f16_derived = 0;        // 1 with ALQ_NO_F16_DERIVED=1: those launches stay on bf16x3 (A/B; default since round 5: they take the split)
-    float *d_bound_L = nullptr, *d_bound_B = nullptr;      // per layer: out = in * L + B (k_fwd_bounds)
-    int *d_bound_src = nullptr;
-    int no_light_kernels = 0;      // ALQ_NO_LIGHT_KERNELS (A/B): forward-only passes keep dec1 / enc2 + pool2 on the two-slot engine as until round 5
-    int no_c3d = 0;                // ALQ_NO_C3D (A/B): the head conv pair on the two-slot engine (igemm4) as in round 3
-    int c3_bwd_rows = 8;           // ALQ_C3D_BWD_ROWS=4 (A/B): the plane-sweep backward kernel in its half-patch form
-    bool last_c3 = false;          // the last forward pass ran the head conv on the plane-sweep engine
-    bool last_c3_bwd = false;      // ... and the last backward pass its backward
-    int no_e3d = 0;                // ALQ_NO_E3D (A/B): pool2 backward, enc2 backward and pool1 backward as three launches as in round 4
-    int last_e3b = 0;              // the last backward pass ran them as one launch (e3d.hip)
-    int e3d_rows = 0;              // ALQ_E3D_ROWS=1 (A/B): that launch on the row-sweep kernel of rounds 5 - 7 instead of the z plane sweep (same bits)
-    int last_e3b_form = 0;         // form of that launch in the last backward pass: 0 none, 1 row sweep, 2 z plane sweep
-    int no_d3d = 0;                // ALQ_NO_D3D (A/B): dec1's forward on the two-slot engine as in round 4
-    int last_d3f = 0;              // the last forward pass ran it on the row-sweep engine (d3d.hip)
-    int no_f3d = 0, last_f3f = 0;  // ALQ_NO_F3D (A/B): enc2's forward on the two-slot engine + the pool as its own launch; the last forward pass ran them fused (f3d.hip)
-    int no_d3b = 0, last_d3b = 0;  // ALQ_NO_D3D_BWD (A/B): only the backward launch on the two-slot engine; the last backward pass ran it on d3d.hip
-    int no_t3d = 0;                // ALQ_NO_T3D (A/B): conv_transpose launches on the two-slot engine (igemm4) as in round 4
-    int last_dcp = 0;              // form of the first conv + pool kernel the last forward pass ran, 0 = it did not run (direct.hip: g_dcp_last_form)
-    int last_t3f = 0, last_t3b = 0;   // conv_transpose launches of the last forward / backward pass that ran on the row-sweep engine
-    bool last_f16_derived = false; // the last forward pass ran a launch on the fp16x2 split with derived input bounds
     int64_t host_pack_elems = 0;   // weight elements that went through the host packers since the model was created (engine info 14)
     void *d_wscal = nullptr;       // 16 bytes: the scalars of the device packers (wpack.hip)
     bool hv_ready = false;         // alq_hess_vecp has allocated its workspaces (first call)
@@ -276,32 +266,31 @@ static int upload1(alq_model *m, IgemmPlan *p) {
     return ALQ_OK;
 }
 
-static bool g_use_v2 = true;
 static int g_knob_override[ALQ_NKNOBS] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // alq_debug_set: >= 0 overrides every model's snapshot
 
 // The kernels' launch helpers read the process-wide g_dbg_knobs / g_no_f16x2; each entry point loads them from the
 // model it was called on, so creating another model (or its environment) never changes a live one.
 static void apply_knobs(const alq_model *m) {
-    for (int k = 0; k < ALQ_NKNOBS; ++k) g_dbg_knobs[k] = g_knob_override[k] >= 0 ? g_knob_override[k] : m->knobs[k];
-    g_no_f16x2 = m->no_f16x2;
-    g_no_xcd_order = m->no_xcd_order;
-    g_no_fixed = m->no_fixed;
+    for (int k = 0; k < ALQ_NKNOBS; ++k) g_dbg_knobs[k] = g_knob_override[k] >= 0 ? g_knob_override[k] : m->sw.knobs[k];
+    g_no_f16x2 = m->sw.no_f16x2;
+    g_no_xcd_order = m->sw.no_xcd_order;
+    g_no_fixed = m->sw.no_fixed;
 }
 
-static int gemm_build(const ConvDesc &d, int max_batch, Gemm *g, const G4Geom *g4 = nullptr) {
+static int gemm_build(const EngineSwitches &sw, const ConvDesc &d, int max_batch, Gemm *g, const G4Geom *g4 = nullptr) {
     ALQ_TRY(igemm_build_plan(d, max_batch, &g->p1));
-    if (g4 && !getenv("ALQ_DISABLE_V4")) {
+    if (g4 && !sw.disable_v4) {
         G4Geom gg = *g4;
         gg.flops_per_patch = g->p1.flops_per_patch;
         ALQ_TRY(igemm4_build_plan(gg, max_batch, &g->p4));
     }
     ALQ_TRY(igemm2_build_plan(g->p1, &g->p2));
     ALQ_TRY(direct_build_plan(g->p1, &g->pd));
-    if (!g_use_v2) { g->p2.ok = false; g->pd.ok = false; }
+    if (sw.disable_v2) { g->p2.ok = false; g->pd.ok = false; }
     ALQ_TRY(igemm3_build_plan(g->p2, &g->p3));
-    if (d.ID == 1 && d.IH == 1 && d.IW == 1 && d.tz.size() == 1 && d.sm == 1 && d.so == 1 && !getenv("ALQ_NO_FCGEMM"))
+    if (d.ID == 1 && d.IH == 1 && d.IW == 1 && d.tz.size() == 1 && d.sm == 1 && d.so == 1 && !sw.no_fcgemm)
         ALQ_TRY(fcgemm_build_plan(d.Ci, d.Co, &g->pfc));       // a wide fully connected layer
-    if (const char *e = getenv("ALQ_DISABLE_V3")) { if (e[0] == '1') g->p3.ok = false; }
+    if (sw.disable_v3) g->p3.ok = false;
     return ALQ_OK;
 }
 
@@ -429,43 +418,44 @@ static int refresh_fallback_forms(alq_model *m) {
     return ALQ_OK;
 }
 
-static int prepare_call(alq_model *m) {
+// first step of every entry point that runs a pass; `fisher`: the pass is a Fisher pass (what alq_model_debug_copy may read)
+static int prepare_call(alq_model *m, bool fisher) {
+    m->last.call_fisher = fisher;
     apply_knobs(m);
-    if (g_dbg_knobs[4] || g_dbg_knobs[5]) ALQ_TRY(refresh_fallback_forms(m));
+    if (!two_slot_allowed()) ALQ_TRY(refresh_fallback_forms(m));
     return ALQ_OK;
+}
+
+// Which engine a gemm_launch call takes.  The debug knobs take the two-slot engine away - except for a split concat view,
+// which only that engine reads.
+enum GemmRoute { ROUTE_DIRECT, ROUTE_FCGEMM, ROUTE_IGEMM4, ROUTE_IGEMM3, ROUTE_IGEMM2, ROUTE_IGEMM };
+static GemmRoute gemm_route(const Gemm &g, const View &in, const View &out, int accumulate, const Igemm2Fuse *fuse) {
+    if (g.pd.ok && !accumulate && !(fuse && (fuse->mask || fuse->osumB || fuse->split))) return ROUTE_DIRECT;
+    if (g.pfc.ok && !accumulate && !fuse && two_slot_allowed()) return ROUTE_FCGEMM;      // wide fc layer: streaming bf16x3 GEMM
+    const bool split_view = in.split != 0 || out.split != 0;
+    if (g.p4.ok && (two_slot_allowed() || split_view)) return ROUTE_IGEMM4;      // two-slot bf16x3 engine
+    if (g.p3.ok && !g_dbg_knobs[KNOB_NO_V3]) return ROUTE_IGEMM3;      // bf16x3 split on the matrix cores (fp32-equivalent accuracy)
+    return g.p2.ok ? ROUTE_IGEMM2 : ROUTE_IGEMM;
 }
 
 // returns in *fused whether the epilogue fusion request was honoured (only the pipelined kernel can)
 static int gemm_launch(alq_ctx *ctx, const Gemm &g, const View &in, const View &out, const float *bias, int relu,
                        int accumulate, int N, int cls, const Igemm2Fuse *fuse = nullptr, bool *fused = nullptr, float fc_in_bound = 0.f) {
-    if (g.pd.ok && !accumulate && !(fuse && (fuse->mask || fuse->osumB || fuse->split))) {
-        if (fused) *fused = fuse != nullptr;
-        return direct_launch(ctx, g.pd, in, out, bias, relu, N, fuse ? fuse->osumA : nullptr, PROF_DIRECT);
+    const GemmRoute route = gemm_route(g, in, out, accumulate, fuse);
+    ALQ_REQUIRE(route <= ROUTE_FCGEMM || g.p4.ok || (in.split == 0 && out.split == 0), ALQ_EUNSUPPORTED, "split concat view without a two-slot plan");
+    if (fused) *fused = fuse != nullptr && route != ROUTE_FCGEMM && route != ROUTE_IGEMM;
+    const int cls3 = cls == PROF_IGEMM_BWD ? PROF_IGEMM3_BWD : PROF_IGEMM3_FWD;
+    switch (route) {
+        case ROUTE_DIRECT: return direct_launch(ctx, g.pd, in, out, bias, relu, N, fuse ? fuse->osumA : nullptr, PROF_DIRECT);
+        case ROUTE_FCGEMM:
+            // forward launches of wide fc layers: fp16 pairs under the per-patch maxima the launch measures (fcgemm.hip, round 6)
+            return fcgemm_launch(ctx, g.pfc, in, out, bias, relu, N, cls3, (g_no_f16x2 || bias || relu) ? 0.f : fc_in_bound,
+                                 (cls == PROF_IGEMM_FWD && !g_no_f16x2) ? g.fc_row_amax : nullptr);
+        case ROUTE_IGEMM4: return igemm4_launch(ctx, g.p4, in, out, bias, relu, accumulate, N, cls3, fuse);
+        case ROUTE_IGEMM3: return igemm3_launch(ctx, g.p2, g.p3, in, out, bias, relu, accumulate, N, cls3, fuse);
+        case ROUTE_IGEMM2: return igemm2_launch(ctx, g.p2, in, out, bias, relu, accumulate, N, cls, fuse);
+        case ROUTE_IGEMM: break;
     }
-    if (g.pfc.ok && !accumulate && !fuse && !g_dbg_knobs[4] && !g_dbg_knobs[5]) {     // wide fc layer: streaming bf16x3 GEMM
-        if (fused) *fused = false;
-        // forward launches of wide fc layers: fp16 pairs under the per-patch maxima the launch measures (fcgemm.hip, round 6)
-        return fcgemm_launch(ctx, g.pfc, in, out, bias, relu, N, cls == PROF_IGEMM_BWD ? PROF_IGEMM3_BWD : PROF_IGEMM3_FWD,
-                             (g_no_f16x2 || bias || relu) ? 0.f : fc_in_bound,
-                             (cls == PROF_IGEMM_FWD && !g_no_f16x2) ? g.fc_row_amax : nullptr);
-    }
-    const bool split_view = in.split != 0 || out.split != 0;
-    ALQ_REQUIRE(!split_view || g.p4.ok, ALQ_EUNSUPPORTED, "split concat view without a two-slot plan");
-    if (g.p4.ok && ((!g_dbg_knobs[4] && !g_dbg_knobs[5]) || split_view)) {      // two-slot bf16x3 engine
-        if (fused) *fused = fuse != nullptr;
-        return igemm4_launch(ctx, g.p4, in, out, bias, relu, accumulate, N,
-                             cls == PROF_IGEMM_BWD ? PROF_IGEMM3_BWD : PROF_IGEMM3_FWD, fuse);
-    }
-    if (g.p3.ok && !g_dbg_knobs[4]) {      // bf16x3 split on the matrix cores (fp32-equivalent accuracy)
-        if (fused) *fused = fuse != nullptr;
-        return igemm3_launch(ctx, g.p2, g.p3, in, out, bias, relu, accumulate, N,
-                             cls == PROF_IGEMM_BWD ? PROF_IGEMM3_BWD : PROF_IGEMM3_FWD, fuse);
-    }
-    if (g.p2.ok) {
-        if (fused) *fused = fuse != nullptr;
-        return igemm2_launch(ctx, g.p2, in, out, bias, relu, accumulate, N, cls, fuse);
-    }
-    if (fused) *fused = false;
     return igemm_launch(ctx, g.p1, in, out, bias, relu, accumulate, N, cls);
 }
 
@@ -478,6 +468,7 @@ static void enum_taps(const int k[3], std::vector<int> *tz, std::vector<int> *ty
 }
 
 static int build_model(alq_model *m, const alq_layer_t *specs, int n_layers) {
+    const EngineSwitches &sw = m->sw;
     m->layers.resize(n_layers);
     // ---- pass 1: shapes ------------------------------------------------------------------
     struct Shp { int D, H, W, C; };
@@ -577,7 +568,6 @@ static int build_model(alq_model *m, const alq_layer_t *specs, int n_layers) {
             worst = std::max(worst, e);
         }
         const long long limit = std::max(1LL, ((1LL << 30) - 64) / std::max(worst, 1LL));
-        m->requested_batch = m->max_batch;
         if (m->max_batch > limit) m->max_batch = (int)limit;
     }
     const int NB = m->max_batch;
@@ -606,7 +596,7 @@ static int build_model(alq_model *m, const alq_layer_t *specs, int n_layers) {
         // two channel groups.  Interleaved slices cost twice the cache lines per staged or stored row (32 of 64
         // bytes used), and the engine's staging and store parts are bound by lines touched.
         bool split_ok = false;
-        if (Cs == Cp && Cs % 8 == 0 && specs[d].type == ALQ_CONV && !getenv("ALQ_DISABLE_V4") && !getenv("ALQ_NO_SPLIT")) {
+        if (Cs == Cp && Cs % 8 == 0 && specs[d].type == ALQ_CONV && !sw.disable_v4 && !sw.no_split) {
             const Layer &dl = m->layers[d];
             G4Geom gf;
             gf.kind = 0;
@@ -702,18 +692,18 @@ static int build_model(alq_model *m, const alq_layer_t *specs, int n_layers) {
             g4.ID = ly.in.D; g4.IH = ly.in.H; g4.IW = ly.in.W; g4.Ci = ly.in.C;
             g4.OD = ly.out.D; g4.OH = ly.out.H; g4.OW = ly.out.W; g4.Co = sp.cout;
             for (int q = 0; q < 3; ++q) { g4.k[q] = sp.k[q]; g4.s[q] = sp.s[q]; g4.lo[q] = ly.lo[q]; }
-            ALQ_TRY(gemm_build(d, NB, &ly.fwd[0], &g4));
+            ALQ_TRY(gemm_build(sw, d, NB, &ly.fwd[0], &g4));
             // a 2-D window of 25 taps or more: the two-slot engine's tiles re-stage too much halo - NET-B's conv2 (24 -> 32 channels,
             // 5 x 5 at 32^2) takes 673 us per 2048 patches there and ~390 on igemm3 (round 6; ALQ_NO_WIDE2D_RULE=1 = the other arm)
-            if (ly.fwd[0].p4.ok && ly.fwd[0].p3.ok && d.ID == 1 && d.tz.size() >= 25 && !getenv("ALQ_NO_WIDE2D_RULE")) ly.fwd[0].p4.ok = false;
+            if (ly.fwd[0].p4.ok && ly.fwd[0].p3.ok && d.ID == 1 && d.tz.size() >= 25 && !sw.no_wide2d_rule) ly.fwd[0].p4.ok = false;
             // a forward launch that stays on igemm3, tiles of one patch: the fp16-pair twin of its weights for Fisher / forward-only passes
             // (run_forward, round 6; ALQ_NO_V3_F16_FWD=1: bf16 triples as before)
             if (!ly.fwd[0].p4.ok && !ly.fwd[0].pd.ok && !ly.fwd[0].pfc.ok && ly.fwd[0].p3.ok && ly.fwd[0].p2.a.PT == 1 && sp.skip_src < 0 &&
-                !getenv("ALQ_NO_V3_F16_FWD") && !getenv("ALQ_NO_V3_F16")) {
+                !sw.no_v3_f16_fwd && !sw.no_v3_f16) {
                 ly.fwd[0].p3_f16 = true;
                 m->v3_fwd_f16 = true;
             }
-            if (!ly.fwd[0].p4.ok && !ly.fwd[0].p3.ok && !ly.fwd[0].pd.ok && sp.cout > 32 && !getenv("ALQ_NO_CO_SPLIT")) {
+            if (!ly.fwd[0].p4.ok && !ly.fwd[0].p3.ok && !ly.fwd[0].pd.ok && sp.cout > 32 && !sw.no_co_split) {
                 for (int w : {32, 48, 16}) {
                     if (sp.cout % w || sp.cout <= w) continue;
                     std::vector<Gemm> parts(sp.cout / w);
@@ -723,7 +713,7 @@ static int build_model(alq_model *m, const alq_layer_t *specs, int n_layers) {
                         dj.Co = w;
                         G4Geom gj = g4;
                         gj.Co = w;
-                        ALQ_TRY(gemm_build(dj, NB, &parts[j], &gj));
+                        ALQ_TRY(gemm_build(sw, dj, NB, &parts[j], &gj));
                         ok = parts[j].p4.ok || parts[j].p3.ok;
                     }
                     if (ok) { ly.fwd_co = std::move(parts); ly.fwd_co_w = w; break; }
@@ -749,11 +739,11 @@ static int build_model(alq_model *m, const alq_layer_t *specs, int n_layers) {
                 gb.flipped = true;
                 gb.ID = ly.out.D; gb.IH = ly.out.H; gb.IW = ly.out.W; gb.Ci = sp.cout;
                 gb.OD = ly.in.D; gb.OH = ly.in.H; gb.OW = ly.in.W; gb.Co = ly.in.C;
-                ALQ_TRY(gemm_build(b, NB, &ly.bwd, &gb));
+                ALQ_TRY(gemm_build(sw, b, NB, &ly.bwd, &gb));
                 ly.has_bwd = true;
                 // a backward launch that stays on igemm3 (no two-slot plan: NET-B's 5 x 5 and 96-channel convs) takes fp16 pairs under the
                 // cotangent bound of a Fisher pass like the two-slot launches do (round 6; ALQ_NO_V3_F16=1: bf16 triples as before)
-                ly.bwd.p3_f16 = !ly.bwd.p4.ok && ly.bwd.p3.ok && !getenv("ALQ_NO_V3_F16");
+                ly.bwd.p3_f16 = !ly.bwd.p4.ok && ly.bwd.p3.ok && !sw.no_v3_f16;
             }
         } else if (sp.type == ALQ_CONVT) {
             // y[p] = sum_{q,t: s*q + t - lo = p} x[q] W[t]; output parity class c = p mod s uses the
@@ -786,7 +776,7 @@ static int build_model(alq_model *m, const alq_layer_t *specs, int n_layers) {
                         gc.OD = ly.out.D; gc.OH = ly.out.H; gc.OW = ly.out.W; gc.Co = sp.cout;
                         for (int q = 0; q < 3; ++q) { gc.k[q] = sp.k[q]; gc.s[q] = sp.s[q]; gc.lo[q] = ly.lo[q]; }
                         gc.cls[0] = cz; gc.cls[1] = cy; gc.cls[2] = cx;
-                        ALQ_TRY(gemm_build(d, NB, &ly.fwd.back(), &gc));
+                        ALQ_TRY(gemm_build(sw, d, NB, &ly.fwd.back(), &gc));
                     }
             ALQ_REQUIRE(sp.s[0] == sp.s[2] || (ly.in.D == 1 && sp.s[0] == 1), ALQ_EUNSUPPORTED,
                         "layer %d: conv_transpose stride must be isotropic", i);
@@ -794,13 +784,13 @@ static int build_model(alq_model *m, const alq_layer_t *specs, int n_layers) {
             g4.ID = ly.in.D; g4.IH = ly.in.H; g4.IW = ly.in.W; g4.Ci = ly.in.C;
             g4.OD = ly.out.D; g4.OH = ly.out.H; g4.OW = ly.out.W; g4.Co = sp.cout;
             for (int q = 0; q < 3; ++q) { g4.k[q] = sp.k[q]; g4.s[q] = sp.s[q]; g4.lo[q] = ly.lo[q]; }
-            if (!getenv("ALQ_DISABLE_V4")) {
+            if (!sw.disable_v4) {
                 G4Geom gf = g4;
                 gf.kind = 2;
                 gf.flops_per_patch = 0;
                 for (const Gemm &c : ly.fwd) gf.flops_per_patch += c.p1.flops_per_patch;
                 ALQ_TRY(igemm4_build_plan(gf, NB, &ly.fwd_all));
-                if (!ly.fwd_all.ok && !getenv("ALQ_NO_CLASS_TILES")) {      // too large to stage once: the classes as tiles of one launch
+                if (!ly.fwd_all.ok && !sw.no_class_tiles) {      // too large to stage once: the classes as tiles of one launch
                     gf.kind = 4;
                     ALQ_TRY(igemm4_build_plan(gf, NB, &ly.fwd_all));
                 }
@@ -819,7 +809,7 @@ static int build_model(alq_model *m, const alq_layer_t *specs, int n_layers) {
                 gb.kind = 1;
                 gb.ID = ly.out.D; gb.IH = ly.out.H; gb.IW = ly.out.W; gb.Ci = sp.cout;
                 gb.OD = ly.in.D; gb.OH = ly.in.H; gb.OW = ly.in.W; gb.Co = ly.in.C;
-                ALQ_TRY(gemm_build(b, NB, &ly.bwd, &gb));
+                ALQ_TRY(gemm_build(sw, b, NB, &ly.bwd, &gb));
                 ly.has_bwd = true;
             }
         } else if (sp.type == ALQ_POOL) {
@@ -834,14 +824,14 @@ static int build_model(alq_model *m, const alq_layer_t *specs, int n_layers) {
                 ALQ_TRY(m->dalloc(&ly.d_Wp, (size_t)sp.cout * ly.F));
                 ALQ_TRY(m->dalloc(&ly.fc_partials, (size_t)NB * ly.fc_slices * sp.cout));
                 if (sp.cout == 2 && ly.F % 1024 == 0 && i == n_layers - 1 && i > 0 && m->layers[i - 1].spec.relu && m->layers[i - 1].pidx > 0 &&
-                    m->layers[i - 1].spec.type == ALQ_CONV && m->layers[i - 1].out.C == 8 && !getenv("ALQ_NO_FC_BITS")) {
+                    m->layers[i - 1].spec.type == ALQ_CONV && m->layers[i - 1].out.C == 8 && !sw.no_fc_bits) {
                     ALQ_TRY(m->dalloc(&ly.fc_maskbits, (size_t)NB * (ly.F / 16)));      // one sign byte per 4 elements
                     ALQ_TRY(m->dalloc(&ly.fc_wv, (size_t)ly.F));
                     ALQ_TRY(m->dalloc(&ly.fc_wv16, (size_t)ly.F));
                     const Layer &cv = m->layers[i - 1];
                     const Igemm4Plan &fp = cv.fwd[0].p4;
                     if (sp.cout == 2 && !sp.relu && fp.ok && fp.NTW == 1 && !fp.multi && fp.a.pair && fp.a.PT == 1 && cv.out.cs == 8 &&
-                        cv.out.c0 == 0 && !cv.out.split && cv.osum && !cv.out_is_skip_src && !getenv("ALQ_NO_FC_FUSE") &&
+                        cv.out.c0 == 0 && !cv.out.split && cv.osum && !cv.out_is_skip_src && !sw.no_fc_fuse &&
                         // the backward pass must be able to work from the bits alone (bits_ok in run_backward)
                         cv.bwd.p4.ok && cv.bwd.p4.NTW == 1 && !cv.bwd.p4.multi && cv.bwd.p4.a.PT == 1 && !cv.dout.split) {
                         ly.fc_slices2 = fp.a.tpg * 4;
@@ -860,16 +850,16 @@ static int build_model(alq_model *m, const alq_layer_t *specs, int n_layers) {
                 d.MD = d.MH = d.MW = 1;
                 d.tz = {0}; d.ty = {0}; d.tx = {0};
                 ly.fwd.resize(1);
-                ALQ_TRY(gemm_build(d, NB, &ly.fwd[0]));
-                if (ly.fwd[0].pfc.ok && !getenv("ALQ_NO_FC_F16_FWD")) {      // forward launch of a wide fc layer on fp16 pairs (measured per-patch maxima)
+                ALQ_TRY(gemm_build(sw, d, NB, &ly.fwd[0]));
+                if (ly.fwd[0].pfc.ok && !sw.no_fc_f16_fwd) {      // forward launch of a wide fc layer on fp16 pairs (measured per-patch maxima)
                     ly.fwd[0].pfc_f16 = true;
                     ALQ_TRY(m->dalloc(&ly.fwd[0].fc_row_amax, (size_t)m->max_batch));
                 }
                 if (!first_param) {
                     ConvDesc b = d;
                     b.Ci = sp.cout; b.Co = (int)ly.F;
-                    ALQ_TRY(gemm_build(b, NB, &ly.bwd));
-                    ly.bwd.pfc_f16 = ly.bwd.pfc.ok && !getenv("ALQ_NO_FC_F16");      // backward launch: fp16 pairs under the static cotangent bound
+                    ALQ_TRY(gemm_build(sw, b, NB, &ly.bwd));
+                    ly.bwd.pfc_f16 = ly.bwd.pfc.ok && !sw.no_fc_f16;      // backward launch: fp16 pairs under the static cotangent bound
                     ly.has_bwd = true;
                 }
             }
@@ -907,6 +897,99 @@ static View flat_view(const View &v) {
     return f;
 }
 
+// [layer][max_batch] derived per-patch output bounds, allocated by the first pass that wants them
+static int ensure_bounds(alq_model *m) {
+    if (m->bound_all) return ALQ_OK;
+    const int nl = (int)m->layers.size();
+    ALQ_TRY(m->dalloc(&m->bound_all, (size_t)nl * m->max_batch));
+    for (int k = 0; k < nl; ++k) m->layers[k].bound_fwd = m->bound_all + (size_t)k * m->max_batch;
+    return ALQ_OK;
+}
+
+// per-(patch, tile) maxima of one launch: at least `len` per patch
+static int ensure_amax_tiles(alq_model *m, size_t len) {
+    if (len <= m->amax_tiles_len) return ALQ_OK;
+    ALQ_TRY(m->dalloc(&m->amax_tiles, (size_t)m->max_batch * len));
+    m->amax_tiles_len = len;
+    return ALQ_OK;
+}
+
+// every layer's out = in * L + B (and its second input, if any) for k_fwd_bounds
+static FwdBoundsArgs fwd_bounds_args(const alq_model *m) {
+    const int nl = (int)m->layers.size();
+    FwdBoundsArgs ba;
+    ba.nl = nl;
+    for (int k = 0; k < nl && k < 16; ++k) {
+        const Layer &lk = m->layers[k];
+        const bool par = lk.pidx >= 0 && lk.spec.type != ALQ_FC;
+        ba.L[k] = par ? lk.out_l1 : 1.f;
+        ba.B[k] = par ? lk.out_bmax : 0.f;
+        ba.src2[k] = lk.spec.skip_src;
+    }
+    return ba;
+}
+
+// ---- forward routes: "engine X runs layer i in this pass".  `prod` / `cons`: the layers that report / read per-patch input maxima
+// (run_forward); `fuse`: the launch's epilogue request as far as the pass has filled it, or null; `light`: a forward-only pass that keeps no activation
+
+// layer i = first conv, fused with the pool behind it (direct_conv_pool_launch)
+static bool dcp_applies(const alq_model *m, int i, const DropSpec *drop) {
+    if (i != 0 || m->layers.size() < 2) return false;
+    const Layer &ly = m->layers[0], &nx = m->layers[1];
+    const alq_layer_t &sp = ly.spec;
+    const View &in = ly.in;
+    return ly.spec.type == ALQ_CONV && nx.spec.type == ALQ_POOL && ly.fwd[0].pd.ok && ly.fwd[0].pd.d_W && in.C == 1 && in.cs == 1 &&
+           sp.cout == 8 && sp.k[0] == 3 && sp.k[1] == 3 && sp.k[2] == 3 && ly.lo[0] == 1 && ly.lo[1] == 1 && ly.lo[2] == 1 &&
+           nx.spec.k[0] == 2 && nx.spec.k[1] == 2 && nx.spec.k[2] == 2 && nx.lo[0] == 0 && nx.lo[1] == 0 && nx.lo[2] == 0 &&
+           in.D % 2 == 0 && in.H % 2 == 0 && in.W % 2 == 0 && nx.out.D * 2 == in.D && nx.out.H * 2 == in.H &&
+           nx.out.W * 2 == in.W && ((ly.out.cs | ly.out.c0 | nx.out.cs | nx.out.c0) & 3) == 0 && !g_dbg_knobs[KNOB_NO_CONV_POOL] &&
+           !(drop && (drop->on(0) || drop->on(1)));       // a dropped layer 0 output cannot share a kernel with the pool
+}
+
+// flip-safe head: only where the launch will contract with the fp16x2 split (input maxima known) and the
+// sign bits are wanted (Fisher pass); stride-1 conv on one dense tensor or a split concat of two
+static bool flipfix_applies(const alq_model *m, const Layer &ly, const Layer &nx, const View &in, const Igemm2Fuse &fz, bool with_sums) {
+    const alq_layer_t &sp = ly.spec;
+    return with_sums && fz.fc_bits && fz.in_amax && !g_no_f16x2 && !m->sw.no_flipfix && ly.d_W32 && ly.fwd_l1 > 0.f &&
+           sp.s[0] == 1 && sp.s[1] == 1 && sp.s[2] == 1 && in.c0 == 0 && nx.F % 64 == 0 &&      // (whole 16-byte words of sign bytes per patch)
+           ((in.split == 0 && in.cs == in.C) || (in.split > 0 && in.cs == in.split && in.C == 2 * in.split));
+}
+
+// the conv under the fused head on the plane-sweep engine (c3d.hip): where its geometry applies and both per-patch input maxima are known
+static bool c3d_fwd_applies(const alq_model *m, const Layer &ly, const Layer &nx, const Igemm2Fuse &fz) {
+    return ly.c3f.ok && ly.c3f.d_W && nx.c3_part && fz.in_amax && fz.in_amax2 && !g_no_f16x2 && !m->sw.no_c3d;
+}
+
+// the row-sweep engine (d3d.hip) where its geometry applies, both per-patch input bounds are known and nothing but the tensor,
+// its channel sums and its sign field is wanted
+// (round 6: forward-only passes too - the entropy filter over a pool is most of a query round - without sums / sign field)
+static bool d3d_fwd_applies(const alq_model *m, int i, const View &in, const Igemm2Fuse *fuse, const std::vector<char> &prod, bool with_sums,
+                            bool light, const DropSpec *drop) {
+    const Layer &ly = m->layers[i];
+    return fuse && ly.d3f.ok && ly.d3f.d_Whi && !m->sw.no_d3d && fuse->in_amax && fuse->in_amax2 && !prod[i] && !g_no_f16x2 && two_slot_allowed() &&
+           ((with_sums && fuse->osumA) || (light && !m->sw.no_light_kernels)) && in.split == 16 && !(drop && drop->on(i));
+}
+
+// enc2 + the pool behind it in one launch (f3d.hip): fp16 pairs under the first layer's measured maximum
+static bool f3d_fwd_applies(const alq_model *m, int i, const View &in, const Igemm2Fuse *fuse, const std::vector<char> &prod,
+                            const std::vector<char> &cons, bool with_sums, bool light, const DropSpec *drop) {
+    const Layer &ly = m->layers[i];
+    const Layer *nx = i + 1 < (int)m->layers.size() ? &m->layers[i + 1] : nullptr;
+    return fuse && ly.f3f.ok && ly.f3f.d_Whi && !m->sw.no_f3d && cons[i] == 2 && fuse->in_amax && !fuse->in_amax2 && !prod[i] && !g_no_f16x2 && two_slot_allowed() &&
+           ((with_sums && fuse->osumA) || (light && !m->sw.no_light_kernels)) && ly.spec.relu && in.split == 0 && !(drop && (drop->on(i) || drop->on(i + 1))) && nx && nx->spec.type == ALQ_POOL &&
+           nx->spec.k[0] == 2 && nx->spec.k[1] == 2 && nx->spec.k[2] == 2 && nx->lo[0] == 0 && nx->lo[1] == 0 && nx->lo[2] == 0 && nx->out.D == 8 && nx->out.H == 8 &&
+           nx->out.W == 8 && nx->out.C == 16 && nx->out.cs == 16 && nx->out.c0 == 0 && !nx->out.split && nx->argmax && !prod[i + 1];
+}
+
+// the row-sweep engine (t3d.hip): bf16 triples like the two-slot launch it replaces, nothing but the tensor, its channel
+// sums and its per-patch maximum to produce (no ReLU behind a conv_transpose of this geometry: no sign field)
+static bool t3d_fwd_applies(const alq_model *m, int i, const std::vector<char> &prod, const std::vector<char> &cons, bool with_sums,
+                            const DropSpec *drop) {
+    const Layer &ly = m->layers[i];
+    return ly.t3f.ok && ly.t3f.d_W && !m->sw.no_t3d && !g_dbg_knobs[KNOB_NO_FWD_FUSE] && two_slot_allowed() && !cons[i] && !ly.spec.relu &&
+           !(drop && drop->on(i)) && (!with_sums || ly.osum) && !(ly.t3f.kind == 8 && prod[i]);
+}
+
 // ------------------------------------------------------------------------------------------
 // keep_all (forward-only calls): every activation stays readable (a feature layer was asked for); otherwise the fc
 // head of a two-class net is fused into the last conv in forward-only calls too (no channel sums, no sign bytes)
@@ -916,35 +999,18 @@ static int run_forward(alq_model *m, const float *d_x, int N, bool with_sums, bo
     bool skip_next = false;      // this layer's outputs were produced by the previous layer's kernel
     bool fc_head_fused = false;  // the logits partials of the fc head came out of the previous conv's epilogue
     bool c3_head = false;        // ... of the plane-sweep engine: one partial per (patch, wave), the head's input sum likewise
-    m->last_head_fused = false;
-    m->last_c3 = false;
-    m->last_t3f = 0;
-    m->last_d3f = 0;
-    m->last_f3f = 0;
-    m->last_dcp = 0;
+    m->last.fwd = {};
     // A conv / conv_transpose launch contracts with the fp16x2 split if it knows max |x| per patch of (every part of)
     // its input ahead of time: the launches that produce those tensors report them (`prod`), the consumers (`cons`)
     // read one scale per tile.  Producers: the first conv + pool kernel and one-patch-per-tile igemm4 launches.
     const bool no16 = g_no_f16x2 != 0;
-    auto use_dcp = [&](int i) {      // layer i = first conv, fused with the pool behind it (direct_conv_pool_launch)
-        if (i != 0 || nl < 2) return false;
-        const Layer &ly = m->layers[0], &nx = m->layers[1];
-        const alq_layer_t &sp = ly.spec;
-        const View &in = ly.in;
-        return ly.spec.type == ALQ_CONV && nx.spec.type == ALQ_POOL && ly.fwd[0].pd.ok && ly.fwd[0].pd.d_W && in.C == 1 && in.cs == 1 &&
-               sp.cout == 8 && sp.k[0] == 3 && sp.k[1] == 3 && sp.k[2] == 3 && ly.lo[0] == 1 && ly.lo[1] == 1 && ly.lo[2] == 1 &&
-               nx.spec.k[0] == 2 && nx.spec.k[1] == 2 && nx.spec.k[2] == 2 && nx.lo[0] == 0 && nx.lo[1] == 0 && nx.lo[2] == 0 &&
-               in.D % 2 == 0 && in.H % 2 == 0 && in.W % 2 == 0 && nx.out.D * 2 == in.D && nx.out.H * 2 == in.H &&
-               nx.out.W * 2 == in.W && ((ly.out.cs | ly.out.c0 | nx.out.cs | nx.out.c0) & 3) == 0 && !g_dbg_knobs[7] &&
-               !(drop && (drop->on(0) || drop->on(1)));       // a dropped layer 0 output cannot share a kernel with the pool
-    };
     std::vector<char> prod(nl, 0), cons(nl, 0);
     const bool light = !with_sums && !keep_all;       // forward-only: fuse objects only for the launches of the fused head
-    if ((with_sums || light) && !no16 && !g_dbg_knobs[3] && !g_dbg_knobs[4] && !g_dbg_knobs[5]) {
+    if ((with_sums || light) && !no16 && !g_dbg_knobs[KNOB_NO_FWD_FUSE] && two_slot_allowed()) {
         auto prod_ok = [&](int p) {
             if (p < 0) return false;
             const Layer &l = m->layers[p];
-            if (p == 0 && use_dcp(0)) return true;
+            if (p == 0 && dcp_applies(m, 0, drop)) return true;
             if (!l.osum) return false;
             if (l.spec.type == ALQ_CONV) return l.fwd[0].p4.ok && !l.fwd[0].pd.ok && !l.fwd[0].pfc.ok && l.fwd[0].p4.a.PT == 1;
             if (l.spec.type == ALQ_CONVT) return l.fwd_all.ok && l.fwd_all.a.PT == 1;
@@ -969,17 +1035,17 @@ static int run_forward(alq_model *m, const float *d_x, int N, bool with_sums, bo
             // 1148 -> 875 us; on a 2000-patch batch against the exact-fp32 engine 129 patches with a flipped fragile unit instead
             // of 115 (bf16x3 everywhere: 109; each engine has its own set against fp64).  Default since round 5 (the round-4
             // verdict: a faster, equally accurate path is not withheld for an accounting ratio); ALQ_NO_F16_DERIVED=1 is the A/B arm.
-            if (m->f16_fwd_mask < 0 && !m->no_f16_derived && nl <= 16 && ((m->f16_fwd_derived >> j) & 1) && l.spec.type == ALQ_CONV && use_dcp(0) &&
+            if (m->sw.f16_fwd_mask < 0 && !m->sw.no_f16_derived && nl <= 16 && ((m->f16_fwd_derived >> j) & 1) && l.spec.type == ALQ_CONV && dcp_applies(m, 0, drop) &&
                 (s_ >= 0) == (l.in.split != 0) && !(drop && drop->layers)) {
                 cons[j] = 2;
                 prod[0] = 1;
                 continue;
             }
-            if (!(j == nl - 2 && m->layers[nl - 1].fc_part2 && l.spec.type == ALQ_CONV) && m->f16_fwd_mask < 0) continue;
+            if (!(j == nl - 2 && m->layers[nl - 1].fc_part2 && l.spec.type == ALQ_CONV) && m->sw.f16_fwd_mask < 0) continue;
             if (l.spec.type == ALQ_CONVT && !pl->fic) continue;                 // MULTI has no F16 variant
             if (!prod_ok(j - 1) || (s_ >= 0 && !prod_ok(s_))) continue;
             if ((s_ >= 0) != (l.in.split != 0)) continue;                       // two parts <-> a split view
-            if (m->f16_fwd_mask >= 0 && !((m->f16_fwd_mask >> j) & 1)) continue;      // diagnostics: consumers by layer bit
+            if (m->sw.f16_fwd_mask >= 0 && !((m->sw.f16_fwd_mask >> j) & 1)) continue;      // diagnostics: consumers by layer bit
             cons[j] = 1; prod[j - 1] = 1;
             if (s_ >= 0) prod[s_] = 1;
         }
@@ -987,41 +1053,27 @@ static int run_forward(alq_model *m, const float *d_x, int N, bool with_sums, bo
             if (!prod[p]) continue;
             Layer &l = m->layers[p];
             if (!l.amax_fwd) ALQ_TRY(m->dalloc(&l.amax_fwd, (size_t)m->max_batch));
-            if (l.spec.type == ALQ_CONV && !(p == 0 && use_dcp(0))) need = std::max(need, (size_t)l.fwd[0].p4.a.tpg * 4);
+            if (l.spec.type == ALQ_CONV && !(p == 0 && dcp_applies(m, 0, drop))) need = std::max(need, (size_t)l.fwd[0].p4.a.tpg * 4);
             if (l.spec.type == ALQ_CONVT) need = std::max(need, (size_t)l.fwd_all.a.tpg * (l.fwd_all.multi ? l.fwd_all.a.ngr : 1) * 4);
             if (l.spec.type == ALQ_CONVT && l.t3f.ok) need = std::max(need, (size_t)16);      // row-sweep engine: one maximum per input plane
         }
-        if (need > m->amax_tiles_len) { ALQ_TRY(m->dalloc(&m->amax_tiles, (size_t)m->max_batch * need)); m->amax_tiles_len = need; }
+        ALQ_TRY(ensure_amax_tiles(m, need));
     }
     bool any_derived = false;
     for (int j = 0; j < nl; ++j) any_derived = any_derived || cons[j] == 2;
-    m->last_f16_derived = any_derived;
-    if (any_derived && !m->bound_all) {
-        ALQ_TRY(m->dalloc(&m->bound_all, (size_t)nl * m->max_batch));
-        for (int k = 0; k < nl; ++k) m->layers[k].bound_fwd = m->bound_all + (size_t)k * m->max_batch;
-    }
+    m->last.fwd.f16_derived = any_derived;
+    if (any_derived) ALQ_TRY(ensure_bounds(m));
     // Forward launches that stay on igemm3 (no two-slot plan: NET-B's conv1 .. conv3) on fp16 pairs, one scale per patch: the
     // measured maximum of every patch of the network input, pushed through the layers' L1 norms, bounds every layer's input.
     // Fisher passes and forward-only passes; not the passes that keep every activation for training, not under dropout.
-    const bool v3f16 = m->v3_fwd_f16 && (with_sums || light) && !no16 && !drop && !any_derived && !use_dcp(0) && nl <= 16 &&
-                       !g_dbg_knobs[3] && !g_dbg_knobs[4] && !g_dbg_knobs[5] && m->layers[0].in.split == 0 && m->layers[0].in.cs == m->layers[0].in.C;
+    const bool v3f16 = m->v3_fwd_f16 && (with_sums || light) && !no16 && !drop && !any_derived && !dcp_applies(m, 0, drop) && nl <= 16 &&
+                       !g_dbg_knobs[KNOB_NO_FWD_FUSE] && two_slot_allowed() && m->layers[0].in.split == 0 && m->layers[0].in.cs == m->layers[0].in.C;
     if (v3f16) {
         if (!m->in_amax) ALQ_TRY(m->dalloc(&m->in_amax, (size_t)m->max_batch));
-        if (!m->bound_all) {
-            ALQ_TRY(m->dalloc(&m->bound_all, (size_t)nl * m->max_batch));
-            for (int k = 0; k < nl; ++k) m->layers[k].bound_fwd = m->bound_all + (size_t)k * m->max_batch;
-        }
+        ALQ_TRY(ensure_bounds(m));
         ALQ_TRY(k_rowmax_abs(ctx, d_x, N, (long long)m->layers[0].in.vox() * m->layers[0].in.C, m->in_amax));
-        FwdBoundsArgs ba;
-        ba.nl = nl;
+        FwdBoundsArgs ba = fwd_bounds_args(m);
         ba.from_input = 1;
-        for (int k = 0; k < nl && k < 16; ++k) {
-            const Layer &lk = m->layers[k];
-            const bool par = lk.pidx >= 0 && lk.spec.type != ALQ_FC;
-            ba.L[k] = par ? lk.out_l1 : 1.f;
-            ba.B[k] = par ? lk.out_bmax : 0.f;
-            ba.src2[k] = lk.spec.skip_src;
-        }
         ALQ_TRY(k_fwd_bounds(ctx, m->in_amax, N, m->max_batch, ba, m->bound_all));
     }
     auto take_amax = [&](Igemm2Fuse &fz, int j) {      // the input maxima of consumer j
@@ -1036,9 +1088,6 @@ static int run_forward(alq_model *m, const float *d_x, int N, bool with_sums, bo
     for (Layer &l : m->layers) l.signs_ready = false;
     // Sign fields (View::sg): in a Fisher pass a forward launch of the two-slot engine also writes one byte per 4 channels
     // with the signs of its ReLU'd output; the backward launches read those instead of the fp32 activations (1/16 of the bytes)
-    auto v4_fwd = [&](const Gemm &g, const View &in, const View &out) {      // gemm_launch's choice for a forward launch with sums
-        return !g.pd.ok && g.p4.ok && ((!g_dbg_knobs[4] && !g_dbg_knobs[5]) || in.split != 0 || out.split != 0);
-    };
     for (int i = 0; i < nl; ++i) {
         Layer &ly = m->layers[i];
         ALQ_REQUIRE(ly.pidx < 0 || ly.weights_set, ALQ_EINVAL, "weights of parameterised layer %d not set", ly.pidx);
@@ -1051,50 +1100,36 @@ static int run_forward(alq_model *m, const float *d_x, int N, bool with_sums, bo
         fz.osumA = with_sums ? ly.osum : nullptr;
         const bool head_conv = i + 2 == nl && m->layers[nl - 1].fc_part2 && ly.spec.type == ALQ_CONV;
         const bool light_here = light && (prod[i] || cons[i] || head_conv);
-        const Igemm2Fuse *fuse = ((with_sums || light_here) && ly.osum && !g_dbg_knobs[3]) ? &fz : nullptr;
+        const Igemm2Fuse *fuse = ((with_sums || light_here) && ly.osum && !g_dbg_knobs[KNOB_NO_FWD_FUSE]) ? &fz : nullptr;
         bool fused = false;
         switch (ly.spec.type) {
             case ALQ_CONV: {
                 // first conv + the pool behind it in one kernel (one input channel, 3x3x3 -> 8, 2x2x2 windows)
                 Layer *nx = i + 1 < nl ? &m->layers[i + 1] : nullptr;
                 const alq_layer_t &sp = ly.spec;
-                if (use_dcp(i)) {
+                if (dcp_applies(m, i, drop)) {
                     if (prod[i]) ALQ_HIP(hipMemsetAsync(ly.amax_fwd, 0, (size_t)N * sizeof(unsigned), ctx->stream));
                     // (the sign field of the full-resolution output: what the last conv's backward launch reads as its ReLU mask)
-                    const bool sg_here = with_sums && !m->no_signs && !m->no_signs0 && sp.relu && ly.out.sg != nullptr;
+                    const bool sg_here = with_sums && !m->sw.no_signs && !m->sw.no_signs0 && sp.relu && ly.out.sg != nullptr;
                     ALQ_TRY(direct_conv_pool_launch(ctx, ly.fwd[0].pd.d_W, in, ly.out, nx->out, ly.d_bias, sp.relu, nx->argmax,
                                                     with_sums ? ly.osum : nullptr, with_sums ? nx->osum : nullptr, N,
                                                     ly.fwd[0].pd.flops_per_patch, prod[i] ? ly.amax_fwd : nullptr,
                                                     sg_here ? ly.out.sg : nullptr, (sg_here && nx->out.sg) ? nx->out.sg : nullptr));
-                    m->last_dcp = g_dcp_last_form;
+                    m->last.fwd.dcp = g_dcp_last_form;
                     ly.signs_ready = sg_here;
                     nx->signs_ready = sg_here && nx->out.sg != nullptr;      // (the pool's output: sign of the window maximum)
-                    if (any_derived) {      // per-patch bounds on every later layer's output from this layer's measured maximum
-                        FwdBoundsArgs ba;
-                        ba.nl = nl;
-                        for (int k = 0; k < nl && k < 16; ++k) {
-                            const Layer &lk = m->layers[k];
-                            const bool par = lk.pidx >= 0 && lk.spec.type != ALQ_FC;
-                            ba.L[k] = par ? lk.out_l1 : 1.f;
-                            ba.B[k] = par ? lk.out_bmax : 0.f;
-                            ba.src2[k] = lk.spec.skip_src;
-                        }
-                        ALQ_TRY(k_fwd_bounds(ctx, ly.amax_fwd, N, m->max_batch, ba, m->bound_all));
-                    }
+                    if (any_derived)      // per-patch bounds on every later layer's output from this layer's measured maximum
+                        ALQ_TRY(k_fwd_bounds(ctx, ly.amax_fwd, N, m->max_batch, fwd_bounds_args(m), m->bound_all));
                     fused = true;
                     skip_next = true;
                     break;
                 }
-                if (fuse && nx && i + 2 == nl && nx->fc_part2 && !g_dbg_knobs[4] && !g_dbg_knobs[5]) {
+                if (fuse && nx && i + 2 == nl && nx->fc_part2 && two_slot_allowed()) {
                     // the fc head is this layer's only consumer in a Fisher pass: logits partials + sign bytes from the
                     // epilogue, the tensor itself is not stored
                     fz.fc_W = nx->fc_wv; fz.fc_F = nx->F; fz.fc_part = nx->fc_part2; fz.fc_bits = with_sums ? nx->fc_maskbits : nullptr;
                     take_amax(fz, i);
-                    // flip-safe head: only where the launch will contract with the fp16x2 split (input maxima known) and the
-                    // sign bits are wanted (Fisher pass); stride-1 conv on one dense tensor or a split concat of two
-                    const bool flipfix = with_sums && fz.fc_bits && fz.in_amax && !g_no_f16x2 && !m->no_flipfix && ly.d_W32 && ly.fwd_l1 > 0.f &&
-                                         sp.s[0] == 1 && sp.s[1] == 1 && sp.s[2] == 1 && in.c0 == 0 && nx->F % 64 == 0 &&      // (whole 16-byte words of sign bytes per patch)
-                                         ((in.split == 0 && in.cs == in.C) || (in.split > 0 && in.cs == in.split && in.C == 2 * in.split));
+                    const bool flipfix = flipfix_applies(m, ly, *nx, in, fz, with_sums);
                     if (flipfix) {
                         if (!m->flip_list) {
                             m->flip_cap = flip_list_len(m->max_batch);      // kernels.hip: per-patch segments of FLIP_PER_BLOCK slots
@@ -1105,8 +1140,7 @@ static int run_forward(alq_model *m, const float *d_x, int N, bool with_sums, bo
                         }
                         fz.flip_cnt = m->flip_cnt; fz.flip_list = m->flip_list; fz.flip_cap = m->flip_cap; fz.flip_l1 = ly.fwd_l1; fz.flip_bias_nonzero = ly.out_bmax > 0.f;
                     }
-                    // the plane-sweep engine (c3d.hip) where its geometry applies and both per-patch input maxima are known
-                    c3_head = ly.c3f.ok && ly.c3f.d_W && nx->c3_part && fz.in_amax && fz.in_amax2 && !g_no_f16x2 && !m->no_c3d;
+                    c3_head = c3d_fwd_applies(m, ly, *nx, fz);
                     if (c3_head)
                         ALQ_TRY(c3d_fwd_launch(ctx, ly.c3f, in, ly.d_bias, N, fz.in_amax, fz.in_amax2, nx->fc_wv, nx->c3_part,
                                                with_sums ? nx->c3_asum : nullptr, reinterpret_cast<unsigned char *>(fz.fc_bits),
@@ -1120,46 +1154,38 @@ static int run_forward(alq_model *m, const float *d_x, int N, bool with_sums, bo
                                            reinterpret_cast<unsigned char *>(nx->fc_maskbits), nx->F, m->flip_overflow));
                     fused = true;
                     fc_head_fused = true;
-                    m->last_head_fused = true;
-                    m->last_c3 = c3_head;
+                    m->last.fwd.head_fused = true;
+                    m->last.fwd.c3 = c3_head;
                     break;
                 }
                 if (fuse) take_amax(fz, i);
-                // the row-sweep engine (d3d.hip) where its geometry applies, both per-patch input bounds are known and nothing but the tensor,
-                // its channel sums and its sign field is wanted
-                // (round 6: forward-only passes too - the entropy filter over a pool is most of a query round - without sums / sign field)
-                if (fuse && ly.d3f.ok && ly.d3f.d_Whi && !m->no_d3d && fz.in_amax && fz.in_amax2 && !prod[i] && !g_no_f16x2 && !g_dbg_knobs[4] && !g_dbg_knobs[5] &&
-                    ((with_sums && fz.osumA) || (light && !m->no_light_kernels)) && in.split == 16 && !(drop && drop->on(i))) {
-                    const bool sgd = with_sums && !m->no_signs && ly.spec.relu && ly.out.sg;
+                if (d3d_fwd_applies(m, i, in, fuse, prod, with_sums, light, drop)) {
+                    const bool sgd = with_sums && !m->sw.no_signs && ly.spec.relu && ly.out.sg;
                     ALQ_TRY(d3d_fwd_launch(ctx, ly.d3f, N, in.p, in.p + in.delta, fz.in_amax, fz.in_amax2, ly.d_bias, ly.spec.relu ? 1 : 0, ly.out.p,
                                            sgd ? ly.out.sg : nullptr, fz.osumA));
                     ly.signs_ready = sgd;
                     fused = true;
-                    m->last_d3f = 1;
+                    m->last.fwd.d3f = 1;
                     break;
                 }
-                // enc2 + the pool behind it in one launch (f3d.hip): fp16 pairs under the first layer's measured maximum
-                if (fuse && ly.f3f.ok && ly.f3f.d_Whi && !m->no_f3d && cons[i] == 2 && fz.in_amax && !fz.in_amax2 && !prod[i] && !g_no_f16x2 && !g_dbg_knobs[4] && !g_dbg_knobs[5] &&
-                    ((with_sums && fz.osumA) || (light && !m->no_light_kernels)) && sp.relu && in.split == 0 && !(drop && (drop->on(i) || drop->on(i + 1))) && nx && nx->spec.type == ALQ_POOL &&
-                    nx->spec.k[0] == 2 && nx->spec.k[1] == 2 && nx->spec.k[2] == 2 && nx->lo[0] == 0 && nx->lo[1] == 0 && nx->lo[2] == 0 && nx->out.D == 8 && nx->out.H == 8 &&
-                    nx->out.W == 8 && nx->out.C == 16 && nx->out.cs == 16 && nx->out.c0 == 0 && !nx->out.split && nx->argmax && !prod[i + 1]) {
-                    const bool sgd = with_sums && !m->no_signs && ly.out.sg;
+                if (f3d_fwd_applies(m, i, in, fuse, prod, cons, with_sums, light, drop)) {
+                    const bool sgd = with_sums && !m->sw.no_signs && ly.out.sg;
                     ALQ_TRY(f3d_fwd_launch(ctx, ly.f3f, N, in.p, fz.in_amax, ly.d_bias, ly.out.p, sgd ? ly.out.sg : nullptr, fz.osumA, nx->out.p, nx->argmax,
                                            with_sums ? nx->osum : nullptr));
                     ly.signs_ready = sgd;
                     nx->signs_ready = false;
                     fused = true;
                     skip_next = true;
-                    m->last_f3f = 1;
+                    m->last.fwd.f3f = 1;
                     break;
                 }
                 if (fuse && prod[i]) fz.out_amax = m->amax_tiles;
-                if (!ly.fwd_co.empty() && !prod[i] && !cons[i] && !g_dbg_knobs[4] && !g_dbg_knobs[5]) {
+                if (!ly.fwd_co.empty() && !prod[i] && !cons[i] && two_slot_allowed()) {
                     // a wide conv as launches over slices of its output channels (no epilogue fusion: channel sums and ReLU masks the plain way)
                     // (round 6) with per-patch bounds on the input at hand (v3f16: igemm3's forward launches above this layer asked for
                     // them) the slices take the two-slot engine's fp16-pair form too: one scale per patch, three products
                     Igemm2Fuse sz;
-                    const bool s16 = v3f16 && i >= 1 && in.split == 0 && ly.spec.skip_src < 0 && !getenv("ALQ_NO_CO_SPLIT_F16");
+                    const bool s16 = v3f16 && i >= 1 && in.split == 0 && ly.spec.skip_src < 0 && !m->sw.no_co_split_f16;
                     if (s16) sz.in_amax = m->layers[i - 1].bound_fwd;
                     for (size_t j = 0; j < ly.fwd_co.size(); ++j) {
                         View oj = ly.out;
@@ -1172,7 +1198,7 @@ static int run_forward(alq_model *m, const float *d_x, int N, bool with_sums, bo
                     ly.signs_ready = false;
                     break;
                 }
-                const bool sg_here = with_sums && fuse && !m->no_signs && ly.spec.relu && ly.out.sg && v4_fwd(ly.fwd[0], in, ly.out);
+                const bool sg_here = with_sums && fuse && !m->sw.no_signs && ly.spec.relu && ly.out.sg && gemm_route(ly.fwd[0], in, ly.out, 0, fuse) == ROUTE_IGEMM4;
                 if (sg_here) fz.sign_out = ly.out.sg;
                 {
                     // igemm3's fp16-pair instantiation for a forward launch without a two-slot plan (NET-B's conv1 .. conv3): one scale per
@@ -1195,23 +1221,20 @@ static int run_forward(alq_model *m, const float *d_x, int N, bool with_sums, bo
                 break;
             }
             case ALQ_CONVT: {
-                // the row-sweep engine (t3d.hip): bf16 triples like the two-slot launch it replaces, nothing but the tensor, its channel
-                // sums and its per-patch maximum to produce (no ReLU behind a conv_transpose of this geometry: no sign field)
-                if (ly.t3f.ok && ly.t3f.d_W && !m->no_t3d && !g_dbg_knobs[3] && !g_dbg_knobs[4] && !g_dbg_knobs[5] && !cons[i] && !ly.spec.relu &&
-                    !(drop && drop->on(i)) && (!with_sums || ly.osum) && !(ly.t3f.kind == 8 && prod[i])) {
+                if (t3d_fwd_applies(m, i, prod, cons, with_sums, drop)) {
                     const bool want_amax = prod[i] != 0;
                     ALQ_TRY(t3d_fwd_launch(ctx, ly.t3f, in, ly.out, ly.d_bias, N, with_sums ? ly.osum : nullptr, want_amax ? m->amax_tiles : nullptr));
                     if (want_amax) ALQ_TRY(k_rowmax_u32(ctx, m->amax_tiles, 16, N, ly.amax_fwd));
                     ly.signs_ready = false;
                     fused = true;
-                    m->last_t3f += 1;
+                    m->last.fwd.t3f += 1;
                     break;
                 }
-                if (ly.fwd_all.ok && !g_dbg_knobs[4] && !g_dbg_knobs[5]) {
+                if (ly.fwd_all.ok && two_slot_allowed()) {
                     const bool want_amax = fuse && prod[i];
                     if (fuse) take_amax(fz, i);
                     if (want_amax) fz.out_amax = m->amax_tiles;
-                    const bool sg_here = with_sums && fuse && !m->no_signs && ly.spec.relu && ly.out.sg;
+                    const bool sg_here = with_sums && fuse && !m->sw.no_signs && ly.spec.relu && ly.out.sg;
                     if (sg_here) fz.sign_out = ly.out.sg;
                     ALQ_TRY(igemm4_launch(ctx, ly.fwd_all, in, ly.out, ly.d_bias, ly.spec.relu, 0, N, PROF_IGEMM3_FWD, fuse));
                     ly.signs_ready = sg_here;
@@ -1240,10 +1263,8 @@ static int run_forward(alq_model *m, const float *d_x, int N, bool with_sums, bo
                     else if (prev_spatial) ALQ_TRY(k_rowsum_field(ctx, m->layers[i - 1].osum, m->layers[i - 1].out.vox(), N, ly.asum));
                     else ALQ_TRY(k_chansum(ctx, flat_view(in), ly.asum, N));
                 }
-                if (ly.dense_fc_small && fc_head_fused && c3_head) {
-                    ALQ_TRY(k_fc_small_finish_diff(ctx, ly.c3_part, 4, ly.d_bias, N, ly.out.p));
-                } else if (ly.dense_fc_small && fc_head_fused) {
-                    ALQ_TRY(k_fc_small_finish_diff(ctx, ly.fc_part2, ly.fc_slices2, ly.d_bias, N, ly.out.p));
+                if (ly.dense_fc_small && fc_head_fused) {      // the plane-sweep engine leaves one partial per (patch, wave)
+                    ALQ_TRY(k_fc_small_finish_diff(ctx, c3_head ? ly.c3_part : ly.fc_part2, c3_head ? 4 : ly.fc_slices2, ly.d_bias, N, ly.out.p));
                 } else if (ly.dense_fc_small) {
                     ALQ_TRY(k_fc_small_fwd(ctx, in.p, ly.F, ly.d_Wp, ly.spec.cout, N, ly.fc_partials, ly.fc_slices,
                                            with_sums ? ly.fc_maskbits : nullptr));
@@ -1296,6 +1317,71 @@ static int side_join(alq_ctx *c) {
     return ALQ_OK;
 }
 
+// ---- backward routes of a Fisher pass.  `fuse`: the launch's epilogue request (null when nothing below wants one); `acc`: the launch
+// accumulates into a slice the skip destination wrote; `hand`: it hands per-patch maxima of what it stores to the launch below
+
+// a pool whose producer is the first parameterised layer: 2x2(x2) windows tiling the input exactly
+static bool pool_first_ok(const Layer &pl, const Layer &src) {
+    return pl.spec.type == ALQ_POOL && src.pidx == 0 && src.spec.type != ALQ_FC && pl.spec.k[1] == 2 && pl.spec.k[2] == 2 &&
+           (pl.spec.k[0] == 1 || pl.spec.k[0] == 2) && pl.lo[0] == 0 && pl.lo[1] == 0 && pl.lo[2] == 0 &&
+           src.out.D == pl.out.D * pl.spec.k[0] && src.out.H == pl.out.H * 2 && src.out.W == pl.out.W * 2 &&
+           (pl.out.C == 4 || pl.out.C == 8 || pl.out.C == 16) && ((pl.dout.cs | pl.dout.c0 | pl.out.cs | pl.out.c0) & 3) == 0 &&
+           src.spec.relu && !g_dbg_knobs[KNOB_NO_POOL_FIRST];
+}
+
+// [pool (i)] <- [ReLU conv (i - 1), a skip source whose consumer wrote its cotangent] <- [pool (i - 2)] <- [first conv (i - 3)]: one
+// launch produces both channel-sum fields (e3d.hip); the conv's own box-filter dot product runs as usual when the loop gets there
+static bool e3d_bwd_applies(const alq_model *m, int i, bool prev_is_src) {
+    const Layer &ly = m->layers[i];
+    if (!(ly.spec.type == ALQ_POOL && i >= 3 && !m->sw.no_e3d && two_slot_allowed() && !g_no_f16x2 && !m->sw.no_bound16 && !m->sw.no_signs &&
+          !g_dbg_knobs[KNOB_NO_BWD_FUSE] && !g_dbg_knobs[KNOB_NO_POOL_FIRST]))
+        return false;
+    const Layer &cv = m->layers[i - 1], &p1 = m->layers[i - 2], &c0 = m->layers[i - 3];
+    return cv.spec.type == ALQ_CONV && cv.e3b.ok && cv.e3b.d_Whi && cv.spec.relu && cv.signs_ready && cv.out.sg && prev_is_src &&
+           p1.spec.type == ALQ_POOL && pool_first_ok(p1, c0) && c0.dsum_partial && p1.signs_ready && p1.out.sg && p1.spec.k[0] == 2 &&
+           ly.spec.k[0] == 2 && ly.spec.k[1] == 2 && ly.spec.k[2] == 2 && ly.lo[0] == 0 && ly.lo[1] == 0 && ly.lo[2] == 0 &&
+           ly.dout.D == 8 && ly.dout.H == 8 && ly.dout.W == 8 && ly.dout.C == 16 && ly.dout.cs == 16 && ly.dout.c0 == 0 && !ly.dout.split &&
+           cv.dout.cs == 16 && cv.dout.c0 == 0 && !cv.dout.split && cv.out.cs == 16 && cv.out.c0 == 0 && p1.out.cs == 8 && p1.out.c0 == 0 &&
+           p1.out.C == 8 && c0.out.D == 32 && cv.dout_bound > 0.f && cv.dsum && c0.dsum;
+}
+
+// the two-class head (layer i) over a ReLU conv: every patch has the same head cotangent (the unit cotangent), so nothing of
+// the size of the conv's output is written; the conv's backward contraction reads [sign] * wv (wv = W0 - W1, set with the weights)
+static bool head_bits_apply(const alq_model *m, int i, bool prev_param, bool prev_is_src) {
+    const Layer &ly = m->layers[i];
+    const Layer *prev = i > 0 ? &m->layers[i - 1] : nullptr;
+    return ly.dense_fc_small && ly.fc_maskbits && prev_param && prev->out.cs == prev->out.C &&
+           prev->out.c0 == 0 && two_slot_allowed() && prev->bwd.p4.ok && prev->bwd.p4.NTW == 1 && !prev->bwd.p4.multi &&
+           prev->bwd.p4.a.PT == 1 && !prev->dout.split && !prev_is_src &&
+           // ... and that launch must not accumulate (a skip source right below the conv): the
+           // accumulating instantiations of the engine are the plain ones
+           !(i >= 2 && m->layers[i - 2].out_is_skip_src && prev->spec.skip_src < 0);
+}
+
+// the head conv's backward on the plane-sweep engine (c3d.hip): the NET-C pattern - channels 0..7 = the skip source (first conv,
+// ReLU: masked by its sign field and only summed), channels 8..15 = a layer without ReLU (stored and summed)
+static bool c3d_bwd_applies(const alq_model *m, const Layer &ly, const unsigned short *vec16c, const Igemm2Fuse *fuse, int acc) {
+    return ly.c3b.ok && ly.c3b.d_W && vec16c && !m->sw.no_c3d && !g_no_f16x2 && fuse && !acc && fuse->in_vec_amax > 0.f &&
+           fuse->split == 8 && fuse->store_from == 8 && fuse->mask_bits && fuse->mask_from == 0 && fuse->mask_to == 8 && fuse->osumA && fuse->osumB &&
+           ly.din.split == 8 && ly.din.cs == 8 && ly.din.C == 16;
+}
+
+// the row-sweep engine (t3d.hip) for the backward-data pass of a stride-2 conv_transpose: fp16 pairs under the static
+// bound like the two-slot launch it replaces; the producer below is a ReLU conv whose sign field masks the result
+static bool t3d_bwd_applies(const alq_model *m, const Layer &ly, const Igemm2Fuse *fuse, int acc, bool hand, bool prev_param) {
+    return ly.spec.type == ALQ_CONVT && ly.t3b.ok && ly.t3b.d_W && !m->sw.no_t3d && two_slot_allowed() && !g_no_f16x2 && !acc && fuse && !hand &&
+           fuse->in_bound > 0.f && !fuse->in_amax && fuse->split == 0 && fuse->store_from == 0 && fuse->osumA && !fuse->osumB && fuse->mask_from == 0 &&
+           (!fuse->mask || fuse->mask_bits) && !ly.dout.split && !ly.din.split && prev_param;
+}
+
+// the plane-sweep kernel of d3d.hip for the backward-data pass of the conv over a split concat (NET-C's dec1): fp16 pairs under the static
+// bound like the two-slot launch it replaces; channels [0, 16) = the skip source's cotangent (stored), [16, 32) = the producer's (stored + summed)
+static bool d3d_bwd_applies(const alq_model *m, const Layer &ly, const Igemm2Fuse *fuse, int acc, bool hand) {
+    return ly.spec.type == ALQ_CONV && ly.d3f.ok && ly.d3f.d_Bhi && !m->sw.no_d3d && !m->sw.no_d3b && two_slot_allowed() && !g_no_f16x2 && !acc && fuse && !hand &&
+           fuse->in_bound > 0.f && !fuse->in_amax && fuse->split == 16 && fuse->store_from == 0 && !fuse->mask && !fuse->osumA && fuse->osumB &&
+           !ly.dout.split && ly.dout.cs == 16 && ly.dout.c0 == 0 && ly.din.split == 16 && ly.din.cs == 16 && ly.din.c0 == 0 && ly.din.C == 32;
+}
+
 static int run_backward_main(alq_model *m, const float *d_x, int N);
 static int run_backward(alq_model *m, const float *d_x, int N) {
     const int rc = run_backward_main(m, d_x, N);
@@ -1309,9 +1395,7 @@ static int run_backward_main(alq_model *m, const float *d_x, int N) {
     ALQ_REQUIRE(m->nclass == 2, ALQ_EUNSUPPORTED, "Fisher scoring is binary (PW_NNAL.py:766), got %d classes", m->nclass);
     ALQ_TRY(k_fill_unit_cotangent(ctx, m->dlogits, N));
     for (Layer &l : m->layers) { l.delta_ready = false; l.dsum_partial = false; l.dout_bits = nullptr; l.dout_vec = nullptr; l.dout_vec16 = nullptr; l.dout_vec16c = nullptr; l.dout_amax = nullptr; }
-    m->last_c3_bwd = false;
-    m->last_t3b = 0;
-    const bool v4_on = !g_dbg_knobs[4] && !g_dbg_knobs[5];
+    m->last.bwd = {};
     {   // bounds on every layer's output cotangent under the unit cotangent (+1, -1): |d out| of the head = 1; a two-class
         // head hands max |W0 - W1| down, a conv / conv_transpose its L1 bound, a pool passes the bound on, a ReLU mask
         // cannot raise it; a tensor with several consumers (skip source) collects the sum.  One fp16x2 scale per LAUNCH
@@ -1330,40 +1414,19 @@ static int run_backward_main(alq_model *m, const float *d_x, int N) {
             if (ly.spec.skip_src >= 0) add(m->layers[ly.spec.skip_src]);
         }
     }
-    // a pool whose producer is the first parameterised layer: 2x2(x2) windows tiling the input exactly
-    auto pool_first_ok = [&](const Layer &pl, const Layer &src) {
-        return pl.spec.type == ALQ_POOL && src.pidx == 0 && src.spec.type != ALQ_FC && pl.spec.k[1] == 2 && pl.spec.k[2] == 2 &&
-               (pl.spec.k[0] == 1 || pl.spec.k[0] == 2) && pl.lo[0] == 0 && pl.lo[1] == 0 && pl.lo[2] == 0 &&
-               src.out.D == pl.out.D * pl.spec.k[0] && src.out.H == pl.out.H * 2 && src.out.W == pl.out.W * 2 &&
-               (pl.out.C == 4 || pl.out.C == 8 || pl.out.C == 16) && ((pl.dout.cs | pl.dout.c0 | pl.out.cs | pl.out.c0) & 3) == 0 &&
-               src.spec.relu && !g_dbg_knobs[6];
-    };
     int e3_conv = -1;      // the conv whose backward ran fused with the pool backward steps around it (e3d.hip), or -1
-    m->last_e3b = 0;
-    m->last_e3b_form = 0;
-    m->last_d3b = 0;
     for (int i = nl - 1; i >= 0; --i) {
         Layer &ly = m->layers[i];
         const bool prev_is_src = (i > 0 && m->layers[i - 1].out_is_skip_src && ly.spec.skip_src < 0);
-        // [pool (i)] <- [ReLU conv (i - 1), a skip source whose consumer wrote its cotangent] <- [pool (i - 2)] <- [first conv (i - 3)]: one
-        // launch produces both channel-sum fields (e3d.hip); the conv's own box-filter dot product runs as usual when the loop gets there
-        if (ly.spec.type == ALQ_POOL && i >= 3 && !m->no_e3d && v4_on && !g_no_f16x2 && !m->no_bound16 && !m->no_signs && !g_dbg_knobs[2] && !g_dbg_knobs[6]) {
+        if (e3d_bwd_applies(m, i, prev_is_src)) {
             Layer &cv = m->layers[i - 1], &p1 = m->layers[i - 2], &c0 = m->layers[i - 3];
-            const bool geo = cv.spec.type == ALQ_CONV && cv.e3b.ok && cv.e3b.d_Whi && cv.spec.relu && cv.signs_ready && cv.out.sg && prev_is_src &&
-                             p1.spec.type == ALQ_POOL && pool_first_ok(p1, c0) && c0.dsum_partial && p1.signs_ready && p1.out.sg && p1.spec.k[0] == 2 &&
-                             ly.spec.k[0] == 2 && ly.spec.k[1] == 2 && ly.spec.k[2] == 2 && ly.lo[0] == 0 && ly.lo[1] == 0 && ly.lo[2] == 0 &&
-                             ly.dout.D == 8 && ly.dout.H == 8 && ly.dout.W == 8 && ly.dout.C == 16 && ly.dout.cs == 16 && ly.dout.c0 == 0 && !ly.dout.split &&
-                             cv.dout.cs == 16 && cv.dout.c0 == 0 && !cv.dout.split && cv.out.cs == 16 && cv.out.c0 == 0 && p1.out.cs == 8 && p1.out.c0 == 0 &&
-                             p1.out.C == 8 && c0.out.D == 32 && cv.dout_bound > 0.f && cv.dsum && c0.dsum;
-            if (geo) {
-                ALQ_TRY(e3d_bwd_launch(ctx, cv.e3b, N, cv.dout.p, ly.dout.p, ly.argmax, cv.out.sg, p1.argmax, p1.out.sg, cv.dsum, c0.dsum, cv.dout_bound, m->e3d_rows != 0));
-                m->last_e3b_form = m->e3d_rows ? 1 : 2;
-                cv.delta_ready = true;
-                c0.delta_ready = true;
-                e3_conv = i - 1;
-                m->last_e3b = 1;
-                continue;
-            }
+            ALQ_TRY(e3d_bwd_launch(ctx, cv.e3b, N, cv.dout.p, ly.dout.p, ly.argmax, cv.out.sg, p1.argmax, p1.out.sg, cv.dsum, c0.dsum, cv.dout_bound, m->sw.e3d_rows != 0));
+            m->last.bwd.e3b_form = m->sw.e3d_rows ? 1 : 2;
+            cv.delta_ready = true;
+            c0.delta_ready = true;
+            e3_conv = i - 1;
+            m->last.bwd.e3b = 1;
+            continue;
         }
         if (e3_conv >= 0 && i == e3_conv - 1) continue;      // the pool below the fused conv: done
         // Every backward op is the LAST writer of its direct input's cotangent (a skip destination
@@ -1417,15 +1480,7 @@ static int run_backward_main(alq_model *m, const float *d_x, int N) {
         bool fused = false;
         if (isfc) {
             ALQ_REQUIRE(!acc, ALQ_EUNSUPPORTED, "layer %d: fc consumer of a skip source", i);
-            const bool bits_ok = ly.dense_fc_small && ly.fc_maskbits && prev_param && prev->out.cs == prev->out.C &&
-                                 prev->out.c0 == 0 && v4_on && prev->bwd.p4.ok && prev->bwd.p4.NTW == 1 && !prev->bwd.p4.multi &&
-                                 prev->bwd.p4.a.PT == 1 && !prev->dout.split && !prev_is_src &&
-                                 // ... and that launch must not accumulate (a skip source right below the conv): the
-                                 // accumulating instantiations of the engine are the plain ones
-                                 !(i >= 2 && m->layers[i - 2].out_is_skip_src && prev->spec.skip_src < 0);
-            if (bits_ok) {
-                // every patch has the same head cotangent (the unit cotangent): nothing of the size of the conv's output
-                // is written; the conv's backward contraction reads [sign] * wv (wv = W0 - W1, set with the weights)
+            if (head_bits_apply(m, i, prev_param, prev_is_src)) {
                 {   // the sums feed only the layer's box-filter dot products (same stream, later)
                     SideStream beside(ctx);
                     ALQ_TRY(k_fc_small_dsum_bits(ctx, ly.fc_maskbits, ly.fc_wv, ly.F, N, prev->dsum));
@@ -1444,12 +1499,12 @@ static int run_backward_main(alq_model *m, const float *d_x, int N) {
             } else {
                 // a wide fc layer's backward GEMM on fp16 pairs under the static bound on its input cotangent (fcgemm.hip, F16)
                 ALQ_TRY(gemm_launch(ctx, ly.bwd, ly.dout, flat_view(ly.din), nullptr, 0, 0, N, PROF_IGEMM_BWD, nullptr, nullptr,
-                                    (ly.dout_bound > 0.f && !m->no_bound16) ? ly.dout_bound : 0.f));
+                                    (ly.dout_bound > 0.f && !m->sw.no_bound16) ? ly.dout_bound : 0.f));
             }
         } else {
             Igemm2Fuse fz;
             const Igemm2Fuse *fuse = nullptr;
-            if (prev_param && !g_dbg_knobs[2]) {
+            if (prev_param && !g_dbg_knobs[KNOB_NO_BWD_FUSE]) {
                 const int Cs = ly.spec.skip_src >= 0 ? m->layers[ly.spec.skip_src].out.C : 0;   // concat: [src | prev]
                 if (prev->spec.relu) {
                     fz.mask = prev->out.p; fz.mask_cs = prev->out.cs; fz.mask_c0 = prev->out.c0; fz.mask_from = Cs;
@@ -1458,7 +1513,7 @@ static int run_backward_main(alq_model *m, const float *d_x, int N) {
                 if (Cs > 0) { fz.split = Cs; fz.osumB = prev->dsum; } else { fz.osumA = prev->dsum; }
                 // the skip source is the first parameterised layer and sits in front of a pool: nothing needs its
                 // cotangent except the channel sums, so mask and sum its columns here and do not store them
-                if (Cs > 0 && (v4_on || ly.din.split) && ly.bwd.p4.ok) {
+                if (Cs > 0 && (two_slot_allowed() || ly.din.split) && ly.bwd.p4.ok) {
                     Layer &sl = m->layers[ly.spec.skip_src];
                     const bool next_pool = ly.spec.skip_src + 1 < nl && pool_first_ok(m->layers[ly.spec.skip_src + 1], sl);
                     const bool sliced = sl.out.p == prev->out.p && sl.out.cs == prev->out.cs && prev->out.c0 == sl.out.c0 + Cs;
@@ -1476,21 +1531,17 @@ static int run_backward_main(alq_model *m, const float *d_x, int N) {
             }
             if (ly.dout_bits) {       // the cotangent of this layer's output exists only as mask bits and one vector
                 fz.in_bits = ly.dout_bits; fz.in_vec = ly.dout_vec; fz.in_vec_amax = ly.dout_vec_amax;
-                fz.in_vec16 = m->no_presplit ? nullptr : ly.dout_vec16;
+                fz.in_vec16 = m->sw.no_presplit ? nullptr : ly.dout_vec16;
                 const unsigned short *vec16c = ly.dout_vec16c;
                 ly.dout_bits = nullptr; ly.dout_vec = nullptr; ly.dout_vec16 = nullptr; ly.dout_vec16c = nullptr;
                 const bool honoured = fuse != nullptr;
-                // the plane-sweep engine (c3d.hip): the NET-C pattern - channels 0..7 = the skip source (first conv, ReLU: masked by
-                // its sign field and only summed), channels 8..15 = a layer without ReLU (stored and summed)
-                const bool c3 = ly.c3b.ok && ly.c3b.d_W && vec16c && !m->no_c3d && !g_no_f16x2 && fuse && !acc && fz.in_vec_amax > 0.f &&
-                                fz.split == 8 && fz.store_from == 8 && fz.mask_bits && fz.mask_from == 0 && fz.mask_to == 8 && fz.osumA && fz.osumB &&
-                                ly.din.split == 8 && ly.din.cs == 8 && ly.din.C == 16;
-                m->last_c3_bwd = c3;
+                const bool c3 = c3d_bwd_applies(m, ly, vec16c, fuse, acc);
+                m->last.bwd.c3_bwd = c3;
                 if (c3) {
                     int ex = 0;
                     (void)std::frexp(fz.in_vec_amax, &ex);
                     ALQ_TRY(c3d_bwd_launch(ctx, ly.c3b, N, reinterpret_cast<const unsigned char *>(fz.in_bits), vec16c, 14 - ex, fz.mask_bits,
-                                           ly.din.p + ly.din.delta, fz.osumA, fz.osumB, m->c3_bwd_rows));
+                                           ly.din.p + ly.din.delta, fz.osumA, fz.osumB, m->sw.c3_bwd_rows));
                 } else {
                     ALQ_TRY(igemm4_launch(ctx, ly.bwd.p4, ly.dout, ly.din, nullptr, 0, acc, N, PROF_IGEMM3_BWD, &fz));
                 }
@@ -1499,15 +1550,15 @@ static int run_backward_main(alq_model *m, const float *d_x, int N) {
                 // Hand the per-patch maxima of what this launch stores to the backward launch below it when that one has
                 // an fp16x2 variant (two column tiles, or one with the prefetch on the contracting side).  Not from the
                 // mask-bit launch above: its staging side is the critical one and the maxima cost more than they gave.
-                const bool p4_here = fuse && v4_on && ly.bwd.p4.ok && !ly.bwd.p4.multi && ly.bwd.p4.a.PT == 1 && !g_no_f16x2;
+                const bool p4_here = fuse && two_slot_allowed() && ly.bwd.p4.ok && !ly.bwd.p4.multi && ly.bwd.p4.a.PT == 1 && !g_no_f16x2;
                 bool hand = false;
                 // (with a static bound for the launch below, nothing needs to be measured here)
-                if (p4_here && prev_param && !acc && !(prev->dout_bound > 0.f && !m->no_bound16) && prev->pidx > 0 && prev->bwd.p4.ok && !prev->bwd.p4.multi && prev->bwd.p4.a.PT == 1 &&
+                if (p4_here && prev_param && !acc && !(prev->dout_bound > 0.f && !m->sw.no_bound16) && prev->pidx > 0 && prev->bwd.p4.ok && !prev->bwd.p4.multi && prev->bwd.p4.a.PT == 1 &&
                     prev->bwd.p4.d_W16 && !prev->dout.split &&
                     ((prev->bwd.p4.NTW == 1 && prev->bwd.p4.fic) || prev->bwd.p4.NTW == 2)) {
                     const size_t len = (size_t)ly.bwd.p4.a.tpg * 4;
                     if (!m->amax_a) { ALQ_TRY(m->dalloc(&m->amax_a, (size_t)m->max_batch)); ALQ_TRY(m->dalloc(&m->amax_b, (size_t)m->max_batch)); }
-                    if (m->amax_tiles_len < len) { ALQ_TRY(m->dalloc(&m->amax_tiles, (size_t)m->max_batch * len)); m->amax_tiles_len = len; }
+                    ALQ_TRY(ensure_amax_tiles(m, len));
                     fz.out_amax = m->amax_tiles;
                     fz.amax_from = fz.split > 0 && fz.split < (1 << 29) ? fz.split : 0;       // the slice the layer below reads
                     hand = true;
@@ -1515,41 +1566,31 @@ static int run_backward_main(alq_model *m, const float *d_x, int N) {
                 // (not for an accumulating launch - a conv right behind a skip source: those run the plain bf16x3 instantiation,
                 // igemm4_launch_impl's `no16`, and must not be routed to an fp16x2-only twin plan)
                 if (p4_here && !acc && ly.dout_amax) fz.in_amax = ly.dout_amax;
-                if (p4_here && !acc && !fz.in_amax && ly.dout_bound > 0.f && !m->no_bound16) fz.in_bound = ly.dout_bound;
+                if (p4_here && !acc && !fz.in_amax && ly.dout_bound > 0.f && !m->sw.no_bound16) fz.in_bound = ly.dout_bound;
                 // a launch without an epilogue request (nothing parameterised below it to mask or sum for) still gets its
                 // fp16x2 scale: an otherwise empty request carries the bound (no mask, no sums: the plain epilogue runs)
-                if (!fuse && !acc && v4_on && ly.bwd.p4.ok && !ly.bwd.p4.multi && ly.bwd.p4.a.PT == 1 && !g_no_f16x2 && !ly.dout_amax &&
-                    ly.dout_bound > 0.f && !m->no_bound16 && !g_dbg_knobs[2]) {
+                if (!fuse && !acc && two_slot_allowed() && ly.bwd.p4.ok && !ly.bwd.p4.multi && ly.bwd.p4.a.PT == 1 && !g_no_f16x2 && !ly.dout_amax &&
+                    ly.dout_bound > 0.f && !m->sw.no_bound16 && !g_dbg_knobs[KNOB_NO_BWD_FUSE]) {
                     fz = Igemm2Fuse();
                     fz.in_bound = ly.dout_bound;
                     fuse = &fz;
                 }
                 // the same bound for a launch that runs on igemm3's fp16-pair instantiation (no two-slot plan)
-                if (!ly.bwd.p4.ok && ly.bwd.p3.ok && ly.bwd.p3.d_W16 && !acc && !g_no_f16x2 && ly.dout_bound > 0.f && !m->no_bound16 && !g_dbg_knobs[2] &&
-                    !g_dbg_knobs[4] && !g_dbg_knobs[5] && !ly.bwd.pd.ok && !ly.bwd.pfc.ok) {
+                if (!ly.bwd.p4.ok && ly.bwd.p3.ok && ly.bwd.p3.d_W16 && !acc && !g_no_f16x2 && ly.dout_bound > 0.f && !m->sw.no_bound16 && !g_dbg_knobs[KNOB_NO_BWD_FUSE] &&
+                    two_slot_allowed() && !ly.bwd.pd.ok && !ly.bwd.pfc.ok) {
                     if (!fuse) { fz = Igemm2Fuse(); fuse = &fz; }
                     fz.in_bound = ly.dout_bound;
                 }
                 const unsigned *mine = ly.dout_amax;
                 ly.dout_amax = nullptr;
-                // the row-sweep engine (t3d.hip) for the backward-data pass of a stride-2 conv_transpose: fp16 pairs under the static
-                // bound like the two-slot launch it replaces; the producer below is a ReLU conv whose sign field masks the result
-                const bool t3 = ly.spec.type == ALQ_CONVT && ly.t3b.ok && ly.t3b.d_W && !m->no_t3d && v4_on && !g_no_f16x2 && !acc && fuse && !hand &&
-                                fz.in_bound > 0.f && !fz.in_amax && fz.split == 0 && fz.store_from == 0 && fz.osumA && !fz.osumB && fz.mask_from == 0 &&
-                                (!fz.mask || fz.mask_bits) && !ly.dout.split && !ly.din.split && prev_param;
-                // the plane-sweep kernel of d3d.hip for the backward-data pass of the conv over a split concat (NET-C's dec1): fp16 pairs under the static
-                // bound like the two-slot launch it replaces; channels [0, 16) = the skip source's cotangent (stored), [16, 32) = the producer's (stored + summed)
-                const bool d3 = ly.spec.type == ALQ_CONV && ly.d3f.ok && ly.d3f.d_Bhi && !m->no_d3d && !m->no_d3b && v4_on && !g_no_f16x2 && !acc && fuse && !hand &&
-                                fz.in_bound > 0.f && !fz.in_amax && fz.split == 16 && fz.store_from == 0 && !fz.mask && !fz.osumA && fz.osumB &&
-                                !ly.dout.split && ly.dout.cs == 16 && ly.dout.c0 == 0 && ly.din.split == 16 && ly.din.cs == 16 && ly.din.c0 == 0 && ly.din.C == 32;
-                if (t3) {
+                if (t3d_bwd_applies(m, ly, fuse, acc, hand, prev_param)) {
                     ALQ_TRY(t3d_bwd_launch(ctx, ly.t3b, ly.dout, ly.din, N, fz.in_bound, fz.mask ? fz.mask_bits : nullptr, fz.osumA));
                     fused = true;
-                    m->last_t3b += 1;
-                } else if (d3) {
+                    m->last.bwd.t3b += 1;
+                } else if (d3d_bwd_applies(m, ly, fuse, acc, hand)) {
                     ALQ_TRY(d3d_bwd_launch(ctx, ly.d3f, N, ly.dout.p, fz.in_bound, ly.din.p, ly.din.p + ly.din.delta, fz.osumB));
                     fused = true;
-                    m->last_d3b = 1;
+                    m->last.bwd.d3b = 1;
                 } else
                 ALQ_TRY(gemm_launch(ctx, ly.bwd, ly.dout, ly.din, nullptr, 0, acc, N, PROF_IGEMM_BWD, fuse, &fused));
                 if (hand) {
@@ -1571,19 +1612,11 @@ static int run_backward_main(alq_model *m, const float *d_x, int N) {
 // must have kept every activation (run_forward(..., keep_all = true)).
 // None of the Fisher pass's fused backward launches (c3d / t3d / e3d / d3d) runs in a general sweep or in the fp64 sweep of
 // alq_hess_vecp: engine info 2, 8, 9, 11, 13 and 17 speak of the LAST backward pass, not of the last Fisher pass before it.
-static void clear_fisher_backward_info(alq_model *m) {
-    m->last_c3_bwd = false;
-    m->last_t3b = 0;
-    m->last_e3b = 0;
-    m->last_e3b_form = 0;
-    m->last_d3b = 0;
-}
-
 static int run_backward_general(alq_model *m, int N, const DropSpec *drop, bool layer_sums = false) {
     alq_ctx *ctx = m->ctx;
     const int nl = (int)m->layers.size();
-    m->last_lsum = layer_sums ? 1 : 0;
-    clear_fisher_backward_info(m);
+    m->last.lsum = layer_sums ? 1 : 0;
+    m->last.bwd = {};
     for (int i = nl - 1; i >= 0; --i) {
         Layer &ly = m->layers[i];
         const bool isfc = ly.spec.type == ALQ_FC;
@@ -1941,8 +1974,7 @@ int alq_forward_dropout(alq_model *m, const float *d_x, int N, float keep_prob, 
     ALQ_HIP(hipSetDevice(m->ctx->device));
     DropSpec ds;
     ALQ_TRY(make_drop(m, keep_prob, seed, first_sample, h_drop_layers, n_drop_layers, &ds));
-    m->last_call_fisher = false;
-    ALQ_TRY(prepare_call(m));
+    ALQ_TRY(prepare_call(m, /*fisher=*/false));
     ALQ_TRY(run_forward(m, d_x, N, false, /*keep_all=*/true, &ds));
     ALQ_TRY(k_softmax(m->ctx, m->logits, m->nclass, N, d_post ? d_post : m->post, d_pred));
     return ALQ_OK;
@@ -1958,8 +1990,7 @@ int alq_param_grads(alq_model *m, const float *d_x, int N, int mode, int cls, co
     ALQ_HIP(hipSetDevice(m->ctx->device));
     DropSpec ds;
     ALQ_TRY(make_drop(m, keep_prob, seed, first_sample, h_drop_layers, n_drop_layers, &ds));
-    m->last_call_fisher = false;
-    ALQ_TRY(prepare_call(m));
+    ALQ_TRY(prepare_call(m, /*fisher=*/false));
     ALQ_TRY(run_forward(m, d_x, N, false, /*keep_all=*/true, &ds));
     float *post = d_post ? d_post : m->post;
     ALQ_TRY(k_softmax(m->ctx, m->logits, m->nclass, N, post, nullptr));
@@ -1977,8 +2008,7 @@ int alq_grad_sqnorms(alq_model *m, const float *d_x, int N, int cls, const int32
     ALQ_HIP(hipSetDevice(m->ctx->device));
     DropSpec ds;
     ALQ_TRY(make_drop(m, 1.f, 0, 0, nullptr, 0, &ds));
-    m->last_call_fisher = false;
-    ALQ_TRY(prepare_call(m));
+    ALQ_TRY(prepare_call(m, /*fisher=*/false));
     ALQ_TRY(run_forward(m, d_x, N, false, /*keep_all=*/true, &ds));
     float *post = d_post ? d_post : m->post;
     ALQ_TRY(k_softmax(m->ctx, m->logits, m->nclass, N, post, nullptr));
@@ -2018,8 +2048,7 @@ int alq_class_layer_sums(alq_model *m, const float *d_x, int N, int J, const int
     }
     DropSpec ds;
     ALQ_TRY(make_drop(m, 1.f, 0, 0, nullptr, 0, &ds));
-    m->last_call_fisher = false;
-    ALQ_TRY(prepare_call(m));
+    ALQ_TRY(prepare_call(m, /*fisher=*/false));
     ALQ_TRY(run_forward(m, d_x, N, false, /*keep_all=*/true, &ds));
     float *post = d_post ? d_post : m->post;
     ALQ_TRY(k_softmax(ctx, m->logits, m->nclass, N, post, nullptr));
@@ -2053,8 +2082,7 @@ int alq_diag_fisher(alq_model *m, const float *d_x, int N, const int32_t *d_cls,
     ALQ_REQUIRE(!bad, ALQ_EINVAL, "alq_diag_fisher: a class outside [0, %d)", m->nclass);
     DropSpec ds;
     ALQ_TRY(make_drop(m, 1.f, 0, 0, nullptr, 0, &ds));
-    m->last_call_fisher = false;
-    ALQ_TRY(prepare_call(m));
+    ALQ_TRY(prepare_call(m, /*fisher=*/false));
     ALQ_TRY(run_forward(m, d_x, N, false, /*keep_all=*/true, &ds));
     ALQ_TRY(k_softmax(ctx, m->logits, m->nclass, N, m->post, nullptr));
     ALQ_TRY(k_logit_cotangent(ctx, m->post, m->nclass, N, 3, 0, d_cls, 1.f, m->dlogits));
@@ -2084,10 +2112,9 @@ int alq_hess_vecp(alq_model *m, const float *d_x, int N, const int32_t *d_labels
     ALQ_TRY(hvp_prepare(m));
     DropSpec ds;
     ALQ_TRY(make_drop(m, 1.f, 0, 0, nullptr, 0, &ds));
-    m->last_call_fisher = false;
-    ALQ_TRY(prepare_call(m));
+    ALQ_TRY(prepare_call(m, /*fisher=*/false));
     ALQ_TRY(run_forward(m, d_x, N, false, /*keep_all=*/true, &ds));
-    clear_fisher_backward_info(m);
+    m->last.bwd = {};      // the fp64 sweep runs none of the Fisher pass's fused backward launches
     return run_hess_vecp(m, d_x, N, d_labels, loss_scale, d_v, h_layer_on, accumulate, d_hv, d_loss);
 }
 
@@ -2134,8 +2161,7 @@ int alq_param_grads_loss(alq_model *m, const float *d_x, int N, const int32_t *d
     ALQ_HIP(hipSetDevice(m->ctx->device));
     DropSpec ds;
     ALQ_TRY(make_drop(m, keep_prob, seed, first_sample, h_drop_layers, n_drop_layers, &ds));
-    m->last_call_fisher = false;
-    ALQ_TRY(prepare_call(m));
+    ALQ_TRY(prepare_call(m, /*fisher=*/false));
     ALQ_TRY(run_forward(m, d_x, N, false, /*keep_all=*/true, &ds));
     float *post = d_post ? d_post : m->post;
     ALQ_TRY(k_softmax(m->ctx, m->logits, m->nclass, N, post, nullptr));
@@ -2270,40 +2296,7 @@ int alq_model_create(alq_ctx *ctx, const alq_layer_t *layers, int n_layers, cons
     alq_model *m = new alq_model();
     m->ctx = ctx;
     m->max_batch = max_batch;
-    {
-        const char *e = getenv("ALQ_DISABLE_V2");   // diagnostics: force the general GEMM kernel (plan-time only)
-        g_use_v2 = !(e && e[0] == '1');
-        m->no_f16x2 = getenv("ALQ_NO_F16X2") != nullptr;
-        m->no_xcd_order = getenv("ALQ_NO_XCD_ORDER") != nullptr;
-        m->no_fixed = getenv("ALQ_NO_FIXED") != nullptr;
-        m->no_bound16 = getenv("ALQ_NO_BOUND16") != nullptr;
-        m->no_flipfix = getenv("ALQ_NO_FLIPFIX") != nullptr;
-        m->no_presplit = getenv("ALQ_NO_PRESPLIT") != nullptr;
-        m->no_c3d = getenv("ALQ_NO_C3D") != nullptr;
-        // 7 (default): the 27 taps packed into 7 k-steps (c3d_bwd7_kernel); 8: the 9-k-step kernel of round 4; 4: its half-patch form
-        m->no_light_kernels = getenv("ALQ_NO_LIGHT_KERNELS") != nullptr;
-        { const char *e = getenv("ALQ_C3D_BWD_ROWS"); m->c3_bwd_rows = (e && atoi(e) == 4) ? 4 : ((e && atoi(e) == 8) ? 8 : 7); }
-        m->no_signs = getenv("ALQ_NO_SIGNS") != nullptr;
-        m->no_signs0 = getenv("ALQ_NO_SIGNS0") != nullptr;
-        if (const char *f = getenv("ALQ_F16_FWD_MASK")) m->f16_fwd_mask = atoi(f);
-        m->no_t3d = getenv("ALQ_NO_T3D") ? 1 : 0;
-        m->no_e3d = getenv("ALQ_NO_E3D") ? 1 : 0;
-        { const char *e = getenv("ALQ_E3D_ROWS"); m->e3d_rows = (e && atoi(e) == 1) ? 1 : 0; }
-        m->no_d3d = getenv("ALQ_NO_D3D") ? 1 : 0;
-        m->no_f3d = getenv("ALQ_NO_F3D") ? 1 : 0;
-        m->no_d3b = getenv("ALQ_NO_D3D_BWD") ? 1 : 0;
-        {   // default since round 5: on.  ALQ_NO_F16_DERIVED=1 (or ALQ_F16_DERIVED=0) keeps that launch on bf16 triples (A/B)
-            const char *e = getenv("ALQ_F16_DERIVED"), *n = getenv("ALQ_NO_F16_DERIVED");
-            m->no_f16_derived = ((e && atoi(e) == 0) || (n && atoi(n) == 1)) ? 1 : 0;
-        }
-        // (ALQ_DCP_NARROW: the first conv + pool kernel on its narrow tile with per-voxel sum / sign stores everywhere, direct.hip)
-        static const char *names[ALQ_NKNOBS] = {"ALQ_DEBUG_REPEAT", "ALQ_DEBUG_FLAGS", "ALQ_NO_BWD_FUSE", "ALQ_NO_FWD_FUSE", "ALQ_NO_V3", "ALQ_NO_V4",
-                                                "ALQ_NO_POOL_FIRST", "ALQ_NO_CONV_POOL", "ALQ_DCP_NARROW", "ALQ_E3D_GRID_CAP"};
-        for (int k = 0; k < ALQ_NKNOBS; ++k) {
-            const char *v = getenv(names[k]);
-            if (v) m->knobs[k] = atoi(v);
-        }
-    }
+    m->sw = read_engine_switches();
     for (int i = 0; i < 4; ++i) m->in_dims[i] = in_dims[i];
     m->epp = (int64_t)in_dims[0] * in_dims[1] * in_dims[2] * in_dims[3];
     const int rc = build_model(m, layers, n_layers);
@@ -2343,7 +2336,7 @@ int alq_model_create(alq_ctx *ctx, const alq_layer_t *layers, int n_layers, cons
             m->f16_fwd_derived = 1 << (nl - 4);
         for (int i = 1; i + 1 < nl; ++i)      // enc2 of NET-C: its fused kernel (f3d.hip) contracts fp16 pairs under the first layer's measured maximum
             if (m->layers[i].f3f.ok && m->f16_fwd_derived) m->f16_fwd_derived |= 1 << i;
-        if (const char *e = getenv("ALQ_F16_DERIVED_MASK")) m->f16_fwd_derived = atoi(e);      // (study: other forward launches on fp16 pairs, by layer bit)
+        if (m->sw.has_f16_derived_mask) m->f16_fwd_derived = m->sw.f16_derived_mask;      // (study: other forward launches on fp16 pairs, by layer bit)
     }
     *out = m;
     return ALQ_OK;
@@ -2757,8 +2750,7 @@ int alq_forward(alq_model *m, const float *d_x, int N, float *d_post, int64_t *d
     ALQ_REQUIRE(N >= 0 && N <= m->max_batch, ALQ_EINVAL, "alq_forward: N=%d exceeds max_batch=%d", N, m->max_batch);
     if (N == 0) return ALQ_OK;
     ALQ_HIP(hipSetDevice(m->ctx->device));
-    m->last_call_fisher = false;
-    ALQ_TRY(prepare_call(m));
+    ALQ_TRY(prepare_call(m, /*fisher=*/false));
     ALQ_TRY(run_forward(m, d_x, N, false, /*keep_all=*/d_feat != nullptr));
     ALQ_TRY(k_softmax(m->ctx, m->logits, m->nclass, N, d_post ? d_post : m->post, d_pred));
     if (d_feat) {
@@ -2833,8 +2825,7 @@ int alq_fisher(alq_model *m, const float *d_x, int N, const float *d_p1_in, doub
         explicit SkipGuard(alq_ctx *ctx) : c(ctx) { c->prof_skip = c->prof_on && (c->prof_pass++ % c->prof_every) != 0; }
         ~SkipGuard() { c->prof_skip = false; }
     } guard(m->ctx);
-    m->last_call_fisher = true;
-    ALQ_TRY(prepare_call(m));
+    ALQ_TRY(prepare_call(m, /*fisher=*/true));
     ALQ_TRY(run_forward(m, d_x, N, true));
     ALQ_TRY(k_softmax(m->ctx, m->logits, m->nclass, N, m->post, nullptr));
     ALQ_TRY(run_backward(m, d_x, N));
@@ -2936,10 +2927,10 @@ int alq_model_debug_copy(alq_model *m, int layer_idx, int what, int N, float *d_
     }
     if (what == 5) {       // per (tile, wave) partials of the logit difference from the fused fc head (last pass)
         const Layer &head = m->layers.back();
-        ALQ_REQUIRE(head.fc_part2 && m->last_head_fused, ALQ_EUNSUPPORTED, "the last pass did not run the fused fc head");
-        const int ns = m->last_c3 ? 4 : head.fc_slices2;      // plane-sweep engine: one partial per (patch, wave)
+        ALQ_REQUIRE(head.fc_part2 && m->last.fwd.head_fused, ALQ_EUNSUPPORTED, "the last pass did not run the fused fc head");
+        const int ns = m->last.fwd.c3 ? 4 : head.fc_slices2;      // plane-sweep engine: one partial per (patch, wave)
         if (elems_out) *elems_out = (int64_t)N * ns;
-        ALQ_HIP(hipMemcpyAsync(d_out, m->last_c3 ? head.c3_part : head.fc_part2, (size_t)N * ns * sizeof(float), hipMemcpyDeviceToDevice,
+        ALQ_HIP(hipMemcpyAsync(d_out, m->last.fwd.c3 ? head.c3_part : head.fc_part2, (size_t)N * ns * sizeof(float), hipMemcpyDeviceToDevice,
                                m->ctx->stream));
         return ALQ_OK;
     }
@@ -2969,7 +2960,7 @@ int alq_model_debug_copy(alq_model *m, int layer_idx, int what, int N, float *d_
         // test hooks for the kernels that write these next to the activation: 11 = channel sums of the layer's output (floats),
         // 12 = the sign field (View::sg) of the rows its output lies in, 13 = a pool layer's arg-max bytes; 12 / 13 as raw bytes
         if (what == 11) {
-            ALQ_REQUIRE(ly.osum && m->last_call_fisher, ALQ_EUNSUPPORTED, "layer %d: no channel sums of its output in the last pass", layer_idx);
+            ALQ_REQUIRE(ly.osum && m->last.call_fisher, ALQ_EUNSUPPORTED, "layer %d: no channel sums of its output in the last pass", layer_idx);
             if (elems_out) *elems_out = (int64_t)N * ly.out.vox();
             ALQ_HIP(hipMemcpyAsync(d_out, ly.osum, (size_t)N * ly.out.vox() * sizeof(float), hipMemcpyDeviceToDevice, m->ctx->stream));
             return ALQ_OK;
@@ -2991,8 +2982,8 @@ int alq_model_debug_copy(alq_model *m, int layer_idx, int what, int N, float *d_
         // the last conv under a fused fc head: a Fisher pass stores neither its output nor the cotangent of it
         const Layer &head = m->layers.back();
         ALQ_REQUIRE(!(layer_idx + 2 == (int)m->layers.size() && head.spec.type == ALQ_FC &&
-                      (what == 0 ? m->last_head_fused
-                                 : (m->last_call_fisher && head.fc_maskbits != nullptr && !g_dbg_knobs[4] && !g_dbg_knobs[5]))),
+                      (what == 0 ? m->last.fwd.head_fused
+                                 : (m->last.call_fisher && head.fc_maskbits != nullptr && two_slot_allowed()))),
                     ALQ_EUNSUPPORTED, "layer %d: this tensor is not materialised in a Fisher pass (fc head fused into the layer: "
                     "create the model under ALQ_NO_FC_BITS=1 to keep it)", layer_idx);
         const View &v = what == 0 ? ly.out : ly.dout;
@@ -3009,33 +3000,41 @@ int alq_model_debug_copy(alq_model *m, int layer_idx, int what, int N, float *d_
 }
 
 int alq_model_engine_info(alq_model *m, int what) {
-    ALQ_REQUIRE(m && ((what >= 0 && what <= 3) || (what >= 5 && what <= 17)), ALQ_EINVAL, "alq_model_engine_info: bad argument");
-    if (what == 17) return m->last_e3b_form;  // form of the fused enc2 backward launch (e3d.hip) in the last backward pass: 0 none, 1 row sweep, 2 z plane sweep
-    if (what == 16) return m->last_dcp;       // form of the first conv + pool kernel in the last forward pass: 0 none, 1 / 2 narrow tile (unaligned / aligned rows), 4 / 5 wide tile, 6 wide tile with 16-byte sum / sign stores
-    if (what == 15) return m->last_lsum;      // the last general backward sweep ran the fused layer-sum kernels (lsum.hip)
-    if (what == 14) return m->host_pack_elems > 0x7fffffffll ? 0x7fffffff : (int)m->host_pack_elems;      // weight elements through the host packers since creation (saturates)
-    if (what == 13) return m->last_c3_bwd ? m->c3_bwd_rows : 0;      // form of the head conv's backward kernel: 7 = 27 taps in 7 k-steps, 8 / 4 = the 9-k-step kernel
-    if (what == 6) return m->last_f16_derived ? 1 : 0;
-    if (what == 7) return m->last_t3f;        // conv_transpose launches of the last forward pass on the row-sweep engine (t3d.hip)
-    if (what == 8) return m->last_t3b;        // ... of the last backward pass
-    if (what == 12) return m->last_f3f;       // the last forward pass ran enc2 + pool2 as one launch (f3d.hip)
-    if (what == 11) return m->last_d3b;       // the last backward pass ran dec1's backward-data launch on the plane-sweep kernel (d3d.hip)
-    if (what == 10) return m->last_d3f;       // the last forward pass ran dec1 on the row-sweep engine (d3d.hip)
-    if (what == 9) return m->last_e3b;        // the last backward pass ran enc2's backward fused with both pool backward steps (e3d.hip)
-    ALQ_HIP(hipSetDevice(m->ctx->device));
-    if (what == 0) return c3d_subnormals_ok(m->ctx);
-    if (what == 1) return m->last_c3 ? 1 : 0;
-    if (what == 2) return m->last_c3_bwd ? 1 : 0;
-    if (what == 5) {       // flip-safe head: marked groups dropped by a full list segment since the model was created
-        if (!m->flip_overflow) return 0;
-        unsigned h = 0;
-        ALQ_HIP(hipMemcpyAsync(&h, m->flip_overflow, sizeof(unsigned), hipMemcpyDeviceToHost, m->ctx->stream));
-        ALQ_HIP(hipStreamSynchronize(m->ctx->stream));
-        return h > 0x7fffffffu ? 0x7fffffff : (int)h;
+    ALQ_REQUIRE(m, ALQ_EINVAL, "alq_model_engine_info: bad argument");
+    switch (what) {      // include/alq.h documents every index
+        case ALQ_INFO_SUBNORMALS_OK:
+            ALQ_HIP(hipSetDevice(m->ctx->device));
+            return c3d_subnormals_ok(m->ctx);
+        case ALQ_INFO_C3D_FWD: return m->last.fwd.c3 ? 1 : 0;
+        case ALQ_INFO_C3D_BWD: return m->last.bwd.c3_bwd ? 1 : 0;
+        case ALQ_INFO_C3D_ONE_ACC:
+            for (const Layer &ly : m->layers)
+                if (ly.c3f.ok) return ly.c3f.oneacc;
+            return 0;
+        case ALQ_INFO_FLIP_OVERFLOW: {      // marked groups beyond their list segment since the model was created
+            ALQ_HIP(hipSetDevice(m->ctx->device));
+            if (!m->flip_overflow) return 0;
+            unsigned h = 0;
+            ALQ_HIP(hipMemcpyAsync(&h, m->flip_overflow, sizeof(unsigned), hipMemcpyDeviceToHost, m->ctx->stream));
+            ALQ_HIP(hipStreamSynchronize(m->ctx->stream));
+            return h > 0x7fffffffu ? 0x7fffffff : (int)h;
+        }
+        case ALQ_INFO_F16_DERIVED: return m->last.fwd.f16_derived ? 1 : 0;
+        case ALQ_INFO_T3D_FWD: return m->last.fwd.t3f;
+        case ALQ_INFO_T3D_BWD: return m->last.bwd.t3b;
+        case ALQ_INFO_E3D_BWD: return m->last.bwd.e3b;
+        case ALQ_INFO_D3D_FWD: return m->last.fwd.d3f;
+        case ALQ_INFO_D3D_BWD: return m->last.bwd.d3b;
+        case ALQ_INFO_F3D_FWD: return m->last.fwd.f3f;
+        case ALQ_INFO_C3D_BWD_FORM: return m->last.bwd.c3_bwd ? m->sw.c3_bwd_rows : 0;
+        case ALQ_INFO_HOST_PACK_ELEMS: return m->host_pack_elems > 0x7fffffffll ? 0x7fffffff : (int)m->host_pack_elems;      // saturates
+        case ALQ_INFO_LSUM: return m->last.lsum;
+        case ALQ_INFO_DCP_FORM: return m->last.fwd.dcp;
+        case ALQ_INFO_E3D_BWD_FORM: return m->last.bwd.e3b_form;
+        default: break;      // 4 is unused
     }
-    for (const Layer &ly : m->layers)
-        if (ly.c3f.ok) return ly.c3f.oneacc;
-    return 0;
+    set_error("alq_model_engine_info: bad argument");
+    return ALQ_EINVAL;
 }
 
 int alq_debug_set(int key, int value) {
