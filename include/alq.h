@@ -444,6 +444,31 @@ int alq_local_var2d(alq_ctx *ctx, const void *d_vol, int vol_is_f64, const int64
 int alq_segment_min(alq_ctx *ctx, const int32_t *d_labels, const int64_t dims[3], int32_t n_labels, const int64_t *d_inds,
                     const double *d_scores, int64_t n, double *d_table);
 
+/* ---- connected components, largest component, hole filling (csrc/ccl.hip) -------------------------------------------- */
+/* Replaces: post_processing.connected_component_analysis_3d (skimage.measure.label + the largest component) and
+ * post_processing.fill_holes (scipy's binary_fill_holes), the two steps eval_utils.get_full_segs(post_process=True) applies to
+ * a segmentation before scoring or saving it.  d_seg: uint8 volume [H, W, S] = dims in C order (z contiguous; S = 1: a 2-D
+ * image), H W S < 2^31.  connectivity 6 / 18 / 26: face, face + edge, face + edge + corner neighbours.
+ *   alq_cc_label         d_labels int32 [H, W, S]: for a selected voxel (!= 0, or == 0 with select_zero) the smallest raveled
+ *                        index of its component, -1 for every other voxel.  A pure function of the input: atomic-min
+ *                        union-find whose roots are minima, the same bits whatever order the workgroups run in.
+ *   alq_cc_keep_largest  d_out uint8 [H, W, S] = 1 on the largest component of the non-zero voxels, 0 elsewhere.  Sizes are
+ *                        exact integer sums; among equal sizes the component whose first voxel comes first in C order wins.
+ *                        skip_origin: the component that holds voxel 0 is no candidate.  d_info int64 [4] = (number of
+ *                        candidates, the winner's root or -1, its size, number of non-zero voxels); without a candidate
+ *                        d_out is all zero.
+ *   alq_fill_holes       d_out = 1 where d_seg != 0 or where the voxel belongs to a 6-connected component of the zero voxels
+ *                        that touches none of the six faces of the volume (binary_fill_holes' default structure).
+ *                        d_info int64 [4] = (enclosed background components, voxels filled, 0, 0).
+ * d_out may be d_seg (in place).  d_work: alq_cc_work_bytes(dims) bytes (64 + 8 per voxel; 0 for dims the calls refuse), 8-byte
+ * aligned like d_info.  ALQ_EINVAL before any launch: a null pointer, another connectivity, an axis below 1, 2^31 voxels or
+ * more.  Stream-ordered, no synchronisation.                                                                                 */
+size_t alq_cc_work_bytes(const int64_t dims[3]);
+int alq_cc_label(alq_ctx *ctx, const uint8_t *d_seg, const int64_t dims[3], int connectivity, int select_zero, int32_t *d_labels);
+int alq_cc_keep_largest(alq_ctx *ctx, const uint8_t *d_seg, const int64_t dims[3], int connectivity, int skip_origin, uint8_t *d_out,
+                        int64_t *d_info, void *d_work);
+int alq_fill_holes(alq_ctx *ctx, const uint8_t *d_seg, const int64_t dims[3], uint8_t *d_out, int64_t *d_info, void *d_work);
+
 /* ---- last-layer closed forms and the stochastic influence recursion (csrc/llfc.hip) -------------------------------- */
 /* Replaces: NN.LLFC_grads / NN.LLFC_hess / NN.PW_LLFC_grads (NN.py:874-1029; duplicated in model_utils.py:137-292) and the
  * iteration of PW_NNAL.stoch_approx_IF (PW_NNAL.py:851-881).  u [d] = the input of the last fc layer (the model's feature

@@ -6,6 +6,8 @@ evaluation (`full_slice_eval`, `full_model_eval`) and the learning curve of a me
 The three metric functions are host NumPy, the reference's operations in its order.  The evaluations that walk many voxels
 keep the predictions on the device: `eval_counts_device` feeds every chunk's prediction tensor to alq_eval_counts, which adds
 to six int64 totals in HBM (and scatters the predictions into a uint8 volume for full_model_eval); 48 bytes come back.
+full_model_eval(..., post_process=True) applies the reference's post-processing (post_processing.py: largest connected
+component, hole filling) to that volume where it lies (alq_cc_keep_largest, alq_fill_holes) before scoring and saving it.
 
 Not mirrored: `grid_based_F1` (patch_utils.generate_grid_samples is outside this package), the dense-CRF post-processing
 (`full_model_pred_DCRF`, `full_test_slice_DCRF`, `DCRF_postprocess_*`), the plotting helpers (`visualize_eval_metrics`, ...)
@@ -164,7 +166,7 @@ def full_slice_eval(model, sess, img_paths, slice_inds, patch_shape, ntb, stats,
     return slice_evals
 
 
-def full_model_eval(expr, model, sess, img_path, mask_path, slice_inds, save_dir=None):
+def full_model_eval(expr, model, sess, img_path, mask_path, slice_inds, save_dir=None, post_process=False):
     """PW_analyze_results.py:594-670: predictions of every voxel of the slices `slice_inds`, their F1 against the mask over
     those slices and, with `save_dir`, `segs.nrrd` (uint8) and `F1_socre.txt` (the reference's spelling).  Returns
     (preds [x, y, z] float64, F1).
@@ -176,7 +178,13 @@ def full_model_eval(expr, model, sess, img_path, mask_path, slice_inds, save_dir
     volume of bytes and 48 bytes of counts come back.  F1 is F1_scores' expression 2 Pr Rc / (Pr + Rc) on those counts, so
     that it equals F1_scores(preds[:, :, slice_inds], mask[:, :, slice_inds]) bit for bit (the reference's line :654 writes
     the same number as 2 / (1/Pr + 1/Rc), which may differ in the last place), and 0 where the reference's float divisions
-    would raise (no predicted positives, no true positives, or no positives at all)."""
+    would raise (no predicted positives, no true positives, or no positives at all).
+
+    `post_process` (eval_utils.get_full_segs' switch; not an argument of the reference's full_model_eval): the uint8 volume is
+    post-processed on the device before it comes back - the largest 26-connected component outside voxel 0's
+    (alq_cc_keep_largest; an all-zero volume when there is none), then the enclosed cavities filled (alq_fill_holes) - and
+    the processed volume is what is returned, scored (alq_eval_counts on its voxels of the same slices) and saved; the
+    unprocessed one goes to `segs_raw.nrrd` / `F1_socre_raw.txt`."""
     torch = sess.torch
     if save_dir:
         if not os.path.exists(save_dir):
@@ -195,18 +203,34 @@ def full_model_eval(expr, model, sess, img_path, mask_path, slice_inds, save_dir
         _, inds_3D = _slice_inds_3D(img_shape, ind)
         eval_counts_device(model, sess, vols, inds_3D, patch_shape, expr.pars['ntb'], expr.pars['stats'], lab, seg=seg,
                            _vols=dv, _counts=counts)
-    P, N, TP, FP, TN, FN = [float(v) for v in counts.cpu().numpy()]
+    F1 = _f1_from_counts(counts)
+    if post_process:
+        if save_dir:
+            nrrd_io.write(os.path.join(save_dir, 'segs_raw.nrrd'), np.uint8(seg.cpu().numpy().reshape(img_shape)))
+            np.savetxt(os.path.join(save_dir, 'F1_socre_raw.txt'), [F1])
+        seg, _ = sess.cc_keep_largest(seg, img_shape, connectivity=26, skip_origin=True, out=seg)
+        seg, _ = sess.fill_holes(seg, img_shape, out=seg)
+        inds = sess.to_device(np.concatenate([_slice_inds_3D(img_shape, ind)[1] for ind in slice_inds]), torch.int64)
+        counts = sess.to_device(np.zeros(6, dtype=np.int64), torch.int64)
+        sess.eval_counts(seg.reshape(-1)[inds].to(torch.int64), inds, lab.reshape(-1), counts, None)
+        F1 = _f1_from_counts(counts)
     segs = seg.cpu().numpy().reshape(img_shape)
-    F1 = 0
-    if TP > 0:                                                  # (then TP + FP > 0 and P > 0)
-        Pr = TP / (TP + FP)
-        Rc = TP / P
-        F1 = 2 * Pr * Rc / (Pr + Rc)
     print('\n F1: %.4f' % F1)
     if save_dir:
         nrrd_io.write(os.path.join(save_dir, 'segs.nrrd'), np.uint8(segs))
         np.savetxt(os.path.join(save_dir, 'F1_socre.txt'), [F1])
     return segs.astype(np.float64), F1
+
+
+def _f1_from_counts(counts):
+    """F1_scores' expression on the six device totals of alq_eval_counts (one copy of 48 bytes); 0 without a true positive."""
+    P, N, TP, FP, TN, FN = [float(v) for v in counts.cpu().numpy()]
+    F1 = 0
+    if TP > 0:                                                  # (then TP + FP > 0 and P > 0)
+        Pr = TP / (TP + FP)
+        Rc = TP / P
+        F1 = 2 * Pr * Rc / (Pr + Rc)
+    return F1
 
 
 def eval_MultimgAL(expr, method_name, img_paths, start_ind=0, save_dir=[], sess=None):

@@ -108,6 +108,10 @@ _SIGNATURES = {
     'alq_fold_rowmax': (C.c_int, [_P, _P, C.c_int, C.c_int64, _P]),
     'alq_local_var2d': (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int, _P, C.c_int64, _P]),
     'alq_segment_min': (C.c_int, [_P, _P, C.POINTER(C.c_int64), C.c_int32, _P, _P, C.c_int64, _P]),
+    'alq_cc_work_bytes': (C.c_size_t, [C.POINTER(C.c_int64)]),
+    'alq_cc_label': (C.c_int, [_P, _P, C.POINTER(C.c_int64), C.c_int, C.c_int, _P]),
+    'alq_cc_keep_largest': (C.c_int, [_P, _P, C.POINTER(C.c_int64), C.c_int, C.c_int, _P, _P, _P]),
+    'alq_fill_holes': (C.c_int, [_P, _P, C.POINTER(C.c_int64), _P, _P, _P]),
     'alq_llfc_grads': (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
     'alq_llfc_hess_max_bytes': (C.c_size_t, []),
     'alq_llfc_hess': (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P]),

@@ -163,6 +163,59 @@ class DeviceSession(object):
         check(self.lib.alq_eval_counts(self._ctx, ptr(pred), ptr(inds), n, ptr(mask), 1 if mask.dtype == torch.float64 else 0,
                                        elems, ptr(counts), ptr(seg)))
 
+    # -- connected components, largest component, hole filling (csrc/ccl.hip) ---------------
+    def _cc_args(self, seg, shape, out=None):
+        torch = self.torch
+        self.bind_stream()
+        shape = tuple(int(v) for v in shape)
+        if len(shape) == 2:
+            shape = shape + (1,)
+        assert len(shape) == 3 and min(shape) >= 1
+        nvox = shape[0] * shape[1] * shape[2]
+        for t in (seg, out):
+            assert t is None or (t.dtype == torch.uint8 and t.is_contiguous() and t.device == self.device and int(t.numel()) == nvox)
+        if nvox >= 2 ** 31:
+            raise ValueError('volume %r has 2^31 voxels or more' % (shape,))
+        return shape, nvox, (C.c_int64 * 3)(*shape)
+
+    def _cc_work(self, dims):
+        return self.empty((int(self.lib.alq_cc_work_bytes(dims)),), self.torch.uint8), self.empty((4,), self.torch.int64)
+
+    def cc_label(self, seg, shape, connectivity=26, select_zero=False):
+        """alq_cc_label: the canonical component labels of a uint8 device volume `seg` of `shape` [H, W, S] (or [H, W]): int32
+        device tensor of that shape, for a selected voxel (!= 0; == 0 with select_zero) the smallest raveled index of its 6- /
+        18- / 26-connected component, -1 elsewhere."""
+        shape, nvox, dims = self._cc_args(seg, shape)
+        labels = self.empty(shape, self.torch.int32)
+        check(self.lib.alq_cc_label(self._ctx, C.c_void_p(seg.data_ptr()), dims, int(connectivity), 1 if select_zero else 0,
+                                    C.c_void_p(labels.data_ptr())))
+        return labels
+
+    def cc_keep_largest(self, seg, shape, connectivity=26, skip_origin=True, out=None):
+        """alq_cc_keep_largest: (mask, info) - the uint8 device mask (of `shape`; `out`, which may be `seg` itself, when given)
+        of the largest component of the non-zero voxels, equal sizes -> the component that starts first in C order, without
+        the component of voxel 0 when skip_origin; info = np.int64 [4] (candidates, winner's root or -1, its size, non-zero
+        voxels), one copy of 32 bytes.  No candidate: an all-zero mask."""
+        shape, nvox, dims = self._cc_args(seg, shape, out)
+        if out is None:
+            out = self.empty(shape, self.torch.uint8)
+        work, info = self._cc_work(dims)
+        check(self.lib.alq_cc_keep_largest(self._ctx, C.c_void_p(seg.data_ptr()), dims, int(connectivity), 1 if skip_origin else 0,
+                                           C.c_void_p(out.data_ptr()), C.c_void_p(info.data_ptr()), C.c_void_p(work.data_ptr())))
+        return out, info.cpu().numpy()
+
+    def fill_holes(self, seg, shape, out=None):
+        """alq_fill_holes: (mask, info) - uint8 device mask = seg != 0 or inside a 6-connected background component that
+        touches no face of the volume (scipy's binary_fill_holes); info = np.int64 [4] (enclosed components, voxels filled,
+        0, 0), one copy of 32 bytes.  `out` may be `seg` itself."""
+        shape, nvox, dims = self._cc_args(seg, shape, out)
+        if out is None:
+            out = self.empty(shape, self.torch.uint8)
+        work, info = self._cc_work(dims)
+        check(self.lib.alq_fill_holes(self._ctx, C.c_void_p(seg.data_ptr()), dims, C.c_void_p(out.data_ptr()),
+                                      C.c_void_p(info.data_ptr()), C.c_void_p(work.data_ptr())))
+        return out, info.cpu().numpy()
+
     # -- RCCL communicator of the sharded pool (pool_shard.attach_comm) --------------------
     def comm_unique_id(self):
         buf = C.create_string_buffer(128)

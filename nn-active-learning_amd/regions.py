@@ -1,8 +1,9 @@
-"""Plain NumPy restatement of the two region primitives of csrc/region.hip: the d x d local-variance map of
+"""Plain NumPy restatement of the region primitives of csrc/region.hip and csrc/ccl.hip: the d x d local-variance map of
 patch_utils.get_vars_2d (patch_utils.py:794-826) and the per-(slice, label) score minimum of PW_NNAL.superpix_scoring
 (PW_NNAL.py:944-1021).  Host code: the reference of the kernel tests and of the tool, and the documentation of the formulas
-(include/alq.h).  No scipy: the box sums are integer prefix sums, which is what scipy's float64 convolution of the uint64 image
-equals wherever it is exact (check_variance_input)."""
+(include/alq.h).  No scipy in the first two: the box sums are integer prefix sums, which is what scipy's float64 convolution of
+the uint64 image equals wherever it is exact (check_variance_input).  The component functions at the end (cc_label_host,
+keep_largest_host, fill_holes_host) state alq_cc_label / alq_cc_keep_largest / alq_fill_holes through scipy.ndimage."""
 import numpy as np
 
 MAX_D = 65
@@ -79,3 +80,69 @@ def segment_min_host(labels, inds, scores, n_labels=None):
     keep = (lab >= 1) & (lab < n_labels)
     np.minimum.at(table, (z[keep], lab[keep]), scores[ok][keep])
     return table
+
+
+# ---- connected components, largest component, hole filling: the semantics of csrc/ccl.hip ------------------------------------
+_CC_RANK = {6: 1, 18: 2, 26: 3}
+
+
+def _as_volume(seg):
+    a = np.asarray(seg)
+    if a.ndim == 2:
+        a = a[:, :, None]
+    if a.ndim != 3:
+        raise ValueError('2-D image or 3-D volume expected')
+    return a
+
+
+def cc_label_host(seg, connectivity=26, select_zero=False):
+    """The labels of alq_cc_label on the host (scipy.ndimage.label; never on the product path): int32, for a selected voxel
+    (!= 0; == 0 with select_zero) the smallest raveled index of its component, -1 elsewhere.  connectivity 6 / 18 / 26 =
+    scipy's generate_binary_structure(3, 1 / 2 / 3); a 2-D image is the volume [H, W, 1]."""
+    from scipy import ndimage
+    a = _as_volume(seg)
+    sel = (a == 0) if select_zero else (a != 0)
+    lab, n = ndimage.label(sel, structure=ndimage.generate_binary_structure(3, _CC_RANK[int(connectivity)]))
+    out = np.full(a.shape, -1, dtype=np.int32)
+    if n:
+        flat = lab.reshape(-1)
+        _, first = np.unique(flat, return_index=True)              # first[l] = the first raveled index with label l (0 = background)
+        if flat.min() != 0:                                        # no background voxel: label 1 is first[0]
+            first = np.concatenate([[0], first])
+        out = np.where(lab > 0, first[lab], -1).astype(np.int32)
+    return out.reshape(np.asarray(seg).shape)
+
+
+def keep_largest_host(seg, connectivity=26, skip_origin=True, with_info=False):
+    """alq_cc_keep_largest on the host: uint8 mask of the largest component of the non-zero voxels; equal sizes -> the
+    component whose first voxel comes first in C order; skip_origin: the component of voxel 0 is no candidate.  with_info:
+    (mask, np.int64 [4] = candidates, winner's root or -1, its size, non-zero voxels).  No candidate: all zero."""
+    a = np.asarray(seg)
+    lab = cc_label_host(a, connectivity).reshape(-1)
+    roots, sizes = np.unique(lab[lab >= 0], return_counts=True)
+    if skip_origin and lab[0] >= 0:
+        keep = roots != lab[0]
+        roots, sizes = roots[keep], sizes[keep]
+    info = np.array([len(roots), -1, 0, int(np.count_nonzero(a))], dtype=np.int64)
+    out = np.zeros(a.shape, dtype=np.uint8)
+    if len(roots):
+        w = int(np.argmax(sizes))                                  # the first maximum; roots ascend
+        info[1], info[2] = roots[w], sizes[w]
+        out = (lab == roots[w]).astype(np.uint8).reshape(a.shape)
+    return (out, info) if with_info else out
+
+
+def fill_holes_host(seg, with_info=False):
+    """alq_fill_holes on the host: uint8 mask = scipy.ndimage.binary_fill_holes(seg) of the 3-D volume (default structure: the
+    zero voxels are 6-connected, and a zero voxel next to any of the six faces is outside).  A 2-D image is the volume
+    [H, W, 1], every voxel of which lies on a face: nothing is filled, as scipy has it for that 3-D array.  with_info:
+    (mask, np.int64 [4] = enclosed background components, voxels filled, 0, 0)."""
+    from scipy import ndimage
+    a = _as_volume(seg)
+    out = ndimage.binary_fill_holes(a != 0).astype(np.uint8)
+    filled = (out != 0) & (a == 0)
+    out = out.reshape(np.asarray(seg).shape)
+    if not with_info:
+        return out
+    n = ndimage.label(filled)[1]                                   # default structure: face neighbours
+    return out, np.array([n, int(filled.sum()), 0, 0], dtype=np.int64)
