@@ -20,24 +20,18 @@
 //    logit-difference partials, sign bytes, flip marks, the head's input sum) is spread over the rows of step z, each
 //    row just before its accumulators are restarted.
 //  * compile-time geometry: every LDS offset is an instruction immediate, no descriptor tables, no per-slot EXEC masks.
-#include "alq_internal.h"
+#include "f16_pair.h"
+#include "sweep_common.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <type_traits>
 #include <vector>
 
 namespace alq {
 
 namespace {
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-template <int V> using IC = std::integral_constant<int, V>;
 // __builtin_amdgcn_sched_barrier mask: VALU (2), SALU (4), all DS (0x80 | 0x100 | 0x200), transcendentals (0x400) may cross;
 // MFMA (8) and vector memory (0x10 | 0x20 | 0x40) may not
 #ifndef C3_SCHED_MASK
@@ -62,12 +56,8 @@ static_assert(C3_WD >= 1 && C3_WD <= 8, "weight-difference slices are fetched 1.
 #ifndef C3_PIPE
 #define C3_PIPE 2
 #endif
-// what may fill the gap behind an MFMA in the sweep's 1 : C3_PIPE pattern: VALU (0x002) + SALU (0x004) + vector memory (0x010) + LDS
-// (0x080).  With VALU alone the address arithmetic, loads and fragment reads piled up in a few gaps (a gap with up to two fillers is
-// free, each further one costs its issue cycles - tools/probe/mfma_chain_probe.hip): -4 % cycles per step, of which the power-limited
-// clock gives back about a third
 #ifndef C3_FILL_MASK
-#define C3_FILL_MASK 0x096
+#define C3_FILL_MASK SW_FILL_MASK
 #endif
 #ifndef C3_PIN_SUMS
 #define C3_PIN_SUMS 1
@@ -185,26 +175,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     // arrays are written by earlier launches only.)
     typedef const unsigned __attribute__((address_space(4))) *cu32p;
     const cu32p amaxA_c = (cu32p)(unsigned long long)a.amaxA, amaxB_c = (cu32p)(unsigned long long)a.amaxB;
-    auto patch_exp = [&](int p) __attribute__((always_inline)) {      // max |x| < 2^ex -> scale 2^(14 - ex); all-zero patch: 0
+    auto patch_exp = [&](int p) __attribute__((always_inline)) {      // (the larger of the two tensors' bounds)
         const unsigned fa = amaxA_c[p], fb = amaxB_c[p];
-        const unsigned fm = fa > fb ? fa : fb;
-        const int ex = (int)((fm >> 23) & 255u) - 126;
-        // (a patch whose maximum is below 2^-82 - fp32 subnormals included - keeps the scale 2^96: 2^(14 - ex) would overflow
-        // the scale or underflow its inverse; such inputs are then simply small fp16 values)
-        const int ce = 14 - ex;
-        return fm ? (ce < 96 ? ce : 96) : 0;
+        return sw_patch_exp(fa > fb ? fa : fb);
     };
-    // ONE buffer resource per array for the whole launch: the patch goes into the scalar offset (not range-checked by the
-    // hardware), a lane with nothing to load or store aims past the array through its VECTOR offset (loads return 0, stores
-    // are dropped).  N < 4096 patches of 1 MiB keep every byte offset below 2^32 (the host checks).
-    auto rsrc_of = [&](const void *base, unsigned long long bytes) __attribute__((always_inline)) {
-        return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, (int)(unsigned)bytes, 0x00020000);
-    };
-    const unsigned OOB = 0xffffff00u;
-    const __amdgpu_buffer_rsrc_t inA_rsrc = rsrc_of(a.inA, (unsigned long long)a.N * patch_f * 4u);
-    const __amdgpu_buffer_rsrc_t inB_rsrc = rsrc_of(a.inB, (unsigned long long)a.N * patch_f * 4u);
-    const __amdgpu_buffer_rsrc_t wd_rsrc = rsrc_of(a.fc_W, (unsigned long long)patch_f * 4u);
-    const __amdgpu_buffer_rsrc_t bits_rsrc = rsrc_of(a.fc_bits, (SUMS && a.fc_bits) ? (unsigned long long)a.N * (patch_f >> 2) : 0ull);
+    const __amdgpu_buffer_rsrc_t inA_rsrc = sw_rsrc(a.inA, (unsigned long long)a.N * patch_f * 4u);
+    const __amdgpu_buffer_rsrc_t inB_rsrc = sw_rsrc(a.inB, (unsigned long long)a.N * patch_f * 4u);
+    const __amdgpu_buffer_rsrc_t wd_rsrc = sw_rsrc(a.fc_W, (unsigned long long)patch_f * 4u);
+    const __amdgpu_buffer_rsrc_t bits_rsrc = sw_rsrc(a.fc_bits, (SUMS && a.fc_bits) ? (unsigned long long)a.N * (patch_f >> 2) : 0ull);
     auto patch_of = [&](int pi) __attribute__((always_inline)) { return (unsigned)(b0 + pi * G); };
 
     // ---- staging: unit u = 0..15 of a plane: row 8 w + (u >> 1), tensor u & 1: 1 KB of fp32 per wave instruction ------------
@@ -231,7 +209,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         *reinterpret_cast<uint2 *>(dst) = uint2{__builtin_bit_cast(unsigned, h01), __builtin_bit_cast(unsigned, h23)};
         *reinterpret_cast<uint2 *>(dst + C3_PIECE) = uint2{__builtin_bit_cast(unsigned, l01), __builtin_bit_cast(unsigned, l23)};
     };
-    // voff = lane * 16 or OOB (no such plane), soff = byte offset of row 8 w of the plane inside the array
+    // voff = lane * 16 or SW_OOB (no such plane), soff = byte offset of row 8 w of the plane inside the array
     auto load_unit = [&](unsigned voff, unsigned soff, auto U) __attribute__((always_inline)) {
         constexpr int u = decltype(U)::value;
         R4[u % C3_PF] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128((u & 1) ? inB_rsrc : inA_rsrc, (int)voff, (int)(soff + (unsigned)((u % 16) >> 1) * 1024u), 0));
@@ -240,7 +218,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     auto cursor = [&](int pi, int z) __attribute__((always_inline)) {
         Cur c;
         const bool ok = pi < np;
-        c.voff = ok ? (unsigned)lane * 16u : OOB;
+        c.voff = ok ? (unsigned)lane * 16u : SW_OOB;
         c.soff = ok ? (patch_of(pi) * patch_f + (unsigned)z * plane_f) * 4u + (unsigned)(wave * 8) * 1024u : 0u;
         if constexpr (C3_ABL & 8) c.soff = (unsigned)(wave * 8) * 1024u;
         return c;
@@ -271,8 +249,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         // all-zero window, +0 in the exact evaluation too); under a non-zero bias +0 can be acc * inv == -bias, or inputs flushed by
         // the fp16 split, with a tiny positive exact value: those are marked (key 0 instead of 0x7fffffff)
         e.zadj = (bias4.x == 0.f && bias4.y == 0.f && bias4.z == 0.f && bias4.w == 0.f) ? 1u : 0u;
-        e.off_w = valid ? epi_lane_f * 4u : OOB;
-        e.off_b = valid ? (epi_lane_f >> 2) : OOB;
+        e.off_w = valid ? epi_lane_f * 4u : SW_OOB;
+        e.off_b = valid ? (epi_lane_f >> 2) : SW_OOB;
         e.row_f = (unsigned)(zo * 32 + wave * 8) * 256u;       // float offset of row 8 w of that plane inside the patch
         e.bits_s = (unsigned)p * (patch_f >> 2);
         return e;
@@ -629,20 +607,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
         for (int i = 0; i < RW; ++i) { acc[s][i][0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[s][i][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
 
-    // ONE buffer resource per array for the whole launch (no per-step descriptor building, few scalar registers): the patch
-    // goes into the scalar offset - which the hardware does not range-check - and a lane with nothing to load or store aims
-    // past the array through its VECTOR offset (loads then return 0, stores are dropped).  N < 4096 patches keep every
-    // offset below 2^32 (the host checks).
-    auto rsrc_of = [&](const void *base, unsigned long long bytes) __attribute__((always_inline)) {
-        return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, (int)(unsigned)bytes, 0x00020000);
-    };
-    const unsigned OOB = 0xffffff00u;
-    const __amdgpu_buffer_rsrc_t vec_rsrc = rsrc_of(a.vec, (unsigned long long)patch_v * 32u);
-    const __amdgpu_buffer_rsrc_t bits_rsrc = rsrc_of(a.bits, (unsigned long long)a.N * patch_v * 2u);
-    const __amdgpu_buffer_rsrc_t mask_rsrc = rsrc_of(a.maskA, a.maskA ? (unsigned long long)a.N * patch_v * 2u : 0ull);
-    const __amdgpu_buffer_rsrc_t dB_rsrc = rsrc_of(a.dB, (unsigned long long)a.N * patch_v * 32u);
-    const __amdgpu_buffer_rsrc_t sA_rsrc = rsrc_of(a.sumA, (unsigned long long)a.N * patch_v * 4u);
-    const __amdgpu_buffer_rsrc_t sB_rsrc = rsrc_of(a.sumB, (unsigned long long)a.N * patch_v * 4u);
+    const __amdgpu_buffer_rsrc_t vec_rsrc = sw_rsrc(a.vec, (unsigned long long)patch_v * 32u);
+    const __amdgpu_buffer_rsrc_t bits_rsrc = sw_rsrc(a.bits, (unsigned long long)a.N * patch_v * 2u);
+    const __amdgpu_buffer_rsrc_t mask_rsrc = sw_rsrc(a.maskA, a.maskA ? (unsigned long long)a.N * patch_v * 2u : 0ull);
+    const __amdgpu_buffer_rsrc_t dB_rsrc = sw_rsrc(a.dB, (unsigned long long)a.N * patch_v * 32u);
+    const __amdgpu_buffer_rsrc_t sA_rsrc = sw_rsrc(a.sumA, (unsigned long long)a.N * patch_v * 4u);
+    const __amdgpu_buffer_rsrc_t sB_rsrc = sw_rsrc(a.sumB, (unsigned long long)a.N * patch_v * 4u);
     auto item_patch = [&](int pi) __attribute__((always_inline)) { return (unsigned)((b0 + pi * G) / NPARTS); };
     auto item_y0 = [&](int pi) __attribute__((always_inline)) { return ((b0 + pi * G) % NPARTS) * NR; };
 
@@ -650,7 +620,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     // edge wave (wave 0: row y0 - 1, wave 3: row y0 + NR; lanes 0..31, zeros outside the patch) ----------------------------
     i32x4 Vh[2], Vl[2], Hh, Hl;
     unsigned Sb[2], Hb = 0u;
-    struct Src { unsigned voff, vvox, soff; };      // lane offset into the sign bytes (or OOB), lane voxel inside the plane, patch offset
+    struct Src { unsigned voff, vvox, soff; };      // lane offset into the sign bytes (or SW_OOB), lane voxel inside the plane, patch offset
     auto src_of = [&](int pi, bool halo) __attribute__((always_inline)) {
         Src c;
         const bool ok = pi < np;
@@ -662,7 +632,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             live = ok && lane < 32 && y >= 0 && y < 32;
         }
         c.vvox = (unsigned)((live ? y : 0) * 32 + (lane & 31));
-        c.voff = live ? c.vvox * 2u : OOB;
+        c.voff = live ? c.vvox * 2u : SW_OOB;
         c.soff = ok ? item_patch(pi) * patch_v * 2u : 0u;
         return c;
     };
@@ -722,11 +692,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         e.row_v = (unsigned)(zo * 32 + (valid ? item_y0(pe) : 0) + wave * RW) * 32u;
         e.inv = valid ? inv : 0.f;
         // lane offsets; an invalid step (no finished plane) sends every access past the arrays
-        e.off_mask = (valid && lq < 2) ? (unsigned)(lj * 2 + lq) : OOB;
-        e.off_dB = (valid && lq >= 2) ? (unsigned)lj * 32u + (unsigned)(lq - 2) * 16u : OOB;
+        e.off_mask = (valid && lq < 2) ? (unsigned)(lj * 2 + lq) : SW_OOB;
+        e.off_dB = (valid && lq >= 2) ? (unsigned)lj * 32u + (unsigned)(lq - 2) * 16u : SW_OOB;
         // sums: after the cross-row add, lanes q = 0 / 1 hold the masked half's sum of half row 0 / 1 (x = j / 16 + j), lanes
         // q = 2 / 3 the stored half's: one 128-byte store per field and row
-        e.off_sum = valid ? (unsigned)((lq & 1) * 16 + lj) * 4u : OOB;
+        e.off_sum = valid ? (unsigned)((lq & 1) * 16 + lj) * 4u : SW_OOB;
         return e;
     };
     auto mask_load = [&](const Epi &E, auto I) __attribute__((always_inline)) {
@@ -778,8 +748,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             const float ts = t_keep + t2;
             const unsigned rowv = E.pv + E.row_v + (unsigned)i * 32u;
             // lanes q < 2 -> the masked half's field, q >= 2 -> the stored half's: two stores, each with the other half of the wave off
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, ts), sA_rsrc, (int)(lq < 2 ? E.off_sum : OOB), (int)(rowv * 4u), 0);
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, ts), sB_rsrc, (int)(lq >= 2 ? E.off_sum : OOB), (int)(rowv * 4u), 0);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, ts), sA_rsrc, (int)(lq < 2 ? E.off_sum : SW_OOB), (int)(rowv * 4u), 0);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, ts), sB_rsrc, (int)(lq >= 2 ? E.off_sum : SW_OOB), (int)(rowv * 4u), 0);
         }
     };
     auto epi_row = [&](auto S, auto I, const Epi &E) __attribute__((always_inline)) {
@@ -1015,16 +985,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
         for (int i = 0; i < RW; ++i) { acc[s][i][0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[s][i][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
 
-    auto rsrc_of = [&](const void *base, unsigned long long bytes) __attribute__((always_inline)) {
-        return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, (int)(unsigned)bytes, 0x00020000);
-    };
-    const unsigned OOB = 0xffffff00u;
-    const __amdgpu_buffer_rsrc_t vec_rsrc = rsrc_of(a.vec, (unsigned long long)patch_v * 32u);
-    const __amdgpu_buffer_rsrc_t bits_rsrc = rsrc_of(a.bits, (unsigned long long)a.N * patch_v * 2u);
-    const __amdgpu_buffer_rsrc_t mask_rsrc = rsrc_of(a.maskA, a.maskA ? (unsigned long long)a.N * patch_v * 2u : 0ull);
-    const __amdgpu_buffer_rsrc_t dB_rsrc = rsrc_of(a.dB, (unsigned long long)a.N * patch_v * 32u);
-    const __amdgpu_buffer_rsrc_t sA_rsrc = rsrc_of(a.sumA, (unsigned long long)a.N * patch_v * 4u);
-    const __amdgpu_buffer_rsrc_t sB_rsrc = rsrc_of(a.sumB, (unsigned long long)a.N * patch_v * 4u);
+    const __amdgpu_buffer_rsrc_t vec_rsrc = sw_rsrc(a.vec, (unsigned long long)patch_v * 32u);
+    const __amdgpu_buffer_rsrc_t bits_rsrc = sw_rsrc(a.bits, (unsigned long long)a.N * patch_v * 2u);
+    const __amdgpu_buffer_rsrc_t mask_rsrc = sw_rsrc(a.maskA, a.maskA ? (unsigned long long)a.N * patch_v * 2u : 0ull);
+    const __amdgpu_buffer_rsrc_t dB_rsrc = sw_rsrc(a.dB, (unsigned long long)a.N * patch_v * 32u);
+    const __amdgpu_buffer_rsrc_t sA_rsrc = sw_rsrc(a.sumA, (unsigned long long)a.N * patch_v * 4u);
+    const __amdgpu_buffer_rsrc_t sB_rsrc = sw_rsrc(a.sumB, (unsigned long long)a.N * patch_v * 4u);
     auto item_patch = [&](int pi) __attribute__((always_inline)) { return (unsigned)(b0 + pi * G); };
 
     // ---- staging of a plane: units u = 0 .. 3 (rows 8 w + 2 u, + 1): as in the kernel above ------------------------------------
@@ -1036,7 +1002,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         const bool ok = pi < np;
         const int y = wave * RW + (lane >> 5);
         c.vvox = (unsigned)(y * 32 + (lane & 31));
-        c.voff = ok ? c.vvox * 2u : OOB;
+        c.voff = ok ? c.vvox * 2u : SW_OOB;
         c.soff = ok ? item_patch(pi) * patch_v * 2u : 0u;
         return c;
     };
@@ -1077,9 +1043,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         e.pv = valid ? item_patch(pe) * patch_v : 0u;
         e.row_v = (unsigned)(zo * 32 + wave * RW) * 32u;
         e.inv = valid ? inv : 0.f;
-        e.off_mask = (valid && lq < 2) ? (unsigned)(lj * 2 + lq) : OOB;
-        e.off_dB = (valid && lq >= 2) ? (unsigned)lj * 32u + (unsigned)(lq - 2) * 16u : OOB;
-        e.off_sum = valid ? (unsigned)((lq & 1) * 16 + lj) * 4u : OOB;
+        e.off_mask = (valid && lq < 2) ? (unsigned)(lj * 2 + lq) : SW_OOB;
+        e.off_dB = (valid && lq >= 2) ? (unsigned)lj * 32u + (unsigned)(lq - 2) * 16u : SW_OOB;
+        e.off_sum = valid ? (unsigned)((lq & 1) * 16 + lj) * 4u : SW_OOB;
         return e;
     };
     auto mask_load = [&](const Epi &E, auto I) __attribute__((always_inline)) {
@@ -1119,8 +1085,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         } else {
             const float ts = t_keep + t2;
             const unsigned rowv = E.pv + E.row_v + (unsigned)i * 32u;
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, ts), sA_rsrc, (int)(lq < 2 ? E.off_sum : OOB), (int)(rowv * 4u), 0);
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, ts), sB_rsrc, (int)(lq >= 2 ? E.off_sum : OOB), (int)(rowv * 4u), 0);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, ts), sA_rsrc, (int)(lq < 2 ? E.off_sum : SW_OOB), (int)(rowv * 4u), 0);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, ts), sB_rsrc, (int)(lq >= 2 ? E.off_sum : SW_OOB), (int)(rowv * 4u), 0);
         }
     };
     auto epi_row = [&](auto S, auto I, const Epi &E) __attribute__((always_inline)) {
@@ -1305,7 +1271,7 @@ int c3d_subnormals_ok(alq_ctx *ctx) {
 int c3d_fwd_build(const View &in, const View &out, const int k[3], const int lo[3], const int s[3], C3dPlan *plan) {
     plan->ok = false;
     if (getenv("ALQ_NO_C3D")) return ALQ_OK;
-    if (!(k[0] == 3 && k[1] == 3 && k[2] == 3 && lo[0] == 1 && lo[1] == 1 && lo[2] == 1 && s[0] == 1 && s[1] == 1 && s[2] == 1)) return ALQ_OK;
+    if (!is_conv3_same(k, lo, s)) return ALQ_OK;
     if (!(in.D == 32 && in.H == 32 && in.W == 32 && out.D == 32 && out.H == 32 && out.W == 32)) return ALQ_OK;
     if (!(in.C == 16 && in.split == 8 && in.cs == 8 && in.c0 == 0 && out.C == 8)) return ALQ_OK;
     plan->D = in.D;
@@ -1319,11 +1285,7 @@ int c3d_fwd_build(const View &in, const View &out, const int k[3], const int lo[
 // voxel v = i >> 3 of the x pair, channel co = i & 7; k-group kg = lane >> 4 -> tensor t = kg >> 1, x parity p = kg & 1):
 // window position q = 2 s + p holds input x = 2 r - 1 + q, i.e. x tap index q - v of output voxel 2 r + v.
 void c3d_fwd_pack(C3dPlan *plan, const std::vector<float> &Bmat) {
-    float amax = 0.f;
-    for (float w : Bmat) amax = std::max(amax, std::fabs(w));
-    int ex = 0;
-    if (amax > 0.f) (void)std::frexp(amax, &ex);
-    plan->w_exp = 14 - ex;
+    plan->w_exp = f16_pair_exp(Bmat.data(), Bmat.size());
     plan->h_W.assign((size_t)18 * 2 * 64 * 8, 0);
     for (int dzi = 0; dzi < 3; ++dzi)
         for (int dyi = 0; dyi < 3; ++dyi)
@@ -1335,14 +1297,8 @@ void c3d_fwd_pack(C3dPlan *plan, const std::vector<float> &Bmat) {
                     for (int c = 0; c < 8; ++c) {
                         float w = 0.f;
                         if (dxi >= 0 && dxi <= 2) w = Bmat[((size_t)((dzi * 3 + dyi) * 3 + dxi) * 16 + 8 * t + c) * 8 + co];
-                        const float ws = std::ldexp(w, plan->w_exp);
-                        const _Float16 h = (_Float16)ws;
-                        const _Float16 l = (_Float16)std::ldexp(ws - (float)h, plan->oneacc ? 0 : 11);
-                        unsigned short hb, lb;
-                        std::memcpy(&hb, &h, 2);
-                        std::memcpy(&lb, &l, 2);
-                        plan->h_W[((size_t)(ks * 2 + 0) * 64 + lane) * 8 + c] = hb;
-                        plan->h_W[((size_t)(ks * 2 + 1) * 64 + lane) * 8 + c] = lb;
+                        f16_pair_split(w, plan->w_exp, plan->oneacc ? 0 : 11, &plan->h_W[((size_t)(ks * 2 + 0) * 64 + lane) * 8 + c],
+                                       &plan->h_W[((size_t)(ks * 2 + 1) * 64 + lane) * 8 + c]);
                     }
                 }
 }
@@ -1352,7 +1308,7 @@ int c3d_fwd_launch(alq_ctx *ctx, const C3dPlan &plan, const View &in, const floa
     ALQ_REQUIRE(plan.ok && plan.d_W, ALQ_EINVAL, "c3d: weights not set");
     ALQ_REQUIRE(in.split == 8 && in.cs == 8 && in.C == 16 && in.D == plan.D && in.H == 32 && in.W == 32 && plan.D == 32, ALQ_EINVAL, "c3d: input view mismatch");
     ALQ_REQUIRE(amaxA && amaxB && fc_W && fc_part && bias, ALQ_EINVAL, "c3d: missing argument");
-    ALQ_REQUIRE(N < 4096, ALQ_EUNSUPPORTED, "c3d: 32-bit byte offsets hold fewer than 4096 patches per pass");
+    SWEEP_REQUIRE_PATCHES(N, "c3d");
     if (N <= 0) return ALQ_OK;
     C3FwdArgs a;
     a.inA = in.p; a.inB = in.p + in.delta; a.W = plan.d_W; a.bias = bias; a.amaxA = amaxA; a.amaxB = amaxB;
@@ -1360,15 +1316,9 @@ int c3d_fwd_launch(alq_ctx *ctx, const C3dPlan &plan, const View &in, const floa
     a.flip_tau = flip_tau; a.clk = nullptr;
     const unsigned grid = (unsigned)std::min(N, 256);
     ProfScope ps(ctx, PROF_IGEMM_F16, plan.flops_per_patch * N);
-    auto go = [&](auto kfn) -> int {
-        ALQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, C3_LDS));
-        hipLaunchKernelGGL(kfn, dim3(grid), dim3(256), C3_LDS, ctx->stream, a);
-        return ALQ_OK;
-    };
-    if (fc_bits) ALQ_TRY(plan.oneacc ? go(c3d_fwd_kernel<true, true>) : go(c3d_fwd_kernel<true, false>));
-    else ALQ_TRY(plan.oneacc ? go(c3d_fwd_kernel<false, true>) : go(c3d_fwd_kernel<false, false>));
-    ALQ_HIP(hipGetLastError());
-    return ALQ_OK;
+    auto go = [&](auto kfn) { return sweep_launch(ctx, kfn, grid, 256, C3_LDS, a); };
+    if (fc_bits) return plan.oneacc ? go(c3d_fwd_kernel<true, true>) : go(c3d_fwd_kernel<true, false>);
+    return plan.oneacc ? go(c3d_fwd_kernel<false, true>) : go(c3d_fwd_kernel<false, false>);
 }
 
 // ---- backward ------------------------------------------------------------------------------------------------------------
@@ -1386,11 +1336,7 @@ int c3d_bwd_build(const View &fwd_in, const View &fwd_out, const int k[3], const
 // output voxel, k-group kg = x offset kg - 1 (kg = 3: zero): the forward tap that links them is (2 - dzi, 2 - di, 2 - kg).
 // A-operand row i = output channel ci (0..15), elements c = the 8 channels co of the cotangent.
 void c3d_bwd_pack(C3dPlan *plan, const std::vector<float> &Bmat) {
-    float amax = 0.f;
-    for (float w : Bmat) amax = std::max(amax, std::fabs(w));
-    int ex = 0;
-    if (amax > 0.f) (void)std::frexp(amax, &ex);
-    plan->w_exp = 14 - ex;
+    plan->w_exp = f16_pair_exp(Bmat.data(), Bmat.size());
     plan->h_W.assign((size_t)9 * 2 * 64 * 8, 0);
     for (int dzi = 0; dzi < 3; ++dzi)
         for (int di = 0; di < 3; ++di)
@@ -1400,14 +1346,7 @@ void c3d_bwd_pack(C3dPlan *plan, const std::vector<float> &Bmat) {
                 for (int c = 0; c < 8; ++c) {
                     float w = 0.f;
                     if (kg < 3) w = Bmat[((size_t)(((2 - dzi) * 3 + (2 - di)) * 3 + (2 - kg)) * 16 + ci) * 8 + c];
-                    const float ws = std::ldexp(w, plan->w_exp);
-                    const _Float16 h = (_Float16)ws;
-                    const _Float16 l = (_Float16)(ws - (float)h);
-                    unsigned short hb, lb;
-                    std::memcpy(&hb, &h, 2);
-                    std::memcpy(&lb, &l, 2);
-                    plan->h_W[((size_t)(ks * 2 + 0) * 64 + lane) * 8 + c] = hb;
-                    plan->h_W[((size_t)(ks * 2 + 1) * 64 + lane) * 8 + c] = lb;
+                    f16_pair_split(w, plan->w_exp, 0, &plan->h_W[((size_t)(ks * 2 + 0) * 64 + lane) * 8 + c], &plan->h_W[((size_t)(ks * 2 + 1) * 64 + lane) * 8 + c]);
                 }
             }
 }
@@ -1428,14 +1367,7 @@ void c3d_bwd7_pack(C3dPlan *plan, const std::vector<float> &Bmat) {
             for (int c = 0; c < 8; ++c) {
                 float w = 0.f;
                 if (dz >= 0) w = Bmat[((size_t)(((2 - dz) * 3 + (2 - dy)) * 3 + (2 - dx)) * 16 + ci) * 8 + c];
-                const float ws = std::ldexp(w, plan->w_exp);
-                const _Float16 h = (_Float16)ws;
-                const _Float16 l = (_Float16)(ws - (float)h);
-                unsigned short hb, lb;
-                std::memcpy(&hb, &h, 2);
-                std::memcpy(&lb, &l, 2);
-                plan->h_W7[((size_t)(f * 2 + 0) * 64 + lane) * 8 + c] = hb;
-                plan->h_W7[((size_t)(f * 2 + 1) * 64 + lane) * 8 + c] = lb;
+                f16_pair_split(w, plan->w_exp, 0, &plan->h_W7[((size_t)(f * 2 + 0) * 64 + lane) * 8 + c], &plan->h_W7[((size_t)(f * 2 + 1) * 64 + lane) * 8 + c]);
             }
         }
 }
@@ -1444,23 +1376,14 @@ void c3d_bwd7_pack(C3dPlan *plan, const std::vector<float> &Bmat) {
 void c3d_presplit_vec(const float *v, long long F, int e, std::vector<unsigned short> *out) {
     out->assign((size_t)F * 2, 0);
     for (long long vox = 0; vox < F / 8; ++vox)
-        for (int c = 0; c < 8; ++c) {
-            const float xs = std::ldexp(v[vox * 8 + c], e);
-            const _Float16 h = (_Float16)xs;
-            const _Float16 l = (_Float16)(xs - (float)h);
-            unsigned short hb, lb;
-            std::memcpy(&hb, &h, 2);
-            std::memcpy(&lb, &l, 2);
-            (*out)[(size_t)vox * 16 + c] = hb;
-            (*out)[(size_t)vox * 16 + 8 + c] = lb;
-        }
+        for (int c = 0; c < 8; ++c) f16_pair_split(v[vox * 8 + c], e, 0, &(*out)[(size_t)vox * 16 + c], &(*out)[(size_t)vox * 16 + 8 + c]);
 }
 
 int c3d_bwd_launch(alq_ctx *ctx, const C3dPlan &plan, int N, const unsigned char *bits, const void *vec16, int e_in, const unsigned char *maskA,
                    float *dB, float *sumA, float *sumB, int rows_per_wave) {
     ALQ_REQUIRE(plan.ok && plan.d_W && plan.D == 32, ALQ_EINVAL, "c3d: backward weights not set");
     ALQ_REQUIRE(bits && vec16 && dB && sumA && sumB, ALQ_EINVAL, "c3d: missing argument");
-    ALQ_REQUIRE(N < 4096, ALQ_EUNSUPPORTED, "c3d: 32-bit byte offsets hold fewer than 4096 patches per pass");
+    SWEEP_REQUIRE_PATCHES(N, "c3d");
     if (N <= 0) return ALQ_OK;
     C3BwdArgs a;
     a.bits = bits; a.vec = vec16; a.W = plan.d_W; a.maskA = maskA; a.dB = dB; a.sumA = sumA; a.sumB = sumB;
@@ -1472,22 +1395,10 @@ int c3d_bwd_launch(alq_ctx *ctx, const C3dPlan &plan, int N, const unsigned char
     const int rows8 = rows_per_wave == 4 ? 0 : 1;
     if (rows_per_wave == 7 && plan.d_W7) {      // the 27 taps in 7 k-steps (default since round 6; ALQ_C3D_BWD_ROWS=8: the 9-k-step kernel)
         a.W = plan.d_W7;
-        auto kfn = c3d_bwd7_kernel;
-        ALQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, P7_LDS));
-        hipLaunchKernelGGL(kfn, dim3((unsigned)std::min(N, 256)), dim3(256), P7_LDS, ctx->stream, a);
-    } else if (rows8) {
-        auto kfn = c3d_bwd_kernel<true, 8>;
-        const int ldsb = 2 * (32 + 2) * B3_ROW + 2 * B3_ROW;
-        ALQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, ldsb));
-        hipLaunchKernelGGL(kfn, dim3((unsigned)std::min(N, 256)), dim3(256), ldsb, ctx->stream, a);
-    } else {
-        auto kfn = c3d_bwd_kernel<true, 4>;
-        const int ldsb = 2 * (16 + 2) * B3_ROW + 2 * B3_ROW;
-        ALQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, ldsb));
-        hipLaunchKernelGGL(kfn, dim3((unsigned)std::min(2 * N, 256)), dim3(256), ldsb, ctx->stream, a);
+        return sweep_launch(ctx, c3d_bwd7_kernel, (unsigned)std::min(N, 256), 256, P7_LDS, a);
     }
-    ALQ_HIP(hipGetLastError());
-    return ALQ_OK;
+    if (rows8) return sweep_launch(ctx, c3d_bwd_kernel<true, 8>, (unsigned)std::min(N, 256), 256, 2 * (32 + 2) * B3_ROW + 2 * B3_ROW, a);
+    return sweep_launch(ctx, c3d_bwd_kernel<true, 4>, (unsigned)std::min(2 * N, 256), 256, 2 * (16 + 2) * B3_ROW + 2 * B3_ROW, a);
 }
 
 }  // namespace alq

@@ -20,7 +20,8 @@
 //     bytes (conflict-free), an x shift is +16 B;
 //   * the first and last input plane of a patch also run the MFMAs of the output planes outside the volume (4 % of the work; their
 //     sets are discarded) - no special steps, no control flow inside a patch except the loop of five times three steps.
-#include "alq_internal.h"
+#include "f16_pair.h"
+#include "sweep_common.h"
 
 #include <algorithm>
 #include <cmath>
@@ -29,13 +30,6 @@
 #include <vector>
 
 namespace alq {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 struct D3Args {
     const float *inA, *inB;       // [N][16^3][16]: channels 0 .. 15 / 16 .. 31 of the concat input (dense)
@@ -51,21 +45,12 @@ struct D3Args {
     int N;
 };
 
-constexpr unsigned D3_OOB = 0xffffff00u;
 constexpr int D3_KG = 18 * 16;                // a k-group block of a row: 18 voxel slots x 8 channels x 2 B
 constexpr int D3_ROWB = 4 * D3_KG;            // one piece of a row: 1152 B
 constexpr int D3_SLOT = 2 * D3_ROWB;          // a row: pieces h, l
 constexpr int D3_PLANE = 18 * D3_SLOT;        // image of a plane: rows y = -1 .. 16: 41,472 B
 constexpr int D3_STRIP = 2 * D3_PLANE;        // the plane being contracted and the one being staged: 82,944 B
 
-__device__ inline __amdgpu_buffer_rsrc_t d3_rsrc(const void *base, unsigned long long bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, (int)(unsigned)bytes, 0x00020000);
-}
-__device__ inline int d3_s(unsigned v) { return __builtin_amdgcn_readfirstlane((int)v); }
-
-template <int V> struct D3IC { static constexpr int value = V; };
-// what may fill the gap behind an MFMA: VALU (2), SALU (4), VMEM (0x10), DS (0x80)
-constexpr int D3_FILL_MASK = 0x096;
 #ifndef D3_PIPE
 #define D3_PIPE 2
 #endif
@@ -97,19 +82,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 
     typedef const unsigned __attribute__((address_space(4))) *cu32p;
     const cu32p amaxA_c = (cu32p)(unsigned long long)a.amaxA, amaxB_c = (cu32p)(unsigned long long)a.amaxB;
-    auto patch_exp = [&](int p) __attribute__((always_inline)) {      // max |x| < 2^ex -> scale 2^(14 - ex); all-zero patch: 0  (c3d_fwd_kernel)
+    auto patch_exp = [&](int p) __attribute__((always_inline)) {      // (the larger of the two halves' bounds)
         const unsigned fa = amaxA_c[p], fb = amaxB_c[p];
-        const unsigned fm = fa > fb ? fa : fb;
-        const int ex = (int)((fm >> 23) & 255u) - 126;
-        const int ce = 14 - ex;
-        return fm ? (ce < 96 ? ce : 96) : 0;
+        return sw_patch_exp(fa > fb ? fa : fb);
     };
 
-    const __amdgpu_buffer_rsrc_t ia_rsrc = d3_rsrc(a.inA, (unsigned long long)a.N * 4096 * 64);
-    const __amdgpu_buffer_rsrc_t ib_rsrc = d3_rsrc(a.inB, (unsigned long long)a.N * 4096 * 64);
-    const __amdgpu_buffer_rsrc_t o_rsrc = d3_rsrc(a.out, (unsigned long long)a.N * 4096 * 64);
-    const __amdgpu_buffer_rsrc_t s_rsrc = d3_rsrc(a.sg, a.sg ? (unsigned long long)a.N * 4096 * 4 : 0ull);
-    const __amdgpu_buffer_rsrc_t u_rsrc = d3_rsrc(a.osum, a.osum ? (unsigned long long)a.N * 4096 * 4 : 0ull);
+    const __amdgpu_buffer_rsrc_t ia_rsrc = sw_rsrc(a.inA, (unsigned long long)a.N * 4096 * 64);
+    const __amdgpu_buffer_rsrc_t ib_rsrc = sw_rsrc(a.inB, (unsigned long long)a.N * 4096 * 64);
+    const __amdgpu_buffer_rsrc_t o_rsrc = sw_rsrc(a.out, (unsigned long long)a.N * 4096 * 64);
+    const __amdgpu_buffer_rsrc_t s_rsrc = sw_rsrc(a.sg, a.sg ? (unsigned long long)a.N * 4096 * 4 : 0ull);
+    const __amdgpu_buffer_rsrc_t u_rsrc = sw_rsrc(a.osum, a.osum ? (unsigned long long)a.N * 4096 * 4 : 0ull);
 
     // staging lane roles: voxel x = lane >> 2 of a row, channels 4 cq .. + 3 of each half: k-group 2 h + (cq >> 1), bytes 8 (cq & 1) ..; image row 4 w + 1 + r
     const int sx = lane >> 2, cq = lane & 3;
@@ -119,13 +101,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const char *const f_base = strip + 4 * wave * D3_SLOT + kg * D3_KG + n * 16;
     // epilogue lane roles: voxel x = n of the output row, channels 4 kg .. + 3
     const unsigned e_out = (unsigned)n * 64u + (unsigned)kg * 16u, e_sg = (unsigned)n * 4u + (unsigned)kg;
-    const unsigned e_sum = kg == 0 ? (unsigned)n * 4u : D3_OOB;
+    const unsigned e_sum = kg == 0 ? (unsigned)n * 4u : SW_OOB;
 
-    // patches of this workgroup (XCD-aware as in t3d.hip): workgroup b of XCD b % 8 takes k = b / 8, b / 8 + G / 8, ... of the patches 8 k + b % 8
-    const int G8 = (int)gridDim.x >> 3, xcd = (int)blockIdx.x & 7, jb = (int)blockIdx.x >> 3;
-    const int npx = a.N > xcd ? (a.N - xcd + 7) >> 3 : 0;
-    const int npw = npx > jb ? (npx - jb + G8 - 1) / G8 : 0;
-    auto patch_of = [&](int i) __attribute__((always_inline)) { return 8 * (jb + (i < npw ? i : npw - 1) * G8) + xcd; };
+    SW_PATCH_ORDER(a.N);
 
     D3Row RA[4];
     // loads of this wave's four rows of plane q of the workgroup's sequence (patch q >> 4, plane q & 15)
@@ -133,8 +111,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         const unsigned row0 = ((unsigned)patch_of(q >> 4) * 16u + (unsigned)(q & 15)) * 16u + 4u * (unsigned)wave;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            RA[r].a = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ia_rsrc, (int)ldA, d3_s((row0 + r) * 1024u), 0));
-            RA[r].b = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ib_rsrc, (int)ldA, d3_s((row0 + r) * 1024u), 0));
+            RA[r].a = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ia_rsrc, (int)ldA, sw_s((row0 + r) * 1024u), 0));
+            RA[r].b = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ib_rsrc, (int)ldA, sw_s((row0 + r) * 1024u), 0));
         }
     };
     // unit u = 2 r + h: half h of row r of RA -> image `img` (scale 2^ce)
@@ -161,7 +139,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     // finish row ry of the plane held by set ST: plane zo of patch p (tv: it exists), then clear the set's row
     auto epi_row = [&](auto ST, auto RY, int p, int zo, bool tv, float inv) __attribute__((always_inline)) {
         constexpr int st = decltype(ST)::value, ry = decltype(RY)::value;
-        const unsigned vrow = (unsigned)d3_s((((unsigned)p * 16u + (unsigned)(tv ? zo : 0)) * 16u + (unsigned)(4 * wave + ry)) * 16u);      // first voxel of the row
+        const unsigned vrow = (unsigned)sw_s((((unsigned)p * 16u + (unsigned)(tv ? zo : 0)) * 16u + (unsigned)(4 * wave + ry)) * 16u);      // first voxel of the row
         const f32x4 c = acc[st][ry], cx = acx[st][ry];      // (not cleared: the first MFMA of the set's next plane starts from zero)
         if (!D3_START) { acc[st][ry] = f32x4{0.f, 0.f, 0.f, 0.f}; acx[st][ry] = f32x4{0.f, 0.f, 0.f, 0.f}; }
         const float v0 = __builtin_fmaxf(__builtin_fmaf(__builtin_fmaf(cx.x, 0x1p-11f, c.x), inv, bias4.x), relu_floor);
@@ -170,14 +148,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         const float v3 = __builtin_fmaxf(__builtin_fmaf(__builtin_fmaf(cx.w, 0x1p-11f, c.w), inv, bias4.w), relu_floor);
         const f32x4 o = f32x4{v0, v1, v2, v3};
         okeep[ry & 1] = o;
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, o), o_rsrc, (int)(tv ? e_out : D3_OOB), (int)(vrow * 64u), 0);
-        ALQ_STORE_HOLD("v"(o));      // (a 16-byte store with a scalar offset reads its data late: nothing may write these registers in the next cycles, t3d_fwd_kernel)
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, o), o_rsrc, (int)(tv ? e_out : SW_OOB), (int)(vrow * 64u), 0);
+        ALQ_STORE_HOLD("v"(o));      // (a 16-byte store with a scalar offset reads its data late: nothing may write these registers in the next cycles)
         const unsigned bits = (v0 > 0.f ? 1u : 0u) | (v1 > 0.f ? 2u : 0u) | (v2 > 0.f ? 4u : 0u) | (v3 > 0.f ? 8u : 0u);
-        __builtin_amdgcn_raw_buffer_store_b8((unsigned char)bits, s_rsrc, (int)(tv ? e_sg : D3_OOB), (int)(vrow * 4u), 0);
+        __builtin_amdgcn_raw_buffer_store_b8((unsigned char)bits, s_rsrc, (int)(tv ? e_sg : SW_OOB), (int)(vrow * 4u), 0);
         float s_ = (v0 + v1) + (v2 + v3);
         s_ += __shfl_xor(s_, 16, 64);
         s_ += __shfl_xor(s_, 32, 64);
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, s_), u_rsrc, (int)(tv ? e_sum : D3_OOB), (int)(vrow * 4u), 0);
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, s_), u_rsrc, (int)(tv ? e_sum : SW_OOB), (int)(vrow * 4u), 0);
     };
 
     // Step s (J = s % 3) of patch i: image q & 1 holds input plane s (q = 16 i + s).  Block r = input row 4 w - 1 + r:
@@ -208,20 +186,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 fl[dx] = *reinterpret_cast<const f16x8 *>(fb + r * D3_SLOT + dx * 16 + D3_ROWB);
             }
         };
-        frag(D3IC<0>{}, Fh[0], Fl[0]);
+        frag(IC<0>{}, Fh[0], Fl[0]);
         auto block = [&](auto R) __attribute__((always_inline)) {
             constexpr int r = decltype(R)::value;
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (r + 1 < 6) frag(D3IC<r + 1>{}, Fh[(r + 1) % 2], Fl[(r + 1) % 2]);
-            if constexpr (r == 0) epi_row(D3IC<S0>{}, D3IC<3>{}, p, s - 2, s >= 2, inv);
-            if constexpr (r == 1) { stage_unit(D3IC<0>{}, img ^ 1, sc, sc11); stage_unit(D3IC<1>{}, img ^ 1, sc, sc11); stage_unit(D3IC<2>{}, img ^ 1, sc, sc11); stage_unit(D3IC<3>{}, img ^ 1, sc, sc11); }
-            if constexpr (r == 2) { stage_unit(D3IC<4>{}, img ^ 1, sc, sc11); stage_unit(D3IC<5>{}, img ^ 1, sc, sc11); stage_unit(D3IC<6>{}, img ^ 1, sc, sc11); stage_unit(D3IC<7>{}, img ^ 1, sc, sc11); }
+            if constexpr (r + 1 < 6) frag(IC<r + 1>{}, Fh[(r + 1) % 2], Fl[(r + 1) % 2]);
+            if constexpr (r == 0) epi_row(IC<S0>{}, IC<3>{}, p, s - 2, s >= 2, inv);
+            if constexpr (r == 1) { stage_unit(IC<0>{}, img ^ 1, sc, sc11); stage_unit(IC<1>{}, img ^ 1, sc, sc11); stage_unit(IC<2>{}, img ^ 1, sc, sc11); stage_unit(IC<3>{}, img ^ 1, sc, sc11); }
+            if constexpr (r == 2) { stage_unit(IC<4>{}, img ^ 1, sc, sc11); stage_unit(IC<5>{}, img ^ 1, sc, sc11); stage_unit(IC<6>{}, img ^ 1, sc, sc11); stage_unit(IC<7>{}, img ^ 1, sc, sc11); }
             if constexpr (r == 3) {
                 fetch(q + 2);
-                epi_row(D3IC<S2>{}, D3IC<0>{}, p, s - 1, s >= 1, inv);
+                epi_row(IC<S2>{}, IC<0>{}, p, s - 1, s >= 1, inv);
             }
-            if constexpr (r == 4) epi_row(D3IC<S2>{}, D3IC<1>{}, p, s - 1, s >= 1, inv);
-            if constexpr (r == 5) epi_row(D3IC<S2>{}, D3IC<2>{}, p, s - 1, s >= 1, inv);
+            if constexpr (r == 4) epi_row(IC<S2>{}, IC<1>{}, p, s - 1, s >= 1, inv);
+            if constexpr (r == 5) epi_row(IC<S2>{}, IC<2>{}, p, s - 1, s >= 1, inv);
             int nm = 0;
 #pragma unroll
             for (int dx = 0; dx < 3; ++dx) {
@@ -248,10 +226,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
             for (int m = 0; m < 27 * ((r == 0 || r == 5) ? 1 : ((r == 1 || r == 4) ? 2 : 3)); ++m) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(D3_FILL_MASK, D3_PIPE, 0);
+                __builtin_amdgcn_sched_group_barrier(SW_FILL_MASK, D3_PIPE, 0);
             }
         };
-        block(D3IC<0>{}); block(D3IC<1>{}); block(D3IC<2>{}); block(D3IC<3>{}); block(D3IC<4>{}); block(D3IC<5>{});
+        block(IC<0>{}); block(IC<1>{}); block(IC<2>{}); block(IC<3>{}); block(IC<4>{}); block(IC<5>{});
         __builtin_amdgcn_sched_barrier(0);
         // (16-byte store data is read late by the hardware: the last rows' registers stay theirs until here, t3d_fwd_kernel)
         const f32x4 k0 = okeep[0], k1 = okeep[1];
@@ -263,28 +241,28 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             fetch(0);
             const int ce = patch_exp(patch_of(0));
             const float sc = __builtin_ldexpf(1.f, ce), sc11 = __builtin_ldexpf(1.f, ce + 11);
-            stage_unit(D3IC<0>{}, 0, sc, sc11); stage_unit(D3IC<1>{}, 0, sc, sc11); stage_unit(D3IC<2>{}, 0, sc, sc11); stage_unit(D3IC<3>{}, 0, sc, sc11);
-            stage_unit(D3IC<4>{}, 0, sc, sc11); stage_unit(D3IC<5>{}, 0, sc, sc11); stage_unit(D3IC<6>{}, 0, sc, sc11); stage_unit(D3IC<7>{}, 0, sc, sc11);
+            stage_unit(IC<0>{}, 0, sc, sc11); stage_unit(IC<1>{}, 0, sc, sc11); stage_unit(IC<2>{}, 0, sc, sc11); stage_unit(IC<3>{}, 0, sc, sc11);
+            stage_unit(IC<4>{}, 0, sc, sc11); stage_unit(IC<5>{}, 0, sc, sc11); stage_unit(IC<6>{}, 0, sc, sc11); stage_unit(IC<7>{}, 0, sc, sc11);
             __builtin_amdgcn_sched_barrier(0);
             fetch(1);
         }
         for (int i = 0; i < npw; ++i) {
             for (int k = 0; k < 5; ++k) {
-                step(D3IC<0>{}, i, 3 * k);
-                step(D3IC<1>{}, i, 3 * k + 1);
-                step(D3IC<2>{}, i, 3 * k + 2);
+                step(IC<0>{}, i, 3 * k);
+                step(IC<1>{}, i, 3 * k + 1);
+                step(IC<2>{}, i, 3 * k + 2);
             }
-            step(D3IC<0>{}, i, 15);
+            step(IC<0>{}, i, 15);
             // behind the last input plane: row 3 of plane 14 (set 2), plane 15 (set 0) - cleared: it is plane 0 of the next patch, whose first
             // contributions come from its own input plane, not from a plane in front of it
             __builtin_amdgcn_sched_barrier(0);
             const int p = patch_of(i);
             const float inv = __builtin_ldexpf(1.f, -(patch_exp(p) + a.e_w));
-            epi_row(D3IC<2>{}, D3IC<3>{}, p, 14, true, inv);
-            epi_row(D3IC<0>{}, D3IC<0>{}, p, 15, true, inv);
-            epi_row(D3IC<0>{}, D3IC<1>{}, p, 15, true, inv);
-            epi_row(D3IC<0>{}, D3IC<2>{}, p, 15, true, inv);
-            epi_row(D3IC<0>{}, D3IC<3>{}, p, 15, true, inv);
+            epi_row(IC<2>{}, IC<3>{}, p, 14, true, inv);
+            epi_row(IC<0>{}, IC<0>{}, p, 15, true, inv);
+            epi_row(IC<0>{}, IC<1>{}, p, 15, true, inv);
+            epi_row(IC<0>{}, IC<2>{}, p, 15, true, inv);
+            epi_row(IC<0>{}, IC<3>{}, p, 15, true, inv);
 #pragma unroll
             for (int ry = 0; ry < 4; ++ry) { acc[0][ry] = f32x4{0.f, 0.f, 0.f, 0.f}; acx[0][ry] = f32x4{0.f, 0.f, 0.f, 0.f}; }
             __builtin_amdgcn_sched_barrier(0);
@@ -336,9 +314,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
     for (int c = 0; c < 15; ++c) asm volatile("" : "+a"(wh[c]), "+a"(wl[c]));
 
-    const __amdgpu_buffer_rsrc_t i_rsrc = d3_rsrc(a.dout, (unsigned long long)a.N * 4096 * 64);
-    const __amdgpu_buffer_rsrc_t o_rsrc = d3_rsrc(cb ? a.dinB : a.dinA, (unsigned long long)a.N * 4096 * 64);
-    const __amdgpu_buffer_rsrc_t u_rsrc = d3_rsrc(a.sumB, a.sumB ? (unsigned long long)a.N * 4096 * 4 : 0ull);
+    const __amdgpu_buffer_rsrc_t i_rsrc = sw_rsrc(a.dout, (unsigned long long)a.N * 4096 * 64);
+    const __amdgpu_buffer_rsrc_t o_rsrc = sw_rsrc(cb ? a.dinB : a.dinA, (unsigned long long)a.N * 4096 * 64);
+    const __amdgpu_buffer_rsrc_t u_rsrc = sw_rsrc(a.sumB, a.sumB ? (unsigned long long)a.N * 4096 * 4 : 0ull);
 
     // staging lane roles: voxel x = lane >> 2 of a row, channels 4 cq .. + 3: k-group cq >> 1, bytes 8 (cq & 1) ..; image row 4 w + 1 + r
     const int sx = lane >> 2, cq = lane & 3;
@@ -350,19 +328,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const char *const f22 = strip + 8 * rg * DB_SLOT + (kg >> 1) * DB_SLOT + (kg & 1) * DB_KG + (n + 2) * 16;
     // epilogue lane roles: voxel x = n of the output row, channels 16 cb + 4 kg .. + 3
     const unsigned e_out = (unsigned)n * 64u + (unsigned)kg * 16u;
-    const unsigned e_sum = (kg == 0 && cb == 1) ? (unsigned)n * 4u : D3_OOB;
+    const unsigned e_sum = (kg == 0 && cb == 1) ? (unsigned)n * 4u : SW_OOB;
 
-    const int G8 = (int)gridDim.x >> 3, xcd = (int)blockIdx.x & 7, jb = (int)blockIdx.x >> 3;
-    const int npx = a.N > xcd ? (a.N - xcd + 7) >> 3 : 0;
-    const int npw = npx > jb ? (npx - jb + G8 - 1) / G8 : 0;
-    auto patch_of = [&](int i) __attribute__((always_inline)) { return 8 * (jb + (i < npw ? i : npw - 1) * G8) + xcd; };
+    SW_PATCH_ORDER(a.N);
 
     f32x4 RA[4];
     auto fetch = [&](int q) __attribute__((always_inline)) {
         const unsigned row0 = ((unsigned)patch_of(q >> 4) * 16u + (unsigned)(q & 15)) * 16u + 4u * (unsigned)wave;
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-            RA[r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(i_rsrc, (int)ldA, d3_s((row0 + r) * 1024u), 0));
+            RA[r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(i_rsrc, (int)ldA, sw_s((row0 + r) * 1024u), 0));
     };
     auto stage_unit = [&](auto U, int img, float sc, float sc11) __attribute__((always_inline)) {
         constexpr int r = decltype(U)::value;
@@ -385,19 +360,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 
     auto epi_row = [&](auto ST, auto RY, int p, int zo, bool tv) __attribute__((always_inline)) {
         constexpr int st = decltype(ST)::value, ry = decltype(RY)::value;
-        const unsigned vrow = (unsigned)d3_s((((unsigned)p * 16u + (unsigned)(tv ? zo : 0)) * 16u + (unsigned)(8 * rg + ry)) * 16u);
+        const unsigned vrow = (unsigned)sw_s((((unsigned)p * 16u + (unsigned)(tv ? zo : 0)) * 16u + (unsigned)(8 * rg + ry)) * 16u);
         const f32x4 c = acc[st][ry], cx = acx[st][ry];
         if (!D3_START) { acc[st][ry] = f32x4{0.f, 0.f, 0.f, 0.f}; acx[st][ry] = f32x4{0.f, 0.f, 0.f, 0.f}; }
         const float v0 = __builtin_fmaf(cx.x, 0x1p-11f, c.x) * a.inv, v1 = __builtin_fmaf(cx.y, 0x1p-11f, c.y) * a.inv;
         const float v2 = __builtin_fmaf(cx.z, 0x1p-11f, c.z) * a.inv, v3 = __builtin_fmaf(cx.w, 0x1p-11f, c.w) * a.inv;
         const f32x4 o = f32x4{v0, v1, v2, v3};
         okeep[ry & 1] = o;
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, o), o_rsrc, (int)(tv ? e_out : D3_OOB), (int)(vrow * 64u), 0);
-        ALQ_STORE_HOLD("v"(o));      // (a 16-byte store with a scalar offset reads its data late: nothing may write these registers in the next cycles, t3d_fwd_kernel)
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, o), o_rsrc, (int)(tv ? e_out : SW_OOB), (int)(vrow * 64u), 0);
+        ALQ_STORE_HOLD("v"(o));      // (a 16-byte store with a scalar offset reads its data late: nothing may write these registers in the next cycles)
         float s_ = (v0 + v1) + (v2 + v3);
         s_ += __shfl_xor(s_, 16, 64);
         s_ += __shfl_xor(s_, 32, 64);
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, s_), u_rsrc, (int)(tv ? e_sum : D3_OOB), (int)(vrow * 4u), 0);
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, s_), u_rsrc, (int)(tv ? e_sum : SW_OOB), (int)(vrow * 4u), 0);
     };
 
     // Step s (J = s % 3) of patch i: image q & 1 holds input plane s (q = 16 i + s); block r = input row 8 rg - 1 + r (r = 0 .. 9).
@@ -422,7 +397,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             fh[1] = *reinterpret_cast<const f16x8 *>(fb + r * DB_SLOT);
             fl[1] = *reinterpret_cast<const f16x8 *>(fb + r * DB_SLOT + DB_ROWB);
         };
-        frag(D3IC<0>{}, Fh[0], Fl[0]);
+        frag(IC<0>{}, Fh[0], Fl[0]);
         auto mm = [&](auto ST, auto RY, auto KS, const f16x8 &xh, const f16x8 &xl) __attribute__((always_inline)) {
             constexpr int st = decltype(ST)::value, ry = decltype(RY)::value, ks = decltype(KS)::value;
             // K step 0 of dz = 0 is the first contribution to its row of plane s + 1: it starts the accumulators (no clearing pass over the set)
@@ -435,18 +410,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         auto block = [&](auto R) __attribute__((always_inline)) {
             constexpr int r = decltype(R)::value;
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (r + 1 < 10) frag(D3IC<r + 1>{}, Fh[(r + 1) % 2], Fl[(r + 1) % 2]);
-            if constexpr (r == 0) epi_row(D3IC<S0>{}, D3IC<7>{}, p, s - 2, s >= 2);
-            if constexpr (r == 2) { stage_unit(D3IC<0>{}, img ^ 1, sc, sc11); stage_unit(D3IC<1>{}, img ^ 1, sc, sc11); }
-            if constexpr (r == 3) { stage_unit(D3IC<2>{}, img ^ 1, sc, sc11); stage_unit(D3IC<3>{}, img ^ 1, sc, sc11); }
+            if constexpr (r + 1 < 10) frag(IC<r + 1>{}, Fh[(r + 1) % 2], Fl[(r + 1) % 2]);
+            if constexpr (r == 0) epi_row(IC<S0>{}, IC<7>{}, p, s - 2, s >= 2);
+            if constexpr (r == 2) { stage_unit(IC<0>{}, img ^ 1, sc, sc11); stage_unit(IC<1>{}, img ^ 1, sc, sc11); }
+            if constexpr (r == 3) { stage_unit(IC<2>{}, img ^ 1, sc, sc11); stage_unit(IC<3>{}, img ^ 1, sc, sc11); }
             if constexpr (r == 4) fetch(q + 2);
-            if constexpr (r >= 3) epi_row(D3IC<S2>{}, D3IC<r - 3>{}, p, s - 1, s >= 1);
+            if constexpr (r >= 3) epi_row(IC<S2>{}, IC<r - 3>{}, p, s - 1, s >= 1);
             const f16x8 ph = Fh[r % 2][0], pl = Fl[r % 2][0], qh = Fh[r % 2][1], ql = Fl[r % 2][1];
             // K step index of (dz, pi): dz * 5 + pi;  sets: dz = 0 -> S0, 1 -> S1, 2 -> S2
 #define D3B_ALLDZ(RYV, PIV, XH, XL)                                                   \
-            mm(D3IC<S0>{}, D3IC<RYV>{}, D3IC<0 * 5 + PIV>{}, XH, XL);                 \
-            mm(D3IC<S1>{}, D3IC<RYV>{}, D3IC<1 * 5 + PIV>{}, XH, XL);                 \
-            mm(D3IC<S2>{}, D3IC<RYV>{}, D3IC<2 * 5 + PIV>{}, XH, XL);
+            mm(IC<S0>{}, IC<RYV>{}, IC<0 * 5 + PIV>{}, XH, XL);                 \
+            mm(IC<S1>{}, IC<RYV>{}, IC<1 * 5 + PIV>{}, XH, XL);                 \
+            mm(IC<S2>{}, IC<RYV>{}, IC<2 * 5 + PIV>{}, XH, XL);
             // (dx 0 | dx 1) of input row r: output rows r - dy, K step pi = dy
             if constexpr (r <= 7) { D3B_ALLDZ((r <= 7 ? r : 0), 0, ph, pl) }
             if constexpr (r >= 1 && r <= 8) { D3B_ALLDZ((r >= 1 && r <= 8 ? r - 1 : 0), 1, ph, pl) }
@@ -458,11 +433,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
             for (int m = 0; m < 9 * ((r == 0 || r == 9) ? 2 : ((r == 1 || r == 8) ? 3 : 5)); ++m) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(D3_FILL_MASK, D3_PIPE, 0);
+                __builtin_amdgcn_sched_group_barrier(SW_FILL_MASK, D3_PIPE, 0);
             }
         };
-        block(D3IC<0>{}); block(D3IC<1>{}); block(D3IC<2>{}); block(D3IC<3>{}); block(D3IC<4>{});
-        block(D3IC<5>{}); block(D3IC<6>{}); block(D3IC<7>{}); block(D3IC<8>{}); block(D3IC<9>{});
+        block(IC<0>{}); block(IC<1>{}); block(IC<2>{}); block(IC<3>{}); block(IC<4>{});
+        block(IC<5>{}); block(IC<6>{}); block(IC<7>{}); block(IC<8>{}); block(IC<9>{});
         __builtin_amdgcn_sched_barrier(0);
         const f32x4 k0 = okeep[0], k1 = okeep[1];
         asm volatile("" :: "v"(k0), "v"(k1));
@@ -471,26 +446,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     if (npw > 0) {
         {
             fetch(0);
-            stage_unit(D3IC<0>{}, 0, a.scale, a.scale11); stage_unit(D3IC<1>{}, 0, a.scale, a.scale11);
-            stage_unit(D3IC<2>{}, 0, a.scale, a.scale11); stage_unit(D3IC<3>{}, 0, a.scale, a.scale11);
+            stage_unit(IC<0>{}, 0, a.scale, a.scale11); stage_unit(IC<1>{}, 0, a.scale, a.scale11);
+            stage_unit(IC<2>{}, 0, a.scale, a.scale11); stage_unit(IC<3>{}, 0, a.scale, a.scale11);
             __builtin_amdgcn_sched_barrier(0);
             fetch(1);
         }
         for (int i = 0; i < npw; ++i) {
             for (int k = 0; k < 5; ++k) {
-                step(D3IC<0>{}, i, 3 * k);
-                step(D3IC<1>{}, i, 3 * k + 1);
-                step(D3IC<2>{}, i, 3 * k + 2);
+                step(IC<0>{}, i, 3 * k);
+                step(IC<1>{}, i, 3 * k + 1);
+                step(IC<2>{}, i, 3 * k + 2);
             }
-            step(D3IC<0>{}, i, 15);
+            step(IC<0>{}, i, 15);
             // behind the last input plane: row 7 of plane 14 (set 2), plane 15 (set 0) - cleared for plane 0 of the next patch
             __builtin_amdgcn_sched_barrier(0);
             const int p = patch_of(i);
-            epi_row(D3IC<2>{}, D3IC<7>{}, p, 14, true);
-            epi_row(D3IC<0>{}, D3IC<0>{}, p, 15, true); epi_row(D3IC<0>{}, D3IC<1>{}, p, 15, true);
-            epi_row(D3IC<0>{}, D3IC<2>{}, p, 15, true); epi_row(D3IC<0>{}, D3IC<3>{}, p, 15, true);
-            epi_row(D3IC<0>{}, D3IC<4>{}, p, 15, true); epi_row(D3IC<0>{}, D3IC<5>{}, p, 15, true);
-            epi_row(D3IC<0>{}, D3IC<6>{}, p, 15, true); epi_row(D3IC<0>{}, D3IC<7>{}, p, 15, true);
+            epi_row(IC<2>{}, IC<7>{}, p, 14, true);
+            epi_row(IC<0>{}, IC<0>{}, p, 15, true); epi_row(IC<0>{}, IC<1>{}, p, 15, true);
+            epi_row(IC<0>{}, IC<2>{}, p, 15, true); epi_row(IC<0>{}, IC<3>{}, p, 15, true);
+            epi_row(IC<0>{}, IC<4>{}, p, 15, true); epi_row(IC<0>{}, IC<5>{}, p, 15, true);
+            epi_row(IC<0>{}, IC<6>{}, p, 15, true); epi_row(IC<0>{}, IC<7>{}, p, 15, true);
 #pragma unroll
             for (int ry = 0; ry < 8; ++ry) { acc[0][ry] = f32x4{0.f, 0.f, 0.f, 0.f}; acx[0][ry] = f32x4{0.f, 0.f, 0.f, 0.f}; }
             __builtin_amdgcn_sched_barrier(0);
@@ -503,7 +478,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 int d3d_build(const View &in, const View &out, const int k[3], const int lo[3], const int s[3], D3dPlan *plan) {
     plan->ok = false;
     if (getenv("ALQ_NO_D3D")) return ALQ_OK;
-    if (!(k[0] == 3 && k[1] == 3 && k[2] == 3 && s[0] == 1 && s[1] == 1 && s[2] == 1 && lo[0] == 1 && lo[1] == 1 && lo[2] == 1)) return ALQ_OK;
+    if (!is_conv3_same(k, lo, s)) return ALQ_OK;
     if (!(in.D == 16 && in.H == 16 && in.W == 16 && out.D == 16 && out.H == 16 && out.W == 16 && in.C == 32 && in.split == 16 && in.cs == 16 && in.c0 == 0 &&
           out.C == 16 && out.cs == 16 && out.c0 == 0 && out.split == 0)) return ALQ_OK;
     plan->flops_per_patch = 2.0 * 27 * 32 * 16 * 4096.0;
@@ -513,11 +488,7 @@ int d3d_build(const View &in, const View &out, const int k[3], const int lo[3], 
 
 // W: TF conv filter [tap = (tz * 3 + ty) * 3 + tx][ci (32)][co (16)].  Fragment of a tap: lane -> row co = lane & 15, k-group kg = lane >> 4: ci = 8 kg + c.
 void d3d_pack(D3dPlan *plan, const float *W) {
-    float amax = 0.f;
-    for (size_t i = 0; i < (size_t)27 * 32 * 16; ++i) amax = std::max(amax, std::fabs(W[i]));
-    int ex = 0;
-    if (amax > 0.f) (void)std::frexp(amax, &ex);
-    plan->w_exp = 14 - ex;
+    plan->w_exp = f16_pair_exp(W, (size_t)27 * 32 * 16);
     plan->h_Whi.assign((size_t)27 * 64 * 8, 0);
     plan->h_Wlo.assign((size_t)27 * 64 * 8, 0);
     for (int tap = 0; tap < 27; ++tap)
@@ -525,15 +496,8 @@ void d3d_pack(D3dPlan *plan, const float *W) {
             const int co = lane & 15, kg = lane >> 4;
             for (int c = 0; c < 8; ++c) {
                 const float w = W[((size_t)tap * 32 + 8 * kg + c) * 16 + co];
-                const float ws = std::ldexp(w, plan->w_exp);
-                const _Float16 h = (_Float16)ws;
-                const _Float16 l = (_Float16)std::ldexp(ws - (float)h, 11);
-                unsigned short hb, lb;
-                std::memcpy(&hb, &h, 2);
-                std::memcpy(&lb, &l, 2);
                 const size_t o = ((size_t)tap * 64 + lane) * 8 + c;
-                plan->h_Whi[o] = hb;
-                plan->h_Wlo[o] = lb;
+                f16_pair_split(w, plan->w_exp, 11, &plan->h_Whi[o], &plan->h_Wlo[o]);
             }
         }
 }
@@ -556,15 +520,8 @@ void d3d_bwd_pack(D3dPlan *plan, const float *W) {
                         const int co = 8 * (kg & 1) + c, ci = 16 * cb + r;
                         const int tap = ((2 - dz) * 3 + (2 - dy)) * 3 + (2 - dx);
                         const float w = any ? W[((size_t)tap * 32 + ci) * 16 + co] : 0.f;
-                        const float ws = std::ldexp(w, plan->w_exp);
-                        const _Float16 hh = (_Float16)ws;
-                        const _Float16 ll = (_Float16)std::ldexp(ws - (float)hh, 11);
-                        unsigned short hb, lb;
-                        std::memcpy(&hb, &hh, 2);
-                        std::memcpy(&lb, &ll, 2);
                         const size_t o = ((size_t)((cb * 3 + dz) * 5 + pi) * 64 + lane) * 8 + c;
-                        plan->h_Bhi[o] = hb;
-                        plan->h_Blo[o] = lb;
+                        f16_pair_split(w, plan->w_exp, 11, &plan->h_Bhi[o], &plan->h_Blo[o]);
                     }
                 }
 }
@@ -572,45 +529,29 @@ void d3d_bwd_pack(D3dPlan *plan, const float *W) {
 int d3d_bwd_launch(alq_ctx *ctx, const D3dPlan &plan, int N, const float *dout, float in_bound, float *dinA, float *dinB, float *sumB) {
     ALQ_REQUIRE(plan.ok && plan.d_Bhi && plan.d_Blo, ALQ_EINVAL, "d3d: backward weights not set");
     ALQ_REQUIRE(dout && dinA && dinB && in_bound > 0.f, ALQ_EINVAL, "d3d: missing argument");
-    ALQ_REQUIRE(N < 4096, ALQ_EUNSUPPORTED, "d3d: 32-bit byte offsets hold fewer than 4096 patches per pass");
+    SWEEP_REQUIRE_PATCHES(N, "d3d");
     if (N <= 0) return ALQ_OK;
-    int ex = 0;
-    (void)std::frexp(in_bound, &ex);
-    const int e_in = 14 - ex;
+    const int e_in = f16_pair_exp(&in_bound, 1);
     D3BArgs a;
     a.dout = dout; a.Whi = reinterpret_cast<const unsigned short *>(plan.d_Bhi); a.Wlo = reinterpret_cast<const unsigned short *>(plan.d_Blo);
     a.dinA = dinA; a.dinB = dinB; a.sumB = sumB;
     a.scale = std::ldexp(1.f, e_in); a.scale11 = std::ldexp(1.f, e_in + 11); a.inv = std::ldexp(1.f, -(e_in + plan.w_exp)); a.N = N;
-    const int cus = ctx->num_cus;
-    long long g = std::min<long long>((long long)cus, (long long)N);
-    g = std::max<long long>(8, (g + 7) / 8 * 8);
-    const size_t lds = DB_STRIP;
-    ALQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(d3d_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     ProfScope ps(ctx, PROF_IGEMM_F16, plan.flops_per_patch * N);
-    hipLaunchKernelGGL(d3d_bwd_kernel, dim3((unsigned)g), dim3(256), lds, ctx->stream, a);
-    ALQ_HIP(hipGetLastError());
-    return ALQ_OK;
+    return sweep_launch(ctx, d3d_bwd_kernel, sweep_grid(ctx, N, 1), 256, DB_STRIP, a);
 }
 
 int d3d_fwd_launch(alq_ctx *ctx, const D3dPlan &plan, int N, const float *inA, const float *inB, const unsigned *amaxA, const unsigned *amaxB,
                    const float *bias, int relu, float *out, unsigned char *sg, float *osum) {
     ALQ_REQUIRE(plan.ok && plan.d_Whi && plan.d_Wlo, ALQ_EINVAL, "d3d: weights not set");
     ALQ_REQUIRE(inA && inB && amaxA && amaxB && bias && out, ALQ_EINVAL, "d3d: missing argument");
-    ALQ_REQUIRE(N < 4096, ALQ_EUNSUPPORTED, "d3d: 32-bit byte offsets hold fewer than 4096 patches per pass");
+    SWEEP_REQUIRE_PATCHES(N, "d3d");
     if (N <= 0) return ALQ_OK;
     D3Args a;
     a.inA = inA; a.inB = inB; a.amaxA = amaxA; a.amaxB = amaxB;
     a.Whi = reinterpret_cast<const unsigned short *>(plan.d_Whi); a.Wlo = reinterpret_cast<const unsigned short *>(plan.d_Wlo);
     a.bias = bias; a.out = out; a.sg = sg; a.osum = osum; a.e_w = plan.w_exp; a.relu = relu; a.N = N;
-    const int cus = ctx->num_cus;
-    long long g = std::min<long long>((long long)cus, (long long)N);
-    g = std::max<long long>(8, (g + 7) / 8 * 8);
-    const size_t lds = D3_STRIP;
-    ALQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(d3d_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     ProfScope ps(ctx, PROF_IGEMM_F16, plan.flops_per_patch * N);
-    hipLaunchKernelGGL(d3d_fwd_kernel, dim3((unsigned)g), dim3(256), lds, ctx->stream, a);
-    ALQ_HIP(hipGetLastError());
-    return ALQ_OK;
+    return sweep_launch(ctx, d3d_fwd_kernel, sweep_grid(ctx, N, 1), 256, D3_STRIP, a);
 }
 
 }  // namespace alq

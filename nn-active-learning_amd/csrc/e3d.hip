@@ -26,7 +26,8 @@
 //   * rows outside the volume are fetched from the nearest row inside and staged with scale 0 - no per-lane predication.
 // Loads run two steps ahead (one for the small, cache-resident pooled tensors); loop body straight-line, first pass void: see
 // t3d_fwd_kernel for why.
-#include "alq_internal.h"
+#include "f16_pair.h"
+#include "sweep_common.h"
 
 #include <algorithm>
 #include <cmath>
@@ -35,13 +36,6 @@
 #include <vector>
 
 namespace alq {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 struct E3Args {
     const float *skip;            // [N][16^3][16] cotangent of enc2's output from its skip consumer (dense)
@@ -58,7 +52,6 @@ struct E3Args {
     int N;
 };
 
-constexpr unsigned E3_OOB = 0xffffff00u;
 constexpr int E3_ROWB = 18 * 32 + 16;         // 18 voxel slots (x = -1 .. 16) x 16 channels x 2 B, + 16: a row slot (2 pieces) is 32 mod 64 bytes, so the two tile rows of a fragment read land on disjoint banks
 constexpr int E3_SLOT = 2 * E3_ROWB;          // pieces h, l
 constexpr int E3_RING = 6;                    // row slots per plane
@@ -66,14 +59,6 @@ constexpr int E3_PLANE = E3_RING * E3_SLOT;
 constexpr int E3_STRIP = 6 * E3_PLANE;        // planes 4 q - 1 .. 4 q + 4
 constexpr int E3_WLO = 9 * 2 * 1024;          // lo weight fragments
 constexpr int E3_SINK = E3_SLOT;              // behind the ring: where the void steps' rows go (see the staging)
-
-__device__ inline __amdgpu_buffer_rsrc_t e3_rsrc(const void *base, unsigned long long bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, (int)(unsigned)bytes, 0x00020000);
-}
-
-// a scalar the compiler must keep scalar: with ~100 live SGPRs it moved some row offsets to vector registers and wrapped every
-// buffer access that used them in a waterfall loop
-__device__ inline int e3_s(unsigned v) { return __builtin_amdgcn_readfirstlane((int)v); }
 
 struct E3RowA { f32x4 sk; unsigned sg; };      // what staging one row needs, per lane: skip cotangent + enc2's sign byte,
 struct E3RowB { f32x4 dp; unsigned am; };      // pooled cotangent + pool2's arg-max bytes
@@ -102,17 +87,17 @@ __global__ __launch_bounds__(256, 2) void e3d_bwd_kernel(const E3Args a) {
 #pragma unroll
     for (int c = 0; c < 9; ++c)
 #pragma unroll
-        for (int s = 0; s < 2; ++s) asm volatile("" : "+v"(wh[c][s]));      // arrived before the loop (t3d_fwd_kernel)
+        for (int s = 0; s < 2; ++s) asm volatile("" : "+v"(wh[c][s]));      // arrived before the loop
     const char *wl = e3lds + lane * 16;
 
-    const __amdgpu_buffer_rsrc_t sk_rsrc = e3_rsrc(a.skip, (unsigned long long)a.N * 4096 * 64);
-    const __amdgpu_buffer_rsrc_t dp_rsrc = e3_rsrc(a.dpool, (unsigned long long)a.N * 512 * 64);
-    const __amdgpu_buffer_rsrc_t a2_rsrc = e3_rsrc(a.am2, (unsigned long long)a.N * 512 * 16);
-    const __amdgpu_buffer_rsrc_t s2_rsrc = e3_rsrc(a.sg2, (unsigned long long)a.N * 4096 * 4);
-    const __amdgpu_buffer_rsrc_t a1_rsrc = e3_rsrc(a.am1, (unsigned long long)a.N * 4096 * 8);
-    const __amdgpu_buffer_rsrc_t s1_rsrc = e3_rsrc(a.sg1, (unsigned long long)a.N * 4096 * 2);
-    const __amdgpu_buffer_rsrc_t d2_rsrc = e3_rsrc(a.dsum2, (unsigned long long)a.N * 4096 * 4);
-    const __amdgpu_buffer_rsrc_t d1_rsrc = e3_rsrc(a.dsum1, (unsigned long long)a.N * 32768 * 4);
+    const __amdgpu_buffer_rsrc_t sk_rsrc = sw_rsrc(a.skip, (unsigned long long)a.N * 4096 * 64);
+    const __amdgpu_buffer_rsrc_t dp_rsrc = sw_rsrc(a.dpool, (unsigned long long)a.N * 512 * 64);
+    const __amdgpu_buffer_rsrc_t a2_rsrc = sw_rsrc(a.am2, (unsigned long long)a.N * 512 * 16);
+    const __amdgpu_buffer_rsrc_t s2_rsrc = sw_rsrc(a.sg2, (unsigned long long)a.N * 4096 * 4);
+    const __amdgpu_buffer_rsrc_t a1_rsrc = sw_rsrc(a.am1, (unsigned long long)a.N * 4096 * 8);
+    const __amdgpu_buffer_rsrc_t s1_rsrc = sw_rsrc(a.sg1, (unsigned long long)a.N * 4096 * 2);
+    const __amdgpu_buffer_rsrc_t d2_rsrc = sw_rsrc(a.dsum2, (unsigned long long)a.N * 4096 * 4);
+    const __amdgpu_buffer_rsrc_t d1_rsrc = sw_rsrc(a.dsum1, (unsigned long long)a.N * 32768 * 4);
 
     // staging lane roles: voxel x = lane >> 2 of a row, channels 4 cq .. + 3
     const int sx = lane >> 2, cq = lane & 3;
@@ -120,7 +105,7 @@ __global__ __launch_bounds__(256, 2) void e3d_bwd_kernel(const E3Args a) {
     const unsigned ldA = (unsigned)lane * 16u, ldS = (unsigned)lane;
     const unsigned ldP = (unsigned)(sx >> 1) * 64u + (unsigned)cq * 16u, ldM = (unsigned)(sx >> 1) * 16u + (unsigned)cq * 4u;
     const unsigned lanepar4 = (unsigned)(sx & 1) * 0x01010101u;
-    const unsigned st2 = cq == 0 ? (unsigned)sx * 4u : E3_OOB;
+    const unsigned st2 = cq == 0 ? (unsigned)sx * 4u : SW_OOB;
     // fragment lane roles: column (ry, j), K step s: window position q = 2 s + (kg >> 1) -> voxel x = 2 j - 1 + q = slot 2 j + q, channel half kg & 1
     const int f_off = (2 * j + (kg >> 1)) * 32 + (kg & 1) * 16 + wave * E3_PLANE;      // (+ the wave's first plane of the six)
     // epilogue lane roles: pooled voxel (z, y0 + ry, x = 2 j + (kg >> 1)) of pool1, channels 4 (kg & 1) .. + 3; window sums shared with lane ^ 16
@@ -129,10 +114,9 @@ __global__ __launch_bounds__(256, 2) void e3d_bwd_kernel(const E3Args a) {
     const unsigned e_sg = (unsigned)(ry * 16 + 2 * j + (kg >> 1)) * 2u + (unsigned)(kg & 1);
     const unsigned e_d1 = (unsigned)(hi ? 32 * 128 : 0) + (unsigned)(2 * ry) * 128u + (unsigned)(2 * (2 * j + (kg >> 1))) * 4u;      // + dy2 * 128
 
-    // unit order as in t3d.hip: workgroup b of XCD b % 8 takes units v = b / 8, b / 8 + G / 8, ...: patch 8 (v >> 2) + b % 8, planes 4 (v & 3) + wave
-    const int G8 = (int)gridDim.x >> 3, xcd = (int)blockIdx.x & 7, jb = (int)blockIdx.x >> 3;
-    const int np = a.N > xcd ? (a.N - xcd + 7) >> 3 : 0;
-    const int nv = 4 * np;
+    // four units per patch: workgroup jb takes the units v = jb, jb + G8, ... of its XCD: patch 8 (v >> 2) + xcd, planes 4 (v & 3) + wave
+    SW_XCD_DEAL(a.N);
+    const int nv = 4 * npx;
     const int nunits = nv > jb ? (nv - jb + G8 - 1) / G8 : 0;
     const int total = nunits * 9;       // nine steps per unit: t = 0 .. 8 stage rows 2 t - 1, 2 t and contract tile y0 = 2 t - 2 (t = 0: nothing to contract)
 
@@ -161,8 +145,8 @@ __global__ __launch_bounds__(256, 2) void e3d_bwd_kernel(const E3Args a) {
             int p, zz, yy, t;
             rowof(S, r, &p, &zz, &yy, &t);
             const unsigned row = ((unsigned)p * 16u + (unsigned)clampi(zz)) * 16u + (unsigned)clampi(yy);             // row index of the 16^3 grid
-            R[r].sk = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(sk_rsrc, (int)ldA, e3_s(row * 1024u), 0));
-            R[r].sg = (unsigned)(unsigned char)__builtin_amdgcn_raw_buffer_load_b8(s2_rsrc, (int)ldS, e3_s(row * 64u), 0);
+            R[r].sk = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(sk_rsrc, (int)ldA, sw_s(row * 1024u), 0));
+            R[r].sg = (unsigned)(unsigned char)__builtin_amdgcn_raw_buffer_load_b8(s2_rsrc, (int)ldS, sw_s(row * 64u), 0);
         }
     };
     auto fetchB = [&](int S, E3RowB *R) __attribute__((always_inline)) {
@@ -171,8 +155,8 @@ __global__ __launch_bounds__(256, 2) void e3d_bwd_kernel(const E3Args a) {
             int p, zz, yy, t;
             rowof(S, r, &p, &zz, &yy, &t);
             const unsigned prow = ((unsigned)p * 8u + (unsigned)(clampi(zz) >> 1)) * 8u + (unsigned)(clampi(yy) >> 1);   // row index of the 8^3 grid
-            R[r].dp = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(dp_rsrc, (int)ldP, e3_s(prow * 512u), 0));
-            R[r].am = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(a2_rsrc, (int)ldM, e3_s(prow * 128u), 0);
+            R[r].dp = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(dp_rsrc, (int)ldP, sw_s(prow * 512u), 0));
+            R[r].am = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(a2_rsrc, (int)ldM, sw_s(prow * 128u), 0);
         }
     };
 
@@ -200,9 +184,9 @@ __global__ __launch_bounds__(256, 2) void e3d_bwd_kernel(const E3Args a) {
             const int y0 = 2 * t - 2;
             const bool tv = live && t >= 1;
             const unsigned trow = ((unsigned)p * 16u + (unsigned)z) * 16u + (unsigned)(tv ? y0 : 0);          // first row of the tile in pool1's grid
-            const unsigned am1w = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(a1_rsrc, (int)e_am, e3_s(trow * 128u), 0);
-            const unsigned sg1b = (unsigned)(unsigned char)__builtin_amdgcn_raw_buffer_load_b8(s1_rsrc, (int)e_sg, e3_s(trow * 32u), 0);
-            const unsigned d1row = (unsigned)e3_s((((unsigned)p * 32u + (unsigned)(2 * z)) * 32u + (unsigned)(tv ? 2 * y0 : 0)) * 128u);     // row (2 z, 2 y0) of enc1's grid, bytes
+            const unsigned am1w = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(a1_rsrc, (int)e_am, sw_s(trow * 128u), 0);
+            const unsigned sg1b = (unsigned)(unsigned char)__builtin_amdgcn_raw_buffer_load_b8(s1_rsrc, (int)e_sg, sw_s(trow * 32u), 0);
+            const unsigned d1row = (unsigned)sw_s((((unsigned)p * 32u + (unsigned)(2 * z)) * 32u + (unsigned)(tv ? 2 * y0 : 0)) * 128u);     // row (2 z, 2 y0) of enc1's grid, bytes
             const f32x2 old0 = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(d1_rsrc, (int)e_d1, (int)d1row, 0));
             const f32x2 old1 = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(d1_rsrc, (int)(e_d1 + 128u), (int)d1row, 0));
             // ---- stage this wave's three rows into ring slot (yy + 6) % 6 of their planes
@@ -231,7 +215,7 @@ __global__ __launch_bounds__(256, 2) void e3d_bwd_kernel(const E3Args a) {
                     s_ += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, s_), 0x4E, 0xf, 0xf, true));      // quad_perm [2, 3, 0, 1]
                     const bool own = rv && pi >= 1 && pi <= 4;
                     const unsigned row = ((unsigned)p * 16u + (unsigned)clampi(zz)) * 16u + (unsigned)clampi(yy);
-                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, s_), d2_rsrc, (int)(own ? st2 : E3_OOB), e3_s(row * 64u), 0);
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, s_), d2_rsrc, (int)(own ? st2 : SW_OOB), sw_s(row * 64u), 0);
                 }
                 const float x0 = g0 * scr, x1 = g1 * scr, x2 = g2 * scr, x3 = g3 * scr;
                 const f16x2 h01 = __builtin_convertvector(f32x2{x0, x1}, f16x2), h23 = __builtin_convertvector(f32x2{x2, x3}, f16x2);
@@ -293,8 +277,8 @@ __global__ __launch_bounds__(256, 2) void e3d_bwd_kernel(const E3Args a) {
             }
             // enc1's grid: voxel (2 z + dz, 2 (y0 + ry) + dy, 2 x + dx); the lane's four sums = (dy, dx) of its dz
             const f32x2 n0 = f32x2{old0.x + mine.x, old0.y + mine.y}, n1 = f32x2{old1.x + mine.z, old1.y + mine.w};
-            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(i32x2, n0), d1_rsrc, (int)(tv ? e_d1 : E3_OOB), (int)d1row, 0);
-            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(i32x2, n1), d1_rsrc, (int)(tv ? e_d1 + 128u : E3_OOB), (int)d1row, 0);
+            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(i32x2, n0), d1_rsrc, (int)(tv ? e_d1 : SW_OOB), (int)d1row, 0);
+            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(i32x2, n1), d1_rsrc, (int)(tv ? e_d1 + 128u : SW_OOB), (int)d1row, 0);
         }
     }
 }
@@ -351,17 +335,17 @@ __global__ __launch_bounds__(512) void e3d_bwdz_kernel(const E3Args a) {
 #pragma unroll
     for (int c = 0; c < 9; ++c)
 #pragma unroll
-        for (int s = 0; s < 2; ++s) asm volatile("" : "+v"(wh[c][s]));      // arrived before the loop (t3d_fwd_kernel)
+        for (int s = 0; s < 2; ++s) asm volatile("" : "+v"(wh[c][s]));      // arrived before the loop
     const char *wl = e3lds + lane * 16;
 
-    const __amdgpu_buffer_rsrc_t sk_rsrc = e3_rsrc(a.skip, (unsigned long long)a.N * 4096 * 64);
-    const __amdgpu_buffer_rsrc_t dp_rsrc = e3_rsrc(a.dpool, (unsigned long long)a.N * 512 * 64);
-    const __amdgpu_buffer_rsrc_t a2_rsrc = e3_rsrc(a.am2, (unsigned long long)a.N * 512 * 16);
-    const __amdgpu_buffer_rsrc_t s2_rsrc = e3_rsrc(a.sg2, (unsigned long long)a.N * 4096 * 4);
-    const __amdgpu_buffer_rsrc_t a1_rsrc = e3_rsrc(a.am1, (unsigned long long)a.N * 4096 * 8);
-    const __amdgpu_buffer_rsrc_t s1_rsrc = e3_rsrc(a.sg1, (unsigned long long)a.N * 4096 * 2);
-    const __amdgpu_buffer_rsrc_t d2_rsrc = e3_rsrc(a.dsum2, (unsigned long long)a.N * 4096 * 4);
-    const __amdgpu_buffer_rsrc_t d1_rsrc = e3_rsrc(a.dsum1, (unsigned long long)a.N * 32768 * 4);
+    const __amdgpu_buffer_rsrc_t sk_rsrc = sw_rsrc(a.skip, (unsigned long long)a.N * 4096 * 64);
+    const __amdgpu_buffer_rsrc_t dp_rsrc = sw_rsrc(a.dpool, (unsigned long long)a.N * 512 * 64);
+    const __amdgpu_buffer_rsrc_t a2_rsrc = sw_rsrc(a.am2, (unsigned long long)a.N * 512 * 16);
+    const __amdgpu_buffer_rsrc_t s2_rsrc = sw_rsrc(a.sg2, (unsigned long long)a.N * 4096 * 4);
+    const __amdgpu_buffer_rsrc_t a1_rsrc = sw_rsrc(a.am1, (unsigned long long)a.N * 4096 * 8);
+    const __amdgpu_buffer_rsrc_t s1_rsrc = sw_rsrc(a.sg1, (unsigned long long)a.N * 4096 * 2);
+    const __amdgpu_buffer_rsrc_t d2_rsrc = sw_rsrc(a.dsum2, (unsigned long long)a.N * 4096 * 4);
+    const __amdgpu_buffer_rsrc_t d1_rsrc = sw_rsrc(a.dsum1, (unsigned long long)a.N * 32768 * 4);
 
     // staging lane roles (as in the row sweep): voxel x = lane >> 2 of a row, channels 4 cq .. + 3
     const int sx = lane >> 2, cq = lane & 3;
@@ -369,7 +353,7 @@ __global__ __launch_bounds__(512) void e3d_bwdz_kernel(const E3Args a) {
     const unsigned ldA = (unsigned)lane * 16u, ldS = (unsigned)lane;
     const unsigned ldP = (unsigned)(sx >> 1) * 64u + (unsigned)cq * 16u, ldM = (unsigned)(sx >> 1) * 16u + (unsigned)cq * 4u;
     const unsigned lanepar4 = (unsigned)(sx & 1) * 0x01010101u;
-    const unsigned st2 = cq == 0 ? (unsigned)sx * 4u : E3_OOB;
+    const unsigned st2 = cq == 0 ? (unsigned)sx * 4u : SW_OOB;
     // fragment lane roles: column (ry, j), K step s: window position q = 2 s + (kg >> 1) -> slot 2 j + q, channel half kg & 1; tile row 2 w + ry
     // reads input rows 2 w + ry + dy - 1 = image rows 2 w + ry + dy
     const int f_off = (2 * j + (kg >> 1)) * 32 + (kg & 1) * 16 + (2 * wave + ry) * E3_SLOT;
@@ -393,7 +377,7 @@ __global__ __launch_bounds__(512) void e3d_bwdz_kernel(const E3Args a) {
         int p, z;
         plane(m, &p, &z);
         const unsigned row = ((unsigned)p * 16u + (unsigned)z) * 16u + (unsigned)(2 * wave);      // row index of the 16^3 grid: y = 2 w
-        const int so_sk = e3_s(row * 1024u), so_sg = e3_s(row * 64u);
+        const int so_sk = sw_s(row * 1024u), so_sg = sw_s(row * 64u);
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
             R[r].sk = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(sk_rsrc, (int)(ldA + (unsigned)r * 1024u), so_sk, 0));
@@ -404,8 +388,8 @@ __global__ __launch_bounds__(512) void e3d_bwdz_kernel(const E3Args a) {
         int p, z;
         plane(m, &p, &z);
         const unsigned prow = ((unsigned)p * 8u + (unsigned)(z >> 1)) * 8u + (unsigned)wave;       // row index of the 8^3 grid: rows 2 w, 2 w + 1 -> w
-        R->dp = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(dp_rsrc, (int)ldP, e3_s(prow * 512u), 0));
-        R->am = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(a2_rsrc, (int)ldM, e3_s(prow * 128u), 0);
+        R->dp = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(dp_rsrc, (int)ldP, sw_s(prow * 512u), 0));
+        R->am = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(a2_rsrc, (int)ldM, sw_s(prow * 128u), 0);
     };
 
     E3RowA RA[2][2];
@@ -431,15 +415,15 @@ __global__ __launch_bounds__(512) void e3d_bwdz_kernel(const E3Args a) {
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
             // what the epilogue of this step's tile needs, requested now (see the row sweep)
             const unsigned trow = ((unsigned)po * 16u + (unsigned)zo) * 16u + (unsigned)(2 * wave);          // first row of the tile in pool1's grid
-            const unsigned am1w = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(a1_rsrc, (int)e_am, e3_s(trow * 128u), 0);
-            const unsigned sg1b = (unsigned)(unsigned char)__builtin_amdgcn_raw_buffer_load_b8(s1_rsrc, (int)e_sg, e3_s(trow * 32u), 0);
-            const unsigned d1row = (unsigned)e3_s((((unsigned)po * 32u + (unsigned)(2 * zo)) * 32u + (unsigned)(4 * wave)) * 128u);     // row (2 z, 2 y0) of enc1's grid, bytes
+            const unsigned am1w = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(a1_rsrc, (int)e_am, sw_s(trow * 128u), 0);
+            const unsigned sg1b = (unsigned)(unsigned char)__builtin_amdgcn_raw_buffer_load_b8(s1_rsrc, (int)e_sg, sw_s(trow * 32u), 0);
+            const unsigned d1row = (unsigned)sw_s((((unsigned)po * 32u + (unsigned)(2 * zo)) * 32u + (unsigned)(4 * wave)) * 128u);     // row (2 z, 2 y0) of enc1's grid, bytes
             const f32x2 old0 = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(d1_rsrc, (int)e_d1, (int)d1row, 0));
             const f32x2 old1 = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(d1_rsrc, (int)(e_d1 + 128u), (int)d1row, 0));
             // ---- stage rows 2 w, 2 w + 1 of plane s into image s & 3
             const unsigned srow = ((unsigned)p * 16u + (unsigned)z) * 16u + (unsigned)(2 * wave);
-            const int so_d2 = e3_s(srow * 64u);
-            char *img = strip + e3_s(live ? (unsigned)(s & 3) * (unsigned)E3Z_IMG : (unsigned)(E3Z_SINK - (2 * wave + 1) * E3_SLOT)) + w_off;
+            const int so_d2 = sw_s(srow * 64u);
+            char *img = strip + sw_s(live ? (unsigned)(s & 3) * (unsigned)E3Z_IMG : (unsigned)(E3Z_SINK - (2 * wave + 1) * E3_SLOT)) + w_off;
             const float scr = a.scale;
 #pragma unroll
             for (int r = 0; r < 2; ++r) {
@@ -458,7 +442,7 @@ __global__ __launch_bounds__(512) void e3d_bwdz_kernel(const E3Args a) {
                     float s_ = (g0 + g1) + (g2 + g3);
                     s_ += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, s_), 0xB1, 0xf, 0xf, true));      // quad_perm [1, 0, 3, 2]
                     s_ += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, s_), 0x4E, 0xf, 0xf, true));      // quad_perm [2, 3, 0, 1]
-                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, s_), d2_rsrc, (int)(live ? st2 + (unsigned)r * 64u : E3_OOB), so_d2, 0);
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, s_), d2_rsrc, (int)(live ? st2 + (unsigned)r * 64u : SW_OOB), so_d2, 0);
                 }
                 const float x0 = g0 * scr, x1 = g1 * scr, x2 = g2 * scr, x3 = g3 * scr;
                 const f16x2 h01 = __builtin_convertvector(f32x2{x0, x1}, f16x2), h23 = __builtin_convertvector(f32x2{x2, x3}, f16x2);
@@ -472,8 +456,8 @@ __global__ __launch_bounds__(512) void e3d_bwdz_kernel(const E3Args a) {
             fetchB(s + 1, &RB);      // (first: the wait for these, one step from now, must not cover the two-step requests behind them - vmcnt retires in order)
             fetchA(s + 2, RA[b]);
             // ---- contract the tile (rows 2 w + ry) of output plane s - 2: input planes s - 3 + dz, input rows 2 w + ry + dy - 1
-            const int io[3] = {e3_s(zo == 0 ? (unsigned)E3Z_ZERO : (unsigned)((s + 1) & 3) * (unsigned)E3Z_IMG), e3_s((unsigned)((s + 2) & 3) * (unsigned)E3Z_IMG),
-                               e3_s(zo == 15 ? (unsigned)E3Z_ZERO : (unsigned)((s + 3) & 3) * (unsigned)E3Z_IMG)};
+            const int io[3] = {sw_s(zo == 0 ? (unsigned)E3Z_ZERO : (unsigned)((s + 1) & 3) * (unsigned)E3Z_IMG), sw_s((unsigned)((s + 2) & 3) * (unsigned)E3Z_IMG),
+                               sw_s(zo == 15 ? (unsigned)E3Z_ZERO : (unsigned)((s + 3) & 3) * (unsigned)E3Z_IMG)};
             f32x4 c = f32x4{0.f, 0.f, 0.f, 0.f}, cl = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int dy = 0; dy < 3; ++dy) {
@@ -512,8 +496,8 @@ __global__ __launch_bounds__(512) void e3d_bwdz_kernel(const E3Args a) {
                 mine = f32x4{(hi ? sw[4] : sw[0]) + g0, (hi ? sw[5] : sw[1]) + g1, (hi ? sw[6] : sw[2]) + g2, (hi ? sw[7] : sw[3]) + g3};
             }
             const f32x2 n0 = f32x2{old0.x + mine.x, old0.y + mine.y}, n1 = f32x2{old1.x + mine.z, old1.y + mine.w};
-            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(i32x2, n0), d1_rsrc, (int)(tv ? e_d1 : E3_OOB), (int)d1row, 0);
-            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(i32x2, n1), d1_rsrc, (int)(tv ? e_d1 + 128u : E3_OOB), (int)d1row, 0);
+            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(i32x2, n0), d1_rsrc, (int)(tv ? e_d1 : SW_OOB), (int)d1row, 0);
+            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(i32x2, n1), d1_rsrc, (int)(tv ? e_d1 + 128u : SW_OOB), (int)d1row, 0);
         }
     }
 }
@@ -522,7 +506,7 @@ __global__ __launch_bounds__(512) void e3d_bwdz_kernel(const E3Args a) {
 int e3d_build(const View &in, const View &out, const int k[3], const int lo[3], const int s[3], E3dPlan *plan) {
     plan->ok = false;
     if (getenv("ALQ_NO_E3D")) return ALQ_OK;
-    if (!(k[0] == 3 && k[1] == 3 && k[2] == 3 && s[0] == 1 && s[1] == 1 && s[2] == 1 && lo[0] == 1 && lo[1] == 1 && lo[2] == 1)) return ALQ_OK;
+    if (!is_conv3_same(k, lo, s)) return ALQ_OK;
     if (!(in.D == 16 && in.H == 16 && in.W == 16 && out.D == 16 && out.H == 16 && out.W == 16 && in.C == 8 && out.C == 16 && in.split == 0 && out.split == 0)) return ALQ_OK;
     plan->flops_per_patch = 2.0 * 27 * 8 * 16 * 4096.0;
     plan->ok = true;
@@ -533,11 +517,7 @@ int e3d_build(const View &in, const View &out, const int k[3], const int lo[3], 
 // ci = r & 7), k-group kg = lane >> 4: window position q = 2 s + (kg >> 1), co = 8 (kg & 1) + c.  The input row of (dz, dy) lies at
 // offset (dz - 1, dy - 1) from the output row, the window position q at x offset q - 1 - px: tap = (1 - offset) per dimension.
 void e3d_pack(E3dPlan *plan, const float *W) {
-    float amax = 0.f;
-    for (size_t i = 0; i < (size_t)27 * 8 * 16; ++i) amax = std::max(amax, std::fabs(W[i]));
-    int ex = 0;
-    if (amax > 0.f) (void)std::frexp(amax, &ex);
-    plan->w_exp = 14 - ex;
+    plan->w_exp = f16_pair_exp(W, (size_t)27 * 8 * 16);
     plan->h_Whi.assign((size_t)9 * 2 * 64 * 8, 0);
     plan->h_Wlo.assign((size_t)9 * 2 * 64 * 8, 0);
     for (int dz = 0; dz < 3; ++dz)
@@ -549,15 +529,8 @@ void e3d_pack(E3dPlan *plan, const float *W) {
                     for (int c = 0; c < 8; ++c) {
                         const int co = 8 * (kg & 1) + c;
                         const float w = (tx >= 0 && tx <= 2) ? W[((size_t)((tz * 3 + ty) * 3 + tx) * 8 + ci) * 16 + co] : 0.f;
-                        const float ws = std::ldexp(w, plan->w_exp);
-                        const _Float16 h = (_Float16)ws;
-                        const _Float16 l = (_Float16)std::ldexp(ws - (float)h, 11);
-                        unsigned short hb, lb;
-                        std::memcpy(&hb, &h, 2);
-                        std::memcpy(&lb, &l, 2);
                         const size_t o = ((size_t)((dz * 3 + dy) * 2 + s) * 64 + lane) * 8 + c;
-                        plan->h_Whi[o] = hb;
-                        plan->h_Wlo[o] = lb;
+                        f16_pair_split(w, plan->w_exp, 11, &plan->h_Whi[o], &plan->h_Wlo[o]);
                     }
                 }
 }
@@ -566,34 +539,20 @@ int e3d_bwd_launch(alq_ctx *ctx, const E3dPlan &plan, int N, const float *skip, 
                    const unsigned char *am1, const unsigned char *sg1, float *dsum2, float *dsum1, float in_bound, bool rows) {
     ALQ_REQUIRE(plan.ok && plan.d_Whi && plan.d_Wlo, ALQ_EINVAL, "e3d: weights not set");
     ALQ_REQUIRE(skip && dpool && am2 && sg2 && am1 && sg1 && dsum2 && dsum1 && in_bound > 0.f, ALQ_EINVAL, "e3d: missing argument");
-    ALQ_REQUIRE(N < 4096, ALQ_EUNSUPPORTED, "e3d: 32-bit byte offsets hold fewer than 4096 patches per pass");
+    SWEEP_REQUIRE_PATCHES(N, "e3d");
     if (N <= 0) return ALQ_OK;
-    int ex = 0;
-    (void)std::frexp(in_bound, &ex);
-    const int e_in = 14 - ex;
+    const int e_in = f16_pair_exp(&in_bound, 1);
     E3Args a;
     a.skip = skip; a.dpool = dpool; a.am2 = am2; a.sg2 = sg2; a.Whi = reinterpret_cast<const unsigned short *>(plan.d_Whi);
     a.Wlo = reinterpret_cast<const unsigned short *>(plan.d_Wlo); a.am1 = am1; a.sg1 = sg1; a.dsum2 = dsum2; a.dsum1 = dsum1;
     a.scale = std::ldexp(1.f, e_in); a.inv = std::ldexp(1.f, -(e_in + plan.w_exp)); a.N = N;
-    const int cus = ctx->num_cus;
-    if (!rows) {      // the z plane sweep: a 512-thread workgroup per CU over whole patches
-        long long g = std::min<long long>(cus, N);
-        g = std::max<long long>(8, (g + 7) / 8 * 8);
-        if (g_dbg_knobs[KNOB_E3D_GRID_CAP] > 0) g = std::min<long long>(g, g_dbg_knobs[KNOB_E3D_GRID_CAP]);      // tests: a few workgroups, so that a handful of patches makes multi-patch streams
-        ALQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(e3d_bwdz_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, E3Z_LDS));
-        ProfScope ps(ctx, PROF_IGEMM_F16, plan.flops_per_patch * N);
-        hipLaunchKernelGGL(e3d_bwdz_kernel, dim3((unsigned)g), dim3(512), (size_t)E3Z_LDS, ctx->stream, a);
-        ALQ_HIP(hipGetLastError());
-        return ALQ_OK;
-    }
-    long long g = std::min<long long>(2LL * cus, (long long)N * 4);
-    g = std::max<long long>(8, (g + 7) / 8 * 8);
-    const size_t lds = E3_WLO + E3_STRIP + E3_SINK;
-    ALQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(e3d_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     ProfScope ps(ctx, PROF_IGEMM_F16, plan.flops_per_patch * N);
-    hipLaunchKernelGGL(e3d_bwd_kernel, dim3((unsigned)g), dim3(256), lds, ctx->stream, a);
-    ALQ_HIP(hipGetLastError());
-    return ALQ_OK;
+    if (!rows) {      // the z plane sweep: a 512-thread workgroup per CU over whole patches
+        unsigned g = sweep_grid(ctx, N, 1);
+        if (g_dbg_knobs[KNOB_E3D_GRID_CAP] > 0) g = std::min<unsigned>(g, (unsigned)g_dbg_knobs[KNOB_E3D_GRID_CAP]);      // tests: a few workgroups, so that a handful of patches makes multi-patch streams
+        return sweep_launch(ctx, e3d_bwdz_kernel, g, 512, E3Z_LDS, a);
+    }
+    return sweep_launch(ctx, e3d_bwd_kernel, sweep_grid(ctx, (long long)N * 4, 2), 256, E3_WLO + E3_STRIP + E3_SINK, a);
 }
 
 }  // namespace alq

@@ -294,6 +294,16 @@ static int gemm_build(const EngineSwitches &sw, const ConvDesc &d, int max_batch
     return ALQ_OK;
 }
 
+// packed 16-bit weights of a layer kernel to the device: *d is allocated on the first call and kept; the copy is queued on the
+// context's stream (the caller synchronises once per kernel family, before h may change)
+static int upload_u16(alq_model *m, void **d, const std::vector<unsigned short> &h) {
+    unsigned short *dw = reinterpret_cast<unsigned short *>(*d);
+    if (!dw) ALQ_TRY(m->dalloc(&dw, h.size()));
+    *d = dw;
+    ALQ_HIP(hipMemcpyAsync(dw, h.data(), h.size() * sizeof(unsigned short), hipMemcpyHostToDevice, m->ctx->stream));
+    return ALQ_OK;
+}
+
 static int set4(alq_model *m, Igemm4Plan *p4, const std::vector<float> &Bmat) {
     igemm4_pack_weights(p4, Bmat);
     hipStream_t st = m->ctx->stream;
@@ -2443,58 +2453,37 @@ int alq_model_set_weights(alq_model *m, int t, const float *W, const float *b) {
             // one accumulator (pieces at their true scale) only where the matrix cores honour fp16 subnormals
             if (ly.c3f.oneacc && !c3d_subnormals_ok(m->ctx)) ly.c3f.oneacc = 0;
             c3d_fwd_pack(&ly.c3f, B);
-            unsigned short *dw = reinterpret_cast<unsigned short *>(ly.c3f.d_W);
-            if (!dw) ALQ_TRY(m->dalloc(&dw, ly.c3f.h_W.size()));
-            ly.c3f.d_W = dw;
-            ALQ_HIP(hipMemcpyAsync(dw, ly.c3f.h_W.data(), ly.c3f.h_W.size() * sizeof(unsigned short), hipMemcpyHostToDevice, m->ctx->stream));
+            ALQ_TRY(upload_u16(m, &ly.c3f.d_W, ly.c3f.h_W));
             ALQ_HIP(hipStreamSynchronize(m->ctx->stream));
         }
         if (ly.c3b.ok && ly.has_bwd && c3d_subnormals_ok(m->ctx)) {      // (the backward kernel exists in the one-accumulator form only)
             c3d_bwd_pack(&ly.c3b, B);
-            unsigned short *dw = reinterpret_cast<unsigned short *>(ly.c3b.d_W);
-            if (!dw) ALQ_TRY(m->dalloc(&dw, ly.c3b.h_W.size()));
-            ly.c3b.d_W = dw;
-            ALQ_HIP(hipMemcpyAsync(dw, ly.c3b.h_W.data(), ly.c3b.h_W.size() * sizeof(unsigned short), hipMemcpyHostToDevice, m->ctx->stream));
+            ALQ_TRY(upload_u16(m, &ly.c3b.d_W, ly.c3b.h_W));
             c3d_bwd7_pack(&ly.c3b, B);          // the 7-k-step form of the same weights (c3d_bwd7_kernel)
-            unsigned short *dw7 = reinterpret_cast<unsigned short *>(ly.c3b.d_W7);
-            if (!dw7) ALQ_TRY(m->dalloc(&dw7, ly.c3b.h_W7.size()));
-            ly.c3b.d_W7 = dw7;
-            ALQ_HIP(hipMemcpyAsync(dw7, ly.c3b.h_W7.data(), ly.c3b.h_W7.size() * sizeof(unsigned short), hipMemcpyHostToDevice, m->ctx->stream));
+            ALQ_TRY(upload_u16(m, &ly.c3b.d_W7, ly.c3b.h_W7));
             ALQ_HIP(hipStreamSynchronize(m->ctx->stream));
         }
         if (ly.e3b.ok && ly.has_bwd && c3d_subnormals_ok(m->ctx)) {      // (fp16 pairs at their true scale: the one-accumulator form)
             e3d_pack(&ly.e3b, W);
-            unsigned short *dh = reinterpret_cast<unsigned short *>(ly.e3b.d_Whi), *dl = reinterpret_cast<unsigned short *>(ly.e3b.d_Wlo);
-            if (!dh) { ALQ_TRY(m->dalloc(&dh, ly.e3b.h_Whi.size())); ALQ_TRY(m->dalloc(&dl, ly.e3b.h_Wlo.size())); }
-            ly.e3b.d_Whi = dh; ly.e3b.d_Wlo = dl;
-            ALQ_HIP(hipMemcpyAsync(dh, ly.e3b.h_Whi.data(), ly.e3b.h_Whi.size() * sizeof(unsigned short), hipMemcpyHostToDevice, m->ctx->stream));
-            ALQ_HIP(hipMemcpyAsync(dl, ly.e3b.h_Wlo.data(), ly.e3b.h_Wlo.size() * sizeof(unsigned short), hipMemcpyHostToDevice, m->ctx->stream));
+            ALQ_TRY(upload_u16(m, &ly.e3b.d_Whi, ly.e3b.h_Whi));
+            ALQ_TRY(upload_u16(m, &ly.e3b.d_Wlo, ly.e3b.h_Wlo));
             ALQ_HIP(hipStreamSynchronize(m->ctx->stream));
         }
         if (ly.f3f.ok && !c3d_subnormals_ok(m->ctx)) ly.f3f.ok = false;      // (one-accumulator fp16 pairs)
         if (ly.f3f.ok) {
             f3d_pack(&ly.f3f, W);
-            unsigned short *dh = reinterpret_cast<unsigned short *>(ly.f3f.d_Whi), *dl = reinterpret_cast<unsigned short *>(ly.f3f.d_Wlo);
-            if (!dh) { ALQ_TRY(m->dalloc(&dh, ly.f3f.h_Whi.size())); ALQ_TRY(m->dalloc(&dl, ly.f3f.h_Wlo.size())); }
-            ly.f3f.d_Whi = dh; ly.f3f.d_Wlo = dl;
-            ALQ_HIP(hipMemcpyAsync(dh, ly.f3f.h_Whi.data(), ly.f3f.h_Whi.size() * sizeof(unsigned short), hipMemcpyHostToDevice, m->ctx->stream));
-            ALQ_HIP(hipMemcpyAsync(dl, ly.f3f.h_Wlo.data(), ly.f3f.h_Wlo.size() * sizeof(unsigned short), hipMemcpyHostToDevice, m->ctx->stream));
+            ALQ_TRY(upload_u16(m, &ly.f3f.d_Whi, ly.f3f.h_Whi));
+            ALQ_TRY(upload_u16(m, &ly.f3f.d_Wlo, ly.f3f.h_Wlo));
             ALQ_HIP(hipStreamSynchronize(m->ctx->stream));
         }
         if (ly.d3f.ok) {
             d3d_pack(&ly.d3f, W);
-            unsigned short *dh = reinterpret_cast<unsigned short *>(ly.d3f.d_Whi), *dl = reinterpret_cast<unsigned short *>(ly.d3f.d_Wlo);
-            if (!dh) { ALQ_TRY(m->dalloc(&dh, ly.d3f.h_Whi.size())); ALQ_TRY(m->dalloc(&dl, ly.d3f.h_Wlo.size())); }
-            ly.d3f.d_Whi = dh; ly.d3f.d_Wlo = dl;
-            ALQ_HIP(hipMemcpyAsync(dh, ly.d3f.h_Whi.data(), ly.d3f.h_Whi.size() * sizeof(unsigned short), hipMemcpyHostToDevice, m->ctx->stream));
-            ALQ_HIP(hipMemcpyAsync(dl, ly.d3f.h_Wlo.data(), ly.d3f.h_Wlo.size() * sizeof(unsigned short), hipMemcpyHostToDevice, m->ctx->stream));
+            ALQ_TRY(upload_u16(m, &ly.d3f.d_Whi, ly.d3f.h_Whi));
+            ALQ_TRY(upload_u16(m, &ly.d3f.d_Wlo, ly.d3f.h_Wlo));
             if (ly.has_bwd) {
                 d3d_bwd_pack(&ly.d3f, W);
-                unsigned short *bh = reinterpret_cast<unsigned short *>(ly.d3f.d_Bhi), *bl = reinterpret_cast<unsigned short *>(ly.d3f.d_Blo);
-                if (!bh) { ALQ_TRY(m->dalloc(&bh, ly.d3f.h_Bhi.size())); ALQ_TRY(m->dalloc(&bl, ly.d3f.h_Blo.size())); }
-                ly.d3f.d_Bhi = bh; ly.d3f.d_Blo = bl;
-                ALQ_HIP(hipMemcpyAsync(bh, ly.d3f.h_Bhi.data(), ly.d3f.h_Bhi.size() * sizeof(unsigned short), hipMemcpyHostToDevice, m->ctx->stream));
-                ALQ_HIP(hipMemcpyAsync(bl, ly.d3f.h_Blo.data(), ly.d3f.h_Blo.size() * sizeof(unsigned short), hipMemcpyHostToDevice, m->ctx->stream));
+                ALQ_TRY(upload_u16(m, &ly.d3f.d_Bhi, ly.d3f.h_Bhi));
+                ALQ_TRY(upload_u16(m, &ly.d3f.d_Blo, ly.d3f.h_Blo));
             }
             ALQ_HIP(hipStreamSynchronize(m->ctx->stream));
         }
@@ -2529,11 +2518,8 @@ int alq_model_set_weights(alq_model *m, int t, const float *W, const float *b) {
             }
         }
         if (ly.fwd_all.ok) ALQ_TRY(set4(m, &ly.fwd_all, Bfull));
-        auto up3 = [&](T3dPlan *pl) -> int {
-            unsigned short *dw = reinterpret_cast<unsigned short *>(pl->d_W);
-            if (!dw) ALQ_TRY(m->dalloc(&dw, pl->h_W.size()));
-            pl->d_W = dw;
-            ALQ_HIP(hipMemcpyAsync(dw, pl->h_W.data(), pl->h_W.size() * sizeof(unsigned short), hipMemcpyHostToDevice, m->ctx->stream));
+        auto up3 = [&](T3dPlan *pl) -> int {      // (the t3d plans do not keep their host copy)
+            ALQ_TRY(upload_u16(m, &pl->d_W, pl->h_W));
             ALQ_HIP(hipStreamSynchronize(m->ctx->stream));
             std::vector<unsigned short>().swap(pl->h_W);
             return ALQ_OK;

@@ -20,7 +20,8 @@
 //   * 9 (z, y) tap pairs x 6 (3) piece products = 54 (27) MFMAs per tile of 16 cells, 25 % of the K slots zero (x parity 1 has
 //     no d_x = 1 tap; backward: the 4th x tap slot) - irrelevant under the HBM bound.
 // Two 256-thread workgroups per CU (two waves per SIMD): one wave's loads / stores / split run beside the other's MFMAs.
-#include "alq_internal.h"
+#include "f16_pair.h"
+#include "sweep_common.h"
 #ifndef T3_CLOBBER
 #define T3_CLOBBER : "memory"
 #endif
@@ -32,15 +33,6 @@
 #include <vector>
 
 namespace alq {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 struct T3FwdArgs {
     const float *in;             // [N][16][16][16][16] dense
@@ -62,15 +54,11 @@ struct T3BwdArgs {
     int N;
 };
 
-constexpr unsigned T3_OOB = 0xffffff00u;
 // forward LDS strip of a wave: [row 0: plane iz, row 1: plane iz - 1][3 pieces][17 voxel slots (slot 0 = x -1: zero)][16 ch x 2 B]
 constexpr int T3F_ROWB = 17 * 32, T3F_WAVE = 2 * 3 * T3F_ROWB;
 // backward: [6 rows][2 pieces][34 voxel slots (32, 33: zero)][8 ch x 2 B]
 constexpr int T3B_ROWB = 34 * 16, T3B_WAVE = 6 * 2 * T3B_ROWB;
 
-__device__ inline __amdgpu_buffer_rsrc_t t3_rsrc(const void *base, unsigned long long bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, (int)(unsigned)bytes, 0x00020000);
-}
 // x -> (hi, rem): hi = bf16(x) round-to-nearest packed pairwise, rem = x - hi (exact) - the split of igemm4.hip
 __device__ inline unsigned t3_split2(float &a, float &b) {
     const bf16x2 h = __builtin_convertvector(f32x2{a, b}, bf16x2);
@@ -135,20 +123,20 @@ __global__ __launch_bounds__(256, 2) void t3d_fwd_kernel(const T3FwdArgs a) {
 #pragma unroll
         for (int pc = 0; pc < 3; ++pc) asm volatile("" : "+v"(wr[c][pc]));
     asm volatile("" : "+v"(bias4));
-    const __amdgpu_buffer_rsrc_t in_rsrc = t3_rsrc(a.in, (unsigned long long)a.N * 16 * 16 * 16 * 16 * 4);
-    const __amdgpu_buffer_rsrc_t out_rsrc = t3_rsrc(a.out, (unsigned long long)a.N * 32 * 32 * 32 * 8 * 4);
-    const __amdgpu_buffer_rsrc_t sum_rsrc = t3_rsrc(a.osum, SUMS ? (unsigned long long)a.N * 32 * 32 * 32 * 4 : 0ull);
+    const __amdgpu_buffer_rsrc_t in_rsrc = sw_rsrc(a.in, (unsigned long long)a.N * 16 * 16 * 16 * 16 * 4);
+    const __amdgpu_buffer_rsrc_t out_rsrc = sw_rsrc(a.out, (unsigned long long)a.N * 32 * 32 * 32 * 8 * 4);
+    const __amdgpu_buffer_rsrc_t sum_rsrc = sw_rsrc(a.osum, SUMS ? (unsigned long long)a.N * 32 * 32 * 32 * 4 : 0ull);
     const unsigned ld_off = (unsigned)lane * 16u;
     const unsigned st_off = (unsigned)(2 * n + (kg >> 1)) * 32u + (unsigned)(kg & 1) * 16u;      // inside a 1 KB output row
-    const unsigned sm_off = (kg & 1) ? T3_OOB : (unsigned)(2 * n + (kg >> 1)) * 4u;              // lanes with the channel-half 0 store the sums
+    const unsigned sm_off = (kg & 1) ? SW_OOB : (unsigned)(2 * n + (kg >> 1)) * 4u;              // lanes with the channel-half 0 store the sums
     const int total = t3_total_tiles(a.N);
 
     f32x4 R0[T3F_PF], R1[T3F_PF];      // rows (iz, iy) and (iz - 1, iy) of the tiles in flight
     auto fetch = [&](int T, f32x4 &r0, f32x4 &r1) __attribute__((always_inline)) {
         const T3Cur c = t3_tile(T, total, wave);
         const unsigned row0 = ((unsigned)(c.p * 16 + c.iz) * 16u + (unsigned)c.s) * 1024u;      // byte offset of row (p, iz, iy)
-        r0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, (int)(c.ok ? ld_off : T3_OOB), (int)row0, 0));
-        r1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, (int)((c.ok && c.iz > 0) ? ld_off : T3_OOB), (int)(row0 - 16u * 1024u), 0));
+        r0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, (int)(c.ok ? ld_off : SW_OOB), (int)row0, 0));
+        r1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, (int)((c.ok && c.iz > 0) ? ld_off : SW_OOB), (int)(row0 - 16u * 1024u), 0));
     };
 #pragma unroll
     for (int k = 0; k < T3F_PF; ++k) { R0[k] = f32x4{0.f, 0.f, 0.f, 0.f}; R1[k] = f32x4{0.f, 0.f, 0.f, 0.f}; }
@@ -159,7 +147,7 @@ __global__ __launch_bounds__(256, 2) void t3d_fwd_kernel(const T3FwdArgs a) {
 #pragma unroll
         for (int pc = 0; pc < 3; ++pc) fo[d][pc] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
     float amx = 0.f;
-    const __amdgpu_buffer_rsrc_t amx_rsrc = t3_rsrc(a.out_amax, AMAX ? (unsigned long long)a.N * 16 * 4 : 0ull);
+    const __amdgpu_buffer_rsrc_t amx_rsrc = sw_rsrc(a.out_amax, AMAX ? (unsigned long long)a.N * 16 * 4 : 0ull);
     // The body is straight-line (no branch, no atomic) and there are no loads in front of the loop: the first pass over the body
     // (T0 = -T3F_PF) only issues the first fetches - its own tiles are void (zero rows, stores aimed past the arrays).  With that
     // shape the compiler's vmcnt counting lets the loads of the next T3F_PF - 1 tiles and the stores of the last ones stay in
@@ -169,7 +157,7 @@ __global__ __launch_bounds__(256, 2) void t3d_fwd_kernel(const T3FwdArgs a) {
     if (total > 0)
     for (int T0 = -T3F_PF; T0 < total; T0 += T3F_PF) {
         const bool live = T0 >= 0;
-        const unsigned st_o = live ? st_off : T3_OOB, sm_o = live ? sm_off : T3_OOB;
+        const unsigned st_o = live ? st_off : SW_OOB, sm_o = live ? sm_off : SW_OOB;
 #pragma unroll
         for (int k = 0; k < T3F_PF; ++k) {
             const int T = T0 + k;
@@ -268,7 +256,7 @@ __global__ __launch_bounds__(256, 2) void t3d_fwd_kernel(const T3FwdArgs a) {
                     float mx = amx;
 #pragma unroll
                     for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-                    const unsigned off = (live && iy == 15 && lane == 0) ? 0u : T3_OOB;
+                    const unsigned off = (live && iy == 15 && lane == 0) ? 0u : SW_OOB;
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, mx), amx_rsrc, (int)off, (int)((unsigned)(p * 16 + iz) * 4u), 0);
                     amx = iy == 15 ? 0.f : amx;
                 }
@@ -309,17 +297,17 @@ __global__ __launch_bounds__(256, 2) void t3d_bwd_kernel(const T3BwdArgs a) {
     for (int c = 0; c < 9; ++c)
 #pragma unroll
         for (int pc = 0; pc < 2; ++pc) asm volatile("" : "+v"(wr[c][pc]));      // arrived before the tile loop (see the forward kernel)
-    const __amdgpu_buffer_rsrc_t in_rsrc = t3_rsrc(a.dout, (unsigned long long)a.N * 32 * 32 * 32 * 8 * 4);
-    const __amdgpu_buffer_rsrc_t out_rsrc = t3_rsrc(a.din, (unsigned long long)a.N * 16 * 16 * 16 * 16 * 4);
-    const __amdgpu_buffer_rsrc_t sum_rsrc = t3_rsrc(a.dsum, SUMS ? (unsigned long long)a.N * 16 * 16 * 16 * 4 : 0ull);
-    const __amdgpu_buffer_rsrc_t msk_rsrc = t3_rsrc(a.mask_bits, MASK ? (unsigned long long)a.N * 16 * 16 * 16 * 4 : 0ull);
+    const __amdgpu_buffer_rsrc_t in_rsrc = sw_rsrc(a.dout, (unsigned long long)a.N * 32 * 32 * 32 * 8 * 4);
+    const __amdgpu_buffer_rsrc_t out_rsrc = sw_rsrc(a.din, (unsigned long long)a.N * 16 * 16 * 16 * 16 * 4);
+    const __amdgpu_buffer_rsrc_t sum_rsrc = sw_rsrc(a.dsum, SUMS ? (unsigned long long)a.N * 16 * 16 * 16 * 4 : 0ull);
+    const __amdgpu_buffer_rsrc_t msk_rsrc = sw_rsrc(a.mask_bits, MASK ? (unsigned long long)a.N * 16 * 16 * 16 * 4 : 0ull);
     const unsigned ld_off = (unsigned)lane * 16u;
     const unsigned st_off = (unsigned)n * 64u + (unsigned)kg * 16u;       // cell n, channels 4 kg .. + 3 inside a 1 KB row of d_in
     const unsigned mk_off = (unsigned)n * 4u + (unsigned)kg;
     // channel sums leave once per PAIR of tiles (rows iy odd, iy - 1: one aligned 128-byte line of d_sum): lanes kg = 0 carry the
     // even row's 16 sums, lanes kg = 1 the odd row's (every lane holds its cell's sum after the butterfly)
     static_assert(T3B_PF == 2, "the sum store pairs the two tiles of a pass over the body");
-    const unsigned sm_off = kg < 2 ? (unsigned)n * 4u + (unsigned)kg * 64u : T3_OOB;
+    const unsigned sm_off = kg < 2 ? (unsigned)n * 4u + (unsigned)kg * 64u : SW_OOB;
     const float sc = a.scale;
     const int total = t3_total_tiles(a.N);
 
@@ -338,7 +326,7 @@ __global__ __launch_bounds__(256, 2) void t3d_bwd_kernel(const T3BwdArgs a) {
         const int iy = 15 - c.s;
         // source rows (z = 2 iz + tz, y = 2 iy + ty) at ((p * 32 + z) * 32 + y) * 1024; z = 32 does not exist
         const unsigned b0 = (((unsigned)c.p * 32u + (unsigned)(2 * c.iz)) * 32u + (unsigned)(2 * iy)) * 1024u;
-        const unsigned okl = c.ok ? ld_off : T3_OOB, ok2 = (c.ok && 2 * c.iz + 2 < 32) ? ld_off : T3_OOB;
+        const unsigned okl = c.ok ? ld_off : SW_OOB, ok2 = (c.ok && 2 * c.iz + 2 < 32) ? ld_off : SW_OOB;
 #pragma unroll
         for (int tz = 0; tz < 3; ++tz)
 #pragma unroll
@@ -346,7 +334,7 @@ __global__ __launch_bounds__(256, 2) void t3d_bwd_kernel(const T3BwdArgs a) {
                 r[tz * 2 + ty] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, (int)(tz < 2 ? okl : ok2),
                                                                                                  (int)(b0 + (unsigned)tz * 32768u + (unsigned)ty * 1024u), 0));
         if constexpr (MASK)
-            mk = (unsigned)(unsigned char)__builtin_amdgcn_raw_buffer_load_b8(msk_rsrc, (int)(c.ok ? mk_off : T3_OOB),
+            mk = (unsigned)(unsigned char)__builtin_amdgcn_raw_buffer_load_b8(msk_rsrc, (int)(c.ok ? mk_off : SW_OOB),
                                                                              (int)((((unsigned)c.p * 16u + (unsigned)c.iz) * 16u + (unsigned)iy) * 64u), 0);
     };
 #pragma unroll
@@ -366,7 +354,7 @@ __global__ __launch_bounds__(256, 2) void t3d_bwd_kernel(const T3BwdArgs a) {
     if (total > 0)
     for (int T0 = -T3B_PF; T0 < total; T0 += T3B_PF) {
         const bool live = T0 >= 0;
-        const unsigned st_o = live ? st_off : T3_OOB, sm_o = live ? sm_off : T3_OOB;
+        const unsigned st_o = live ? st_off : SW_OOB, sm_o = live ? sm_off : SW_OOB;
         float s_odd = 0.f;      // the sums of the pass's first tile (odd iy)
 #pragma unroll
         for (int k = 0; k < T3B_PF; ++k) {
@@ -477,9 +465,9 @@ __global__ __launch_bounds__(512, 2) void t3d8_fwd_kernel(const T8FwdArgs a) {
     char *strip = t3lds + T8_WBYTES + wave * T8_WAVE;
     f32x4 bias4 = *reinterpret_cast<const f32x4 *>(a.bias + 4 * kg);
     asm volatile("" : "+v"(bias4));
-    const __amdgpu_buffer_rsrc_t in_rsrc = t3_rsrc(a.in, (unsigned long long)a.N * 8 * 8 * 8 * 32 * 4);
-    const __amdgpu_buffer_rsrc_t out_rsrc = t3_rsrc(a.out, (unsigned long long)a.N * 16 * 16 * 16 * 16 * 4);
-    const __amdgpu_buffer_rsrc_t sum_rsrc = t3_rsrc(a.osum, SUMS ? (unsigned long long)a.N * 16 * 16 * 16 * 4 : 0ull);
+    const __amdgpu_buffer_rsrc_t in_rsrc = sw_rsrc(a.in, (unsigned long long)a.N * 8 * 8 * 8 * 32 * 4);
+    const __amdgpu_buffer_rsrc_t out_rsrc = sw_rsrc(a.out, (unsigned long long)a.N * 16 * 16 * 16 * 16 * 4);
+    const __amdgpu_buffer_rsrc_t sum_rsrc = sw_rsrc(a.osum, SUMS ? (unsigned long long)a.N * 16 * 16 * 16 * 4 : 0ull);
     const int iz = wave;
     const char *wl = t3lds + lane * 16;
     const int npw = a.N > (int)blockIdx.x ? (a.N - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x : 0;      // patches of this workgroup
@@ -495,7 +483,7 @@ __global__ __launch_bounds__(512, 2) void t3d8_fwd_kernel(const T8FwdArgs a) {
         const bool ok = u >= 0 && u < npw;
         const int p = (int)blockIdx.x + (int)gridDim.x * (ok ? u : 0);
         const unsigned pb = (((unsigned)p * 8u + (unsigned)iz) * 8u + (unsigned)(2 * j)) * 1024u;      // row (p, iz, 2 j)
-        const unsigned o0 = ok ? ld_off : T3_OOB, o1 = (ok && iz > 0) ? ld_off : T3_OOB;
+        const unsigned o0 = ok ? ld_off : SW_OOB, o1 = (ok && iz > 0) ? ld_off : SW_OOB;
         rr[0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, (int)o0, (int)pb, 0));
         rr[1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, (int)o0, (int)(pb + 1024u), 0));
         rr[2] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, (int)o1, (int)(pb - 8u * 1024u), 0));
@@ -590,7 +578,7 @@ __global__ __launch_bounds__(512, 2) void t3d8_fwd_kernel(const T8FwdArgs a) {
             for (int i = 0; i < 8; ++i) {
                 const int pz = i >> 2, py = (i >> 1) & 1, px = i & 1;
                 const unsigned vox = vb + (unsigned)(pz * 256 + py * 16 + px);
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, vv[i]), out_rsrc, (int)(live ? vox * 64u + (unsigned)kg * 16u : T3_OOB), 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, vv[i]), out_rsrc, (int)(live ? vox * 64u + (unsigned)kg * 16u : SW_OOB), 0, 0);
             }
             if constexpr (SUMS) {      // channel sums: the two cross-lane steps of all eight parities side by side (one LDS round trip each, not sixteen)
                 float s1[8], s2[8];
@@ -604,7 +592,7 @@ __global__ __launch_bounds__(512, 2) void t3d8_fwd_kernel(const T8FwdArgs a) {
                 for (int i = 0; i < 8; ++i) {
                     const int pz = i >> 2, py = (i >> 1) & 1, px = i & 1;
                     const unsigned vox = vb + (unsigned)(pz * 256 + py * 16 + px);
-                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, s1[i]), sum_rsrc, (int)((live && kg == 0) ? vox * 4u : T3_OOB), 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, s1[i]), sum_rsrc, (int)((live && kg == 0) ? vox * 4u : SW_OOB), 0, 0);
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -707,11 +695,7 @@ void t3d8_fwd_pack(T3dPlan *plan, const float *W) {
 // Backward A fragment of (tz, ty): lane -> row ci = lane & 15, k-group = x tap tx = lane >> 4 (3: zero), k = co.  fp16 pairs of
 // w * 2^e_w at their true scale.
 void t3d_bwd_pack(T3dPlan *plan, const float *W) {
-    float amax = 0.f;
-    for (size_t i = 0; i < (size_t)27 * 8 * 16; ++i) amax = std::max(amax, std::fabs(W[i]));
-    int ex = 0;
-    if (amax > 0.f) (void)std::frexp(amax, &ex);
-    plan->w_exp = 14 - ex;
+    plan->w_exp = f16_pair_exp(W, (size_t)27 * 8 * 16);
     plan->h_W.assign((size_t)9 * 2 * 64 * 8, 0);
     for (int tz = 0; tz < 3; ++tz)
         for (int ty = 0; ty < 3; ++ty)
@@ -719,27 +703,17 @@ void t3d_bwd_pack(T3dPlan *plan, const float *W) {
                 const int ci = lane & 15, tx = lane >> 4;
                 for (int co = 0; co < 8; ++co) {
                     const float w = tx < 3 ? W[((size_t)((tz * 3 + ty) * 3 + tx) * 8 + co) * 16 + ci] : 0.f;
-                    const float ws = std::ldexp(w, plan->w_exp);
-                    const _Float16 h = (_Float16)ws;
-                    const _Float16 l = (_Float16)(ws - (float)h);
-                    unsigned short hb, lb;
-                    std::memcpy(&hb, &h, 2);
-                    std::memcpy(&lb, &l, 2);
-                    plan->h_W[((size_t)((tz * 3 + ty) * 2 + 0) * 64 + lane) * 8 + co] = hb;
-                    plan->h_W[((size_t)((tz * 3 + ty) * 2 + 1) * 64 + lane) * 8 + co] = lb;
+                    f16_pair_split(w, plan->w_exp, 0, &plan->h_W[((size_t)((tz * 3 + ty) * 2 + 0) * 64 + lane) * 8 + co],
+                                   &plan->h_W[((size_t)((tz * 3 + ty) * 2 + 1) * 64 + lane) * 8 + co]);
                 }
             }
 }
 
 static unsigned t3_grid(alq_ctx *ctx, int N) {
-    // two workgroups per CU; units = 4 per patch, dealt per XCD (t3_unit): a multiple of 8 workgroups
-    const int cus = ctx->num_cus;
-    const long long units = (long long)N * 4;
+    // two workgroups per CU; units = 4 per patch, dealt per XCD (t3_tile)
     int per_cu = 2;
     if (const char *e = getenv("ALQ_T3D_WGS")) per_cu = std::max(1, std::min(2, atoi(e)));      // (tuning / diagnostics)
-    long long g = std::min<long long>((long long)per_cu * cus, units);
-    g = std::max<long long>(8, (g + 7) / 8 * 8);
-    return (unsigned)g;
+    return sweep_grid(ctx, (long long)N * 4, per_cu);
 }
 
 int t3d_fwd_launch(alq_ctx *ctx, const T3dPlan &plan, const View &in, const View &out, const float *bias, int N, float *osum, unsigned *out_amax) {
@@ -747,25 +721,17 @@ int t3d_fwd_launch(alq_ctx *ctx, const T3dPlan &plan, const View &in, const View
     if (plan.kind == 8) {
         ALQ_REQUIRE(in.cs == 32 && in.c0 == 0 && in.split == 0 && out.cs == 16 && out.c0 == 0 && out.split == 0 && in.D == 8 && in.H == 8 && in.W == 8 &&
                     out.D == 16 && bias && !out_amax, ALQ_EINVAL, "t3d8: view mismatch");
-        ALQ_REQUIRE(N < 4096, ALQ_EUNSUPPORTED, "t3d: 32-bit byte offsets hold fewer than 4096 patches per pass");
+        SWEEP_REQUIRE_PATCHES(N, "t3d");
         if (N <= 0) return ALQ_OK;
         T8FwdArgs a8;
         a8.in = in.p; a8.out = out.p; a8.W = reinterpret_cast<const unsigned short *>(plan.d_W); a8.bias = bias; a8.osum = osum; a8.N = N;
-        const int cus = ctx->num_cus;
-        const dim3 grid8((unsigned)std::min(N, cus));
         ProfScope ps8(ctx, PROF_IGEMM3_FWD, plan.flops_per_patch * N);
-        auto go = [&](auto kfn) -> int {
-            ALQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, T8_WBYTES + 8 * T8_WAVE));
-            hipLaunchKernelGGL(kfn, grid8, dim3(512), T8_WBYTES + 8 * T8_WAVE, ctx->stream, a8);
-            return ALQ_OK;
-        };
-        ALQ_TRY(osum ? go(t3d8_fwd_kernel<true>) : go(t3d8_fwd_kernel<false>));
-        ALQ_HIP(hipGetLastError());
-        return ALQ_OK;
+        auto go = [&](auto kfn) { return sweep_launch(ctx, kfn, (unsigned)std::min(N, ctx->num_cus), 512, T8_WBYTES + 8 * T8_WAVE, a8); };
+        return osum ? go(t3d8_fwd_kernel<true>) : go(t3d8_fwd_kernel<false>);
     }
     ALQ_REQUIRE(in.cs == 16 && in.c0 == 0 && in.split == 0 && out.cs == 8 && out.c0 == 0 && out.split == 0 && in.D == 16 && out.D == 32 && bias,
                 ALQ_EINVAL, "t3d: view mismatch");
-    ALQ_REQUIRE(N < 4096, ALQ_EUNSUPPORTED, "t3d: 32-bit byte offsets hold fewer than 4096 patches per pass");
+    SWEEP_REQUIRE_PATCHES(N, "t3d");
     if (N <= 0) return ALQ_OK;
     T3FwdArgs a;
     a.in = in.p; a.out = out.p; a.W = reinterpret_cast<const unsigned short *>(plan.d_W); a.bias = bias; a.osum = osum; a.out_amax = out_amax; a.N = N;
@@ -784,11 +750,9 @@ int t3d_bwd_launch(alq_ctx *ctx, const T3dPlan &plan, const View &dout, const Vi
     if (plan.kind == 8) return t3d8_bwd_launch(ctx, plan, dout, din, N, in_bound, mask_bits, dsum);
     ALQ_REQUIRE(dout.cs == 8 && dout.c0 == 0 && dout.split == 0 && din.cs == 16 && din.c0 == 0 && din.split == 0 && din.D == 16 && dout.D == 32 && in_bound > 0.f,
                 ALQ_EINVAL, "t3d: view mismatch");
-    ALQ_REQUIRE(N < 4096, ALQ_EUNSUPPORTED, "t3d: 32-bit byte offsets hold fewer than 4096 patches per pass");
+    SWEEP_REQUIRE_PATCHES(N, "t3d");
     if (N <= 0) return ALQ_OK;
-    int ex = 0;
-    (void)std::frexp(in_bound, &ex);
-    const int e_in = 14 - ex;
+    const int e_in = f16_pair_exp(&in_bound, 1);
     T3BwdArgs a;
     a.dout = dout.p; a.din = din.p; a.W = reinterpret_cast<const unsigned short *>(plan.d_W); a.mask_bits = mask_bits; a.dsum = dsum;
     a.scale = std::ldexp(1.f, e_in); a.inv = std::ldexp(1.f, -(e_in + plan.w_exp)); a.N = N;

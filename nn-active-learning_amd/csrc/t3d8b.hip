@@ -15,7 +15,8 @@
 //     k-group fall on disjoint banks;
 //   * epilogue: ReLU mask from the sign byte, 16-byte stores (a lane holds 4 channels of one voxel), channel sums: 16 channels in
 //     the wave, the other 16 from the partner wave through LDS.
-#include "alq_internal.h"
+#include "f16_pair.h"
+#include "sweep_common.h"
 
 #include <algorithm>
 #include <cmath>
@@ -24,13 +25,6 @@
 #include <vector>
 
 namespace alq {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 struct T8BwdArgs {
     const float *dout;            // [N][16^3][16] cotangent of up1's output (dense)
@@ -42,7 +36,6 @@ struct T8BwdArgs {
     int N;
 };
 
-constexpr unsigned T8B_OOB = 0xffffff00u;
 constexpr int T8B_KG = 17 * 16;               // a k-group block of a row: 17 voxel slots (x = 0 .. 16) x 8 channels x 2 B
 constexpr int T8B_PIECE = 2 * T8B_KG;         // one piece of a row: 544 B
 constexpr int T8B_ROW = 2 * T8B_PIECE + 16;   // 1104 B: + 16 so that a shifted row ends in front of the next one
@@ -51,10 +44,6 @@ constexpr int T8B_RING = 3 * T8B_PLANE;
 constexpr int T8B_XCH = 4 * 16 * 4;           // partial channel sums of the odd channel block: 4 tiles x 16 voxels
 constexpr int T8B_LDS = T8B_RING + T8B_XCH;
 
-__device__ inline __amdgpu_buffer_rsrc_t t8b_rsrc(const void *base, unsigned long long bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, (int)(unsigned)bytes, 0x00020000);
-}
-__device__ inline int t8b_s(unsigned v) { return __builtin_amdgcn_readfirstlane((int)v); }
 // byte offset of row y inside a plane image: every other row PAIR is shifted by 16 bytes
 __device__ __host__ inline int t8b_row(int y) { return y * T8B_ROW + ((y >> 1) & 1) * 16; }
 
@@ -76,10 +65,10 @@ __global__ __launch_bounds__(256, 2) void t3d8_bwd_kernel(const T8BwdArgs a) {
 #pragma unroll
     for (int c = 0; c < 15; ++c) asm volatile("" : "+v"(wh[c]), "+v"(wl[c]));      // arrived before the loop
 
-    const __amdgpu_buffer_rsrc_t i_rsrc = t8b_rsrc(a.dout, (unsigned long long)a.N * 4096 * 64);
-    const __amdgpu_buffer_rsrc_t o_rsrc = t8b_rsrc(a.din, (unsigned long long)a.N * 512 * 128);
-    const __amdgpu_buffer_rsrc_t m_rsrc = t8b_rsrc(a.mask_bits, a.mask_bits ? (unsigned long long)a.N * 512 * 8 : 0ull);
-    const __amdgpu_buffer_rsrc_t u_rsrc = t8b_rsrc(a.dsum, a.dsum ? (unsigned long long)a.N * 512 * 4 : 0ull);
+    const __amdgpu_buffer_rsrc_t i_rsrc = sw_rsrc(a.dout, (unsigned long long)a.N * 4096 * 64);
+    const __amdgpu_buffer_rsrc_t o_rsrc = sw_rsrc(a.din, (unsigned long long)a.N * 512 * 128);
+    const __amdgpu_buffer_rsrc_t m_rsrc = sw_rsrc(a.mask_bits, a.mask_bits ? (unsigned long long)a.N * 512 * 8 : 0ull);
+    const __amdgpu_buffer_rsrc_t u_rsrc = sw_rsrc(a.dsum, a.dsum ? (unsigned long long)a.N * 512 * 4 : 0ull);
 
     // staging lane roles: voxel x = lane >> 2 of a row, channels 4 cq .. + 3: k-group cq >> 1, bytes 8 (cq & 1) ..
     const int sx = lane >> 2, cq = lane & 3;
@@ -99,11 +88,7 @@ __global__ __launch_bounds__(256, 2) void t3d8_bwd_kernel(const T8BwdArgs a) {
     // epilogue lane roles: output voxel n of the tile, channels 16 cb + 4 kg .. + 3
     const unsigned e_out = (unsigned)(cb * 64 + kg * 16), e_msk = (unsigned)(cb * 4 + kg);
 
-    // patches of this workgroup (XCD-aware as in t3d.hip)
-    const int G8 = (int)gridDim.x >> 3, xcd = (int)blockIdx.x & 7, jb = (int)blockIdx.x >> 3;
-    const int npx = a.N > xcd ? (a.N - xcd + 7) >> 3 : 0;
-    const int npw = npx > jb ? (npx - jb + G8 - 1) / G8 : 0;
-    auto patch_of = [&](int i) __attribute__((always_inline)) { return 8 * (jb + (i < npw ? i : npw - 1) * G8) + xcd; };
+    SW_PATCH_ORDER(a.N);
 
     // this wave's rows of a staging group: 32 rows (two planes x 16) over 4 waves = 8 rows: list index k = 8 wave + j -> plane pa + (k >> 4), row k & 15
     f32x4 RA[8];
@@ -113,7 +98,7 @@ __global__ __launch_bounds__(256, 2) void t3d8_bwd_kernel(const T8BwdArgs a) {
             const int k = 8 * wave + j;
             const int pz = pa + (k >> 4);
             const unsigned row = ((unsigned)p * 16u + (unsigned)(pz < 16 ? pz : 15)) * 16u + (unsigned)(k & 15);
-            RA[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(i_rsrc, (int)ldA, t8b_s(row * 1024u), 0));
+            RA[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(i_rsrc, (int)ldA, sw_s(row * 1024u), 0));
         }
     };
     auto stage = [&](int pa, bool on) __attribute__((always_inline)) {
@@ -144,7 +129,7 @@ __global__ __launch_bounds__(256, 2) void t3d8_bwd_kernel(const T8BwdArgs a) {
             f32x4 R0[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                R0[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(i_rsrc, (int)ldA, t8b_s((((unsigned)p * 16u) * 16u + (unsigned)(4 * wave + j)) * 1024u), 0));
+                R0[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(i_rsrc, (int)ldA, sw_s((((unsigned)p * 16u) * 16u + (unsigned)(4 * wave + j)) * 1024u), 0));
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 char *dst = ring + t8b_row(4 * wave + j) + w_off;
@@ -163,7 +148,7 @@ __global__ __launch_bounds__(256, 2) void t3d8_bwd_kernel(const T8BwdArgs a) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const unsigned vox = ((unsigned)p * 8u + (unsigned)zq) * 64u + (unsigned)(tp + 2 * j) * 16u;      // first voxel of the tile
-            mb[j] = a.mask_bits ? (unsigned)(unsigned char)__builtin_amdgcn_raw_buffer_load_b8(m_rsrc, (int)((unsigned)n * 8u + e_msk), t8b_s(vox * 8u), 0) : 0xfu;
+            mb[j] = a.mask_bits ? (unsigned)(unsigned char)__builtin_amdgcn_raw_buffer_load_b8(m_rsrc, (int)((unsigned)n * 8u + e_msk), sw_s(vox * 8u), 0) : 0xfu;
         }
         __syncthreads();
         if (g + 1 < total) fetch(patch_of((g + 1) >> 3), 2 * ((g + 1) & 7) + 1);
@@ -189,7 +174,7 @@ __global__ __launch_bounds__(256, 2) void t3d8_bwd_kernel(const T8BwdArgs a) {
         float part[2];
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            const unsigned vox = (unsigned)t8b_s((((unsigned)p * 8u + (unsigned)zq) * 64u + (unsigned)(tp + 2 * j) * 16u));
+            const unsigned vox = (unsigned)sw_s((((unsigned)p * 8u + (unsigned)zq) * 64u + (unsigned)(tp + 2 * j) * 16u));
             const unsigned m = mb[j];
             const float v0 = (m & 1u) ? __builtin_fmaf(cx[j].x, 0x1p-11f, c[j].x) * a.inv : 0.f, v1 = (m & 2u) ? __builtin_fmaf(cx[j].y, 0x1p-11f, c[j].y) * a.inv : 0.f;
             const float v2 = (m & 4u) ? __builtin_fmaf(cx[j].z, 0x1p-11f, c[j].z) * a.inv : 0.f, v3 = (m & 8u) ? __builtin_fmaf(cx[j].w, 0x1p-11f, c[j].w) * a.inv : 0.f;
@@ -206,9 +191,9 @@ __global__ __launch_bounds__(256, 2) void t3d8_bwd_kernel(const T8BwdArgs a) {
         if (cb == 0 && a.dsum) {
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                const unsigned vox = (unsigned)t8b_s((((unsigned)p * 8u + (unsigned)zq) * 64u + (unsigned)(tp + 2 * j) * 16u));
+                const unsigned vox = (unsigned)sw_s((((unsigned)p * 8u + (unsigned)zq) * 64u + (unsigned)(tp + 2 * j) * 16u));
                 const float s_ = part[j] + xch[(tp + 2 * j) * 16 + n];
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, s_), u_rsrc, (int)(kg == 0 ? (unsigned)n * 4u : T8B_OOB), (int)(vox * 4u), 0);
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, s_), u_rsrc, (int)(kg == 0 ? (unsigned)n * 4u : SW_OOB), (int)(vox * 4u), 0);
             }
         }
     }
@@ -219,11 +204,7 @@ __global__ __launch_bounds__(256, 2) void t3d8_bwd_kernel(const T8BwdArgs a) {
 // k-group kg = lane >> 4: window position half h = kg >> 1, co = 8 (kg & 1) + c; the position (ty, tx) of (pi, h): pi < 3: (pi, h); pi = 3: (h, 2); pi = 4: (2, 2) for
 // h = 0, none for h = 1.
 void t3d8_bwd_pack(T3dPlan *plan, const float *W) {
-    float amax = 0.f;
-    for (size_t i = 0; i < (size_t)27 * 16 * 32; ++i) amax = std::max(amax, std::fabs(W[i]));
-    int ex = 0;
-    if (amax > 0.f) (void)std::frexp(amax, &ex);
-    plan->w_exp = 14 - ex;
+    plan->w_exp = f16_pair_exp(W, (size_t)27 * 16 * 32);
     plan->h_W.assign((size_t)2 * 2 * 15 * 64 * 8, 0);
     for (int cb = 0; cb < 2; ++cb)
         for (int tz = 0; tz < 3; ++tz)
@@ -236,15 +217,8 @@ void t3d8_bwd_pack(T3dPlan *plan, const float *W) {
                     for (int c = 0; c < 8; ++c) {
                         const int co = 8 * (kg & 1) + c, ci = 16 * cb + r;
                         const float w = any ? W[((size_t)((tz * 3 + ty) * 3 + tx) * 16 + co) * 32 + ci] : 0.f;
-                        const float ws = std::ldexp(w, plan->w_exp);
-                        const _Float16 hh = (_Float16)ws;
-                        const _Float16 ll = (_Float16)std::ldexp(ws - (float)hh, 11);
-                        unsigned short hb, lb;
-                        std::memcpy(&hb, &hh, 2);
-                        std::memcpy(&lb, &ll, 2);
                         const size_t f = (size_t)(cb * 15 + tz * 5 + pi);
-                        plan->h_W[(((size_t)0 * 30 + f) * 64 + lane) * 8 + c] = hb;
-                        plan->h_W[(((size_t)1 * 30 + f) * 64 + lane) * 8 + c] = lb;
+                        f16_pair_split(w, plan->w_exp, 11, &plan->h_W[(((size_t)0 * 30 + f) * 64 + lane) * 8 + c], &plan->h_W[(((size_t)1 * 30 + f) * 64 + lane) * 8 + c]);
                     }
                 }
 }
@@ -253,22 +227,14 @@ int t3d8_bwd_launch(alq_ctx *ctx, const T3dPlan &plan, const View &dout, const V
     ALQ_REQUIRE(plan.ok && plan.d_W && plan.kind == 8, ALQ_EINVAL, "t3d8: backward weights not set");
     ALQ_REQUIRE(dout.cs == 16 && dout.c0 == 0 && dout.split == 0 && dout.D == 16 && din.cs == 32 && din.c0 == 0 && din.split == 0 && din.D == 8 && in_bound > 0.f,
                 ALQ_EINVAL, "t3d8: view mismatch");
-    ALQ_REQUIRE(N < 4096, ALQ_EUNSUPPORTED, "t3d8: 32-bit byte offsets hold fewer than 4096 patches per pass");
+    SWEEP_REQUIRE_PATCHES(N, "t3d8");
     if (N <= 0) return ALQ_OK;
-    int ex = 0;
-    (void)std::frexp(in_bound, &ex);
-    const int e_in = 14 - ex;
+    const int e_in = f16_pair_exp(&in_bound, 1);
     T8BwdArgs a;
     a.dout = dout.p; a.din = din.p; a.W = reinterpret_cast<const unsigned short *>(plan.d_W); a.mask_bits = mask_bits; a.dsum = dsum;
     a.scale = std::ldexp(1.f, e_in); a.scale11 = std::ldexp(1.f, e_in + 11); a.inv = std::ldexp(1.f, -(e_in + plan.w_exp)); a.N = N;
-    const int cus = ctx->num_cus;
-    long long g = std::min<long long>(2LL * cus, (long long)N);
-    g = std::max<long long>(8, (g + 7) / 8 * 8);
-    ALQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(t3d8_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)T8B_LDS));
     ProfScope ps(ctx, PROF_IGEMM_F16, plan.flops_per_patch * N);
-    hipLaunchKernelGGL(t3d8_bwd_kernel, dim3((unsigned)g), dim3(256), T8B_LDS, ctx->stream, a);
-    ALQ_HIP(hipGetLastError());
-    return ALQ_OK;
+    return sweep_launch(ctx, t3d8_bwd_kernel, sweep_grid(ctx, N, 2), 256, T8B_LDS, a);
 }
 
 }  // namespace alq
