@@ -1,14 +1,13 @@
 // Model plan + orchestration behind the C ABI: shapes, activation / cotangent workspaces
-// (concat skips = channel slices of one buffer), weight re-layout into the GEMM engine's
-// packed form, and the forward / Fisher launch sequences.
+// (concat skips = channel slices of one buffer) and the forward / Fisher launch sequences.
+// The structures are in model_types.h; weights reach the engines' packed forms in weights.hip.
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstring>
 #include <string>
-#include <memory>
 
-#include "alq_internal.h"
+#include "model_types.h"
 
 namespace alq {
 
@@ -37,180 +36,9 @@ static void same_pads(int in, int k, int s, int *out, int *lo) {
     *lo = total / 2;
 }
 
-struct Layer {
-    alq_layer_t spec;
-    int pidx = -1;             // parameterised-layer index t, or -1
-    View in, out;              // activation views (in = incl. concatenated skip channels)
-    View din, dout;            // cotangent views, same geometry
-    int lo[3] = {0, 0, 0};     // SAME pad-before (conv: of the fwd conv; convT: of the conv it transposes)
-    bool dense_fc_small = false;
-    int64_t F = 0;             // fc: input features
-    // weights
-    int64_t w_elems = 0, b_elems = 0;
-    float *d_bias = nullptr;
-    float *d_Wp = nullptr;     // skinny fc: [nout][F] in activation-memory order
-    std::vector<Gemm> fwd;        // 1 contraction (conv / fc) or one per output parity class (convT)
-    // conv whose output is too wide for the matrix-core engines (NET-B's 96-channel conv: igemm2 / igemm3 hold <= 48, the two-slot
-    // engine <= 32 output channels) and would run on the fp32 engine: the same contraction as launches of fwd_co_w output channels
-    // each, writing channel slices of the output (round 6)
-    std::vector<Gemm> fwd_co;
-    int fwd_co_w = 0;
-    Igemm4Plan fwd_all;           // convT: every output class from one staged block (igemm4.hip), when eligible
-    Gemm bwd;
-    bool has_bwd = false;
-    bool weights_set = false;
-    // wide fc layer packed on the device (alq_model_set_weights_device): the raw fp32 weights stay resident in activation-memory
-    // order [o][f_mem]; the forms only the debug knobs select (igemm / igemm2 / igemm3 behind the streaming GEMM) are packed from
-    // them on the host when a call first needs them (refresh_fallback_forms)
-    float *d_Wres = nullptr;
-    bool fallback_stale = false;
-    // workspaces
-    uint8_t *argmax = nullptr;
-    float *asum = nullptr, *dsum = nullptr;
-    double *ls_field = nullptr; // [max_batch, out voxels] (fc: [max_batch]): field of alq_class_layer_sums, filled once per call
-    float *osum = nullptr;     // channel sums of this layer's OUTPUT (spatial layers): next layers' asum
-    bool delta_ready = false;  // backward: the cotangent of our output is already masked and dsum is filled
-    bool signs_ready = false;  // Fisher pass: the forward launch wrote the sign field of our output (View::sg)
-    bool dsum_partial = false; // backward, first layer: the skip destination has written its share of dsum
-    float *fc_partials = nullptr;
-    // fc head of a Fisher pass on top of a ReLU conv: its input cotangent is [input > 0] * fc_wv for every patch; the
-    // forward pass leaves the signs (one byte per 4 elements), the backward pass of the conv below contracts them
-    // directly (igemm4 BITSRC)
-    unsigned *fc_maskbits = nullptr;
-    float *fc_wv = nullptr;
-    unsigned *fc_wv16 = nullptr;       // fc_wv pre-split into fp16 pairs for the fp16x2 contraction of the conv below (BITSRC)
-    float fc_wv_amax = 0.f;            // max |W0 - W1| of a two-output head (host side, set with the weights)
-    const unsigned *dout_amax = nullptr;   // per-patch max |cotangent of this layer's output| of the running backward pass, or null
-    unsigned *amax_fwd = nullptr;          // [max_batch] per-patch max |output| of a forward pass that asked for it
-    float dout_vec_amax = 0.f;
-    // Static bounds for the fp16x2 contraction of backward launches (no data pass needed): bwd_l1 = max over the input
-    // channels of sum_{taps, output channels} |W| (set with the weights), i.e. |cotangent of the input| <= bwd_l1 * max
-    // |cotangent of the output|; dout_bound = the bound on this layer's output cotangent in the running Fisher pass
-    // (unit cotangent at the logits, chained down by run_backward_main).
-    double bwd_l1 = 0;
-    float dout_bound = 0.f;
-    // flip-safe fused head (the conv under a two-class head): plain fp32 copy of the weights in TF layout [tap][ci][co] for the
-    // exact re-evaluation, and max over co of sum_{tap, ci} |W|
-    float *d_W32 = nullptr;
-    float fwd_l1 = 0.f;
-    float out_l1 = 0.f, out_bmax = 0.f;    // |out| <= out_l1 * max |in| + out_bmax (conv: = fwd_l1; conv_transpose: all taps), set with the weights
-    unsigned *bound_fwd = nullptr;         // per-patch bound on |out| derived from the first layer's measured maximum (k_fwd_bounds)
-    float *fc_part2 = nullptr;         // partial logits per (tile, wave) when the conv below computes them in its epilogue
-    int fc_slices2 = 0;
-    // plane-sweep engine (c3d.hip) for the conv under the fused two-class head (and its backward): plans on the conv layer,
-    // per-(patch, wave) partials of the logit difference / of the head's input sum on the head layer
-    C3dPlan c3f, c3b;
-    D3dPlan d3f;                           // forward on the row-sweep engine of d3d.hip (NET-C's dec1)
-    F3dPlan f3f;                           // forward fused with the max-pool behind it (f3d.hip; NET-C's enc2)
-    E3dPlan e3b;                           // backward fused with the pool backward steps on either side (e3d.hip; NET-C's enc2)
-    T3dPlan t3f, t3b;                      // row-sweep engine for the stride-2 conv_transpose (t3d.hip), forward / backward-data
-    float *c3_part = nullptr, *c3_asum = nullptr;
-    unsigned short *fc_wv16c = nullptr;    // fc_wv as fp16 pairs at their true scale, [voxel][h8 | l8] (c3d_presplit_vec), for c3b
-    const unsigned short *dout_vec16c = nullptr;   // set on the conv below for one backward pass, like dout_vec16
-    const unsigned *dout_bits = nullptr;   // set on the conv below for the duration of one backward pass
-    const float *dout_vec = nullptr;
-    const unsigned *dout_vec16 = nullptr;
-    int fc_slices = 0;
-    bool out_is_skip_src = false;
-    // convT class tap lists (indices into the k^3 tap enumeration)
-    std::vector<std::vector<int>> class_taps;
-    // alq_hess_vecp (hvp.hip): the plain fp32 weights in the TF layout.  The host keeps the copy alq_model_set_weights was given
-    // (hv_src = 1) or notes that the layer holds them resident in fp32 (hv_src = 2: a device-packed wide fc layer's d_Wres;
-    // hv_src = 3: a skinny fc layer's d_Wp); the device copy
-    // hv_W and the call's fp64 tensors of this layer's output - activation hv_A, its cotangent hv_D, their tangents hv_Ra / hv_Rd,
-    // dense [max_batch, vox, C] - are allocated and filled by the first product.  hv_stale: hv_W is older than the weights.
-    std::vector<float> hv_hW;
-    int hv_src = 0;
-    bool hv_stale = false;
-    float *hv_W = nullptr;
-    double *hv_A = nullptr, *hv_D = nullptr, *hv_Ra = nullptr, *hv_Rd = nullptr;
-};
-
 }  // namespace alq
 
 using namespace alq;
-
-// What the last pass of a model ran (alq_model_engine_info).  run_forward starts from fwd = {}; run_backward_main, run_backward_general
-// and the fp64 sweep of alq_hess_vecp start from bwd = {}: the backward part speaks of the LAST backward pass, whichever kind it was.
-struct PassInfo {
-    struct Fwd {
-        bool head_fused = false;   // the pass did not store the last conv's output (fc head fused into it)
-        bool c3 = false;           // it ran the head conv on the plane-sweep engine (c3d.hip)
-        int t3f = 0;               // conv_transpose launches on the row-sweep engine (t3d.hip)
-        int d3f = 0;               // dec1 ran on the row-sweep engine (d3d.hip)
-        int f3f = 0;               // enc2 and the pool behind it ran fused (f3d.hip)
-        int dcp = 0;               // form of the first conv + pool kernel, 0 = it did not run (direct.hip: g_dcp_last_form)
-        bool f16_derived = false;  // a launch ran on the fp16x2 split with derived input bounds
-    } fwd;
-    struct Bwd {                   // launches of a Fisher pass's backward sweep only
-        bool c3_bwd = false;       // the head conv's backward ran on the plane-sweep engine
-        int t3b = 0;               // conv_transpose launches on the row-sweep engine
-        int e3b = 0;               // pool2 backward, enc2 backward and pool1 backward ran as one launch (e3d.hip)
-        int e3b_form = 0;          // form of that launch: 0 none, 1 row sweep, 2 z plane sweep
-        int d3b = 0;               // dec1's backward-data launch ran on d3d.hip
-    } bwd;
-    int lsum = 0;                  // the last GENERAL backward sweep ran the fused layer-sum kernels (set by run_backward_general only)
-    bool call_fisher = false;      // the last entry point ran a Fisher pass (prepare_call)
-};
-
-struct alq_model {
-    alq_ctx *ctx = nullptr;
-    int max_batch = 0;
-    EngineSwitches sw;               // engine-selection switches, read from the environment ONCE, when this model is created
-                                     // (engine_switches.h); every call applies the model's own snapshot
-    PassInfo last;                   // what the last pass ran (alq_model_engine_info, alq_model_debug_copy)
-    // per-patch max |x| (float bits) of the two producers of the fused-head conv's input, for its fp16x2 contraction
-    unsigned *amax_a = nullptr, *amax_b = nullptr, *amax_tiles = nullptr;
-    unsigned *flip_cnt = nullptr, *flip_list = nullptr;     // candidates of the flip-safe fused head (igemm4 FCF + F16)
-    int flip_cap = 0;
-    unsigned *bound_all = nullptr;          // [layer][max_batch] derived per-patch output bounds (float bits), k_fwd_bounds
-    unsigned *in_amax = nullptr;            // [max_batch] measured max |x| of every patch of the network input (igemm3's forward fp16 pairs)
-    bool v3_fwd_f16 = false;                // some forward conv launch stays on igemm3 and has the fp16-pair twin packed (set at build)
-    unsigned *flip_overflow = nullptr;      // marked groups beyond the scan's lists since the model was created: drained by the sweep path of flip_fix_kernel (kernels.hip), none dropped
-    size_t amax_tiles_len = 0;
-    int in_dims[4] = {1, 1, 1, 1};
-    int nclass = 0;
-    int L = 0;
-    std::vector<Layer> layers;
-    std::vector<void *> allocs;
-    float *logits = nullptr, *dlogits = nullptr, *post = nullptr;
-    double *S = nullptr, *sizes = nullptr, *Apart = nullptr;
-    double *Spart = nullptr;       // [L][max_batch][nslab_max] box-dot slab partials
-    int *nslab = nullptr;          // [L] slabs actually written per layer
-    int nslab_max = 1;
-    float *wg_partial = nullptr;   // slab partials of the weight-gradient kernels (grown on demand)
-    size_t wg_partial_len = 0;
-    double *gn_partial = nullptr;  // per-(sample, workgroup) partials of the gradient-norm kernels (grown on demand)
-    size_t gn_partial_len = 0;
-    double *df_scratch = nullptr;  // alq_diag_fisher (dfisher.hip), allocated by its first call: sample-group partials of a conv layer's
-                                   // weights, per-sample channel sums, squared fc cotangents - whichever is largest
-    // alq_class_layer_sums (lsum.hip), allocated by its first call: the layers' class-independent fields (Layer::ls_field), the
-    // slab partials [L][max_batch][ls_nslab_max] of one class slot and the slabs each layer writes
-    double *ls_part = nullptr;
-    std::vector<int> ls_nslab;
-    int ls_nslab_max = 0;
-    float *x_stage = nullptr;      // [max_batch, elems per patch]: rows gathered by the *_rows entry points
-    int64_t epp = 0;               // elements per patch
-    int f16_fwd_derived = 0;       // layers (bits) whose forward launch takes the fp16x2 split with DERIVED input bounds (see run_forward)
-    int64_t host_pack_elems = 0;   // weight elements that went through the host packers since the model was created (engine info 14)
-    void *d_wscal = nullptr;       // 16 bytes: the scalars of the device packers (wpack.hip)
-    bool hv_ready = false;         // alq_hess_vecp has allocated its workspaces (first call)
-    double *hv_part = nullptr;     // slab partials of the weight products (hvp_wgrad_partial_doubles)
-    double *hv_p64 = nullptr;      // [max_batch, c]: the posteriors of the call in fp64
-
-    template <typename T>
-    int dalloc(T **p, size_t count) {
-        void *q = nullptr;
-        const size_t bytes = std::max<size_t>(count * sizeof(T), 256);
-        if (hipMalloc(&q, bytes) != hipSuccess) {
-            set_error("hipMalloc of %zu bytes failed", bytes);
-            return ALQ_ENOMEM;
-        }
-        allocs.push_back(q);
-        *p = reinterpret_cast<T *>(q);
-        return ALQ_OK;
-    }
-};
 
 // ------------------------------------------------------------------------------------------
 int alq_ctx::prof_begin(int cls, hipEvent_t *e0, hipEvent_t *e1) {
@@ -252,20 +80,6 @@ int alq_ctx::prof_collect() {
 }
 
 // ------------------------------------------------------------------------------------------
-static int upload1(alq_model *m, IgemmPlan *p) {
-    if (!p->d_W) ALQ_TRY(m->dalloc(&p->d_W, p->h_W.size()));
-    ALQ_HIP(hipMemcpyAsync(p->d_W, p->h_W.data(), p->h_W.size() * sizeof(float), hipMemcpyHostToDevice,
-                           m->ctx->stream));
-    if (p->smallc) {
-        if (!p->d_koff) ALQ_TRY(m->dalloc(&p->d_koff, p->h_koff.size()));
-        ALQ_HIP(hipMemcpyAsync(p->d_koff, p->h_koff.data(), p->h_koff.size() * sizeof(int),
-                               hipMemcpyHostToDevice, m->ctx->stream));
-    }
-    ALQ_HIP(hipStreamSynchronize(m->ctx->stream));
-    std::vector<float>().swap(p->h_W);
-    return ALQ_OK;
-}
-
 static int g_knob_override[ALQ_NKNOBS] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // alq_debug_set: >= 0 overrides every model's snapshot
 
 // The kernels' launch helpers read the process-wide g_dbg_knobs / g_no_f16x2; each entry point loads them from the
@@ -291,140 +105,6 @@ static int gemm_build(const EngineSwitches &sw, const ConvDesc &d, int max_batch
     if (d.ID == 1 && d.IH == 1 && d.IW == 1 && d.tz.size() == 1 && d.sm == 1 && d.so == 1 && !sw.no_fcgemm)
         ALQ_TRY(fcgemm_build_plan(d.Ci, d.Co, &g->pfc));       // a wide fully connected layer
     if (sw.disable_v3) g->p3.ok = false;
-    return ALQ_OK;
-}
-
-// packed 16-bit weights of a layer kernel to the device: *d is allocated on the first call and kept; the copy is queued on the
-// context's stream (the caller synchronises once per kernel family, before h may change)
-static int upload_u16(alq_model *m, void **d, const std::vector<unsigned short> &h) {
-    unsigned short *dw = reinterpret_cast<unsigned short *>(*d);
-    if (!dw) ALQ_TRY(m->dalloc(&dw, h.size()));
-    *d = dw;
-    ALQ_HIP(hipMemcpyAsync(dw, h.data(), h.size() * sizeof(unsigned short), hipMemcpyHostToDevice, m->ctx->stream));
-    return ALQ_OK;
-}
-
-static int set4(alq_model *m, Igemm4Plan *p4, const std::vector<float> &Bmat) {
-    igemm4_pack_weights(p4, Bmat);
-    hipStream_t st = m->ctx->stream;
-    if (!p4->d_tdesc) {
-        ALQ_TRY(m->dalloc(&p4->d_tdesc, p4->h_tdesc.size()));
-        ALQ_TRY(m->dalloc(&p4->d_sdesc, p4->h_sdesc.size()));
-        ALQ_TRY(m->dalloc(&p4->d_pdesc, p4->h_pdesc.size()));
-        ALQ_TRY(m->dalloc(&p4->d_ttab, p4->h_ttab.size()));
-        ALQ_TRY(m->dalloc(&p4->d_vdesc, p4->h_vdesc.size()));
-        ALQ_HIP(hipMemcpyAsync(p4->d_vdesc, p4->h_vdesc.data(), p4->h_vdesc.size() * sizeof(int), hipMemcpyHostToDevice, st));
-        ALQ_HIP(hipMemcpyAsync(p4->d_tdesc, p4->h_tdesc.data(), p4->h_tdesc.size() * sizeof(int), hipMemcpyHostToDevice, st));
-        ALQ_HIP(hipMemcpyAsync(p4->d_sdesc, p4->h_sdesc.data(), p4->h_sdesc.size() * sizeof(int), hipMemcpyHostToDevice, st));
-        ALQ_HIP(hipMemcpyAsync(p4->d_pdesc, p4->h_pdesc.data(), p4->h_pdesc.size() * sizeof(int), hipMemcpyHostToDevice, st));
-        ALQ_HIP(hipMemcpyAsync(p4->d_ttab, p4->h_ttab.data(), p4->h_ttab.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    }
-    unsigned short *dw = reinterpret_cast<unsigned short *>(p4->d_W);
-    if (!dw) ALQ_TRY(m->dalloc(&dw, p4->h_W.size()));
-    p4->d_W = dw;
-    ALQ_HIP(hipMemcpyAsync(dw, p4->h_W.data(), p4->h_W.size() * sizeof(unsigned short), hipMemcpyHostToDevice, st));
-    if (!p4->h_W16.empty()) {
-        unsigned short *dw16 = reinterpret_cast<unsigned short *>(p4->d_W16);
-        if (!dw16) ALQ_TRY(m->dalloc(&dw16, p4->h_W16.size()));
-        p4->d_W16 = dw16;
-        ALQ_HIP(hipMemcpyAsync(dw16, p4->h_W16.data(), p4->h_W16.size() * sizeof(unsigned short), hipMemcpyHostToDevice, st));
-    }
-    ALQ_HIP(hipStreamSynchronize(st));
-    std::vector<unsigned short>().swap(p4->h_W);
-    std::vector<unsigned short>().swap(p4->h_W16);
-    if (p4->alt16) ALQ_TRY(set4(m, p4->alt16.get(), Bmat));       // the fp16x2-only twin: own tables, two-piece weights
-    return ALQ_OK;
-}
-
-// parts: 1 = the streaming GEMM's forms of a wide fc layer (pfc), 2 = every other engine's
-static int gemm_set(alq_model *m, Gemm *g, const std::vector<float> &Bmat, int parts = 3) {
-    if ((parts & 2) && g->p4.ok) ALQ_TRY(set4(m, &g->p4, Bmat));
-    if ((parts & 1) && g->pfc.ok) {
-        fcgemm_pack_weights(&g->pfc, Bmat);
-        unsigned short *dw = reinterpret_cast<unsigned short *>(g->pfc.d_W);
-        if (!dw) ALQ_TRY(m->dalloc(&dw, g->pfc.h_W.size()));
-        g->pfc.d_W = dw;
-        ALQ_HIP(hipMemcpyAsync(dw, g->pfc.h_W.data(), g->pfc.h_W.size() * sizeof(unsigned short), hipMemcpyHostToDevice,
-                               m->ctx->stream));
-        ALQ_HIP(hipStreamSynchronize(m->ctx->stream));
-        std::vector<unsigned short>().swap(g->pfc.h_W);
-        if (g->pfc_f16 && c3d_subnormals_ok(m->ctx)) {      // the fp16-pair twin for launches with a static input bound (backward, Fisher pass)
-            fcgemm_pack_weights_f16(&g->pfc, Bmat);
-            unsigned short *dw16 = reinterpret_cast<unsigned short *>(g->pfc.d_W16);
-            if (!dw16) ALQ_TRY(m->dalloc(&dw16, g->pfc.h_W16.size()));
-            g->pfc.d_W16 = dw16;
-            ALQ_HIP(hipMemcpyAsync(dw16, g->pfc.h_W16.data(), g->pfc.h_W16.size() * sizeof(unsigned short), hipMemcpyHostToDevice, m->ctx->stream));
-            ALQ_HIP(hipStreamSynchronize(m->ctx->stream));
-            std::vector<unsigned short>().swap(g->pfc.h_W16);
-        }
-    }
-    if (!(parts & 2)) return ALQ_OK;
-    if (g->pd.ok) {      // direct kernel reads the B matrix [K][Co] as it is
-        if (!g->pd.d_W) ALQ_TRY(m->dalloc(&g->pd.d_W, Bmat.size()));
-        ALQ_HIP(hipMemcpyAsync(g->pd.d_W, Bmat.data(), Bmat.size() * sizeof(float), hipMemcpyHostToDevice, m->ctx->stream));
-        ALQ_HIP(hipStreamSynchronize(m->ctx->stream));
-    }
-    if (g->p2.ok) {
-        igemm2_pack_weights(&g->p2, Bmat);
-        if (!g->p2.d_tdesc) {
-            ALQ_TRY(m->dalloc(&g->p2.d_tdesc, g->p2.h_tdesc.size()));
-            ALQ_TRY(m->dalloc(&g->p2.d_sdesc, g->p2.h_sdesc.size()));
-            ALQ_HIP(hipMemcpyAsync(g->p2.d_tdesc, g->p2.h_tdesc.data(), g->p2.h_tdesc.size() * sizeof(int),
-                                   hipMemcpyHostToDevice, m->ctx->stream));
-            ALQ_HIP(hipMemcpyAsync(g->p2.d_sdesc, g->p2.h_sdesc.data(), g->p2.h_sdesc.size() * sizeof(int),
-                                   hipMemcpyHostToDevice, m->ctx->stream));
-            g->p2.a.tdesc = g->p2.d_tdesc;
-            g->p2.a.sdesc = g->p2.d_sdesc;
-        }
-        if (g->p3.ok) {
-            igemm3_pack_weights(g->p2, &g->p3, Bmat);
-            unsigned short *dw = reinterpret_cast<unsigned short *>(g->p3.d_W);
-            if (!dw) ALQ_TRY(m->dalloc(&dw, g->p3.h_W.size()));
-            g->p3.d_W = dw;
-            ALQ_HIP(hipMemcpyAsync(dw, g->p3.h_W.data(), g->p3.h_W.size() * sizeof(unsigned short), hipMemcpyHostToDevice,
-                                   m->ctx->stream));
-            ALQ_HIP(hipStreamSynchronize(m->ctx->stream));
-            std::vector<unsigned short>().swap(g->p3.h_W);
-            if (g->p3_f16 && !g->p4.ok) {      // (round 6) the fp16-pair twin for launches with a static input bound
-                igemm3_pack_weights_f16(g->p2, &g->p3, Bmat);
-                unsigned short *dw16 = reinterpret_cast<unsigned short *>(g->p3.d_W16);
-                if (!dw16) ALQ_TRY(m->dalloc(&dw16, g->p3.h_W16.size()));
-                g->p3.d_W16 = dw16;
-                ALQ_HIP(hipMemcpyAsync(dw16, g->p3.h_W16.data(), g->p3.h_W16.size() * sizeof(unsigned short), hipMemcpyHostToDevice, m->ctx->stream));
-                ALQ_HIP(hipStreamSynchronize(m->ctx->stream));
-                std::vector<unsigned short>().swap(g->p3.h_W16);
-            }
-        }
-        if (!g->p2.d_W) ALQ_TRY(m->dalloc(&g->p2.d_W, g->p2.h_W.size()));
-        ALQ_HIP(hipMemcpyAsync(g->p2.d_W, g->p2.h_W.data(), g->p2.h_W.size() * sizeof(float), hipMemcpyHostToDevice,
-                               m->ctx->stream));
-        ALQ_HIP(hipStreamSynchronize(m->ctx->stream));
-        std::vector<float>().swap(g->p2.h_W);
-        return ALQ_OK;
-    }
-    igemm_pack_weights(&g->p1, Bmat);
-    return upload1(m, &g->p1);
-}
-
-// A wide fc layer whose weights were last set from the device holds stale forms for the engines behind the streaming GEMM;
-// gemm_launch selects those only under the debug knobs 4 / 5: pack them now, from the resident fp32 copy, with the host's code.
-static int refresh_fallback_forms(alq_model *m) {
-    for (Layer &ly : m->layers) {
-        if (!ly.fallback_stale) continue;
-        const int64_t F = ly.F;
-        const int Co = ly.spec.cout;
-        std::vector<float> Wp((size_t)Co * F);
-        ALQ_HIP(hipMemcpyAsync(Wp.data(), ly.d_Wres, Wp.size() * sizeof(float), hipMemcpyDeviceToHost, m->ctx->stream));
-        ALQ_HIP(hipStreamSynchronize(m->ctx->stream));
-        std::vector<float> B((size_t)F * Co);
-        for (int64_t f = 0; f < F; ++f)
-            for (int o = 0; o < Co; ++o) B[(size_t)f * Co + o] = Wp[(size_t)o * F + f];
-        ALQ_TRY(gemm_set(m, &ly.fwd[0], B, 2));
-        if (ly.has_bwd) ALQ_TRY(gemm_set(m, &ly.bwd, Wp, 2));
-        ALQ_HIP(hipStreamSynchronize(m->ctx->stream));
-        m->host_pack_elems += ly.w_elems;
-        ly.fallback_stale = false;
-    }
     return ALQ_OK;
 }
 
@@ -1823,9 +1503,7 @@ static int hvp_prepare(alq_model *m) {
         ALQ_REQUIRE(ly.weights_set && ly.hv_src != 0, ALQ_EINVAL, "alq_hess_vecp: weights of parameterised layer %d not set", ly.pidx);
         if (!ly.hv_stale) continue;
         if (ly.hv_src == 1) {
-            ALQ_HIP(hipMemcpyAsync(ly.hv_W, ly.hv_hW.data(), (size_t)ly.w_elems * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-            ALQ_HIP(hipStreamSynchronize(ctx->stream));
-            std::vector<float>().swap(ly.hv_hW);      // hv_W holds them until the next set_weights
+            ALQ_TRY(upload_release(m, &ly.hv_W, &ly.hv_hW));      // hv_W holds them until the next set_weights
         } else {
             const float *res = ly.hv_src == 2 ? ly.d_Wres : ly.d_Wp;      // both [o][f_mem]
             ALQ_REQUIRE(res != nullptr, ALQ_EINVAL, "alq_hess_vecp: layer %d has no resident weights", ly.pidx);
@@ -2363,340 +2041,9 @@ int alq_model_destroy(alq_model *m) {
 int alq_model_num_param_layers(const alq_model *m) { return m ? m->L : ALQ_EINVAL; }
 int alq_model_max_batch(const alq_model *m) { return m ? m->max_batch : ALQ_EINVAL; }
 
-int alq_model_param_sizes(const alq_model *m, int t, int64_t *w_elems, int64_t *b_elems) {
-    ALQ_REQUIRE(m != nullptr, ALQ_EINVAL, "null model");
-    for (const Layer &ly : m->layers)
-        if (ly.pidx == t) {
-            if (w_elems) *w_elems = ly.w_elems;
-            if (b_elems) *b_elems = ly.b_elems;
-            return ALQ_OK;
-        }
-    set_error("no parameterised layer %d", t);
-    return ALQ_EINVAL;
-}
-
 int alq_model_layer_out_elems(const alq_model *m, int layer_idx, int64_t *elems) {
     ALQ_REQUIRE(m && elems && layer_idx >= 0 && layer_idx < (int)m->layers.size(), ALQ_EINVAL, "bad layer index");
     *elems = m->layers[layer_idx].out.elems();
-    return ALQ_OK;
-}
-
-int alq_model_set_weights(alq_model *m, int t, const float *W, const float *b) {
-    ALQ_REQUIRE(m && W && b, ALQ_EINVAL, "alq_model_set_weights: null argument");
-    ALQ_HIP(hipSetDevice(m->ctx->device));
-    Layer *lyp = nullptr;
-    for (Layer &l : m->layers)
-        if (l.pidx == t) lyp = &l;
-    ALQ_REQUIRE(lyp != nullptr, ALQ_EINVAL, "no parameterised layer %d", t);
-    Layer &ly = *lyp;
-    const alq_layer_t &sp = ly.spec;
-    // Which kernels get their weights packed below depends on whether the matrix cores keep fp16 subnormals: the answer is a
-    // property of the device, probed once per context.  A probe that could not RUN must not select engines (it used to read as
-    // "flushes subnormals" for this call only: the plans of one layer then differed from the others' for good): retry, then fail.
-    for (int tries = 0; tries < 3 && m->ctx->f16_subnormal_mfma < 0; ++tries) (void)c3d_subnormals_ok(m->ctx);
-    ALQ_REQUIRE(m->ctx->f16_subnormal_mfma >= 0, ALQ_EHIP, "alq_model_set_weights: the fp16-subnormal probe of the matrix cores could not run (device error)");
-    ALQ_HIP(hipMemcpyAsync(ly.d_bias, b, ly.b_elems * sizeof(float), hipMemcpyHostToDevice, m->ctx->stream));
-    const int Ci = ly.in.C, Co = sp.cout;
-    const int ntaps = sp.k[0] * sp.k[1] * sp.k[2];
-    if (sp.type == ALQ_CONV || sp.type == ALQ_CONVT) {
-        // conv W[tap][ci][co], conv_transpose W[tap][co][ci]: L1 norm of everything that multiplies into input channel ci
-        double best = 0;
-        for (int ci = 0; ci < Ci; ++ci) {
-            double s = 0;
-            for (int tp = 0; tp < ntaps; ++tp)
-                for (int co = 0; co < Co; ++co)
-                    s += std::fabs((double)(sp.type == ALQ_CONV ? W[((size_t)tp * Ci + ci) * Co + co] : W[((size_t)tp * Co + co) * Ci + ci]));
-            best = std::max(best, s);
-        }
-        ly.bwd_l1 = best;
-        // |out[.., co]| <= (sum over everything that multiplies into channel co) * max |in| + |b[co]|: for a conv_transpose all taps
-        // are counted (an output point sees a subset of them: the bound is only looser)
-        double ob = 0, bm = 0;
-        for (int co = 0; co < Co; ++co) {
-            double t = 0;
-            for (int tp = 0; tp < ntaps; ++tp)
-                for (int ci = 0; ci < Ci; ++ci)
-                    t += std::fabs((double)(sp.type == ALQ_CONV ? W[((size_t)tp * Ci + ci) * Co + co] : W[((size_t)tp * Co + co) * Ci + ci]));
-            ob = std::max(ob, t);
-            bm = std::max(bm, std::fabs((double)b[co]));
-        }
-        ly.out_l1 = (float)(ob * (1.0 + 1e-6));
-        ly.out_bmax = (float)(bm * (1.0 + 1e-6));
-    }
-    if (sp.type == ALQ_CONV) {
-        double best = 0;
-        for (int co = 0; co < Co; ++co) {
-            double s = 0;
-            for (int tp = 0; tp < ntaps; ++tp)
-                for (int ci = 0; ci < Ci; ++ci) s += std::fabs((double)W[((size_t)tp * Ci + ci) * Co + co]);
-            best = std::max(best, s);
-        }
-        ly.fwd_l1 = (float)(best * (1.0 + 1e-6));
-        const int li = (int)(lyp - &m->layers[0]);
-        if (li + 2 == (int)m->layers.size() && m->layers[li + 1].fc_part2) {      // the conv under a fused two-class head
-            if (!ly.d_W32) ALQ_TRY(m->dalloc(&ly.d_W32, (size_t)ly.w_elems));
-            ALQ_HIP(hipMemcpyAsync(ly.d_W32, W, ly.w_elems * sizeof(float), hipMemcpyHostToDevice, m->ctx->stream));
-        }
-    }
-    if (sp.type == ALQ_CONV) {
-        // TF [tap][ci][co] is already the fwd B matrix [(tap, ci)][co]
-        std::vector<float> B(W, W + ly.w_elems);
-        ALQ_TRY(gemm_set(m, &ly.fwd[0], B));
-        for (size_t j = 0; j < ly.fwd_co.size(); ++j) {      // the output-channel slices of a wide conv: columns [j w, (j + 1) w) of B
-            const int w = ly.fwd_co_w, K = ntaps * Ci;
-            std::vector<float> Bj((size_t)K * w);
-            for (int k = 0; k < K; ++k)
-                for (int c = 0; c < w; ++c) Bj[(size_t)k * w + c] = B[(size_t)k * Co + j * w + c];
-            ALQ_TRY(gemm_set(m, &ly.fwd_co[j], Bj));
-        }
-        if (ly.c3f.ok) {
-            // one accumulator (pieces at their true scale) only where the matrix cores honour fp16 subnormals
-            if (ly.c3f.oneacc && !c3d_subnormals_ok(m->ctx)) ly.c3f.oneacc = 0;
-            c3d_fwd_pack(&ly.c3f, B);
-            ALQ_TRY(upload_u16(m, &ly.c3f.d_W, ly.c3f.h_W));
-            ALQ_HIP(hipStreamSynchronize(m->ctx->stream));
-        }
-        if (ly.c3b.ok && ly.has_bwd && c3d_subnormals_ok(m->ctx)) {      // (the backward kernel exists in the one-accumulator form only)
-            c3d_bwd_pack(&ly.c3b, B);
-            ALQ_TRY(upload_u16(m, &ly.c3b.d_W, ly.c3b.h_W));
-            c3d_bwd7_pack(&ly.c3b, B);          // the 7-k-step form of the same weights (c3d_bwd7_kernel)
-            ALQ_TRY(upload_u16(m, &ly.c3b.d_W7, ly.c3b.h_W7));
-            ALQ_HIP(hipStreamSynchronize(m->ctx->stream));
-        }
-        if (ly.e3b.ok && ly.has_bwd && c3d_subnormals_ok(m->ctx)) {      // (fp16 pairs at their true scale: the one-accumulator form)
-            e3d_pack(&ly.e3b, W);
-            ALQ_TRY(upload_u16(m, &ly.e3b.d_Whi, ly.e3b.h_Whi));
-            ALQ_TRY(upload_u16(m, &ly.e3b.d_Wlo, ly.e3b.h_Wlo));
-            ALQ_HIP(hipStreamSynchronize(m->ctx->stream));
-        }
-        if (ly.f3f.ok && !c3d_subnormals_ok(m->ctx)) ly.f3f.ok = false;      // (one-accumulator fp16 pairs)
-        if (ly.f3f.ok) {
-            f3d_pack(&ly.f3f, W);
-            ALQ_TRY(upload_u16(m, &ly.f3f.d_Whi, ly.f3f.h_Whi));
-            ALQ_TRY(upload_u16(m, &ly.f3f.d_Wlo, ly.f3f.h_Wlo));
-            ALQ_HIP(hipStreamSynchronize(m->ctx->stream));
-        }
-        if (ly.d3f.ok) {
-            d3d_pack(&ly.d3f, W);
-            ALQ_TRY(upload_u16(m, &ly.d3f.d_Whi, ly.d3f.h_Whi));
-            ALQ_TRY(upload_u16(m, &ly.d3f.d_Wlo, ly.d3f.h_Wlo));
-            if (ly.has_bwd) {
-                d3d_bwd_pack(&ly.d3f, W);
-                ALQ_TRY(upload_u16(m, &ly.d3f.d_Bhi, ly.d3f.h_Bhi));
-                ALQ_TRY(upload_u16(m, &ly.d3f.d_Blo, ly.d3f.h_Blo));
-            }
-            ALQ_HIP(hipStreamSynchronize(m->ctx->stream));
-        }
-        if (ly.has_bwd) {
-            std::vector<float> Bb((size_t)ntaps * Co * Ci);
-            for (int tp = 0; tp < ntaps; ++tp)
-                for (int ci = 0; ci < Ci; ++ci)
-                    for (int co = 0; co < Co; ++co)
-                        Bb[((size_t)tp * Co + co) * Ci + ci] = W[((size_t)tp * Ci + ci) * Co + co];
-            ALQ_TRY(gemm_set(m, &ly.bwd, Bb));
-        }
-    } else if (sp.type == ALQ_CONVT) {
-        // TF [tap][co][ci]; the two-slot plans index taps in the full k^3 enumeration, the older engines by class
-        std::vector<float> Bfull((size_t)ntaps * Ci * Co);
-        for (int tp = 0; tp < ntaps; ++tp)
-            for (int ci = 0; ci < Ci; ++ci)
-                for (int co = 0; co < Co; ++co)
-                    Bfull[((size_t)tp * Ci + ci) * Co + co] = W[((size_t)tp * Co + co) * Ci + ci];
-        for (size_t c = 0; c < ly.fwd.size(); ++c) {
-            const std::vector<int> &tl = ly.class_taps[c];
-            std::vector<float> B((size_t)tl.size() * Ci * Co);
-            for (size_t j = 0; j < tl.size(); ++j)
-                for (int ci = 0; ci < Ci; ++ci)
-                    for (int co = 0; co < Co; ++co)
-                        B[((size_t)j * Ci + ci) * Co + co] = W[((size_t)tl[j] * Co + co) * Ci + ci];
-            const bool p4ok = ly.fwd[c].p4.ok && !ly.fwd_all.ok;     // per-class two-slot plan: only without the fused form
-            ly.fwd[c].p4.ok = false;
-            ALQ_TRY(gemm_set(m, &ly.fwd[c], B));
-            if (p4ok) {
-                ly.fwd[c].p4.ok = true;
-                ALQ_TRY(set4(m, &ly.fwd[c].p4, Bfull));
-            }
-        }
-        if (ly.fwd_all.ok) ALQ_TRY(set4(m, &ly.fwd_all, Bfull));
-        auto up3 = [&](T3dPlan *pl) -> int {      // (the t3d plans do not keep their host copy)
-            ALQ_TRY(upload_u16(m, &pl->d_W, pl->h_W));
-            ALQ_HIP(hipStreamSynchronize(m->ctx->stream));
-            std::vector<unsigned short>().swap(pl->h_W);
-            return ALQ_OK;
-        };
-        if (ly.t3f.ok) { if (ly.t3f.kind == 8) t3d8_fwd_pack(&ly.t3f, W); else t3d_fwd_pack(&ly.t3f, W); ALQ_TRY(up3(&ly.t3f)); }
-        if (ly.t3b.ok && ly.has_bwd && ly.t3b.kind == 8) { t3d8_bwd_pack(&ly.t3b, W); ALQ_TRY(up3(&ly.t3b)); }      // (two accumulators)
-        else if (ly.t3b.ok && ly.has_bwd && c3d_subnormals_ok(m->ctx)) { t3d_bwd_pack(&ly.t3b, W); ALQ_TRY(up3(&ly.t3b)); }      // (one-accumulator fp16 pairs)
-        if (ly.has_bwd) {
-            std::vector<float> Bb(W, W + ly.w_elems);   // [(tap, co)][ci] as stored
-            ALQ_TRY(gemm_set(m, &ly.bwd, Bb));
-        }
-    } else {
-        // fc: TF W[o][f_tf]; activation memory order f_mem = ((d*H+h)*W+w)*C+c, reference flatten
-        // order f_tf = ((c*W+w)*H+h)*D+d (tf.transpose = full axis reversal, NN.py:296-301)
-        const int D = ly.in.D, H = ly.in.H, Wd = ly.in.W, C = ly.in.C;
-        const int64_t F = ly.F;
-        std::vector<float> Wp((size_t)Co * F);
-        for (int d = 0; d < D; ++d)
-            for (int h = 0; h < H; ++h)
-                for (int w = 0; w < Wd; ++w)
-                    for (int c = 0; c < C; ++c) {
-                        const int64_t fm = (((int64_t)d * H + h) * Wd + w) * C + c;
-                        const int64_t ft = (((int64_t)c * Wd + w) * H + h) * D + d;
-                        for (int o = 0; o < Co; ++o) Wp[(size_t)o * F + fm] = W[(size_t)o * F + ft];
-                    }
-        {   // |cotangent of input f| <= sum_o |W[o][f]| * max |cotangent of the output|: the layer's L1 bound for the chain of static
-            // fp16x2 bounds of the backward pass (like bwd_l1 of a conv)
-            std::vector<double> col((size_t)F, 0.0);
-            for (int o = 0; o < Co; ++o)
-                for (int64_t f = 0; f < F; ++f) col[(size_t)f] += std::fabs((double)W[(size_t)o * F + f]);
-            double best = 0;
-            for (int64_t f = 0; f < F; ++f) best = std::max(best, col[(size_t)f]);
-            ly.bwd_l1 = best;
-        }
-        if (ly.dense_fc_small) {
-            ly.fc_wv_amax = 0.f;
-            if (Co == 2 && !ly.fc_wv)      // a two-class head that is not fused into a conv: still the bound its input cotangent obeys under the unit cotangent
-                for (int64_t f = 0; f < F; ++f) ly.fc_wv_amax = std::max(ly.fc_wv_amax, std::fabs((0.f + Wp[(size_t)f]) - Wp[(size_t)F + f]));
-            if (Co == 2 && ly.fc_wv) {      // the head's input cotangent under the unit cotangent (+1, -1): W0 - W1, set with the weights
-                std::vector<float> wv((size_t)F);
-                for (int64_t f = 0; f < F; ++f) {
-                    wv[(size_t)f] = (0.f + Wp[(size_t)f]) - Wp[(size_t)F + f];
-                    ly.fc_wv_amax = std::max(ly.fc_wv_amax, std::fabs(wv[(size_t)f]));
-                }
-                ALQ_HIP(hipMemcpyAsync(ly.fc_wv, wv.data(), wv.size() * sizeof(float), hipMemcpyHostToDevice, m->ctx->stream));
-                ALQ_HIP(hipStreamSynchronize(m->ctx->stream));
-                if (ly.fc_wv16 && ly.fc_wv_amax > 0.f && F % 4 == 0) {
-                    // the same vector as fp16 pairs of x * 2^e, e = 14 - exponent(max |x|) (the scale igemm4_launch derives from
-                    // fc_wv_amax): per 4 consecutive values [h0 h1 | h2 h3 | l0 l1 | l2 l3], h = fp16(x 2^e), l = fp16((x 2^e - h) 2^11)
-                    int ex = 0;
-                    (void)std::frexp(ly.fc_wv_amax, &ex);
-                    const int e = 14 - ex;
-                    std::vector<unsigned> sp((size_t)F);
-                    auto hb = [](float v) { const _Float16 h = (_Float16)v; unsigned short b; std::memcpy(&b, &h, 2); return (unsigned)b; };
-                    for (int64_t f = 0; f < F; f += 4) {
-                        unsigned h[4], l[4];
-                        for (int k = 0; k < 4; ++k) {
-                            const float xs = std::ldexp(wv[(size_t)f + k], e);
-                            const _Float16 hh = (_Float16)xs;
-                            h[k] = hb(xs);
-                            l[k] = hb(std::ldexp(xs - (float)hh, 11));
-                        }
-                        sp[(size_t)f] = h[0] | (h[1] << 16); sp[(size_t)f + 1] = h[2] | (h[3] << 16);
-                        sp[(size_t)f + 2] = l[0] | (l[1] << 16); sp[(size_t)f + 3] = l[2] | (l[3] << 16);
-                    }
-                    ALQ_HIP(hipMemcpyAsync(ly.fc_wv16, sp.data(), sp.size() * sizeof(unsigned), hipMemcpyHostToDevice, m->ctx->stream));
-                    ALQ_HIP(hipStreamSynchronize(m->ctx->stream));
-                    if (ly.fc_wv16c && F % 8 == 0) {      // the same scale, pieces at their true scale, per voxel [h8 | l8] (plane-sweep backward)
-                        std::vector<unsigned short> sc;
-                        c3d_presplit_vec(wv.data(), F, e, &sc);
-                        ALQ_HIP(hipMemcpyAsync(ly.fc_wv16c, sc.data(), sc.size() * sizeof(unsigned short), hipMemcpyHostToDevice, m->ctx->stream));
-                        ALQ_HIP(hipStreamSynchronize(m->ctx->stream));
-                    }
-                }
-            }
-            ALQ_HIP(hipMemcpyAsync(ly.d_Wp, Wp.data(), Wp.size() * sizeof(float), hipMemcpyHostToDevice, m->ctx->stream));
-            ALQ_HIP(hipStreamSynchronize(m->ctx->stream));
-        } else {
-            std::vector<float> B((size_t)F * Co);
-            for (int64_t f = 0; f < F; ++f)
-                for (int o = 0; o < Co; ++o) B[(size_t)f * Co + o] = Wp[(size_t)o * F + f];
-            ALQ_TRY(gemm_set(m, &ly.fwd[0], B));
-            if (ly.has_bwd) ALQ_TRY(gemm_set(m, &ly.bwd, Wp));   // [(o)][f_mem]
-        }
-    }
-    ALQ_HIP(hipStreamSynchronize(m->ctx->stream));
-    ly.weights_set = true;
-    ly.fallback_stale = false;
-    m->host_pack_elems += ly.w_elems;
-    // what alq_hess_vecp contracts with (its next call fills hv_W): a skinny fc layer's exact fp32 weights are already
-    // resident (d_Wp, activation-memory order); any other layer's engines hold split forms only, so the host keeps the array
-    if (ly.spec.type == ALQ_FC && ly.dense_fc_small && ly.d_Wp) {
-        std::vector<float>().swap(ly.hv_hW);
-        ly.hv_src = 3;
-    } else {
-        ly.hv_hW.assign(W, W + ly.w_elems);
-        ly.hv_src = 1;
-    }
-    ly.hv_stale = true;
-    return ALQ_OK;
-}
-
-// the layers alq_model_set_weights_device packs on the device: fc layers whose forward and backward Gemm both run on the
-// streaming GEMM of fcgemm.hip (and on nothing else by default)
-static bool packs_on_device(const Layer &ly) {
-    return ly.spec.type == ALQ_FC && !ly.dense_fc_small && ly.fwd.size() == 1 && ly.fwd[0].pfc.ok && !ly.fwd[0].pd.ok &&
-           (!ly.has_bwd || (ly.bwd.pfc.ok && !ly.bwd.pd.ok)) && ly.spec.cout <= 65535;
-}
-
-int alq_model_layer_packs_on_device(const alq_model *m, int t) {
-    ALQ_REQUIRE(m != nullptr, ALQ_EINVAL, "null model");
-    for (const Layer &ly : m->layers)
-        if (ly.pidx == t) return packs_on_device(ly) ? 1 : 0;
-    set_error("no parameterised layer %d", t);
-    return ALQ_EINVAL;
-}
-
-int alq_model_set_weights_device(alq_model *m, int t, const float *d_W, const float *d_b) {
-    ALQ_REQUIRE(m && d_W && d_b, ALQ_EINVAL, "alq_model_set_weights_device: null argument");
-    ALQ_HIP(hipSetDevice(m->ctx->device));
-    Layer *lyp = nullptr;
-    for (Layer &l : m->layers)
-        if (l.pidx == t) lyp = &l;
-    ALQ_REQUIRE(lyp != nullptr, ALQ_EINVAL, "no parameterised layer %d", t);
-    Layer &ly = *lyp;
-    alq_ctx *ctx = m->ctx;
-    if (!packs_on_device(ly)) {      // no device packers for this layer's engines: its slice goes through the host's
-        std::vector<float> W((size_t)ly.w_elems), b((size_t)ly.b_elems);
-        ALQ_HIP(hipMemcpyAsync(W.data(), d_W, W.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-        ALQ_HIP(hipMemcpyAsync(b.data(), d_b, b.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-        ALQ_HIP(hipStreamSynchronize(ctx->stream));
-        return alq_model_set_weights(m, t, W.data(), b.data());
-    }
-    for (int tries = 0; tries < 3 && ctx->f16_subnormal_mfma < 0; ++tries) (void)c3d_subnormals_ok(ctx);
-    ALQ_REQUIRE(ctx->f16_subnormal_mfma >= 0, ALQ_EHIP, "alq_model_set_weights_device: the fp16-subnormal probe of the matrix cores could not run (device error)");
-    const int Co = ly.spec.cout;
-    const int64_t F = ly.F;
-    if (!m->d_wscal) { unsigned char *q = nullptr; ALQ_TRY(m->dalloc(&q, 64)); m->d_wscal = q; }
-    if (!ly.d_Wres) ALQ_TRY(m->dalloc(&ly.d_Wres, (size_t)ly.w_elems));
-    ALQ_HIP(hipMemcpyAsync(ly.d_bias, d_b, ly.b_elems * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-    ALQ_TRY(wpack_stats(ctx, d_W, Co, F, m->d_wscal));
-    ALQ_TRY(wpack_permute(ctx, d_W, ly.d_Wres, Co, ly.in.D, ly.in.H, ly.in.W, ly.in.C));
-    const bool sub = c3d_subnormals_ok(ctx) != 0;
-    auto pack = [&](Gemm *g, int K, int N, int kmajor) -> int {
-        ALQ_REQUIRE(g->pfc.K == K && g->pfc.N == N, ALQ_EINVAL, "alq_model_set_weights_device: plan %d x %d, layer %d x %d", g->pfc.K, g->pfc.N, K, N);
-        unsigned short *dw = reinterpret_cast<unsigned short *>(g->pfc.d_W);
-        if (!dw) ALQ_TRY(m->dalloc(&dw, (size_t)K * N * 3));
-        g->pfc.d_W = dw;
-        unsigned short *dw16 = nullptr;
-        if (g->pfc_f16 && sub) {
-            dw16 = reinterpret_cast<unsigned short *>(g->pfc.d_W16);
-            if (!dw16) ALQ_TRY(m->dalloc(&dw16, (size_t)K * N * 2));
-            g->pfc.d_W16 = dw16;
-        }
-        return wpack_fc(ctx, ly.d_Wres, F, K, N, kmajor, dw, dw16, m->d_wscal);
-    };
-    ALQ_TRY(pack(&ly.fwd[0], (int)F, Co, 0));              // B[f_mem][o]
-    if (ly.has_bwd) ALQ_TRY(pack(&ly.bwd, Co, (int)F, 1)); // B[o][f_mem]
-    // the host scalars the launches take their power-of-two scales from: 12 bytes device-to-host
-    unsigned long long sc[2] = {0, 0};
-    ALQ_HIP(hipMemcpyAsync(sc, m->d_wscal, 16, hipMemcpyDeviceToHost, ctx->stream));
-    ALQ_HIP(hipStreamSynchronize(ctx->stream));
-    double l1;
-    std::memcpy(&l1, &sc[0], 8);
-    ly.bwd_l1 = l1;
-    float amax;
-    const unsigned ab = (unsigned)(sc[1] & 0xffffffffull);
-    std::memcpy(&amax, &ab, 4);
-    int ex = 0;
-    if (amax > 0.f) (void)std::frexp(amax, &ex);
-    if (ly.fwd[0].pfc_f16 && sub) ly.fwd[0].pfc.w_exp = 14 - ex;
-    if (ly.has_bwd && ly.bwd.pfc_f16 && sub) ly.bwd.pfc.w_exp = 14 - ex;
-    ly.weights_set = true;
-    ly.fallback_stale = true;
-    std::vector<float>().swap(ly.hv_hW);
-    ly.hv_src = 2;
-    ly.hv_stale = true;
     return ALQ_OK;
 }
 

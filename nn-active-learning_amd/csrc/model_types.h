@@ -1,0 +1,208 @@
+// The model plan of libalq.so: what model.hip (plans, passes, the C ABI) and weights.hip (weight setting) share.
+#pragma once
+#include <algorithm>
+
+#include "alq_internal.h"
+
+namespace alq {
+
+struct Layer {
+    alq_layer_t spec;
+    int pidx = -1;             // parameterised-layer index t, or -1
+    View in, out;              // activation views (in = incl. concatenated skip channels)
+    View din, dout;            // cotangent views, same geometry
+    int lo[3] = {0, 0, 0};     // SAME pad-before (conv: of the fwd conv; convT: of the conv it transposes)
+    bool dense_fc_small = false;
+    int64_t F = 0;             // fc: input features
+    // weights
+    int64_t w_elems = 0, b_elems = 0;
+    float *d_bias = nullptr;
+    float *d_Wp = nullptr;     // skinny fc: [nout][F] in activation-memory order
+    std::vector<Gemm> fwd;        // 1 contraction (conv / fc) or one per output parity class (convT)
+    // conv whose output is too wide for the matrix-core engines (NET-B's 96-channel conv: igemm2 / igemm3 hold <= 48, the two-slot
+    // engine <= 32 output channels) and would run on the fp32 engine: the same contraction as launches of fwd_co_w output channels
+    // each, writing channel slices of the output (round 6)
+    std::vector<Gemm> fwd_co;
+    int fwd_co_w = 0;
+    Igemm4Plan fwd_all;           // convT: every output class from one staged block (igemm4.hip), when eligible
+    Gemm bwd;
+    bool has_bwd = false;
+    bool weights_set = false;
+    // wide fc layer packed on the device (alq_model_set_weights_device): the raw fp32 weights stay resident in activation-memory
+    // order [o][f_mem]; the forms only the debug knobs select (igemm / igemm2 / igemm3 behind the streaming GEMM) are packed from
+    // them on the host when a call first needs them (refresh_fallback_forms)
+    float *d_Wres = nullptr;
+    bool fallback_stale = false;
+    // workspaces
+    uint8_t *argmax = nullptr;
+    float *asum = nullptr, *dsum = nullptr;
+    double *ls_field = nullptr; // [max_batch, out voxels] (fc: [max_batch]): field of alq_class_layer_sums, filled once per call
+    float *osum = nullptr;     // channel sums of this layer's OUTPUT (spatial layers): next layers' asum
+    bool delta_ready = false;  // backward: the cotangent of our output is already masked and dsum is filled
+    bool signs_ready = false;  // Fisher pass: the forward launch wrote the sign field of our output (View::sg)
+    bool dsum_partial = false; // backward, first layer: the skip destination has written its share of dsum
+    float *fc_partials = nullptr;
+    // fc head of a Fisher pass on top of a ReLU conv: its input cotangent is [input > 0] * fc_wv for every patch; the
+    // forward pass leaves the signs (one byte per 4 elements), the backward pass of the conv below contracts them
+    // directly (igemm4 BITSRC)
+    unsigned *fc_maskbits = nullptr;
+    float *fc_wv = nullptr;
+    unsigned *fc_wv16 = nullptr;       // fc_wv pre-split into fp16 pairs for the fp16x2 contraction of the conv below (BITSRC)
+    float fc_wv_amax = 0.f;            // max |W0 - W1| of a two-output head (host side, set with the weights)
+    const unsigned *dout_amax = nullptr;   // per-patch max |cotangent of this layer's output| of the running backward pass, or null
+    unsigned *amax_fwd = nullptr;          // [max_batch] per-patch max |output| of a forward pass that asked for it
+    float dout_vec_amax = 0.f;
+    // Static bounds for the fp16x2 contraction of backward launches (no data pass needed): bwd_l1 = max over the input
+    // channels of sum_{taps, output channels} |W| (set with the weights), i.e. |cotangent of the input| <= bwd_l1 * max
+    // |cotangent of the output|; dout_bound = the bound on this layer's output cotangent in the running Fisher pass
+    // (unit cotangent at the logits, chained down by run_backward_main).
+    double bwd_l1 = 0;
+    float dout_bound = 0.f;
+    // flip-safe fused head (the conv under a two-class head): plain fp32 copy of the weights in TF layout [tap][ci][co] for the
+    // exact re-evaluation, and max over co of sum_{tap, ci} |W|
+    float *d_W32 = nullptr;
+    float fwd_l1 = 0.f;
+    float out_l1 = 0.f, out_bmax = 0.f;    // |out| <= out_l1 * max |in| + out_bmax (conv: = fwd_l1; conv_transpose: all taps), set with the weights
+    unsigned *bound_fwd = nullptr;         // per-patch bound on |out| derived from the first layer's measured maximum (k_fwd_bounds)
+    float *fc_part2 = nullptr;         // partial logits per (tile, wave) when the conv below computes them in its epilogue
+    int fc_slices2 = 0;
+    // plane-sweep engine (c3d.hip) for the conv under the fused two-class head (and its backward): plans on the conv layer,
+    // per-(patch, wave) partials of the logit difference / of the head's input sum on the head layer
+    C3dPlan c3f, c3b;
+    D3dPlan d3f;                           // forward on the row-sweep engine of d3d.hip (NET-C's dec1)
+    F3dPlan f3f;                           // forward fused with the max-pool behind it (f3d.hip; NET-C's enc2)
+    E3dPlan e3b;                           // backward fused with the pool backward steps on either side (e3d.hip; NET-C's enc2)
+    T3dPlan t3f, t3b;                      // row-sweep engine for the stride-2 conv_transpose (t3d.hip), forward / backward-data
+    float *c3_part = nullptr, *c3_asum = nullptr;
+    unsigned short *fc_wv16c = nullptr;    // fc_wv as fp16 pairs at their true scale, [voxel][h8 | l8] (c3d_presplit_vec), for c3b
+    const unsigned short *dout_vec16c = nullptr;   // set on the conv below for one backward pass, like dout_vec16
+    const unsigned *dout_bits = nullptr;   // set on the conv below for the duration of one backward pass
+    const float *dout_vec = nullptr;
+    const unsigned *dout_vec16 = nullptr;
+    int fc_slices = 0;
+    bool out_is_skip_src = false;
+    // convT class tap lists (indices into the k^3 tap enumeration)
+    std::vector<std::vector<int>> class_taps;
+    // alq_hess_vecp (hvp.hip): the plain fp32 weights in the TF layout.  The host keeps the copy alq_model_set_weights was given
+    // (hv_src = 1) or notes that the layer holds them resident in fp32 (hv_src = 2: a device-packed wide fc layer's d_Wres;
+    // hv_src = 3: a skinny fc layer's d_Wp); the device copy
+    // hv_W and the call's fp64 tensors of this layer's output - activation hv_A, its cotangent hv_D, their tangents hv_Ra / hv_Rd,
+    // dense [max_batch, vox, C] - are allocated and filled by the first product.  hv_stale: hv_W is older than the weights.
+    std::vector<float> hv_hW;
+    int hv_src = 0;
+    bool hv_stale = false;
+    float *hv_W = nullptr;
+    double *hv_A = nullptr, *hv_D = nullptr, *hv_Ra = nullptr, *hv_Rd = nullptr;
+};
+
+}  // namespace alq
+
+// What the last pass of a model ran (alq_model_engine_info).  run_forward starts from fwd = {}; run_backward_main, run_backward_general
+// and the fp64 sweep of alq_hess_vecp start from bwd = {}: the backward part speaks of the LAST backward pass, whichever kind it was.
+struct PassInfo {
+    struct Fwd {
+        bool head_fused = false;   // the pass did not store the last conv's output (fc head fused into it)
+        bool c3 = false;           // it ran the head conv on the plane-sweep engine (c3d.hip)
+        int t3f = 0;               // conv_transpose launches on the row-sweep engine (t3d.hip)
+        int d3f = 0;               // dec1 ran on the row-sweep engine (d3d.hip)
+        int f3f = 0;               // enc2 and the pool behind it ran fused (f3d.hip)
+        int dcp = 0;               // form of the first conv + pool kernel, 0 = it did not run (direct.hip: g_dcp_last_form)
+        bool f16_derived = false;  // a launch ran on the fp16x2 split with derived input bounds
+    } fwd;
+    struct Bwd {                   // launches of a Fisher pass's backward sweep only
+        bool c3_bwd = false;       // the head conv's backward ran on the plane-sweep engine
+        int t3b = 0;               // conv_transpose launches on the row-sweep engine
+        int e3b = 0;               // pool2 backward, enc2 backward and pool1 backward ran as one launch (e3d.hip)
+        int e3b_form = 0;          // form of that launch: 0 none, 1 row sweep, 2 z plane sweep
+        int d3b = 0;               // dec1's backward-data launch ran on d3d.hip
+    } bwd;
+    int lsum = 0;                  // the last GENERAL backward sweep ran the fused layer-sum kernels (set by run_backward_general only)
+    bool call_fisher = false;      // the last entry point ran a Fisher pass (prepare_call)
+};
+
+struct alq_model {
+    alq_ctx *ctx = nullptr;
+    int max_batch = 0;
+    alq::EngineSwitches sw;          // engine-selection switches, read from the environment ONCE, when this model is created
+                                     // (engine_switches.h); every call applies the model's own snapshot
+    PassInfo last;                   // what the last pass ran (alq_model_engine_info, alq_model_debug_copy)
+    // per-patch max |x| (float bits) of the two producers of the fused-head conv's input, for its fp16x2 contraction
+    unsigned *amax_a = nullptr, *amax_b = nullptr, *amax_tiles = nullptr;
+    unsigned *flip_cnt = nullptr, *flip_list = nullptr;     // candidates of the flip-safe fused head (igemm4 FCF + F16)
+    int flip_cap = 0;
+    unsigned *bound_all = nullptr;          // [layer][max_batch] derived per-patch output bounds (float bits), k_fwd_bounds
+    unsigned *in_amax = nullptr;            // [max_batch] measured max |x| of every patch of the network input (igemm3's forward fp16 pairs)
+    bool v3_fwd_f16 = false;                // some forward conv launch stays on igemm3 and has the fp16-pair twin packed (set at build)
+    unsigned *flip_overflow = nullptr;      // marked groups beyond the scan's lists since the model was created: drained by the sweep path of flip_fix_kernel (kernels.hip), none dropped
+    size_t amax_tiles_len = 0;
+    int in_dims[4] = {1, 1, 1, 1};
+    int nclass = 0;
+    int L = 0;
+    std::vector<alq::Layer> layers;
+    std::vector<void *> allocs;
+    float *logits = nullptr, *dlogits = nullptr, *post = nullptr;
+    double *S = nullptr, *sizes = nullptr, *Apart = nullptr;
+    double *Spart = nullptr;       // [L][max_batch][nslab_max] box-dot slab partials
+    int *nslab = nullptr;          // [L] slabs actually written per layer
+    int nslab_max = 1;
+    float *wg_partial = nullptr;   // slab partials of the weight-gradient kernels (grown on demand)
+    size_t wg_partial_len = 0;
+    double *gn_partial = nullptr;  // per-(sample, workgroup) partials of the gradient-norm kernels (grown on demand)
+    size_t gn_partial_len = 0;
+    double *df_scratch = nullptr;  // alq_diag_fisher (dfisher.hip), allocated by its first call: sample-group partials of a conv layer's
+                                   // weights, per-sample channel sums, squared fc cotangents - whichever is largest
+    // alq_class_layer_sums (lsum.hip), allocated by its first call: the layers' class-independent fields (Layer::ls_field), the
+    // slab partials [L][max_batch][ls_nslab_max] of one class slot and the slabs each layer writes
+    double *ls_part = nullptr;
+    std::vector<int> ls_nslab;
+    int ls_nslab_max = 0;
+    float *x_stage = nullptr;      // [max_batch, elems per patch]: rows gathered by the *_rows entry points
+    int64_t epp = 0;               // elements per patch
+    int f16_fwd_derived = 0;       // layers (bits) whose forward launch takes the fp16x2 split with DERIVED input bounds (see run_forward)
+    int64_t host_pack_elems = 0;   // weight elements that went through the host packers since the model was created (engine info 14)
+    void *d_wscal = nullptr;       // 16 bytes: the scalars of the device packers (wpack.hip)
+    bool hv_ready = false;         // alq_hess_vecp has allocated its workspaces (first call)
+    double *hv_part = nullptr;     // slab partials of the weight products (hvp_wgrad_partial_doubles)
+    double *hv_p64 = nullptr;      // [max_batch, c]: the posteriors of the call in fp64
+
+    template <typename T>
+    int dalloc(T **p, size_t count) {
+        void *q = nullptr;
+        const size_t bytes = std::max<size_t>(count * sizeof(T), 256);
+        if (hipMalloc(&q, bytes) != hipSuccess) {
+            alq::set_error("hipMalloc of %zu bytes failed", bytes);
+            return ALQ_ENOMEM;
+        }
+        allocs.push_back(q);
+        *p = reinterpret_cast<T *>(q);
+        return ALQ_OK;
+    }
+};
+
+// *d (a T * or the void * of a plan): count elements of T on the device, allocated on the first call and kept
+template <typename T, typename D>
+int ensure(alq_model *m, D **d, size_t count) {
+    T *p = static_cast<T *>(*d);
+    if (!p) ALQ_TRY(m->dalloc(&p, count));
+    *d = p;
+    return ALQ_OK;
+}
+
+// Host array to such a buffer: the copy is queued on the context's stream, and the caller synchronises before h may change
+template <typename T, typename D>
+int upload(alq_model *m, D **d, const std::vector<T> &h) {
+    ALQ_TRY(ensure<T>(m, d, h.size()));
+    ALQ_HIP(hipMemcpyAsync(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, m->ctx->stream));
+    return ALQ_OK;
+}
+
+// ... for the plans that do not keep their host copy: upload, synchronise, release h
+template <typename T, typename D>
+int upload_release(alq_model *m, D **d, std::vector<T> *h) {
+    ALQ_TRY(upload(m, d, *h));
+    ALQ_HIP(hipStreamSynchronize(m->ctx->stream));
+    std::vector<T>().swap(*h);
+    return ALQ_OK;
+}
+
+namespace alq { int refresh_fallback_forms(alq_model *m); }      // weights.hip
