@@ -469,6 +469,37 @@ int alq_cc_keep_largest(alq_ctx *ctx, const uint8_t *d_seg, const int64_t dims[3
                         int64_t *d_info, void *d_work);
 int alq_fill_holes(alq_ctx *ctx, const uint8_t *d_seg, const int64_t dims[3], uint8_t *d_out, int64_t *d_info, void *d_work);
 
+/* ---- dense CRF on a two-class posterior map: exact mean-field inference (csrc/dcrf.hip) --------------------------------- */
+/* Replaces: PW_analyze_results.DCRF_postprocess_2D (PW_analyze_results.py:539-591), pydensecrf's DenseCRF2D with 2 labels, a
+ * smoothness kernel (create_pairwise_gaussian) and an appearance kernel (create_pairwise_bilateral), NORMALIZE_SYMMETRIC, Potts
+ * compatibilities, `niter` mean-field iterations and the arg-max - with the two Gaussian filters evaluated exactly on a window
+ * instead of on the library's permutohedral lattice.  dims = [S, H, W]: S independent slices, each plane contiguous in C order;
+ * d_post, d_img float [S, H, W] (class-1 posteriors, image), both read-only.  Per slice, over the pixels raveled in C order:
+ *   p = d_post, 0 read as 1e-10;  nl = -log p;  U = float32([1 - nl, nl])  (the reference's unary as it stands: label 0 gets
+ *   1 + log p);  k(i, j) = exp(-|f_i - f_j|^2 / 2) with f = (row / sdims[0], column / sdims[1]) for the smoothness kernel and
+ *   (row / sdims[0], column / sdims[1], img / schan) for the appearance kernel, on the window |d row| <= R_0, |d column| <= R_1,
+ *   R = ceil(sdims sqrt(48 ln 2)) (6 and 29 for the defaults; the weight dropped is below 2^-24 of the peak), k(i, i) = 1;
+ *   n_i = 1 / sqrt(sum_j k(i, j) + 1e-20) and (K~ Q)_i = n_i sum_j k(i, j) n_j Q_j over the same window, per kernel;
+ *   Q = softmax(-U), then niter times Q = softmax(-U + compat_smooth K~_smooth Q + compat_app K~_app Q) over the two labels.
+ * d_q1 float [S, H, W] = Q_1 after the last iteration, d_map uint8 [S, H, W] = [Q_1 > Q_0] (a tie gives 0); either may be
+ * NULL, not both.  par NULL: the reference's values {1, 1}, {5, 5}, 1, 20, 30, 5.  d_work: alq_dcrf_work_bytes(dims) bytes
+ * (20 per pixel; 0 for dims the call refuses), 4-byte aligned, disjoint from the outputs.  fp32 arithmetic, every sum in one
+ * fixed order, no atomics: the same input gives the same bits.  2 + niter launches (one for niter = 0).
+ * ALQ_EINVAL before any launch: a null required pointer, d_q1 and d_map both NULL, an axis below 1, 2^31 pixels or more, niter
+ * outside [0, 64], a non-positive sdims or schan, a non-finite parameter.  ALQ_EUNSUPPORTED: a window radius above 31 or windows
+ * whose staged tile exceeds the LDS of a compute unit (sdims above 5.37), more than 65535 slices.  Stream-ordered, no
+ * synchronisation, no host read-back.                                                                                       */
+typedef struct alq_dcrf_params {
+    float sdims_smooth[2];     /* smoothness kernel: scale of the row and of the column coordinate */
+    float sdims_app[2];        /* appearance kernel: the same */
+    float schan;               /* appearance kernel: scale of the intensity */
+    float compat_smooth, compat_app;
+    int32_t niter;
+} alq_dcrf_params;
+size_t alq_dcrf_work_bytes(const int64_t dims[3]);
+int alq_dcrf2d(alq_ctx *ctx, const float *d_post, const float *d_img, const int64_t dims[3], const alq_dcrf_params *par,
+               float *d_q1, uint8_t *d_map, void *d_work);
+
 /* ---- last-layer closed forms and the stochastic influence recursion (csrc/llfc.hip) -------------------------------- */
 /* Replaces: NN.LLFC_grads / NN.LLFC_hess / NN.PW_LLFC_grads (NN.py:874-1029; duplicated in model_utils.py:137-292) and the
  * iteration of PW_NNAL.stoch_approx_IF (PW_NNAL.py:851-881).  u [d] = the input of the last fc layer (the model's feature

@@ -8,10 +8,13 @@ keep the predictions on the device: `eval_counts_device` feeds every chunk's pre
 to six int64 totals in HBM (and scatters the predictions into a uint8 volume for full_model_eval); 48 bytes come back.
 full_model_eval(..., post_process=True) applies the reference's post-processing (post_processing.py: largest connected
 component, hole filling) to that volume where it lies (alq_cc_keep_largest, alq_fill_holes) before scoring and saving it.
+The dense-CRF post-processing (`DCRF_postprocess_2D`, `full_model_pred_DCRF`) runs on the device as well: alq_dcrf2d computes
+the reference's CRF model with exact windowed Gaussian filters (nnal_amd.dcrf states the model and is its host oracle) on the
+posteriors where posteriors_device left them.
 
-Not mirrored: `grid_based_F1` (patch_utils.generate_grid_samples is outside this package), the dense-CRF post-processing
-(`full_model_pred_DCRF`, `full_test_slice_DCRF`, `DCRF_postprocess_*`), the plotting helpers (`visualize_eval_metrics`, ...)
-and the super-pixel helpers: they need skimage / pydensecrf / matplotlib and sit beside the scored path, not on it."""
+Not mirrored: `grid_based_F1` (patch_utils.generate_grid_samples is outside this package), `full_test_slice_DCRF` and
+`DCRF_postprocess_3D`, the plotting helpers (`visualize_eval_metrics`, ...) and the super-pixel helpers: they need skimage /
+matplotlib and sit beside the scored path, not on it."""
 import os
 
 import numpy as np
@@ -219,6 +222,76 @@ def full_model_eval(expr, model, sess, img_path, mask_path, slice_inds, save_dir
     if save_dir:
         nrrd_io.write(os.path.join(save_dir, 'segs.nrrd'), np.uint8(segs))
         np.savetxt(os.path.join(save_dir, 'F1_socre.txt'), [F1])
+    return segs.astype(np.float64), F1
+
+
+def DCRF_postprocess_2D(post_map, img_slice, sess=None):
+    """PW_analyze_results.py:539-591: the dense CRF on one 2-D class-1 posterior map -> the [H, W] integer MAP labels.  Zeros
+    of the caller's `post_map` become 1e-10, as the reference's in-place guard (:549) leaves them.  The model is the
+    reference's (2 labels, smoothness sdims (1, 1) compat 20, appearance sdims (5, 5) schan 1 compat 30, NORMALIZE_SYMMETRIC,
+    5 iterations, its unary [1 - nl, nl] as it stands); alq_dcrf2d evaluates it with exact Gaussian filters on the cut-off
+    windows instead of pydensecrf's permutohedral lattice (dcrf.py).  `sess` (not a reference argument): the device session,
+    default device.default_session()."""
+    from . import device
+    sess = sess or device.default_session()
+    img_slice = np.asarray(img_slice)
+    if img_slice.ndim != 2 or tuple(np.shape(post_map)) != img_slice.shape:
+        raise ValueError('post_map %r and img_slice %r must be one 2-D shape' % (np.shape(post_map), img_slice.shape))
+    labels = sess.dcrf2d(post_map, img_slice, img_slice.shape)
+    return labels.cpu().numpy().reshape(img_slice.shape).astype(np.int64)
+
+
+def full_model_pred_DCRF(expr, model, sess, img_path, mask_path, slice_inds, save_dir=None):
+    """PW_analyze_results.py:449-536: the model's posteriors of every voxel of the slices `slice_inds`, post-processed slice by
+    slice with the dense CRF, their F1 against the mask over those slices and, with `save_dir`, `dcrf_segs.nrrd` (uint8, as
+    `segs.nrrd` is here) and `F1_score_dcrf.txt`.  Returns (DCRF_preds [x, y, z] float64, zero outside the slices, F1).
+
+    The reference's call `full_slice_eval(model, img_path, [ind], 'axial', ...)` (:481-490) cannot run as written; the intent
+    is restated exactly as full_model_eval does: expr.pars['patch_shape'], ['ntb'], ['stats'], all the modalities of
+    `img_path` (one path / padded array, or a list of them).  The CRF's image is the first modality (the reference reads a
+    single `img_path`).  Everything between the upload and the result stays on the device: posteriors_device fills one
+    [S, H, W] tensor, the image slices are taken from the resident volume, ONE alq_dcrf2d call labels all slices, the labels
+    are scattered into a uint8 volume and counted against the resident mask by alq_eval_counts; one volume of bytes and 48
+    bytes of counts come back.  F1 is full_model_eval's: F1_scores' expression on those counts, 0 where its divisions
+    would raise."""
+    torch = sess.torch
+    if save_dir:
+        if not os.path.exists(save_dir):
+            os.mkdir(save_dir)
+    mask = mask_path if isinstance(mask_path, np.ndarray) else nrrd_io.read(mask_path)[0]
+    img_paths = [img_path] if isinstance(img_path, (str, np.ndarray)) else list(img_path)
+    patch_shape = expr.pars['patch_shape']
+    vols, img_shape = _padded_volumes(img_paths, patch_shape)
+    if tuple(mask.shape) != img_shape:
+        raise ValueError('mask %r and image %r differ in shape' % (tuple(mask.shape), img_shape))
+    slice_inds = [int(v) for v in slice_inds]
+    H, W = img_shape[:2]
+    S = len(slice_inds)
+    seg = sess.to_device(np.zeros(img_shape, dtype=np.uint8), torch.uint8)
+    F1 = 0
+    if S:
+        dv = patch_utils.DeviceVolumes(sess, vols)
+        lab = _device_labels(sess, mask)
+        post = sess.empty((S, H, W), torch.float32)
+        inds = []
+        for k, ind in enumerate(slice_inds):
+            _, inds_3D = _slice_inds_3D(img_shape, ind)
+            PW_NN.posteriors_device(model, sess, vols, inds_3D, patch_shape, expr.pars['ntb'], expr.pars['stats'], _vols=dv,
+                                    out=post[k].reshape(-1))
+            inds.append(inds_3D)
+        rads = patch_utils.patch_radii(patch_shape)
+        z = sess.to_device(np.asarray(slice_inds, dtype=np.int64) + rads[2], torch.int64)
+        img = dv.tensors[0][rads[0]:rads[0] + H, rads[1]:rads[1] + W].index_select(2, z).permute(2, 0, 1).to(torch.float32).contiguous()
+        labels = sess.dcrf2d(post, img, (S, H, W))
+        seg[:, :, sess.to_device(np.asarray(slice_inds, dtype=np.int64), torch.int64)] = labels.permute(1, 2, 0)
+        d_inds = sess.to_device(np.concatenate(inds), torch.int64)
+        counts = sess.to_device(np.zeros(6, dtype=np.int64), torch.int64)
+        sess.eval_counts(seg.reshape(-1)[d_inds].to(torch.int64), d_inds, lab.reshape(-1), counts, None)
+        F1 = _f1_from_counts(counts)
+    segs = seg.cpu().numpy().reshape(img_shape)
+    if save_dir:
+        nrrd_io.write(os.path.join(save_dir, 'dcrf_segs.nrrd'), np.uint8(segs))
+        np.savetxt(os.path.join(save_dir, 'F1_score_dcrf.txt'), [F1])
     return segs.astype(np.float64), F1
 
 

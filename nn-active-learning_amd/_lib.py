@@ -50,6 +50,12 @@ class LossT(C.Structure):
                 ('d_class_w', C.c_void_p), ('d_sample_w', C.c_void_p), ('d_targets', C.c_void_p), ('d_old_logits', C.c_void_p)]
 
 
+class DcrfParams(C.Structure):
+    """Mirror of alq_dcrf_params (defaults: the reference's DCRF_postprocess_2D call)."""
+    _fields_ = [('sdims_smooth', C.c_float * 2), ('sdims_app', C.c_float * 2), ('schan', C.c_float), ('compat_smooth', C.c_float),
+                ('compat_app', C.c_float), ('niter', C.c_int32)]
+
+
 _P = C.c_void_p
 _SIGNATURES = {
     'alq_last_error': (C.c_char_p, []),
@@ -112,6 +118,8 @@ _SIGNATURES = {
     'alq_cc_label': (C.c_int, [_P, _P, C.POINTER(C.c_int64), C.c_int, C.c_int, _P]),
     'alq_cc_keep_largest': (C.c_int, [_P, _P, C.POINTER(C.c_int64), C.c_int, C.c_int, _P, _P, _P]),
     'alq_fill_holes': (C.c_int, [_P, _P, C.POINTER(C.c_int64), _P, _P, _P]),
+    'alq_dcrf_work_bytes': (C.c_size_t, [C.POINTER(C.c_int64)]),
+    'alq_dcrf2d': (C.c_int, [_P, _P, _P, C.POINTER(C.c_int64), C.POINTER(DcrfParams), _P, _P, _P]),
     'alq_llfc_grads': (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
     'alq_llfc_hess_max_bytes': (C.c_size_t, []),
     'alq_llfc_hess': (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P]),

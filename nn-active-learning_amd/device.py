@@ -216,6 +216,44 @@ class DeviceSession(object):
                                       C.c_void_p(info.data_ptr()), C.c_void_p(work.data_ptr())))
         return out, info.cpu().numpy()
 
+    # -- dense CRF on a two-class posterior map (csrc/dcrf.hip) ------------------------------
+    def dcrf2d(self, post, img, dims, params=None, want_q=False):
+        """alq_dcrf2d: the dense CRF of DCRF_postprocess_2D (nnal_amd.dcrf states the model) on S independent slices,
+        dims = [S, H, W] (or [H, W]: one slice).  `post`, `img`: class-1 posteriors and image, float32 device tensors of S H W
+        elements (neither is written) or arrays, which are uploaded as float32; zeros of a NumPy `post` become 1e-10 in the
+        caller's array, as the reference's call leaves them.  `params`: a dict of dcrf.DEFAULTS entries and / or `niter` to
+        replace (None: the reference's values, 5 iterations).  Returns the uint8 device tensor [S, H, W] of MAP labels, or
+        (labels, q1) with the float32 class-1 marginals after the last iteration when want_q.  Nothing is copied back."""
+        from . import dcrf
+        torch = self.torch
+        self.bind_stream()
+        dims = tuple(int(v) for v in dims)
+        if len(dims) == 2:
+            dims = (1,) + dims
+        assert len(dims) == 3 and min(dims) >= 1
+        n = dims[0] * dims[1] * dims[2]
+        if isinstance(post, np.ndarray):
+            post[post == 0] += 1e-10                      # PW_analyze_results.py:549
+        tens = []
+        for t in (post, img):
+            if not isinstance(t, torch.Tensor):
+                t = self.to_device(np.ascontiguousarray(t, dtype=np.float32), torch.float32)
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.device == self.device and int(t.numel()) == n
+            tens.append(t)
+        kw = dict(params or {})
+        niter = int(kw.pop('niter', dcrf.NITER))
+        par = dcrf.make_params(**kw)
+        cpar = _lib.DcrfParams((C.c_float * 2)(*par['sdims_smooth']), (C.c_float * 2)(*par['sdims_app']), par['schan'],
+                               par['compat_smooth'], par['compat_app'], niter)
+        cdims = (C.c_int64 * 3)(*dims)
+        work = self.empty((max(4, int(self.lib.alq_dcrf_work_bytes(cdims))),), torch.uint8)
+        labels = self.empty(dims, torch.uint8)
+        q1 = self.empty(dims, torch.float32) if want_q else None
+        check(self.lib.alq_dcrf2d(self._ctx, C.c_void_p(tens[0].data_ptr()), C.c_void_p(tens[1].data_ptr()), cdims, C.byref(cpar),
+                                  C.c_void_p(q1.data_ptr()) if want_q else None, C.c_void_p(labels.data_ptr()),
+                                  C.c_void_p(work.data_ptr())))
+        return (labels, q1) if want_q else labels
+
     # -- RCCL communicator of the sharded pool (pool_shard.attach_comm) --------------------
     def comm_unique_id(self):
         buf = C.create_string_buffer(128)
