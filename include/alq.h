@@ -76,6 +76,26 @@ int alq_model_destroy(alq_model *m);
  * offsets allow - every allocation below 2^30 floats; NET-C at 32^3: 2047).  A larger batch is walked in passes of this
  * size by the host (the reference feeds `ntb` patches per sess.run, PW_NN.py:447-451: the split never changes a result). */
 int alq_model_max_batch(const alq_model *m);
+/* Fully-convolutional ("dense") models.  alq_model_create also takes a last layer of type ALQ_CONV when k = s = {1,1,1},
+ * relu = 0, skip_src < 0, 2 <= cout <= 8, the layer feeds no concat, and its input is a dense tensor of C channels, C % 4 == 0,
+ * C <= 64 (any other non-fc last layer: ALQ_EUNSUPPORTED, the message names the condition).  Every voxel of the head's output
+ * is then a sample: with V = alq_model_out_voxels (1 for an fc-head model; voxel index v in the activation's memory order)
+ *   alq_forward / alq_forward_dropout   d_post [c, N V] class-major planes (sample n V + v), d_pred int64 [N V];
+ *   alq_param_grads_loss                d_labels int32 [N V] (outside [0, c): unlabelled voxel), loss->d_sample_w [N V],
+ *                                       d_targets / d_old_logits / d_post [c, N V]; statistics with voxels as samples;
+ *   alq_loss_stats                      model-free: call it with N V samples.
+ * The head keeps its weights as plain fp32 [Ci][c] + [c] - the bytes of the TF filter [1, (1,) 1, Ci, c] both weight setters
+ * take.  alq_model_max_batch also keeps N V below 2^31.  alq_fisher*, alq_forward_rows, alq_param_grads, alq_grad_sqnorms,
+ * alq_class_layer_sums, alq_diag_fisher and alq_hess_vecp return ALQ_EUNSUPPORTED for such a model before any launch.       */
+int alq_model_out_voxels(const alq_model *m);
+/* The head's kernels on their own (csrc/dense.hip), model-free: d_x [R, Ci] (16-byte aligned, Ci % 4 == 0, Ci <= 64), d_W [Ci, c],
+ * d_b [c], 2 <= c <= 8 -> d_post [c, R], d_pred int64 [R] or NULL; backward: d_delta [R, c] -> d_dx [R, Ci] (NULL: not wanted) and
+ * d_dW_db = [dW (Ci c), db (c)], through d_work of alq_dense_head_work_bytes(Ci, c) bytes.  Bit-identical from run to run.           */
+size_t alq_dense_head_work_bytes(int Ci, int c);
+int alq_dense_head_fwd(alq_ctx *ctx, const float *d_x, int64_t R, int Ci, int c, const float *d_W, const float *d_b, float *d_post,
+                       int64_t *d_pred);
+int alq_dense_head_bwd(alq_ctx *ctx, const float *d_delta, const float *d_x, int64_t R, int Ci, int c, const float *d_W, float *d_dx,
+                       void *d_work, float *d_dW_db);
 /* Number of parameterised layers L ( = len(grad_posts['1'])/2, PW_NNAL.py:751 ).             */
 int alq_model_num_param_layers(const alq_model *m);
 /* W/b element counts of parameterised layer t (creation order), i.e. prod(W.shape), len(b).  */

@@ -1,6 +1,8 @@
 """`NN_extended.CNN`-schema models on the device (reference: NN_extended.py:20-295): layer dict
 ``{name: [type, specs, op_order]}`` with conv / conv_transpose / pool / fc in 2-D or 3-D, 'con'
-skip connections, fc head (the form `get_gradients` is defined for, NN_extended.py:1025), and the
+skip connections, fc head (the form `get_gradients` is defined for, NN_extended.py:1025) or the 1x1
+conv head of the reference's FCN branch (NN_extended.py:262-294: posteriors [N, *spatial, c], the
+voxel-wise objective of get_FCN_loss, :1285-1335, with `input_vox_weights`), and the
 training hyper-parameters of `set_hypers` (NN_extended.py:24-63) that the device step knows:
 losses CE / CE_softclasses / GCE with class, focal and per-sample weights, optimisers SGD / Adam /
 RMSProp, learning-rate schedules."""
@@ -83,10 +85,14 @@ class CNN(DeviceModel):
         training = [k for k in kwargs if k != 'activation']
         last = list(layer_dict.values())[-1]
         nclass = int(last[1][0]) if isinstance(last[0], str) else int(last[0])          # either layer-dict schema
+        if isinstance(last[0], str) and last[0] == 'conv' and hypers['loss_name'] != 'CE':
+            # a fully-convolutional model trains on get_FCN_loss (NN_extended.py:1285-1335), the only FCN loss the reference defines
+            raise ValueError('loss_name %r on a fully-convolutional model: its objective is the voxel-wise cross-entropy (CE)'
+                             % (hypers['loss_name'],))
         if (bcw is not None or hypers['focal_gamma'] is not None) and nclass != 2:
             raise ValueError('bin_class_weights / focal_gamma need a two-class net (where(labels == 1, .[1], .[0])), got %d classes'
                              % nclass)
         super(CNN, self).__init__(sess or default_session(), layer_dict, in_shape, skips, feature_layer,
                                   dropout, max_batch, name)
-        if training:
+        if training or self.dense:      # (a dense model always trains on get_FCN_loss: non-zero-weight divisor, voxel weights)
             self.set_hypers(hypers)

@@ -384,6 +384,8 @@ def core_set_query(expr, model, sess, all_padded_imgs, pool_inds, labeled_inds):
 def committee_holder(expr, model, sess):
     """`expr.model_holder` (PW_AL.py:780-790), or - for a caller that has none - a net built once like `model` (layer dict,
     input shape, skips, dropout, max_batch, optimiser, grad_layers) on the same session and cached on `expr`."""
+    if getattr(model, 'dense', False):
+        raise NotImplementedError('committee_holder: not defined for a fully-convolutional model (1x1 conv head)')
     holder = getattr(expr, 'model_holder', None)
     if holder is None:
         from .device import DeviceModel

@@ -93,6 +93,7 @@ struct ProfSlot {
 
 #define ALQ_PARAM_BLOCK_BYTES 512
 #define ALQ_LOSS_MAX_BLOCKS 64      // workgroups of loss_cotangent_kernel (grid-stride beyond 64 * 256 samples)
+#define ALQ_DENSE_MAX_BLOCKS 2048   // workgroups (= rows of fp64 partials) of dense_head_bwd_kernel (dense.hip)
 #define ALQ_PARAM_FLAG_OFFSET (ALQ_PARAM_BLOCK_BYTES - 8)   // last word of the block: the bad-index flag of alq_eval_counts
 
 struct alq_ctx {
@@ -673,6 +674,13 @@ int k_sgd(alq_ctx *, float *theta, const float *g, long long n, float lr);
 // loss.hip: cotangent rows [N, c] (null: statistics only) and the three loss statistics (null: rows only) of an alq_loss_t
 int k_loss_cotangent(alq_ctx *, const float *post_cN, int c, int N, const int *labels, const alq_loss_t *loss, float loss_scale,
                      float lwf_scale, float *dlogits, double *d_stats3);
+// dense.hip: the 1x1 conv head of a fully-convolutional model over R = N * V voxels.  x [R, Ci], W [Ci, c] (TF layout of the 1x1
+// filter), post [c, R], pred int64 [R] or null, z (logits) [R, c] or null; backward: delta [R, c] -> dx [R, Ci] (null: none; accumulate:
+// added to what is there) and d_dW_db = [dW (Ci c), db (c)] through `part` (ALQ_DENSE_MAX_BLOCKS x (Ci c + c) doubles)
+int k_dense_head_fwd(alq_ctx *, const float *x, long long R, int Ci, int c, const float *W, const float *b, float *post_cR, int64_t *pred,
+                     float *z);
+int k_dense_head_bwd(alq_ctx *, const float *delta, const float *x, long long R, int Ci, int c, const float *W, float *dx, int accumulate,
+                     double *part, float *d_dW_db);
 int k_rmsprop(alq_ctx *, float *theta, const float *g, float *ms, float *mom, long long n, float lr, float decay, float momentum,
               float eps);
 int k_adam(alq_ctx *, float *theta, const float *g, float *m, float *v, long long n, float lr_t, float b1, float b2, float eps);

@@ -239,8 +239,26 @@ static int build_model(alq_model *m, const alq_layer_t *specs, int n_layers) {
         cur = o;
     }
     m->L = pidx;
-    ALQ_REQUIRE(n_layers > 0 && specs[n_layers - 1].type == ALQ_FC, ALQ_EUNSUPPORTED,
-                "the scored path needs an fc head (get_gradients, NN_extended.py:1025)");
+    if (n_layers > 0 && specs[n_layers - 1].type == ALQ_CONV) {
+        // a fully-convolutional model: the head is a 1x1 conv without ReLU on a dense tensor (dense.hip); anything else that is not an
+        // fc layer stays outside the library
+        const int hl = n_layers - 1;
+        const alq_layer_t &hs = specs[hl];
+        const int Cin = hl > 0 ? outs[hl - 1].C : m->in_dims[3];
+        ALQ_REQUIRE(hs.k[0] == 1 && hs.k[1] == 1 && hs.k[2] == 1, ALQ_EUNSUPPORTED,
+                    "a conv head must be 1x1 (found %dx%dx%d): the scored path needs an fc head or a 1x1 conv head", hs.k[0], hs.k[1], hs.k[2]);
+        ALQ_REQUIRE(!hs.relu, ALQ_EUNSUPPORTED, "a conv head takes no ReLU: its outputs are the logits");
+        ALQ_REQUIRE(hs.skip_src < 0, ALQ_EUNSUPPORTED, "a conv head on a concat (skip source %d) is unsupported", hs.skip_src);
+        ALQ_REQUIRE(hs.cout >= 2 && hs.cout <= 8, ALQ_EUNSUPPORTED, "a conv head of %d classes is unsupported (2 .. 8)", hs.cout);
+        ALQ_REQUIRE(dest_of[hl] < 0, ALQ_EUNSUPPORTED, "a conv head cannot be a skip source");
+        ALQ_REQUIRE(Cin % 4 == 0 && Cin <= 64, ALQ_EUNSUPPORTED, "a conv head on %d channels is unsupported (a multiple of 4, at most 64)", Cin);
+        ALQ_REQUIRE(hl == 0 || dest_of[hl - 1] < 0, ALQ_EUNSUPPORTED, "a conv head whose input is also a skip source is unsupported");
+        m->dense = true;
+        m->V = (int64_t)outs[hl].D * outs[hl].H * outs[hl].W;
+    } else {
+        ALQ_REQUIRE(n_layers > 0 && specs[n_layers - 1].type == ALQ_FC, ALQ_EUNSUPPORTED,
+                    "the scored path needs an fc head (get_gradients, NN_extended.py:1025) or a 1x1 conv head");
+    }
     m->nclass = outs[n_layers - 1].C;
     ALQ_REQUIRE(m->nclass >= 2 && m->nclass <= 64, ALQ_EUNSUPPORTED, "%d classes unsupported", m->nclass);
     {   // The GEMM engines address a tensor with unsigned 32-bit BYTE offsets from its base, and the two halves of a split
@@ -259,6 +277,11 @@ static int build_model(alq_model *m, const alq_layer_t *specs, int n_layers) {
         }
         const long long limit = std::max(1LL, ((1LL << 30) - 64) / std::max(worst, 1LL));
         if (m->max_batch > limit) m->max_batch = (int)limit;
+        if (m->dense) {      // the posterior planes [c, NB V] and the cotangent rows [NB V, c] are allocations of the head's output size
+                             // (in `worst` already); the voxels of one pass are indexed in 32 bits
+            const long long lim2 = std::max(1LL, ((1LL << 31) - 1) / (long long)m->V);
+            if (m->max_batch > lim2) m->max_batch = (int)lim2;
+        }
     }
     const int NB = m->max_batch;
     ALQ_REQUIRE(m->L <= 16, ALQ_EUNSUPPORTED, "%d parameterised layers > 16", m->L);
@@ -338,7 +361,7 @@ static int build_model(alq_model *m, const alq_layer_t *specs, int n_layers) {
     }
     m->logits = act[n_layers - 1].p;
     m->dlogits = dact[n_layers - 1].p;
-    ALQ_TRY(m->dalloc(&m->post, (size_t)NB * m->nclass));
+    ALQ_TRY(m->dalloc(&m->post, (size_t)NB * m->nclass * m->V));
     ALQ_TRY(m->dalloc(&m->S, (size_t)NB * m->L));
     ALQ_TRY(m->dalloc(&m->sizes, (size_t)m->L));
     ALQ_TRY(m->dalloc(&m->Apart, (size_t)((NB + 63) / 64) * m->L * m->L));
@@ -361,6 +384,15 @@ static int build_model(alq_model *m, const alq_layer_t *specs, int n_layers) {
         }
         ly.out = act[i];
         ly.dout = dact[i];
+        if (m->dense && i == n_layers - 1) {      // the 1x1 conv head: plain fp32 weights [Ci][c], no engine plans, no statistics buffers
+            ALQ_REQUIRE(ly.in.cs == ly.in.C && ly.in.c0 == 0 && !ly.in.split, ALQ_EUNSUPPORTED, "layer %d: conv head on a concat slice", i);
+            ly.dense_head = true;
+            h_sizes[ly.pidx] = (double)(ly.w_elems + ly.b_elems);
+            ALQ_TRY(m->dalloc(&ly.d_bias, (size_t)ly.b_elems));
+            ALQ_TRY(m->dalloc(&ly.d_W32, (size_t)ly.w_elems));
+            ALQ_TRY(m->dalloc(&m->dh_part, (size_t)ALQ_DENSE_MAX_BLOCKS * (ly.w_elems + ly.b_elems)));
+            continue;
+        }
         if (ly.spec.type != ALQ_FC) ALQ_TRY(m->dalloc(&ly.osum, (size_t)NB * ly.out.vox()));
         if (ly.pidx >= 0) {
             h_sizes[ly.pidx] = (double)(ly.w_elems + ly.b_elems);
@@ -709,6 +741,7 @@ static int run_forward(alq_model *m, const float *d_x, int N, bool with_sums, bo
         size_t need = 0;
         for (int j = 1; j < nl; ++j) {
             const Layer &l = m->layers[j];
+            if (l.dense_head) continue;
             const Igemm4Plan *pl = l.spec.type == ALQ_CONV ? &l.fwd[0].p4 : (l.spec.type == ALQ_CONVT ? &l.fwd_all : nullptr);
             if (!pl || !pl->ok || !pl->d_W16 || pl->multi || pl->a.PT != 1 || !l.osum) continue;
             if (l.spec.type == ALQ_CONV && (l.fwd[0].pd.ok || l.fwd[0].pfc.ok)) continue;
@@ -781,6 +814,7 @@ static int run_forward(alq_model *m, const float *d_x, int N, bool with_sums, bo
     for (int i = 0; i < nl; ++i) {
         Layer &ly = m->layers[i];
         ALQ_REQUIRE(ly.pidx < 0 || ly.weights_set, ALQ_EINVAL, "weights of parameterised layer %d not set", ly.pidx);
+        if (ly.dense_head) break;      // the caller runs the head (dense_forward_head): posteriors straight from its input
         if (skip_next) { skip_next = false; continue; }
         View in = ly.in;
         if (i == 0) in.p = const_cast<float *>(d_x);
@@ -1307,7 +1341,7 @@ static int run_backward_general(alq_model *m, int N, const DropSpec *drop, bool 
     const int nl = (int)m->layers.size();
     m->last.lsum = layer_sums ? 1 : 0;
     m->last.bwd = {};
-    for (int i = nl - 1; i >= 0; --i) {
+    for (int i = m->dense ? nl - 2 : nl - 1; i >= 0; --i) {      // (a dense model: the head's own kernel has written the cotangent of its input)
         Layer &ly = m->layers[i];
         const bool isfc = ly.spec.type == ALQ_FC;
         const bool prev_is_src = (i > 0 && m->layers[i - 1].out_is_skip_src && ly.spec.skip_src < 0);
@@ -1352,7 +1386,7 @@ static int run_param_grads(alq_model *m, const float *d_x, int N, int sum_n, flo
     alq_ctx *ctx = m->ctx;
     long long need = 0;
     for (Layer &ly : m->layers) {
-        if (ly.pidx < 0 || ly.spec.type == ALQ_FC) continue;
+        if (ly.pidx < 0 || ly.spec.type == ALQ_FC || ly.dense_head) continue;
         const bool convt = ly.spec.type == ALQ_CONVT;
         need = std::max(need, wgrad_partial_floats(convt ? ly.in : ly.dout, convt ? ly.dout : ly.in, ly.spec.k) * N);
     }
@@ -1368,7 +1402,9 @@ static int run_param_grads(alq_model *m, const float *d_x, int N, int sum_n, flo
         View in = ly.in;
         if (i == 0) in.p = const_cast<float *>(d_x);
         const int one[3] = {1, 1, 1};
-        if (ly.spec.type == ALQ_CONV) {
+        if (ly.dense_head) {
+            // written by the head's backward launch (dense_backward_head)
+        } else if (ly.spec.type == ALQ_CONV) {
             ALQ_TRY(k_wgrad(ctx, ly.dout, in, ly.spec.k, one, ly.lo, N, sum_n, m->wg_partial, d_out + off, stride));
             ALQ_TRY(k_bgrad(ctx, ly.dout, N, sum_n, d_out + off + ly.w_elems, stride));
         } else if (ly.spec.type == ALQ_CONVT) {
@@ -1643,8 +1679,30 @@ static int run_hess_vecp(alq_model *m, const float *d_x, int N, const int32_t *d
     return backward(true);
 }
 
+// ---- fully-convolutional models: the head's launches and the refusals of the fc-only entry points
+#define ALQ_REFUSE_DENSE(m, who)                                                                                                \
+    ALQ_REQUIRE(!(m) || !(m)->dense, ALQ_EUNSUPPORTED, "%s: not defined for a fully-convolutional model (1x1 conv head)", who)
+
+// posteriors [c, N V] (and predictions, and the logits into the head's output buffer) from the head's input, after run_forward
+static int dense_forward_head(alq_model *m, const float *d_x, int N, float *d_post, int64_t *d_pred, bool want_logits) {
+    Layer &h = m->layers.back();
+    const float *x = m->layers.size() == 1 ? d_x : h.in.p;
+    return k_dense_head_fwd(m->ctx, x, (long long)N * m->V, h.in.C, m->nclass, h.d_W32, h.d_bias, d_post ? d_post : m->post, d_pred,
+                            want_logits ? h.out.p : nullptr);
+}
+
+// the head's cotangent rows (m->dlogits) -> the cotangent of its input and its own slice [dW, db] of the flat gradient
+static int dense_backward_head(alq_model *m, const float *d_x, int N, float *d_grads, long long P) {
+    Layer &h = m->layers.back();
+    const float *x = m->layers.size() == 1 ? d_x : h.in.p;
+    return k_dense_head_bwd(m->ctx, m->dlogits, x, (long long)N * m->V, h.in.C, m->nclass, h.d_W32, h.pidx == 0 ? nullptr : h.din.p, 0,
+                            m->dh_part, d_grads + (P - h.w_elems - h.b_elems));
+}
+
 // =========================================================================================== C ABI
 extern "C" {
+
+int alq_model_out_voxels(const alq_model *m) { return m ? (int)m->V : ALQ_EINVAL; }
 
 int64_t alq_model_num_params(const alq_model *m) {
     if (!m) return ALQ_EINVAL;
@@ -1664,6 +1722,7 @@ int alq_forward_dropout(alq_model *m, const float *d_x, int N, float keep_prob, 
     ALQ_TRY(make_drop(m, keep_prob, seed, first_sample, h_drop_layers, n_drop_layers, &ds));
     ALQ_TRY(prepare_call(m, /*fisher=*/false));
     ALQ_TRY(run_forward(m, d_x, N, false, /*keep_all=*/true, &ds));
+    if (m->dense) return dense_forward_head(m, d_x, N, d_post, d_pred, false);
     ALQ_TRY(k_softmax(m->ctx, m->logits, m->nclass, N, d_post ? d_post : m->post, d_pred));
     return ALQ_OK;
 }
@@ -1671,6 +1730,7 @@ int alq_forward_dropout(alq_model *m, const float *d_x, int N, float keep_prob, 
 int alq_param_grads(alq_model *m, const float *d_x, int N, int mode, int cls, const int32_t *d_labels, float loss_scale,
                     float keep_prob, uint64_t seed, int64_t first_sample, const int32_t *h_drop_layers, int n_drop_layers,
                     int per_sample, float *d_grads, float *d_post, double *d_loss) {
+    ALQ_REFUSE_DENSE(m, "alq_param_grads");
     ALQ_REQUIRE(m && d_x && d_grads, ALQ_EINVAL, "alq_param_grads: null argument");
     ALQ_REQUIRE(N >= 1 && N <= m->max_batch, ALQ_EINVAL, "alq_param_grads: N=%d outside [1, max_batch=%d]", N, m->max_batch);
     ALQ_REQUIRE(mode == 0 || (mode == 1 && d_labels), ALQ_EINVAL, "alq_param_grads: mode %d / labels", mode);
@@ -1689,6 +1749,7 @@ int alq_param_grads(alq_model *m, const float *d_x, int N, int mode, int cls, co
 }
 
 int alq_grad_sqnorms(alq_model *m, const float *d_x, int N, int cls, const int32_t *d_cls, float *d_post, double *d_sq) {
+    ALQ_REFUSE_DENSE(m, "alq_grad_sqnorms");
     ALQ_REQUIRE(m && d_x && d_sq, ALQ_EINVAL, "alq_grad_sqnorms: null argument");
     ALQ_REQUIRE(N >= 1 && N <= m->max_batch, ALQ_EINVAL, "alq_grad_sqnorms: N=%d outside [1, max_batch=%d]", N, m->max_batch);
     ALQ_REQUIRE(d_cls || (cls == -1 && m->nclass == 2) || (cls >= 0 && cls < m->nclass), ALQ_EINVAL,
@@ -1707,6 +1768,7 @@ int alq_grad_sqnorms(alq_model *m, const float *d_x, int N, int cls, const int32
 }
 
 int alq_class_layer_sums(alq_model *m, const float *d_x, int N, int J, const int32_t *d_cls, float *d_post, double *d_g) {
+    ALQ_REFUSE_DENSE(m, "alq_class_layer_sums");
     ALQ_REQUIRE(m && d_x && d_cls && d_g, ALQ_EINVAL, "alq_class_layer_sums: null argument");
     ALQ_REQUIRE(N >= 1 && N <= m->max_batch, ALQ_EINVAL, "alq_class_layer_sums: N=%d outside [1, max_batch=%d]", N, m->max_batch);
     ALQ_REQUIRE(J >= 1 && J <= 64, ALQ_EINVAL, "alq_class_layer_sums: %d class slots outside [1, 64]", J);
@@ -1756,6 +1818,7 @@ int alq_class_layer_sums(alq_model *m, const float *d_x, int N, int J, const int
 }
 
 int alq_diag_fisher(alq_model *m, const float *d_x, int N, const int32_t *d_cls, double *d_acc) {
+    ALQ_REFUSE_DENSE(m, "alq_diag_fisher");
     ALQ_REQUIRE(m && d_x && d_cls && d_acc, ALQ_EINVAL, "alq_diag_fisher: null argument");
     ALQ_REQUIRE(N >= 1 && N <= m->max_batch, ALQ_EINVAL, "alq_diag_fisher: N=%d outside [1, max_batch=%d]", N, m->max_batch);
     alq_ctx *ctx = m->ctx;
@@ -1794,6 +1857,7 @@ int alq_threshold_mask(alq_ctx *ctx, const double *d_v, int64_t n, double thr, f
 
 int alq_hess_vecp(alq_model *m, const float *d_x, int N, const int32_t *d_labels, float loss_scale, const float *d_v,
                   const uint8_t *h_layer_on, int accumulate, double *d_hv, double *d_loss) {
+    ALQ_REFUSE_DENSE(m, "alq_hess_vecp");
     ALQ_REQUIRE(m && d_x && d_labels && d_v && d_hv, ALQ_EINVAL, "alq_hess_vecp: null argument");
     ALQ_REQUIRE(N >= 1 && N <= m->max_batch, ALQ_EINVAL, "alq_hess_vecp: N=%d outside [1, max_batch=%d]", N, m->max_batch);
     ALQ_HIP(hipSetDevice(m->ctx->device));
@@ -1852,6 +1916,14 @@ int alq_param_grads_loss(alq_model *m, const float *d_x, int N, const int32_t *d
     ALQ_TRY(prepare_call(m, /*fisher=*/false));
     ALQ_TRY(run_forward(m, d_x, N, false, /*keep_all=*/true, &ds));
     float *post = d_post ? d_post : m->post;
+    if (m->dense) {      // every voxel is a sample: the same cotangent kernel over N V columns, then the head's own backward launch
+        const long long P = alq_model_num_params(m);
+        ALQ_TRY(dense_forward_head(m, d_x, N, post, nullptr, false));
+        ALQ_TRY(k_loss_cotangent(m->ctx, post, m->nclass, (int)(N * m->V), d_labels, loss, loss_scale, lwf_scale, m->dlogits, d_stats3));
+        ALQ_TRY(dense_backward_head(m, d_x, N, d_grads, P));
+        if (m->layers.back().pidx > 0) ALQ_TRY(run_backward_general(m, N, &ds));      // (a head that is the only parameterised layer: nothing below)
+        return run_param_grads(m, d_x, N, 1, d_grads, P);
+    }
     ALQ_TRY(k_softmax(m->ctx, m->logits, m->nclass, N, post, nullptr));
     ALQ_TRY(k_loss_cotangent(m->ctx, post, m->nclass, N, d_labels, loss, loss_scale, lwf_scale, m->dlogits, d_stats3));
     ALQ_TRY(run_backward_general(m, N, &ds));
@@ -2085,7 +2157,8 @@ int alq_forward(alq_model *m, const float *d_x, int N, float *d_post, int64_t *d
     ALQ_HIP(hipSetDevice(m->ctx->device));
     ALQ_TRY(prepare_call(m, /*fisher=*/false));
     ALQ_TRY(run_forward(m, d_x, N, false, /*keep_all=*/d_feat != nullptr));
-    ALQ_TRY(k_softmax(m->ctx, m->logits, m->nclass, N, d_post ? d_post : m->post, d_pred));
+    if (m->dense) ALQ_TRY(dense_forward_head(m, d_x, N, d_post, d_pred, d_feat && feature_layer_idx == (int)m->layers.size() - 1));
+    else ALQ_TRY(k_softmax(m->ctx, m->logits, m->nclass, N, d_post ? d_post : m->post, d_pred));
     if (d_feat) {
         ALQ_REQUIRE(feature_layer_idx >= 0 && feature_layer_idx < (int)m->layers.size(), ALQ_EINVAL, "bad feature layer");
         const View &v = m->layers[feature_layer_idx].out;
@@ -2146,6 +2219,7 @@ int alq_topk_uncertain(alq_ctx *ctx, const double *d_keys, int64_t n, int64_t B,
 
 int alq_fisher(alq_model *m, const float *d_x, int N, const float *d_p1_in, double diag_load, float *d_p1_out,
                double *d_g0, double *d_g1, double *d_A, double *d_trace, double *d_Asum) {
+    ALQ_REFUSE_DENSE(m, "alq_fisher");
     ALQ_REQUIRE(m && d_x, ALQ_EINVAL, "alq_fisher: null argument");
     ALQ_REQUIRE(N >= 0 && N <= m->max_batch, ALQ_EINVAL, "alq_fisher: N=%d exceeds max_batch=%d", N, m->max_batch);
     ALQ_HIP(hipSetDevice(m->ctx->device));
@@ -2178,6 +2252,7 @@ static int stage_rows(alq_model *m, const float *d_pool, const int64_t *d_rows, 
 
 int alq_forward_rows(alq_model *m, const float *d_pool, const int64_t *d_rows, int N, float *d_post, int64_t *d_pred,
                      float *d_feat, int feature_layer_idx) {
+    ALQ_REFUSE_DENSE(m, "alq_forward_rows");
     ALQ_REQUIRE(m != nullptr, ALQ_EINVAL, "alq_forward_rows: null model");
     ALQ_REQUIRE(N >= 0 && N <= m->max_batch, ALQ_EINVAL, "alq_forward_rows: N=%d exceeds max_batch=%d", N, m->max_batch);
     if (N == 0) return ALQ_OK;
@@ -2188,6 +2263,7 @@ int alq_forward_rows(alq_model *m, const float *d_pool, const int64_t *d_rows, i
 
 int alq_fisher_rows(alq_model *m, const float *d_pool, const int64_t *d_rows, int N, const float *d_p1_in, double diag_load,
                     float *d_p1_out, double *d_g0, double *d_g1, double *d_A, double *d_trace, double *d_Asum) {
+    ALQ_REFUSE_DENSE(m, "alq_fisher_rows");
     ALQ_REQUIRE(m != nullptr, ALQ_EINVAL, "alq_fisher_rows: null model");
     ALQ_REQUIRE(N >= 0 && N <= m->max_batch, ALQ_EINVAL, "alq_fisher_rows: N=%d exceeds max_batch=%d", N, m->max_batch);
     ALQ_HIP(hipSetDevice(m->ctx->device));
@@ -2323,7 +2399,7 @@ int alq_model_debug_copy(alq_model *m, int layer_idx, int what, int N, float *d_
         if (elems_out) *elems_out = (int64_t)N * v.elems();
         return debug_view_copy(m->ctx, v, N, d_out);
     }
-    ALQ_REQUIRE(ly.pidx >= 0 && (what == 2 || what == 3), ALQ_EINVAL, "layer has no channel-sum fields");
+    ALQ_REQUIRE(ly.pidx >= 0 && !ly.dense_head && (what == 2 || what == 3), ALQ_EINVAL, "layer has no channel-sum fields");
     const bool isfc = ly.spec.type == ALQ_FC;
     const int64_t e = (int64_t)N * (isfc ? 1 : (what == 2 ? ly.in.vox() : ly.out.vox()));
     if (elems_out) *elems_out = e;

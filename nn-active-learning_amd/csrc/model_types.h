@@ -13,6 +13,7 @@ struct Layer {
     View din, dout;            // cotangent views, same geometry
     int lo[3] = {0, 0, 0};     // SAME pad-before (conv: of the fwd conv; convT: of the conv it transposes)
     bool dense_fc_small = false;
+    bool dense_head = false;   // the 1x1 conv head of a fully-convolutional model (dense.hip): no engine plans, weights in d_W32 as [Ci][c]
     int64_t F = 0;             // fc: input features
     // weights
     int64_t w_elems = 0, b_elems = 0;
@@ -137,6 +138,9 @@ struct alq_model {
     size_t amax_tiles_len = 0;
     int in_dims[4] = {1, 1, 1, 1};
     int nclass = 0;
+    bool dense = false;            // fully-convolutional: the last layer is a 1x1 conv head, every voxel of its output is a sample
+    int64_t V = 1;                 // samples (voxels of the head's output) per patch; 1 for an fc head
+    double *dh_part = nullptr;     // dense head backward: per-workgroup partials of dW and db (dense.hip)
     int L = 0;
     std::vector<alq::Layer> layers;
     std::vector<void *> allocs;

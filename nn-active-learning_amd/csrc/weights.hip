@@ -248,7 +248,10 @@ int alq_model_set_weights(alq_model *m, int t, const float *W, const float *b) {
     Layer &ly = *lyp;
     ALQ_TRY(require_subnormal_probe(m->ctx, "alq_model_set_weights"));
     ALQ_HIP(hipMemcpyAsync(ly.d_bias, b, ly.b_elems * sizeof(float), hipMemcpyHostToDevice, m->ctx->stream));
-    if (ly.spec.type == ALQ_CONV) ALQ_TRY(set_conv(m, ly, W, b));
+    if (ly.dense_head) {      // the 1x1 conv head of a fully-convolutional model: TF [1, (1,) 1, Ci, c] is the [Ci][c] the kernels read
+        conv_norms(W, b, 1, ly.in.C, ly.spec.cout, false, &ly.bwd_l1, &ly.out_l1, &ly.out_bmax);
+        ALQ_HIP(hipMemcpyAsync(ly.d_W32, W, ly.w_elems * sizeof(float), hipMemcpyHostToDevice, m->ctx->stream));
+    } else if (ly.spec.type == ALQ_CONV) ALQ_TRY(set_conv(m, ly, W, b));
     else if (ly.spec.type == ALQ_CONVT) ALQ_TRY(set_convt(m, ly, W, b));
     else ALQ_TRY(set_fc(m, ly, W));
     ALQ_HIP(hipStreamSynchronize(m->ctx->stream));
@@ -282,6 +285,14 @@ int alq_model_set_weights_device(alq_model *m, int t, const float *d_W, const fl
     if (!lyp) return ALQ_EINVAL;
     Layer &ly = *lyp;
     alq_ctx *ctx = m->ctx;
+    if (ly.dense_head) {      // plain fp32 [Ci][c] + [c]: device to device, nothing to pack
+        ALQ_HIP(hipMemcpyAsync(ly.d_W32, d_W, ly.w_elems * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+        ALQ_HIP(hipMemcpyAsync(ly.d_bias, d_b, ly.b_elems * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+        ly.weights_set = true;
+        std::vector<float>().swap(ly.hv_hW);
+        ly.hv_src = 0;
+        return ALQ_OK;
+    }
     if (!packs_on_device(ly)) {      // no device packers for this layer's engines: its slice goes through the host's
         std::vector<float> W((size_t)ly.w_elems), b((size_t)ly.b_elems);
         ALQ_HIP(hipMemcpyAsync(W.data(), d_W, W.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));

@@ -7,6 +7,7 @@ device through `sess.run(getattr(model, var), feed_dict)` (PW_NN.py:466,522).  H
 for device memory, the stream and (in pool_shard.py) torch.distributed.
 """
 import ctypes as C
+import functools
 import os
 from collections import OrderedDict
 
@@ -485,6 +486,8 @@ class DeviceSession(object):
         for h in (getattr(model, 'input_weights', None), getattr(model, 'input_vox_weights', None)):
             if h is not None and h in feed_dict:
                 iw = feed_dict[h]
+        if getattr(model, 'dense', False):
+            return model._run_dense(fetch, feed_dict, x, kp, iw)
         if fetch.name == 'LwF_train_step':
             lwf = (feed_dict[model.y__], float(feed_dict[model.lambda_o]), float(feed_dict[model.T]))
             return model.train_on_batch(x, feed_dict[model.y_], keep_prob=kp, input_weights=iw, lwf=lwf)
@@ -663,6 +666,18 @@ def tf_param_shapes(layers, in_shape):
     return out
 
 
+def out_map_shape(layers, in_shape):
+    """Spatial shape of the last layer's output map (SAME padding: pools round up, transposed convs multiply)."""
+    nd = len(in_shape) - 1
+    spatial = [int(v) for v in in_shape[:-1]]
+    for d in layers:
+        if d['type'] == ALQ_CONVT:
+            spatial = [a * b for a, b in zip(spatial, d['s'][3 - nd:])]
+        elif d['type'] == ALQ_POOL:
+            spatial = [-(-a // b) for a, b in zip(spatial, d['s'][3 - nd:])]
+    return tuple(spatial)
+
+
 class LazyVarDict(OrderedDict):
     """`model.var_dict`: name -> [W, b] host arrays in TF layouts.  When the weights were last set from device memory
     (DeviceModel.set_weights_device, every training step) the host copies are stale: `refresh` - a callable that fetches
@@ -758,6 +773,12 @@ class DeviceModel(object):
         self._create_env = {k: v for k, v in os.environ.items() if k.startswith('ALQ_')}     # engine switches are read at creation
         self.L = self.lib.alq_model_num_param_layers(self._m)
         self.nclass = self.layers[-1]['cout']
+        # a fully-convolutional model (1x1 conv head, csrc/dense.hip): every voxel of the head's output map is a sample
+        self.dense = self.layers[-1]['type'] == ALQ_CONV
+        self.out_voxels = int(self.lib.alq_model_out_voxels(self._m))
+        self.out_map_shape = out_map_shape(self.layers, self.in_shape) if self.dense else ()
+        if self.dense and int(np.prod(self.out_map_shape)) != self.out_voxels:
+            raise AssertionError('output map %r against %d voxels in the library' % (self.out_map_shape, self.out_voxels))
         self.elems_per_patch = int(np.prod(self.in_shape))
         # reference-style attributes
         self.x = Handle('x')
@@ -797,6 +818,7 @@ class DeviceModel(object):
         self.hypers = None
         self._obj = None
         self.input_weights = Handle('input_weights')      # per-sample loss weights [n], fed through feed_dict
+        self.input_vox_weights = Handle('input_vox_weights', self.out_map_shape) if self.dense else None      # [n, *spatial] (get_FCN_loss)
         self.labels = Handle('labels')
         self.pt = Handle('pt')
         self.labels.model = self.pt.model = self
@@ -956,7 +978,7 @@ class DeviceModel(object):
 
     def _check_input_weights(self, input_weights):
         """Per-sample weights belong to NN_extended.get_loss (NN_extended.py:1252-1255); NN.py's loss has none."""
-        if input_weights is not None and self._obj is None:
+        if input_weights is not None and self._obj is None and not self.dense:
             raise ValueError('input_weights on a model without training hypers: the batch-mean cross-entropy of NN.py:583-588 '
                              'takes no sample weights (build the NN_extended.CNN with loss_name=\'CE\' for the weighted mean)')
 
@@ -1009,8 +1031,8 @@ class DeviceModel(object):
         torch = self.sess.torch
         t, n = self._as_device_batch(x)
         self._check_input_weights(input_weights)
-        if self._obj is not None:
-            y = self._onehot(labels, n) if targets is None else targets
+        if self._obj is not None or self.dense:
+            y = self._onehot(labels, n * self.out_voxels) if targets is None else targets
             return self._objective_pass(t, n, y, 1., None, input_weights, None, want_grad=False)[1]
         lab = self.sess.to_device(np.asarray(labels, dtype=np.int32).reshape(n), torch.int32)
         loss = 0.
@@ -1027,8 +1049,8 @@ class DeviceModel(object):
         torch = self.sess.torch
         t, n = self._as_device_batch(x)
         self._check_input_weights(input_weights)
-        if self._obj is not None:
-            y = self._onehot(labels, n) if targets is None else targets
+        if self._obj is not None or self.dense:
+            y = self._onehot(labels, n * self.out_voxels) if targets is None else targets
             g, _ = self._objective_pass(t, n, y, 1., None, input_weights, None)
             return self.unflatten(g.cpu().numpy(), self.hess_layer_idx(layers))
         lab = self.sess.to_device(np.asarray(labels, dtype=np.int32).reshape(n), torch.int32)
@@ -1196,50 +1218,52 @@ class DeviceModel(object):
         from . import losses
         torch = self.sess.torch
         self.sess.bind_stream()
-        obj = self._obj or dict(kind=losses.CE, divisor='N', q=0.7, gamma=None, class_w=None)
-        kind, c = obj['kind'], self.nclass
+        # (a dense model: V samples per patch, always the non-zero-weight divisor of get_FCN_loss, NN_extended.py:1285-1335)
+        obj = self._obj or dict(kind=losses.CE, divisor='nonzero' if self.dense else 'N', q=0.7, gamma=None, class_w=None)
+        kind, c, V = obj['kind'], self.nclass, self.out_voxels
+        ns = n * V
         y = np.asarray(y)
-        if y.shape != (c, n):
-            raise ValueError('labels must be [%d, %d] columns, got %r' % (c, n, y.shape))
+        if y.shape != (c, ns):
+            raise ValueError('labels must be [%d, %d] columns, got %r' % (c, ns, y.shape))
         lab = np.where(y.sum(0) > 0, y.argmax(0), -1).astype(np.int32)
         labd = self.sess.to_device(lab, torch.int32)
         tgd = self.sess.to_device(y.astype(np.float32), torch.float32) if kind != losses.CE else None
-        sw = None if input_weights is None else np.asarray(input_weights, dtype=np.float32).reshape(n)
+        sw = None if input_weights is None else np.asarray(input_weights, dtype=np.float32).reshape(ns)
         swd = None if sw is None else self.sess.to_device(sw, torch.float32)
         cw = obj['class_w']
         gamma = obj['gamma'] if (obj['gamma'] is not None and obj['gamma'] > 0) else None
         old, lam, T = None, 0., 1.
         if lwf is not None:
-            old = self.sess.to_device(np.asarray(lwf[0], dtype=np.float32).reshape(c, n), torch.float32)
+            old = self.sess.to_device(np.asarray(lwf[0], dtype=np.float32).reshape(c, ns), torch.float32)
             lam, T = float(lwf[1]), float(lwf[2])
         kp, arr, nl, seed = self._drop_args(keep_prob, seed)
         cuts = [(a, min(n, a + self.max_batch)) for a in range(0, n, self.max_batch)]
 
         def spec(a, b):
-            keep = [None if v is None else v[:, a:b].contiguous() for v in (tgd, old)]
+            keep = [None if v is None else v[:, a * V:b * V].contiguous() for v in (tgd, old)]
             L = LossT(kind, -1. if gamma is None else gamma, obj['q'], T, cw.data_ptr() if cw is not None else None,
-                      swd.data_ptr() + a * 4 if swd is not None else None, keep[0].data_ptr() if keep[0] is not None else None,
+                      swd.data_ptr() + a * V * 4 if swd is not None else None, keep[0].data_ptr() if keep[0] is not None else None,
                       keep[1].data_ptr() if keep[1] is not None else None)
             return L, keep
 
         def stats_only(dst):
             for k, (a, b) in enumerate(cuts):
-                pb = self.sess.empty((c, b - a), torch.float32)
+                pb = self.sess.empty((c, (b - a) * V), torch.float32)
                 check(self.lib.alq_forward_dropout(self._m, C.c_void_p(t.data_ptr() + a * self.elems_per_patch * 4), b - a, kp, seed, a,
                                                    arr, nl, C.c_void_p(pb.data_ptr()), None))
                 L, keep = spec(a, b)
-                check(self.lib.alq_loss_stats(self.sess.ctx, C.c_void_p(pb.data_ptr()), c, b - a, C.c_void_p(labd.data_ptr() + a * 4),
+                check(self.lib.alq_loss_stats(self.sess.ctx, C.c_void_p(pb.data_ptr()), c, (b - a) * V, C.c_void_p(labd.data_ptr() + a * V * 4),
                                               C.byref(L), C.c_void_p(dst.data_ptr() + k * 24)))
                 del keep
 
         stats = torch.zeros((len(cuts), 3), dtype=torch.float64, device=self.sess.device)
         post_scale = False
         if kind == losses.CE_SOFT:
-            s = 1. / n
+            s = 1. / ns
         elif kind == losses.GCE:
             s = 1.           # reduce_mean over the classes leaves a vector over samples: the optimiser differentiates its sum
         elif obj['divisor'] == 'N':
-            s = 1. / n
+            s = 1. / ns
         elif gamma is None:
             w = (lab >= 0).astype(np.float64)
             if cw is not None:
@@ -1261,7 +1285,7 @@ class DeviceModel(object):
                 g = self.sess.empty((self.num_params,), torch.float32)
                 L, keep = spec(a, b)
                 check(self.lib.alq_param_grads_loss(self._m, C.c_void_p(t.data_ptr() + a * self.elems_per_patch * 4), b - a,
-                                                    C.c_void_p(labd.data_ptr() + a * 4), C.byref(L), float(s), lam / n, kp, seed, a,
+                                                    C.c_void_p(labd.data_ptr() + a * V * 4), C.byref(L), float(s), lam / ns, kp, seed, a,
                                                     arr, nl, C.c_void_p(g.data_ptr()), None, C.c_void_p(stats.data_ptr() + k * 24)))
                 gsum += g
                 del keep
@@ -1274,14 +1298,14 @@ class DeviceModel(object):
         if kind == losses.CE and obj['divisor'] == 'N':
             loss = 0.
             for (a, b), row in zip(cuts, st):          # the arithmetic of the default step: per-pass means, weighted
-                loss += float(row[0] / (b - a)) * (b - a) / n
+                loss += float(row[0] / ((b - a) * V)) * ((b - a) * V) / ns
         elif kind == losses.CE:
             cnt = st[:, 1].sum()
             loss = float(st[:, 0].sum() / cnt) if cnt else 0.
         else:
-            loss = float(st[:, 0].sum() / n)      # GCE: the mean of the reference's per-sample loss vector
+            loss = float(st[:, 0].sum() / ns)      # GCE: the mean of the reference's per-sample loss vector
         if lwf is not None:
-            loss = loss + lam * float(st[:, 2].sum() / n)
+            loss = loss + lam * float(st[:, 2].sum() / ns)
         return gsum, loss
 
     def lwf_loss(self, x, y_onehot, lwf, keep_prob=1., seed=None, input_weights=None):
@@ -1304,10 +1328,10 @@ class DeviceModel(object):
         torch = self.sess.torch
         t, n = self._as_device_batch(x)
         y = np.asarray(y_onehot)
-        if y.shape != (self.nclass, n):
-            raise ValueError('labels must be [%d, %d] one-hot columns, got %r' % (self.nclass, n, y.shape))
+        if y.shape != (self.nclass, n * self.out_voxels):
+            raise ValueError('labels must be [%d, %d] one-hot columns, got %r' % (self.nclass, n * self.out_voxels, y.shape))
         self._check_input_weights(input_weights)
-        if self._obj is not None or lwf is not None:
+        if self._obj is not None or lwf is not None or self.dense:
             gsum, loss = self._objective_pass(t, n, y, keep_prob, seed, input_weights, lwf)
         else:
             lab = np.where(y.sum(0) > 0, y.argmax(0), -1).astype(np.int32)
@@ -1690,15 +1714,16 @@ class DeviceModel(object):
         torch = self.sess.torch
         self.sess.bind_stream()
         kp, arr, nl, seed = self._drop_args(keep_prob, seed)
-        post = self.sess.empty((self.nclass, n), torch.float32)
-        pred = self.sess.empty((n,), torch.int64) if want_pred else None
+        V = self.out_voxels          # samples per patch: 1, or the voxels of a dense model's output map
+        post = self.sess.empty((self.nclass, n * V), torch.float32)
+        pred = self.sess.empty((n * V,), torch.int64) if want_pred else None
         for a in range(0, n, self.max_batch):
             b = min(n, a + self.max_batch)
-            pb = self.sess.empty((self.nclass, b - a), torch.float32)
+            pb = self.sess.empty((self.nclass, (b - a) * V), torch.float32)
             check(self.lib.alq_forward_dropout(self._m, C.c_void_p(t.data_ptr() + a * self.elems_per_patch * 4), b - a, kp, seed,
                                                int(first_sample) + a, arr, nl, C.c_void_p(pb.data_ptr()),
-                                               C.c_void_p(pred.data_ptr() + a * 8) if want_pred else None))
-            post[:, a:b] = pb
+                                               C.c_void_p(pred.data_ptr() + a * V * 8) if want_pred else None))
+            post[:, a * V:b * V] = pb
         return post, pred
 
     def forward_device(self, t, n, want_pred=False, want_feat=False, rows=None):
@@ -1707,8 +1732,11 @@ class DeviceModel(object):
         Returns device tensors (post [c,n], pred, feat)."""
         torch = self.sess.torch
         self.sess.bind_stream()
-        post = self.sess.empty((self.nclass, n), torch.float32)
-        pred = self.sess.empty((n,), torch.int64) if want_pred else None
+        V = self.out_voxels          # samples per patch: 1, or the voxels of a dense model's output map
+        if rows is not None and self.dense:
+            raise NotImplementedError('forward_device(rows=...): not defined for a fully-convolutional model (1x1 conv head)')
+        post = self.sess.empty((self.nclass, n * V), torch.float32)
+        pred = self.sess.empty((n * V,), torch.int64) if want_pred else None
         feat = self.sess.empty((n, self.feature_dim), torch.float32) if want_feat else None
         if rows is not None:
             assert rows.dtype == torch.int64 and rows.is_contiguous() and int(rows.numel()) == n
@@ -1716,9 +1744,9 @@ class DeviceModel(object):
         # with two pipelines against 0.3601 s with one, same box)
         for a in range(0, n, self.max_batch):
             b = min(n, a + self.max_batch)
-            pb = self.sess.empty((self.nclass, b - a), torch.float32)
+            pb = self.sess.empty((self.nclass, (b - a) * V), torch.float32)
             outs = (C.c_void_p(pb.data_ptr()),
-                    C.c_void_p(pred.data_ptr() + a * 8) if want_pred else None,
+                    C.c_void_p(pred.data_ptr() + a * V * 8) if want_pred else None,
                     C.c_void_p(feat.data_ptr() + a * self.feature_dim * 4) if want_feat else None,
                     self.feature_idx if want_feat else -1)
             if rows is None:
@@ -1726,8 +1754,52 @@ class DeviceModel(object):
             else:
                 check(self.lib.alq_forward_rows(self._m, C.c_void_p(t.data_ptr()), C.c_void_p(rows.data_ptr() + a * 8),
                                                 b - a, *outs))
-            post[:, a:b] = pb
+            post[:, a * V:b * V] = pb
         return post, pred, feat
+
+    def forward_maps_device(self, t, n, keep_prob=1., want_pred=False, seed=None):
+        """A dense model's outputs as maps, on the device: (posteriors [n, *spatial, c] float32 - `model.posteriors` of the
+        reference's FCN branch, NN_extended.py:262-294 - and prediction [n, *spatial] int64 or None)."""
+        if not self.dense:
+            raise NotImplementedError('forward_maps_device: the model has an fc head (no output map)')
+        if float(keep_prob) < 1. and len(self.dropout_layers):
+            post, pred = self.forward_dropout_device(t, n, keep_prob, seed=seed, want_pred=want_pred)
+        else:
+            post, pred, _ = self.forward_device(t, n, want_pred)
+        maps = post.reshape((self.nclass, n) + self.out_map_shape).movedim(0, -1)
+        return maps, (pred.reshape((n,) + self.out_map_shape) if pred is not None else None)
+
+    def _run_dense(self, fetch, feed_dict, x, kp, iw):
+        """sess.run of a dense model: `posteriors` [n, *spatial, c], `prediction` [n, *spatial], `feature_layer`, `loss` and
+        `train_step` with `y_` one-hot [n, *spatial, c] (an all-zero row: unlabelled voxel, NN_extended.py:1291-1293) and
+        `input_vox_weights` [n, *spatial]."""
+        name = fetch.name
+        if name in ('posteriors', 'prediction'):
+            t, n = self._as_device_batch(x)
+            maps, pred = self.forward_maps_device(t, n, kp, want_pred=name == 'prediction')
+            return (pred if name == 'prediction' else maps.contiguous()).cpu().numpy()
+        if name == 'feature_layer':
+            return self.forward(x, want=(name,), keep_prob=kp)[name]
+        if name not in ('loss', 'train_step'):
+            raise NotImplementedError('sess.run(model.%s) is not defined for a fully-convolutional model (1x1 conv head)' % name)
+        y = np.asarray(feed_dict[self.y_])
+        n = int(np.asarray(x).shape[0]) if not isinstance(x, self.sess.torch.Tensor) else int(x.shape[0])
+        if tuple(y.shape) != (n,) + self.out_map_shape + (self.nclass,):
+            raise ValueError('y_ must be one-hot %r, got %r' % ((n,) + self.out_map_shape + (self.nclass,), tuple(y.shape)))
+        ycols = np.ascontiguousarray(y.reshape(-1, self.nclass).T)
+        if iw is not None:
+            iw = np.asarray(iw)
+            if tuple(iw.shape) != (n,) + self.out_map_shape:
+                raise ValueError('input_vox_weights must be %r, got %r' % ((n,) + self.out_map_shape, tuple(iw.shape)))
+            iw = iw.reshape(-1)
+        if name == 'loss':
+            t, n = self._as_device_batch(x)
+            return self._objective_pass(t, n, ycols, kp, None, iw, None, want_grad=False)[1]
+        ph = getattr(self, 'par_placeholders', None)
+        fed = [h in feed_dict for h in ph] if ph else []
+        if any(fed) and not all(fed):
+            raise KeyError('a PFT step needs a mask for every entry of par_placeholders')
+        return self.train_on_batch(x, ycols, keep_prob=kp, pft_mask=[feed_dict[h] for h in ph] if any(fed) else None, input_weights=iw)
 
     def forward(self, x, want=('posteriors',), keep_prob=1.):
         t, n = self._as_device_batch(x)
@@ -2029,3 +2101,22 @@ class DeviceModel(object):
             self.close()
         except Exception:
             pass
+
+
+
+def _fc_only(fn):
+    """The method is defined for fc-head models: on a fully-convolutional one it raises before it touches the device."""
+    @functools.wraps(fn)
+    def guarded(self, *args, **kwargs):
+        if getattr(self, 'dense', False):
+            raise NotImplementedError('%s: not defined for a fully-convolutional model (1x1 conv head)' % fn.__name__)
+        return fn(self, *args, **kwargs)
+    return guarded
+
+
+for _name in ('get_gradients', 'grad_log_post', 'param_grads_device', 'grad_sqnorms_device', 'hess_vecp_device', 'hess_vecp',
+              'fisher_device', 'fisher', 'shrunk_class_gradients', 'class_layer_sums_device', 'fisher_classes',
+              'diagonal_fisher_device', 'diagonal_fisher', 'diagonal_fisher_rows_device', 'llfc_reference_order', 'llfc_grads_device',
+              'llfc_hess_device', 'llfc_stoch_if_features_device', 'llfc_stoch_if_device'):
+    setattr(DeviceModel, _name, _fc_only(getattr(DeviceModel, _name)))
+del _name

@@ -88,6 +88,25 @@ def net_c_2d(nclass=2):
     return layers, skips
 
 
+def _dense_head(layers, nclass, dim):
+    """The layer dict with its fc head replaced by the 1x1 conv head of the reference's FCN builder (create_NN.py:273)."""
+    out = OrderedDict((k, v) for k, v in layers.items() if v[0] != 'fc')
+    out['last'] = ['conv', [nclass, [1] * dim], 'M']
+    return out
+
+
+def net_c_dense(nclass=2):
+    """NET-C as a fully-convolutional net: every voxel of the input patch gets a posterior.  Returns (layer_dict, skips)."""
+    layers, skips = net_c(nclass)
+    return _dense_head(layers, nclass, 3), skips
+
+
+def net_c_2d_dense(nclass=2):
+    """The 2-D analogue of NET-C with the 1x1 conv head.  Returns (layer_dict, skips)."""
+    layers, skips = net_c_2d(nclass)
+    return _dense_head(layers, nclass, 2), skips
+
+
 def is_extended(layer_dict):
     """The two schemas differ in the position of the type string."""
     first = next(iter(layer_dict.values()))
