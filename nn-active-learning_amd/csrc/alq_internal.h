@@ -776,4 +776,22 @@ int committee_update_impl(alq_ctx *, const float *d_p1, int64_t n, int member, i
 int eval_counts_impl(alq_ctx *, const int64_t *d_pred, const int64_t *d_inds, int64_t n, const void *d_mask, int mask_is_f64,
                      int64_t mask_elems, int64_t *d_counts, uint8_t *d_seg, int *d_bad);
 
+// ------------------------------------------------------------------ behind the pass-through entry points (ctx.hip) and the debug copies (model.hip)
+int gather_normalize_impl(alq_ctx *, const void *const *, int, int, const int64_t[3], const int64_t[3],
+                          const int64_t *, int64_t, const int32_t[3], const double *, int, int, void *);
+int score_entropy_impl(alq_ctx *, const float *, int64_t, double *, float *);
+int synth_impl(alq_ctx *, uint64_t, int64_t, int64_t, int64_t, float *);
+int gather_rows_impl(alq_ctx *, const float *, const int64_t *, int64_t, int64_t, float *);
+int debug_view_copy(alq_ctx *, const View &, int, float *);
+int debug_f64_copy(alq_ctx *, const double *, long long, float *);
+size_t topk_work_bytes_impl(int64_t n);
+int topk_impl(alq_ctx *, const double *, int64_t, int64_t, int64_t *, void *);
+// the argument checks of an alq_loss_t, shared by alq_loss_stats (ctx.hip) and alq_param_grads_loss (grads.hip)
+int loss_check(const char *who, const float *d_post_or_x, int c, const int32_t *d_labels, const alq_loss_t *loss);
+// The device flag a kernel raises over values that live on the device (a class or an index out of range): the last word of the context's
+// parameter block.  flag_clear is queued before that kernel, flag_read behind it: one async copy and ONE stream synchronisation.
+inline int *flag_of(alq_ctx *ctx) { return reinterpret_cast<int *>(static_cast<char *>(ctx->param_block) + ALQ_PARAM_FLAG_OFFSET); }
+int flag_clear(alq_ctx *ctx);
+int flag_read(alq_ctx *ctx, int *bad);
+
 }  // namespace alq

@@ -1,7 +1,7 @@
 // Exact Hessian-vector products (alq_hess_vecp): the kernels of the R-operator pass.
 //   Replaces: the Pearlmutter double-backward of Influence.get_hess_vec_product / hessian_vector_product (Influence.py:64-166)
 //   that PW_sample_influence (Influence.py:369-453) hands to scipy's Newton-CG.
-// The driver (model.hip) runs the ordinary forward pass with everything kept, which fixes every ReLU and max-pool decision
+// The driver (grads.hip) runs the ordinary forward pass with everything kept, which fixes every ReLU and max-pool decision
 // (the stored activation's sign, the stored arg-max), and then evaluates on those decisions, in fp64 throughout:
 //   activations        a_l = mask . (op(a_{l-1}; W_l) + b_l), max-pool at the stored arg-max, a 'con' skip as a two-part source;
 //   logits             p = softmax(z), delta = loss_scale (p - y) (hvp_softmax64);

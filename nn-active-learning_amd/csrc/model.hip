@@ -1,33 +1,15 @@
-// Model plan + orchestration behind the C ABI: shapes, activation / cotangent workspaces
-// (concat skips = channel slices of one buffer) and the forward / Fisher launch sequences.
-// The structures are in model_types.h; weights reach the engines' packed forms in weights.hip.
+// Model plan + orchestration behind the C ABI: shapes, activation / cotangent workspaces (concat skips = channel slices of
+// one buffer), engine routing, the forward pass and the fused Fisher backward sweep, with their entry points and the debug hooks.
+// The structures are in model_types.h; weights reach the engines' packed forms in weights.hip; the general gradient path is grads.hip,
+// everything that takes no model (contexts, profiling, the pass-through entry points) ctx.hip.
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstring>
 #include <string>
 
 #include "model_types.h"
 
 namespace alq {
-
-static thread_local char g_err[1024] = "";
-void set_error(const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-
-int gather_normalize_impl(alq_ctx *, const void *const *, int, int, const int64_t[3], const int64_t[3],
-                          const int64_t *, int64_t, const int32_t[3], const double *, int, int, void *);
-int score_entropy_impl(alq_ctx *, const float *, int64_t, double *, float *);
-int synth_impl(alq_ctx *, uint64_t, int64_t, int64_t, int64_t, float *);
-int gather_rows_impl(alq_ctx *, const float *, const int64_t *, int64_t, int64_t, float *);
-int debug_view_copy(alq_ctx *, const View &, int, float *);
-int debug_f64_copy(alq_ctx *, const double *, long long, float *);
-size_t topk_work_bytes_impl(int64_t n);
-int topk_impl(alq_ctx *, const double *, int64_t, int64_t, int64_t *, void *);
 
 static void same_pads(int in, int k, int s, int *out, int *lo) {
     *out = (in + s - 1) / s;
@@ -39,45 +21,6 @@ static void same_pads(int in, int k, int s, int *out, int *lo) {
 }  // namespace alq
 
 using namespace alq;
-
-// ------------------------------------------------------------------------------------------
-int alq_ctx::prof_begin(int cls, hipEvent_t *e0, hipEvent_t *e1) {
-    ProfSlot &s = prof[cls];
-    auto get = [&](hipEvent_t *ev) -> int {
-        if (!s.pool.empty()) {
-            *ev = s.pool.back();
-            s.pool.pop_back();
-            return ALQ_OK;
-        }
-        return hipEventCreate(ev) == hipSuccess ? ALQ_OK : ALQ_EHIP;
-    };
-    if (get(e0) != ALQ_OK || get(e1) != ALQ_OK) return ALQ_EHIP;
-    return hipEventRecord(*e0, stream) == hipSuccess ? ALQ_OK : ALQ_EHIP;
-}
-
-void alq_ctx::prof_end(int cls, hipEvent_t e0, hipEvent_t e1, double flops) {
-    ProfSlot &s = prof[cls];
-    (void)hipEventRecord(e1, stream);
-    s.pending.emplace_back(e0, e1);
-    s.launches += 1;
-    s.flops += flops;
-}
-
-int alq_ctx::prof_collect() {
-    ALQ_HIP(hipStreamSynchronize(stream));
-    for (int c = 0; c < PROF_NUM; ++c) {
-        ProfSlot &s = prof[c];
-        for (auto &pr : s.pending) {
-            float ms = 0.f;
-            ALQ_HIP(hipEventElapsedTime(&ms, pr.first, pr.second));
-            s.ms += ms;
-            s.pool.push_back(pr.first);
-            s.pool.push_back(pr.second);
-        }
-        s.pending.clear();
-    }
-    return ALQ_OK;
-}
 
 // ------------------------------------------------------------------------------------------
 static int g_knob_override[ALQ_NKNOBS] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // alq_debug_set: >= 0 overrides every model's snapshot
@@ -109,7 +52,7 @@ static int gemm_build(const EngineSwitches &sw, const ConvDesc &d, int max_batch
 }
 
 // first step of every entry point that runs a pass; `fisher`: the pass is a Fisher pass (what alq_model_debug_copy may read)
-static int prepare_call(alq_model *m, bool fisher) {
+int prepare_call(alq_model *m, bool fisher) {
     m->last.call_fisher = fisher;
     apply_knobs(m);
     if (!two_slot_allowed()) ALQ_TRY(refresh_fallback_forms(m));
@@ -129,8 +72,8 @@ static GemmRoute gemm_route(const Gemm &g, const View &in, const View &out, int 
 }
 
 // returns in *fused whether the epilogue fusion request was honoured (only the pipelined kernel can)
-static int gemm_launch(alq_ctx *ctx, const Gemm &g, const View &in, const View &out, const float *bias, int relu,
-                       int accumulate, int N, int cls, const Igemm2Fuse *fuse = nullptr, bool *fused = nullptr, float fc_in_bound = 0.f) {
+int gemm_launch(alq_ctx *ctx, const Gemm &g, const View &in, const View &out, const float *bias, int relu,
+                int accumulate, int N, int cls, const Igemm2Fuse *fuse, bool *fused, float fc_in_bound) {
     const GemmRoute route = gemm_route(g, in, out, accumulate, fuse);
     ALQ_REQUIRE(route <= ROUTE_FCGEMM || g.p4.ok || (in.split == 0 && out.split == 0), ALQ_EUNSUPPORTED, "split concat view without a two-slot plan");
     if (fused) *fused = fuse != nullptr && route != ROUTE_FCGEMM && route != ROUTE_IGEMM;
@@ -603,16 +546,7 @@ static int build_model(alq_model *m, const alq_layer_t *specs, int n_layers) {
     return ALQ_OK;
 }
 
-// dropout of a training / MC forward pass: layers whose OUTPUT is dropped (NN.py:169-171), one keep probability
-struct DropSpec {
-    unsigned long long layers = 0;     // bit i = layer i
-    float keep_prob = 1.f;
-    unsigned long long seed = 0;
-    long long first_sample = 0;        // id of patch 0 of this call: masks are keyed by sample id, not by batch position
-    bool on(int i) const { return keep_prob < 1.f && i < 64 && ((layers >> i) & 1ull); }
-};
-
-static View flat_view(const View &v) {
+View flat_view(const View &v) {
     View f;
     f.p = v.p; f.D = f.H = f.W = 1;
     f.C = (int)(v.vox() * v.C); f.cs = f.C; f.c0 = 0;
@@ -715,7 +649,7 @@ static bool t3d_fwd_applies(const alq_model *m, int i, const std::vector<char> &
 // ------------------------------------------------------------------------------------------
 // keep_all (forward-only calls): every activation stays readable (a feature layer was asked for); otherwise the fc
 // head of a two-class net is fused into the last conv in forward-only calls too (no channel sums, no sign bytes)
-static int run_forward(alq_model *m, const float *d_x, int N, bool with_sums, bool keep_all = false, const DropSpec *drop = nullptr) {
+int run_forward(alq_model *m, const float *d_x, int N, bool with_sums, bool keep_all, const DropSpec *drop) {
     alq_ctx *ctx = m->ctx;
     const int nl = (int)m->layers.size();
     bool skip_next = false;      // this layer's outputs were produced by the previous layer's kernel
@@ -1330,175 +1264,8 @@ static int run_backward_main(alq_model *m, const float *d_x, int N) {
     return ALQ_OK;
 }
 
-// General backward-data pass for a cotangent already in m->dlogits ([N, c], w.r.t. the logits as the forward pass left
-// them): every layer's masked pre-activation cotangent ends up in its `dout` view (what the weight gradients need), no
-// shortcut of the Fisher pass is taken (no unit cotangent, no sign-byte input, every tensor stored).  The forward pass
-// must have kept every activation (run_forward(..., keep_all = true)).
-// None of the Fisher pass's fused backward launches (c3d / t3d / e3d / d3d) runs in a general sweep or in the fp64 sweep of
-// alq_hess_vecp: engine info 2, 8, 9, 11, 13 and 17 speak of the LAST backward pass, not of the last Fisher pass before it.
-static int run_backward_general(alq_model *m, int N, const DropSpec *drop, bool layer_sums = false) {
-    alq_ctx *ctx = m->ctx;
-    const int nl = (int)m->layers.size();
-    m->last.lsum = layer_sums ? 1 : 0;
-    m->last.bwd = {};
-    for (int i = m->dense ? nl - 2 : nl - 1; i >= 0; --i) {      // (a dense model: the head's own kernel has written the cotangent of its input)
-        Layer &ly = m->layers[i];
-        const bool isfc = ly.spec.type == ALQ_FC;
-        const bool prev_is_src = (i > 0 && m->layers[i - 1].out_is_skip_src && ly.spec.skip_src < 0);
-        if (drop && drop->on(i))       // out = act * keep / keep_prob: the cotangent takes the same factor
-            ALQ_TRY(k_dropout(ctx, isfc ? flat_view(ly.dout) : ly.dout, N, drop->first_sample, drop->seed, i, drop->keep_prob));
-        if (ly.spec.type == ALQ_POOL) {
-            if (i == 0) break;
-            bool fused = false;
-            ALQ_TRY(k_pool_bwd(ctx, ly.dout, ly.din, ly.argmax, ly.spec.k, ly.lo, N, prev_is_src ? 1 : 0, nullptr, nullptr, &fused, 1));
-            continue;
-        }
-        View dv = isfc ? flat_view(ly.dout) : ly.dout;
-        View av = isfc ? flat_view(ly.out) : ly.out;
-        if (layer_sums)     // ReLU-grad mask in place + this slot's layer sum against the layer's field (lsum.hip)
-            ALQ_TRY(k_lsum_sweep(ctx, dv, ly.spec.relu ? &av : nullptr, isfc, ly.ls_field, N,
-                                 m->ls_part + (size_t)ly.pidx * m->max_batch * m->ls_nslab_max, m->ls_nslab_max));
-        else
-            ALQ_TRY(k_mask_chansum(ctx, dv, ly.spec.relu ? &av : nullptr, ly.dsum, N));      // ReLU-grad mask in place (+ sums, unused)
-        if (ly.pidx == 0) break;      // the first parameterised layer: nothing below needs a cotangent
-        const int acc = prev_is_src ? 1 : 0;
-        if (isfc) {
-            ALQ_REQUIRE(!acc, ALQ_EUNSUPPORTED, "layer %d: fc consumer of a skip source", i);
-            if (ly.dense_fc_small) {
-                bool fused = false;
-                ALQ_TRY(k_fc_small_bwd(ctx, ly.dout.p, ly.spec.cout, ly.d_Wp, ly.F, N, ly.din.p, nullptr, nullptr, 0, &fused));
-            } else {
-                // no bound: ly.dout_bound belongs to the unit cotangent of a Fisher pass (run_backward_main), this
-                // cotangent is arbitrary (loss scale, dropout factors) - the bf16-triple path, whatever ran before
-                ALQ_TRY(gemm_launch(ctx, ly.bwd, ly.dout, flat_view(ly.din), nullptr, 0, 0, N, PROF_IGEMM_BWD, nullptr, nullptr, 0.f));
-            }
-        } else {
-            ALQ_TRY(gemm_launch(ctx, ly.bwd, ly.dout, ly.din, nullptr, 0, acc, N, PROF_IGEMM_BWD));
-        }
-    }
-    return ALQ_OK;
-}
-
-// Weight + bias gradients of every parameterised layer from the tensors a general backward pass left behind, written as
-// one flat vector per sample (or one for the batch): [W_0, b_0, W_1, b_1, ...] in the reference's variable order and
-// TF layouts (conv [k.., ci, co], conv_transpose [k.., co, ci], fc [out, in] with `in` in flatten order, NN.py:272-318).
-static int run_param_grads(alq_model *m, const float *d_x, int N, int sum_n, float *d_out, long long P) {
-    alq_ctx *ctx = m->ctx;
-    long long need = 0;
-    for (Layer &ly : m->layers) {
-        if (ly.pidx < 0 || ly.spec.type == ALQ_FC || ly.dense_head) continue;
-        const bool convt = ly.spec.type == ALQ_CONVT;
-        need = std::max(need, wgrad_partial_floats(convt ? ly.in : ly.dout, convt ? ly.dout : ly.in, ly.spec.k) * N);
-    }
-    if ((size_t)need > m->wg_partial_len) {
-        ALQ_TRY(m->dalloc(&m->wg_partial, (size_t)need));
-        m->wg_partial_len = (size_t)need;
-    }
-    long long off = 0;
-    const long long stride = sum_n ? 0 : P;
-    for (size_t i = 0; i < m->layers.size(); ++i) {
-        Layer &ly = m->layers[i];
-        if (ly.pidx < 0) continue;
-        View in = ly.in;
-        if (i == 0) in.p = const_cast<float *>(d_x);
-        const int one[3] = {1, 1, 1};
-        if (ly.dense_head) {
-            // written by the head's backward launch (dense_backward_head)
-        } else if (ly.spec.type == ALQ_CONV) {
-            ALQ_TRY(k_wgrad(ctx, ly.dout, in, ly.spec.k, one, ly.lo, N, sum_n, m->wg_partial, d_out + off, stride));
-            ALQ_TRY(k_bgrad(ctx, ly.dout, N, sum_n, d_out + off + ly.w_elems, stride));
-        } else if (ly.spec.type == ALQ_CONVT) {
-            ALQ_TRY(k_wgrad(ctx, in, ly.dout, ly.spec.k, ly.spec.s, ly.lo, N, sum_n, m->wg_partial, d_out + off, stride));
-            ALQ_TRY(k_bgrad(ctx, ly.dout, N, sum_n, d_out + off + ly.w_elems, stride));
-        } else {
-            ALQ_TRY(k_fc_wgrad(ctx, ly.dout.p, in, ly.spec.cout, N, sum_n, d_out + off, stride));
-            ALQ_TRY(k_bgrad(ctx, flat_view(ly.dout), N, sum_n, d_out + off + ly.w_elems, stride));
-        }
-        off += ly.w_elems + ly.b_elems;
-    }
-    ALQ_REQUIRE(off == P, ALQ_EINVAL, "parameter count mismatch");
-    return ALQ_OK;
-}
-
-// Per-sample squared norms of every parameterised layer's weight and bias gradient from the tensors a general backward pass
-// left behind (the views run_param_grads reads, split-concat inputs included): d_sq [N, 2L], [n][2t] = ||dW_t||^2,
-// [n][2t + 1] = ||db_t||^2.  Nothing of the size of the parameters is written (gnorm.hip).
-static int run_grad_sqnorms(alq_model *m, const float *d_x, int N, double *d_sq) {
-    alq_ctx *ctx = m->ctx;
-    const int one[3] = {1, 1, 1};
-    long long need = 0;
-    for (Layer &ly : m->layers) {
-        if (ly.pidx < 0 || ly.spec.type == ALQ_FC) continue;
-        const bool convt = ly.spec.type == ALQ_CONVT;
-        need = std::max(need, gnorm_partials(convt ? ly.in : ly.dout, convt ? ly.dout : ly.in, ly.spec.k, convt ? ly.spec.s : one,
-                                             ly.lo) * N);
-    }
-    if ((size_t)need > m->gn_partial_len) {
-        ALQ_TRY(m->dalloc(&m->gn_partial, (size_t)need));
-        m->gn_partial_len = (size_t)need;
-    }
-    const int ld = 2 * m->L;
-    for (size_t i = 0; i < m->layers.size(); ++i) {
-        Layer &ly = m->layers[i];
-        if (ly.pidx < 0) continue;
-        View in = ly.in;
-        if (i == 0) in.p = const_cast<float *>(d_x);
-        const int col = 2 * ly.pidx;
-        if (ly.spec.type == ALQ_CONV) {
-            ALQ_TRY(k_gnorm_weight(ctx, ly.dout, in, ly.spec.k, one, ly.lo, N, m->gn_partial, d_sq, ld, col));
-            ALQ_TRY(k_gnorm_bias(ctx, ly.dout, N, d_sq, ld, col + 1));
-        } else if (ly.spec.type == ALQ_CONVT) {
-            ALQ_TRY(k_gnorm_weight(ctx, in, ly.dout, ly.spec.k, ly.spec.s, ly.lo, N, m->gn_partial, d_sq, ld, col));
-            ALQ_TRY(k_gnorm_bias(ctx, ly.dout, N, d_sq, ld, col + 1));
-        } else {
-            ALQ_TRY(k_gnorm_fc(ctx, ly.dout.p, ly.spec.cout, in, N, d_sq, ld, col));
-        }
-    }
-    return ALQ_OK;
-}
-
-// Squared per-sample gradients summed over the samples, from the tensors a general backward pass left behind (the views
-// run_param_grads reads): d_acc [P] += in the flat order [W_0, b_0, W_1, b_1, ...] and TF layouts of run_param_grads.  Nothing of
-// the size N x P is written (dfisher.hip).
-static int run_diag_fisher(alq_model *m, const float *d_x, int N, double *d_acc) {
-    alq_ctx *ctx = m->ctx;
-    const int one[3] = {1, 1, 1};
-    if (!m->df_scratch) {
-        long long need = 1;
-        for (Layer &ly : m->layers) {
-            if (ly.pidx < 0) continue;
-            need = std::max(need, (long long)m->max_batch * ly.spec.cout);
-            if (ly.spec.type == ALQ_FC) continue;
-            const bool convt = ly.spec.type == ALQ_CONVT;
-            need = std::max(need, dfisher_weight_scratch(convt ? ly.in : ly.dout, convt ? ly.dout : ly.in, ly.spec.k,
-                                                         convt ? ly.spec.s : one, ly.lo, m->max_batch));
-        }
-        ALQ_TRY(m->dalloc(&m->df_scratch, (size_t)need));
-    }
-    long long off = 0;
-    for (size_t i = 0; i < m->layers.size(); ++i) {
-        Layer &ly = m->layers[i];
-        if (ly.pidx < 0) continue;
-        View in = ly.in;
-        if (i == 0) in.p = const_cast<float *>(d_x);
-        double *aw = d_acc + off, *ab = aw + ly.w_elems;
-        if (ly.spec.type == ALQ_CONV) {
-            ALQ_TRY(k_dfisher_weight(ctx, ly.dout, in, ly.spec.k, one, ly.lo, N, m->df_scratch, aw));
-            ALQ_TRY(k_dfisher_bias(ctx, ly.dout, N, m->df_scratch, ab));
-        } else if (ly.spec.type == ALQ_CONVT) {
-            ALQ_TRY(k_dfisher_weight(ctx, in, ly.dout, ly.spec.k, ly.spec.s, ly.lo, N, m->df_scratch, aw));
-            ALQ_TRY(k_dfisher_bias(ctx, ly.dout, N, m->df_scratch, ab));
-        } else {
-            ALQ_TRY(k_dfisher_fc(ctx, ly.dout.p, ly.spec.cout, in, N, m->df_scratch, aw, ab));
-        }
-        off += ly.w_elems + ly.b_elems;
-    }
-    ALQ_REQUIRE(off == alq_model_num_params(m), ALQ_EINVAL, "parameter count mismatch");
-    return ALQ_OK;
-}
-
-static int make_drop(const alq_model *m, float keep_prob, uint64_t seed, int64_t first_sample, const int32_t *h_layers, int n_layers,
-                     DropSpec *d) {
+int make_drop(const alq_model *m, float keep_prob, uint64_t seed, int64_t first_sample, const int32_t *h_layers, int n_layers,
+              DropSpec *d) {
     ALQ_REQUIRE(keep_prob > 0.f && keep_prob <= 1.f, ALQ_EINVAL, "keep_prob %g outside (0, 1]", (double)keep_prob);
     ALQ_REQUIRE(n_layers == 0 || h_layers, ALQ_EINVAL, "dropout layer list missing");
     d->keep_prob = keep_prob; d->seed = seed; d->first_sample = first_sample; d->layers = 0;
@@ -1509,208 +1276,10 @@ static int make_drop(const alq_model *m, float keep_prob, uint64_t seed, int64_t
     return ALQ_OK;
 }
 
-// ------------------------------------------------------------------------------------------ Hessian-vector product (hvp.hip)
-// First call: the tangent tensors of every layer, the slab partials of the weight products and the TF-layout fp32 weights;
-// later calls: only the weights of layers that were set since.
-static int hvp_prepare(alq_model *m) {
-    alq_ctx *ctx = m->ctx;
-    const size_t NB = (size_t)m->max_batch;
-    if (!m->hv_ready) {
-        long long Mmax = 1;
-        for (Layer &ly : m->layers) {
-            ALQ_REQUIRE(ly.spec.type != ALQ_POOL || (ly.spec.skip_src < 0 && &ly != &m->layers[0]), ALQ_EUNSUPPORTED,
-                        "alq_hess_vecp: pool layer first or behind a concat");
-            const size_t el = NB * (size_t)ly.out.vox() * ly.out.C;
-            ALQ_TRY(m->dalloc(&ly.hv_A, el));
-            ALQ_TRY(m->dalloc(&ly.hv_D, el));
-            ALQ_TRY(m->dalloc(&ly.hv_Ra, el));
-            ALQ_TRY(m->dalloc(&ly.hv_Rd, el));
-            if (ly.pidx >= 0) {
-                ALQ_TRY(m->dalloc(&ly.hv_W, (size_t)ly.w_elems));
-                if (ly.spec.type != ALQ_FC) Mmax = std::max<long long>(Mmax, ly.w_elems);
-            }
-        }
-        ALQ_TRY(m->dalloc(&m->hv_part, (size_t)hvp_wgrad_partial_doubles(Mmax)));
-        ALQ_TRY(m->dalloc(&m->hv_p64, NB * (size_t)m->nclass));
-        m->hv_ready = true;
-    }
-    for (Layer &ly : m->layers) {
-        if (ly.pidx < 0) continue;
-        ALQ_REQUIRE(ly.weights_set && ly.hv_src != 0, ALQ_EINVAL, "alq_hess_vecp: weights of parameterised layer %d not set", ly.pidx);
-        if (!ly.hv_stale) continue;
-        if (ly.hv_src == 1) {
-            ALQ_TRY(upload_release(m, &ly.hv_W, &ly.hv_hW));      // hv_W holds them until the next set_weights
-        } else {
-            const float *res = ly.hv_src == 2 ? ly.d_Wres : ly.d_Wp;      // both [o][f_mem]
-            ALQ_REQUIRE(res != nullptr, ALQ_EINVAL, "alq_hess_vecp: layer %d has no resident weights", ly.pidx);
-            ALQ_TRY(k_hvp_unpermute(ctx, res, ly.hv_W, ly.spec.cout, ly.in));
-        }
-        ly.hv_stale = false;
-    }
-    return ALQ_OK;
-}
-
-// Everything behind the forward pass (which fixed the ReLU and pool decisions: Layer::out's signs, the arg-max fields), in fp64 on
-// the call's own tensors: activations, posteriors and first-order cotangents, the tangent pass, the second-order term at the
-// logits, the sweep of the tangent cotangent and the products (hvp.hip).
-static int run_hess_vecp(alq_model *m, const float *d_x, int N, const int32_t *d_labels, float loss_scale, const float *d_v,
-                         const uint8_t *h_layer_on, int accumulate, double *d_hv, double *d_loss) {
-    alq_ctx *ctx = m->ctx;
-    const int nl = (int)m->layers.size();
-    const int one[3] = {1, 1, 1};
-    std::vector<long long> off(nl, 0);
-    {
-        long long o = 0;
-        for (int i = 0; i < nl; ++i) {
-            off[i] = o;
-            if (m->layers[i].pidx >= 0) o += m->layers[i].w_elems + m->layers[i].b_elems;
-        }
-    }
-    auto on = [&](const Layer &ly) { return !h_layer_on || h_layer_on[ly.pidx] != 0; };
-    // the input of layer i out of the per-layer tensors `which`: the network input itself (fp32) for the first layer's
-    // activations and none for its tangent, two producers behind a 'con' skip
-    auto src_in = [&](int i, double *Layer::*which, bool tangent) {
-        const Layer &ly = m->layers[i];
-        if (i == 0) {
-            if (tangent) return HSrc();
-            View in = ly.in;
-            in.p = const_cast<float *>(d_x);
-            return hsrc_view(in);
-        }
-        if (ly.spec.skip_src >= 0) {
-            const Layer &sl = m->layers[ly.spec.skip_src], &pl = m->layers[i - 1];
-            return hsrc_dense(sl.*which, sl.out.C, pl.*which, pl.out.C);
-        }
-        return hsrc_dense(m->layers[i - 1].*which, ly.in.C);
-    };
-    // one forward walk: tangent = false: activations (bias, no v); true: tangents (the v term of switched-on layers)
-    auto forward = [&](bool tangent) -> int {
-        double *Layer::*out = tangent ? &Layer::hv_Ra : &Layer::hv_A;
-        for (int i = 0; i < nl; ++i) {
-            Layer &ly = m->layers[i];
-            if (ly.spec.type == ALQ_POOL) {
-                ALQ_TRY(k_hvp_pool_fwd(ctx, m->layers[i - 1].*out, ly.argmax, ly.*out, ly.in, ly.out, ly.spec.k, ly.lo, N));
-                continue;
-            }
-            const bool lon = tangent && on(ly);
-            const float *V = lon ? d_v + off[i] : nullptr;
-            const float *cb = tangent ? (lon ? d_v + off[i] + ly.w_elems : nullptr) : ly.d_bias;
-            const HSrc a = lon ? src_in(i, &Layer::hv_A, false) : HSrc(), x = src_in(i, out, tangent);
-            if (ly.spec.type == ALQ_FC) {
-                ALQ_TRY(k_hvp_fc_fwd(ctx, a, V, x, ly.hv_W, cb, ly.spec.relu ? hsrc_view(ly.out) : HSrc(), ly.*out, ly.in, ly.spec.cout, N));
-            } else {
-                HGeo g;
-                ALQ_TRY(hvp_geometry(ly.spec.type, 0, ly.in, ly.out, ly.spec.k, ly.spec.s, ly.lo, &g));
-                HDst dst;
-                dst.pa = ly.*out; dst.Ca = ly.out.C;
-                ALQ_TRY(k_hvp_contract(ctx, a, V, x, ly.hv_W, cb, ly.spec.relu ? hsrc_view(ly.out) : HSrc(), dst, g, N));
-            }
-        }
-        return ALQ_OK;
-    };
-    // one backward walk over the tensors `X` (the layers' output cotangents; the head's is filled): second = false: the
-    // first-order cotangents hv_D; true: their tangents hv_Rd (+ the delta . V term of switched-on layers) and the products
-    auto backward = [&](bool second) -> int {
-        double *Layer::*X = second ? &Layer::hv_Rd : &Layer::hv_D;
-        std::vector<char> written(nl, 0);
-        written[nl - 1] = 1;
-        for (int i = nl - 1; i >= 0; --i) {
-            Layer &ly = m->layers[i];
-            ALQ_REQUIRE(written[i], ALQ_EUNSUPPORTED, "alq_hess_vecp: layer %d has no consumer", i);
-            if (ly.spec.type == ALQ_POOL) {
-                ALQ_TRY(k_hvp_pool_bwd(ctx, ly.*X, ly.argmax, m->layers[i - 1].*X, written[i - 1], ly.in, ly.out, ly.spec.k, ly.lo, N));
-                written[i - 1] = 1;
-                continue;
-            }
-            const bool isfc = ly.spec.type == ALQ_FC;
-            const long long orows = (long long)N * ly.out.vox();
-            if (ly.spec.relu) ALQ_TRY(k_hvp_mask(ctx, ly.*X, ly.out.C, hsrc_view(ly.out), orows));
-            const bool lon = second && on(ly);
-            if (second) {
-                double *hv = d_hv + off[i];
-                if (lon) {
-                    const HSrc a = src_in(i, &Layer::hv_A, false), Ra = src_in(i, &Layer::hv_Ra, true);
-                    const HSrc Rd = hsrc_dense(ly.hv_Rd, ly.out.C), dl = i > 0 ? hsrc_dense(ly.hv_D, ly.out.C) : HSrc();
-                    if (isfc) {
-                        ALQ_TRY(k_hvp_fc_wgrad(ctx, ly.hv_Rd, a, ly.hv_D, Ra, ly.in, ly.spec.cout, N, accumulate, hv));
-                    } else if (ly.spec.type == ALQ_CONV) {
-                        ALQ_TRY(k_hvp_wgrad(ctx, Rd, a, dl, Ra, ly.out.C, ly.in.C, ly.out, ly.in, ly.spec.k, one, ly.lo, N, m->hv_part, accumulate,
-                                            hv));
-                    } else {
-                        ALQ_TRY(k_hvp_wgrad(ctx, a, Rd, Ra, dl, ly.in.C, ly.out.C, ly.in, ly.out, ly.spec.k, ly.spec.s, ly.lo, N, m->hv_part,
-                                            accumulate, hv));
-                    }
-                    ALQ_TRY(k_hvp_bias(ctx, ly.hv_Rd, ly.out.C, orows, accumulate, hv + ly.w_elems));
-                } else if (!accumulate) {
-                    ALQ_HIP(hipMemsetAsync(hv, 0, (size_t)(ly.w_elems + ly.b_elems) * sizeof(double), ctx->stream));
-                }
-            }
-            if (i == 0) break;
-            HDst dst;      // the input's cotangent, routed to the producer(s) of the input
-            if (ly.spec.skip_src >= 0) {
-                const int s = ly.spec.skip_src;
-                dst.pa = m->layers[s].*X; dst.Ca = m->layers[s].out.C; dst.acca = written[s];
-                dst.pb = m->layers[i - 1].*X; dst.Cb = m->layers[i - 1].out.C; dst.accb = written[i - 1];
-                written[s] = 1;
-            } else {
-                dst.pa = m->layers[i - 1].*X; dst.Ca = ly.in.C; dst.acca = written[i - 1];
-            }
-            written[i - 1] = 1;
-            const float *V = lon ? d_v + off[i] : nullptr;
-            if (isfc) {
-                ALQ_TRY(k_hvp_fc_bwd(ctx, ly.hv_D, V, ly.*X, ly.hv_W, dst, ly.in, ly.spec.cout, N));
-            } else {
-                HGeo g;
-                ALQ_TRY(hvp_geometry(ly.spec.type, 1, ly.in, ly.out, ly.spec.k, ly.spec.s, ly.lo, &g));
-                ALQ_TRY(k_hvp_contract(ctx, lon ? hsrc_dense(ly.hv_D, ly.out.C) : HSrc(), V, hsrc_dense(ly.*X, ly.out.C), ly.hv_W, nullptr, HSrc(),
-                                       dst, g, N));
-            }
-        }
-        return ALQ_OK;
-    };
-    Layer &head = m->layers[nl - 1];
-    ALQ_REQUIRE(!head.spec.relu, ALQ_EUNSUPPORTED, "alq_hess_vecp: ReLU on the head");
-    ALQ_TRY(forward(false));
-    ALQ_TRY(k_hvp_softmax64(ctx, head.hv_A, d_labels, m->nclass, N, loss_scale, m->post, m->hv_p64, head.hv_D));
-    if (d_loss) ALQ_TRY(k_hvp_loss(ctx, m->post, m->nclass, N, d_labels, loss_scale, d_loss));
-    ALQ_TRY(backward(false));
-    ALQ_TRY(forward(true));
-    ALQ_TRY(k_hvp_softmax2(ctx, m->hv_p64, head.hv_Ra, d_labels, m->nclass, N, loss_scale, head.hv_Rd));
-    return backward(true);
-}
-
-// ---- fully-convolutional models: the head's launches and the refusals of the fc-only entry points
-#define ALQ_REFUSE_DENSE(m, who)                                                                                                \
-    ALQ_REQUIRE(!(m) || !(m)->dense, ALQ_EUNSUPPORTED, "%s: not defined for a fully-convolutional model (1x1 conv head)", who)
-
-// posteriors [c, N V] (and predictions, and the logits into the head's output buffer) from the head's input, after run_forward
-static int dense_forward_head(alq_model *m, const float *d_x, int N, float *d_post, int64_t *d_pred, bool want_logits) {
-    Layer &h = m->layers.back();
-    const float *x = m->layers.size() == 1 ? d_x : h.in.p;
-    return k_dense_head_fwd(m->ctx, x, (long long)N * m->V, h.in.C, m->nclass, h.d_W32, h.d_bias, d_post ? d_post : m->post, d_pred,
-                            want_logits ? h.out.p : nullptr);
-}
-
-// the head's cotangent rows (m->dlogits) -> the cotangent of its input and its own slice [dW, db] of the flat gradient
-static int dense_backward_head(alq_model *m, const float *d_x, int N, float *d_grads, long long P) {
-    Layer &h = m->layers.back();
-    const float *x = m->layers.size() == 1 ? d_x : h.in.p;
-    return k_dense_head_bwd(m->ctx, m->dlogits, x, (long long)N * m->V, h.in.C, m->nclass, h.d_W32, h.pidx == 0 ? nullptr : h.din.p, 0,
-                            m->dh_part, d_grads + (P - h.w_elems - h.b_elems));
-}
-
 // =========================================================================================== C ABI
 extern "C" {
 
 int alq_model_out_voxels(const alq_model *m) { return m ? (int)m->V : ALQ_EINVAL; }
-
-int64_t alq_model_num_params(const alq_model *m) {
-    if (!m) return ALQ_EINVAL;
-    int64_t p = 0;
-    for (const Layer &ly : m->layers)
-        if (ly.pidx >= 0) p += ly.w_elems + ly.b_elems;
-    return p;
-}
 
 int alq_forward_dropout(alq_model *m, const float *d_x, int N, float keep_prob, uint64_t seed, int64_t first_sample,
                         const int32_t *h_drop_layers, int n_drop_layers, float *d_post, int64_t *d_pred) {
@@ -1724,327 +1293,6 @@ int alq_forward_dropout(alq_model *m, const float *d_x, int N, float keep_prob, 
     ALQ_TRY(run_forward(m, d_x, N, false, /*keep_all=*/true, &ds));
     if (m->dense) return dense_forward_head(m, d_x, N, d_post, d_pred, false);
     ALQ_TRY(k_softmax(m->ctx, m->logits, m->nclass, N, d_post ? d_post : m->post, d_pred));
-    return ALQ_OK;
-}
-
-int alq_param_grads(alq_model *m, const float *d_x, int N, int mode, int cls, const int32_t *d_labels, float loss_scale,
-                    float keep_prob, uint64_t seed, int64_t first_sample, const int32_t *h_drop_layers, int n_drop_layers,
-                    int per_sample, float *d_grads, float *d_post, double *d_loss) {
-    ALQ_REFUSE_DENSE(m, "alq_param_grads");
-    ALQ_REQUIRE(m && d_x && d_grads, ALQ_EINVAL, "alq_param_grads: null argument");
-    ALQ_REQUIRE(N >= 1 && N <= m->max_batch, ALQ_EINVAL, "alq_param_grads: N=%d outside [1, max_batch=%d]", N, m->max_batch);
-    ALQ_REQUIRE(mode == 0 || (mode == 1 && d_labels), ALQ_EINVAL, "alq_param_grads: mode %d / labels", mode);
-    ALQ_REQUIRE(mode != 0 || (cls >= 0 && cls < m->nclass), ALQ_EINVAL, "alq_param_grads: class %d", cls);
-    ALQ_HIP(hipSetDevice(m->ctx->device));
-    DropSpec ds;
-    ALQ_TRY(make_drop(m, keep_prob, seed, first_sample, h_drop_layers, n_drop_layers, &ds));
-    ALQ_TRY(prepare_call(m, /*fisher=*/false));
-    ALQ_TRY(run_forward(m, d_x, N, false, /*keep_all=*/true, &ds));
-    float *post = d_post ? d_post : m->post;
-    ALQ_TRY(k_softmax(m->ctx, m->logits, m->nclass, N, post, nullptr));
-    if (d_loss && mode == 1) ALQ_TRY(k_ce_loss(m->ctx, post, m->nclass, N, d_labels, d_loss));
-    ALQ_TRY(k_logit_cotangent(m->ctx, post, m->nclass, N, mode, cls, d_labels, loss_scale, m->dlogits));
-    ALQ_TRY(run_backward_general(m, N, &ds));
-    return run_param_grads(m, d_x, N, per_sample ? 0 : 1, d_grads, alq_model_num_params(m));
-}
-
-int alq_grad_sqnorms(alq_model *m, const float *d_x, int N, int cls, const int32_t *d_cls, float *d_post, double *d_sq) {
-    ALQ_REFUSE_DENSE(m, "alq_grad_sqnorms");
-    ALQ_REQUIRE(m && d_x && d_sq, ALQ_EINVAL, "alq_grad_sqnorms: null argument");
-    ALQ_REQUIRE(N >= 1 && N <= m->max_batch, ALQ_EINVAL, "alq_grad_sqnorms: N=%d outside [1, max_batch=%d]", N, m->max_batch);
-    ALQ_REQUIRE(d_cls || (cls == -1 && m->nclass == 2) || (cls >= 0 && cls < m->nclass), ALQ_EINVAL,
-                "alq_grad_sqnorms: class %d (-1 needs a two-class net, found %d classes)", cls, m->nclass);
-    ALQ_HIP(hipSetDevice(m->ctx->device));
-    DropSpec ds;
-    ALQ_TRY(make_drop(m, 1.f, 0, 0, nullptr, 0, &ds));
-    ALQ_TRY(prepare_call(m, /*fisher=*/false));
-    ALQ_TRY(run_forward(m, d_x, N, false, /*keep_all=*/true, &ds));
-    float *post = d_post ? d_post : m->post;
-    ALQ_TRY(k_softmax(m->ctx, m->logits, m->nclass, N, post, nullptr));
-    const int mode = d_cls ? 3 : (cls < 0 ? 2 : 0);
-    ALQ_TRY(k_logit_cotangent(m->ctx, post, m->nclass, N, mode, cls, d_cls, 1.f, m->dlogits));
-    ALQ_TRY(run_backward_general(m, N, &ds));
-    return run_grad_sqnorms(m, d_x, N, d_sq);
-}
-
-int alq_class_layer_sums(alq_model *m, const float *d_x, int N, int J, const int32_t *d_cls, float *d_post, double *d_g) {
-    ALQ_REFUSE_DENSE(m, "alq_class_layer_sums");
-    ALQ_REQUIRE(m && d_x && d_cls && d_g, ALQ_EINVAL, "alq_class_layer_sums: null argument");
-    ALQ_REQUIRE(N >= 1 && N <= m->max_batch, ALQ_EINVAL, "alq_class_layer_sums: N=%d outside [1, max_batch=%d]", N, m->max_batch);
-    ALQ_REQUIRE(J >= 1 && J <= 64, ALQ_EINVAL, "alq_class_layer_sums: %d class slots outside [1, 64]", J);
-    ALQ_REQUIRE(m->nclass >= 2 && m->nclass <= 64 && m->L <= 64, ALQ_EUNSUPPORTED, "alq_class_layer_sums: %d classes, %d layers",
-                m->nclass, m->L);
-    alq_ctx *ctx = m->ctx;
-    ALQ_HIP(hipSetDevice(ctx->device));
-    // the class slots live on the device: one flag read (a stream synchronisation) before anything is written
-    int *d_bad = reinterpret_cast<int *>(static_cast<char *>(ctx->param_block) + ALQ_PARAM_FLAG_OFFSET);
-    int bad = 0;
-    ALQ_HIP(hipMemsetAsync(d_bad, 0, sizeof(int), ctx->stream));
-    ALQ_TRY(k_lsum_check_classes(ctx, d_cls, J * N, m->nclass, d_bad));
-    ALQ_HIP(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    ALQ_HIP(hipStreamSynchronize(ctx->stream));
-    ALQ_REQUIRE(!bad, ALQ_EINVAL, "alq_class_layer_sums: a class outside [0, %d)", m->nclass);
-    if (!m->ls_part) {
-        m->ls_nslab.assign(m->L, 1);
-        m->ls_nslab_max = 1;
-        for (Layer &ly : m->layers) {
-            if (ly.pidx < 0) continue;
-            const bool isfc = ly.spec.type == ALQ_FC;
-            m->ls_nslab[ly.pidx] = lsum_slabs(ly.dout, isfc, nullptr);
-            m->ls_nslab_max = std::max(m->ls_nslab_max, m->ls_nslab[ly.pidx]);
-            ALQ_TRY(m->dalloc(&ly.ls_field, (size_t)m->max_batch * (isfc ? 1 : (size_t)ly.out.vox())));
-        }
-        ALQ_TRY(m->dalloc(&m->ls_part, (size_t)m->L * m->max_batch * m->ls_nslab_max));
-    }
-    DropSpec ds;
-    ALQ_TRY(make_drop(m, 1.f, 0, 0, nullptr, 0, &ds));
-    ALQ_TRY(prepare_call(m, /*fisher=*/false));
-    ALQ_TRY(run_forward(m, d_x, N, false, /*keep_all=*/true, &ds));
-    float *post = d_post ? d_post : m->post;
-    ALQ_TRY(k_softmax(ctx, m->logits, m->nclass, N, post, nullptr));
-    for (size_t i = 0; i < m->layers.size(); ++i) {      // the fields: once per call, whatever J
-        Layer &ly = m->layers[i];
-        if (ly.pidx < 0) continue;
-        View in = ly.in;
-        if (i == 0) in.p = const_cast<float *>(d_x);
-        ALQ_TRY(k_lsum_field(ctx, in, ly.out, ly.spec.k, ly.spec.s, ly.lo, ly.spec.type, N, ly.ls_field));
-    }
-    for (int j = 0; j < J; ++j) {
-        ALQ_TRY(k_logit_cotangent(ctx, post, m->nclass, N, 3, 0, d_cls + (size_t)j * N, 1.f, m->dlogits));
-        ALQ_TRY(run_backward_general(m, N, &ds, /*layer_sums=*/true));
-        ALQ_TRY(k_lsum_finish(ctx, m->ls_part, m->ls_nslab.data(), m->ls_nslab_max, m->max_batch, m->sizes, N, m->L, J, j, d_g));
-    }
-    return ALQ_OK;
-}
-
-int alq_diag_fisher(alq_model *m, const float *d_x, int N, const int32_t *d_cls, double *d_acc) {
-    ALQ_REFUSE_DENSE(m, "alq_diag_fisher");
-    ALQ_REQUIRE(m && d_x && d_cls && d_acc, ALQ_EINVAL, "alq_diag_fisher: null argument");
-    ALQ_REQUIRE(N >= 1 && N <= m->max_batch, ALQ_EINVAL, "alq_diag_fisher: N=%d outside [1, max_batch=%d]", N, m->max_batch);
-    alq_ctx *ctx = m->ctx;
-    ALQ_HIP(hipSetDevice(ctx->device));
-    // the classes live on the device: one flag read (a stream synchronisation) before anything is written
-    int *d_bad = reinterpret_cast<int *>(static_cast<char *>(ctx->param_block) + ALQ_PARAM_FLAG_OFFSET);
-    int bad = 0;
-    ALQ_HIP(hipMemsetAsync(d_bad, 0, sizeof(int), ctx->stream));
-    ALQ_TRY(k_lsum_check_classes(ctx, d_cls, N, m->nclass, d_bad));
-    ALQ_HIP(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    ALQ_HIP(hipStreamSynchronize(ctx->stream));
-    ALQ_REQUIRE(!bad, ALQ_EINVAL, "alq_diag_fisher: a class outside [0, %d)", m->nclass);
-    DropSpec ds;
-    ALQ_TRY(make_drop(m, 1.f, 0, 0, nullptr, 0, &ds));
-    ALQ_TRY(prepare_call(m, /*fisher=*/false));
-    ALQ_TRY(run_forward(m, d_x, N, false, /*keep_all=*/true, &ds));
-    ALQ_TRY(k_softmax(ctx, m->logits, m->nclass, N, m->post, nullptr));
-    ALQ_TRY(k_logit_cotangent(ctx, m->post, m->nclass, N, 3, 0, d_cls, 1.f, m->dlogits));
-    ALQ_TRY(run_backward_general(m, N, &ds));
-    return run_diag_fisher(m, d_x, N, d_acc);
-}
-
-size_t alq_topk_mask_work_bytes(int64_t n) { return topk_mask_work_bytes_impl(n); }
-
-int alq_topk_mask(alq_ctx *ctx, const double *d_v, int64_t n, int64_t k, float *d_mask, void *d_work) {
-    ALQ_REQUIRE(ctx && (n == 0 || (d_v && d_mask && d_work)), ALQ_EINVAL, "alq_topk_mask: null argument");
-    ALQ_HIP(hipSetDevice(ctx->device));
-    return topk_mask_impl(ctx, d_v, n, k, d_mask, d_work);
-}
-
-int alq_threshold_mask(alq_ctx *ctx, const double *d_v, int64_t n, double thr, float *d_mask) {
-    ALQ_REQUIRE(ctx && n >= 0 && (n == 0 || (d_v && d_mask)), ALQ_EINVAL, "alq_threshold_mask: bad argument");
-    ALQ_HIP(hipSetDevice(ctx->device));
-    return threshold_mask_impl(ctx, d_v, n, thr, d_mask);
-}
-
-int alq_hess_vecp(alq_model *m, const float *d_x, int N, const int32_t *d_labels, float loss_scale, const float *d_v,
-                  const uint8_t *h_layer_on, int accumulate, double *d_hv, double *d_loss) {
-    ALQ_REFUSE_DENSE(m, "alq_hess_vecp");
-    ALQ_REQUIRE(m && d_x && d_labels && d_v && d_hv, ALQ_EINVAL, "alq_hess_vecp: null argument");
-    ALQ_REQUIRE(N >= 1 && N <= m->max_batch, ALQ_EINVAL, "alq_hess_vecp: N=%d outside [1, max_batch=%d]", N, m->max_batch);
-    ALQ_HIP(hipSetDevice(m->ctx->device));
-    ALQ_TRY(hvp_prepare(m));
-    DropSpec ds;
-    ALQ_TRY(make_drop(m, 1.f, 0, 0, nullptr, 0, &ds));
-    ALQ_TRY(prepare_call(m, /*fisher=*/false));
-    ALQ_TRY(run_forward(m, d_x, N, false, /*keep_all=*/true, &ds));
-    m->last.bwd = {};      // the fp64 sweep runs none of the Fisher pass's fused backward launches
-    return run_hess_vecp(m, d_x, N, d_labels, loss_scale, d_v, h_layer_on, accumulate, d_hv, d_loss);
-}
-
-int alq_sgd_step(alq_ctx *ctx, float *d_theta, const float *d_grad, int64_t n, float lr) {
-    ALQ_REQUIRE(ctx && (n == 0 || (d_theta && d_grad)) && n >= 0, ALQ_EINVAL, "alq_sgd_step: bad argument");
-    ALQ_HIP(hipSetDevice(ctx->device));
-    return n ? k_sgd(ctx, d_theta, d_grad, n, lr) : ALQ_OK;
-}
-
-int alq_adam_step(alq_ctx *ctx, float *d_theta, const float *d_grad, float *d_m, float *d_v, int64_t n, float lr, float beta1,
-                  float beta2, float eps, int64_t t) {
-    ALQ_REQUIRE(ctx && (n == 0 || (d_theta && d_grad && d_m && d_v)) && n >= 0 && t >= 1, ALQ_EINVAL, "alq_adam_step: bad argument");
-    ALQ_HIP(hipSetDevice(ctx->device));
-    const double lr_t = (double)lr * std::sqrt(1.0 - std::pow((double)beta2, (double)t)) / (1.0 - std::pow((double)beta1, (double)t));
-    return n ? k_adam(ctx, d_theta, d_grad, d_m, d_v, n, (float)lr_t, beta1, beta2, eps) : ALQ_OK;
-}
-
-static int loss_check(const char *who, const float *d_post_or_x, int c, const int32_t *d_labels, const alq_loss_t *loss) {
-    ALQ_REQUIRE(d_post_or_x && loss, ALQ_EINVAL, "%s: null argument", who);
-    ALQ_REQUIRE(c >= 1, ALQ_EINVAL, "%s: %d classes", who, c);
-    ALQ_REQUIRE(loss->kind == ALQ_LOSS_CE || loss->kind == ALQ_LOSS_CE_SOFT || loss->kind == ALQ_LOSS_GCE, ALQ_EINVAL,
-                "%s: loss kind %d", who, (int)loss->kind);
-    ALQ_REQUIRE(loss->kind != ALQ_LOSS_CE || d_labels, ALQ_EINVAL, "%s: cross-entropy needs labels", who);
-    ALQ_REQUIRE(loss->kind == ALQ_LOSS_CE || loss->d_targets, ALQ_EINVAL, "%s: CE_softclasses / GCE need targets", who);
-    ALQ_REQUIRE(loss->kind != ALQ_LOSS_GCE || loss->gce_q != 0.f, ALQ_EINVAL, "%s: GCE with q = 0", who);
-    ALQ_REQUIRE(!loss->d_old_logits || loss->lwf_T > 0.f, ALQ_EINVAL, "%s: LwF temperature %g", who, (double)loss->lwf_T);
-    return ALQ_OK;
-}
-
-int alq_loss_stats(alq_ctx *ctx, const float *d_post, int c, int N, const int32_t *d_labels, const alq_loss_t *loss, double *d_stats3) {
-    ALQ_REQUIRE(ctx && d_stats3, ALQ_EINVAL, "alq_loss_stats: null argument");
-    ALQ_REQUIRE(N >= 1, ALQ_EINVAL, "alq_loss_stats: N=%d", N);
-    ALQ_TRY(loss_check("alq_loss_stats", d_post, c, d_labels, loss));
-    ALQ_HIP(hipSetDevice(ctx->device));
-    return k_loss_cotangent(ctx, d_post, c, N, d_labels, loss, 1.f, 1.f, nullptr, d_stats3);
-}
-
-int alq_param_grads_loss(alq_model *m, const float *d_x, int N, const int32_t *d_labels, const alq_loss_t *loss, float loss_scale,
-                         float lwf_scale, float keep_prob, uint64_t seed, int64_t first_sample, const int32_t *h_drop_layers,
-                         int n_drop_layers, float *d_grads, float *d_post, double *d_stats3) {
-    ALQ_REQUIRE(m && d_grads, ALQ_EINVAL, "alq_param_grads_loss: null argument");
-    ALQ_REQUIRE(N >= 1 && N <= m->max_batch, ALQ_EINVAL, "alq_param_grads_loss: N=%d outside [1, max_batch=%d]", N, m->max_batch);
-    ALQ_TRY(loss_check("alq_param_grads_loss", d_x, m->nclass, d_labels, loss));
-    ALQ_HIP(hipSetDevice(m->ctx->device));
-    DropSpec ds;
-    ALQ_TRY(make_drop(m, keep_prob, seed, first_sample, h_drop_layers, n_drop_layers, &ds));
-    ALQ_TRY(prepare_call(m, /*fisher=*/false));
-    ALQ_TRY(run_forward(m, d_x, N, false, /*keep_all=*/true, &ds));
-    float *post = d_post ? d_post : m->post;
-    if (m->dense) {      // every voxel is a sample: the same cotangent kernel over N V columns, then the head's own backward launch
-        const long long P = alq_model_num_params(m);
-        ALQ_TRY(dense_forward_head(m, d_x, N, post, nullptr, false));
-        ALQ_TRY(k_loss_cotangent(m->ctx, post, m->nclass, (int)(N * m->V), d_labels, loss, loss_scale, lwf_scale, m->dlogits, d_stats3));
-        ALQ_TRY(dense_backward_head(m, d_x, N, d_grads, P));
-        if (m->layers.back().pidx > 0) ALQ_TRY(run_backward_general(m, N, &ds));      // (a head that is the only parameterised layer: nothing below)
-        return run_param_grads(m, d_x, N, 1, d_grads, P);
-    }
-    ALQ_TRY(k_softmax(m->ctx, m->logits, m->nclass, N, post, nullptr));
-    ALQ_TRY(k_loss_cotangent(m->ctx, post, m->nclass, N, d_labels, loss, loss_scale, lwf_scale, m->dlogits, d_stats3));
-    ALQ_TRY(run_backward_general(m, N, &ds));
-    return run_param_grads(m, d_x, N, 1, d_grads, alq_model_num_params(m));
-}
-
-int alq_rmsprop_step(alq_ctx *ctx, float *d_theta, const float *d_grad, float *d_ms, float *d_mom, int64_t n, float lr, float decay,
-                     float momentum, float eps) {
-    ALQ_REQUIRE(ctx && (n == 0 || (d_theta && d_grad && d_ms && d_mom)) && n >= 0, ALQ_EINVAL, "alq_rmsprop_step: bad argument");
-    ALQ_HIP(hipSetDevice(ctx->device));
-    return n ? k_rmsprop(ctx, d_theta, d_grad, d_ms, d_mom, n, lr, decay, momentum, eps) : ALQ_OK;
-}
-
-int alq_sq_accum(alq_ctx *ctx, const float *d_grads, int64_t per_sample_len, int N, double *d_acc) {
-    ALQ_REQUIRE(ctx && d_grads && d_acc && per_sample_len >= 1 && N >= 1, ALQ_EINVAL, "alq_sq_accum: bad argument");
-    ALQ_HIP(hipSetDevice(ctx->device));
-    return k_sq_accum(ctx, d_grads, per_sample_len, N, d_acc);
-}
-
-int alq_shrink_sum(alq_ctx *ctx, const float *d_grads, int N, int64_t P, const int64_t *h_layer_elems, int L, double *d_out) {
-    ALQ_REQUIRE(ctx && d_grads && h_layer_elems && d_out && N >= 1 && L >= 1 && L <= 64, ALQ_EINVAL, "alq_shrink_sum: bad argument");
-    long long off[65];
-    off[0] = 0;
-    for (int t = 0; t < L; ++t) {
-        ALQ_REQUIRE(h_layer_elems[t] >= 1, ALQ_EINVAL, "alq_shrink_sum: layer %d has %lld elements", t, (long long)h_layer_elems[t]);
-        off[t + 1] = off[t] + h_layer_elems[t];
-    }
-    ALQ_REQUIRE(off[L] == P, ALQ_EINVAL, "alq_shrink_sum: the layers hold %lld elements, a gradient row %lld", off[L], (long long)P);
-    ALQ_HIP(hipSetDevice(ctx->device));
-    return k_shrink_sum(ctx, d_grads, N, P, off, L, d_out);
-}
-
-int alq_fisher_classes(alq_ctx *ctx, const double *d_g, const double *d_w, const double *d_diag, int N, int c, int L, double *d_A) {
-    ALQ_REQUIRE(ctx && d_g && d_w && d_diag && d_A && N >= 1 && c >= 1 && L >= 1, ALQ_EINVAL, "alq_fisher_classes: bad argument");
-    ALQ_HIP(hipSetDevice(ctx->device));
-    return k_fisher_classes(ctx, d_g, d_w, d_diag, N, c, L, d_A);
-}
-
-const char *alq_last_error(void) { return g_err; }
-int alq_version(void) { return 1; }
-
-int alq_ctx_create(int device, void *stream, alq_ctx **out) {
-    ALQ_REQUIRE(out != nullptr, ALQ_EINVAL, "alq_ctx_create: null out");
-    int count = 0;
-    ALQ_HIP(hipGetDeviceCount(&count));
-    ALQ_REQUIRE(device >= 0 && device < count, ALQ_EINVAL, "device %d not present (%d visible)", device, count);
-    ALQ_HIP(hipSetDevice(device));
-    hipDeviceProp_t prop;
-    ALQ_HIP(hipGetDeviceProperties(&prop, device));
-    ALQ_REQUIRE(std::strncmp(prop.gcnArchName, "gfx950", 6) == 0, ALQ_EUNSUPPORTED,
-                "libalq is built for gfx950 (MI355X) only, device %d is %s", device, prop.gcnArchName);
-    alq_ctx *c = new alq_ctx();
-    c->device = device;
-    if (prop.multiProcessorCount > 0) c->num_cus = prop.multiProcessorCount;
-    c->stream = reinterpret_cast<hipStream_t>(stream);
-    if (hipMalloc(&c->param_block, ALQ_PARAM_BLOCK_BYTES) != hipSuccess) {
-        delete c;
-        set_error("alq_ctx_create: hipMalloc failed");
-        return ALQ_ENOMEM;
-    }
-    if (!std::getenv("ALQ_NO_SIDE_STREAM")) {      // diagnostic: everything on one stream
-        if (hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess) {
-            (void)hipGetLastError();
-            if (c->side) (void)hipStreamDestroy(c->side);
-            if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-            c->side = nullptr; c->ev_fork = nullptr; c->ev_join = nullptr;
-        }
-    }
-    *out = c;
-    return ALQ_OK;
-}
-
-int alq_ctx_destroy(alq_ctx *ctx) {
-    if (!ctx) return ALQ_OK;
-    (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->side) {
-        (void)hipStreamSynchronize(ctx->side);
-        (void)hipStreamDestroy(ctx->side);
-        (void)hipEventDestroy(ctx->ev_fork);
-        (void)hipEventDestroy(ctx->ev_join);
-    }
-    (void)alq_comm_destroy(ctx);
-    for (int c = 0; c < PROF_NUM; ++c) {
-        for (auto &pr : ctx->prof[c].pending) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
-        for (auto e : ctx->prof[c].pool) (void)hipEventDestroy(e);
-    }
-    (void)hipFree(ctx->param_block);
-    if (ctx->loss_part) (void)hipFree(ctx->loss_part);
-    delete ctx;
-    return ALQ_OK;
-}
-
-int alq_ctx_use_side_stream(alq_ctx *ctx, int on) {
-    ALQ_REQUIRE(ctx != nullptr, ALQ_EINVAL, "null ctx");
-    ctx->side_off = on == 0;
-    return ALQ_OK;
-}
-
-int alq_ctx_set_stream(alq_ctx *ctx, void *stream) {
-    ALQ_REQUIRE(ctx != nullptr, ALQ_EINVAL, "null ctx");
-    hipStream_t next = reinterpret_cast<hipStream_t>(stream);
-    if (next != ctx->stream) {
-        // the library's hidden state (activation workspaces, partial sums, side-stream work joined into the OLD stream) is
-        // ordered on the old stream only: the new stream waits for everything enqueued there so far
-        ALQ_HIP(hipSetDevice(ctx->device));
-        hipEvent_t ev;
-        ALQ_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        hipError_t e1 = hipEventRecord(ev, ctx->stream);
-        hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(next, ev, 0) : e1;
-        (void)hipEventDestroy(ev);
-        ALQ_REQUIRE(e2 == hipSuccess, ALQ_EHIP, "alq_ctx_set_stream: %s", hipGetErrorString(e2));
-        ctx->stream = next;
-    }
-    return ALQ_OK;
-}
-
-int alq_ctx_synchronize(alq_ctx *ctx) {
-    ALQ_REQUIRE(ctx != nullptr, ALQ_EINVAL, "null ctx");
-    ALQ_HIP(hipStreamSynchronize(ctx->stream));
     return ALQ_OK;
 }
 
@@ -2119,36 +1367,6 @@ int alq_model_layer_out_elems(const alq_model *m, int layer_idx, int64_t *elems)
     return ALQ_OK;
 }
 
-int alq_gather_normalize(alq_ctx *ctx, const void *const *d_vols, int mm, int vol_is_f64,
-                         const int64_t pad_dims[3], const int64_t *d_inds, int64_t n,
-                         const int32_t ps[3], const double *h_stats, int quirk, int out_is_f64, void *d_out) {
-    ALQ_REQUIRE(ctx && d_vols && pad_dims && ps && d_out && (n == 0 || d_inds), ALQ_EINVAL, "alq_gather_normalize: null argument");
-    ALQ_REQUIRE(mm >= 1 && mm <= 16, ALQ_EINVAL, "alq_gather_normalize: %d modalities", mm);
-    ALQ_REQUIRE(quirk == 2 || h_stats, ALQ_EINVAL, "alq_gather_normalize: stats missing");
-    if (n == 0) return ALQ_OK;
-    int64_t orig[3];
-    for (int d = 0; d < 3; ++d) {
-        ALQ_REQUIRE(ps[d] >= 1 && (ps[d] & 1), ALQ_EINVAL, "patch dims must be odd (patch_utils.py:1119-1121), got %d", ps[d]);
-        orig[d] = pad_dims[d] - 2 * ((ps[d] - 1) / 2);
-        ALQ_REQUIRE(orig[d] >= 1, ALQ_EINVAL, "padded volume smaller than the patch");
-    }
-    ALQ_HIP(hipSetDevice(ctx->device));
-    // small device-side parameter block: m pointers + 2m doubles
-    struct Block { const void *ptrs[16]; double stats[32]; } hb;
-    std::memset(&hb, 0, sizeof(hb));
-    for (int j = 0; j < mm; ++j) {
-        hb.ptrs[j] = d_vols[j];
-        if (h_stats) { hb.stats[2 * j] = h_stats[2 * j]; hb.stats[2 * j + 1] = h_stats[2 * j + 1]; }
-    }
-    static_assert(sizeof(Block) <= ALQ_PARAM_FLAG_OFFSET, "parameter block too small");
-    Block *db = reinterpret_cast<Block *>(ctx->param_block);
-    // pageable source: the copy is staged before the call returns, and it is stream-ordered
-    // behind any kernel of an earlier call that still reads the block
-    ALQ_HIP(hipMemcpyAsync(db, &hb, sizeof(Block), hipMemcpyHostToDevice, ctx->stream));
-    return gather_normalize_impl(ctx, db->ptrs, mm, vol_is_f64, pad_dims, orig, d_inds, n, ps, db->stats, quirk,
-                                 out_is_f64, d_out);
-}
-
 int alq_forward(alq_model *m, const float *d_x, int N, float *d_post, int64_t *d_pred, float *d_feat,
                 int feature_layer_idx) {
     ALQ_REQUIRE(m && d_x, ALQ_EINVAL, "alq_forward: null argument");
@@ -2166,55 +1384,6 @@ int alq_forward(alq_model *m, const float *d_x, int N, float *d_post, int64_t *d
         ALQ_HIP(hipMemcpyAsync(d_feat, v.p, (size_t)N * v.elems() * sizeof(float), hipMemcpyDeviceToDevice, m->ctx->stream));
     }
     return ALQ_OK;
-}
-
-int alq_score_entropy(alq_ctx *ctx, const float *d_p1, int64_t n, double *d_absdev, float *d_H) {
-    ALQ_REQUIRE(ctx && (n == 0 || d_p1), ALQ_EINVAL, "alq_score_entropy: null argument");
-    if (n == 0) return ALQ_OK;
-    ALQ_HIP(hipSetDevice(ctx->device));
-    return score_entropy_impl(ctx, d_p1, n, d_absdev, d_H);
-}
-
-int alq_committee_update(alq_ctx *ctx, const float *d_p1, int64_t n, int member, int mode, double *d_mean_p, double *d_mean_h,
-                         double *d_keys) {
-    ALQ_REQUIRE(ctx && n >= 0 && member >= 0, ALQ_EINVAL, "alq_committee_update: bad argument (n=%lld member=%d)", (long long)n,
-                member);
-    ALQ_REQUIRE(mode == ALQ_COMMITTEE_ENSEMBLE || mode == ALQ_COMMITTEE_QBC_JS, ALQ_EINVAL, "alq_committee_update: mode %d", mode);
-    ALQ_REQUIRE(n == 0 || (d_p1 && d_mean_p && (mode == ALQ_COMMITTEE_ENSEMBLE || d_mean_h)), ALQ_EINVAL,
-                "alq_committee_update: null argument");
-    if (n == 0) return ALQ_OK;
-    ALQ_HIP(hipSetDevice(ctx->device));
-    return committee_update_impl(ctx, d_p1, n, member, mode, d_mean_p, d_mean_h, d_keys);
-}
-
-int alq_eval_counts(alq_ctx *ctx, const int64_t *d_pred, const int64_t *d_inds, int64_t n, const void *d_mask, int mask_is_f64,
-                    int64_t mask_elems, int64_t *d_counts, uint8_t *d_seg) {
-    ALQ_REQUIRE(ctx && n >= 0 && mask_elems >= 0, ALQ_EINVAL, "alq_eval_counts: bad argument (n=%lld mask_elems=%lld)", (long long)n,
-                (long long)mask_elems);
-    ALQ_REQUIRE(n == 0 || (d_pred && d_mask && d_counts), ALQ_EINVAL, "alq_eval_counts: null argument");
-    ALQ_REQUIRE(d_inds || n <= mask_elems, ALQ_EINVAL, "alq_eval_counts: %lld samples, a label vector of %lld", (long long)n,
-                (long long)mask_elems);
-    if (n == 0) return ALQ_OK;
-    ALQ_HIP(hipSetDevice(ctx->device));
-    int *d_bad = reinterpret_cast<int *>(static_cast<char *>(ctx->param_block) + ALQ_PARAM_FLAG_OFFSET);
-    if (d_inds) ALQ_HIP(hipMemsetAsync(d_bad, 0, sizeof(int), ctx->stream));
-    ALQ_TRY(eval_counts_impl(ctx, d_pred, d_inds, n, d_mask, mask_is_f64, mask_elems, d_counts, d_seg, d_bad));
-    if (d_inds) {
-        // the indices live on the device: the kernel skipped any outside the volume and raised the flag
-        int bad = 0;
-        ALQ_HIP(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        ALQ_HIP(hipStreamSynchronize(ctx->stream));
-        ALQ_REQUIRE(!bad, ALQ_EINVAL, "alq_eval_counts: an index outside [0, %lld)", (long long)mask_elems);
-    }
-    return ALQ_OK;
-}
-
-size_t alq_topk_work_bytes(int64_t n) { return topk_work_bytes_impl(n); }
-
-int alq_topk_uncertain(alq_ctx *ctx, const double *d_keys, int64_t n, int64_t B, int64_t *d_out_idx, void *d_work) {
-    ALQ_REQUIRE(ctx && (n == 0 || (d_keys && d_work)) && (B == 0 || d_out_idx), ALQ_EINVAL, "alq_topk_uncertain: null argument");
-    ALQ_HIP(hipSetDevice(ctx->device));
-    return topk_impl(ctx, d_keys, n, B, d_out_idx, d_work);
 }
 
 int alq_fisher(alq_model *m, const float *d_x, int N, const float *d_p1_in, double diag_load, float *d_p1_out,
@@ -2269,62 +1438,6 @@ int alq_fisher_rows(alq_model *m, const float *d_pool, const int64_t *d_rows, in
     ALQ_HIP(hipSetDevice(m->ctx->device));
     if (N > 0) ALQ_TRY(stage_rows(m, d_pool, d_rows, N));
     return alq_fisher(m, N > 0 ? m->x_stage : d_pool, N, d_p1_in, diag_load, d_p1_out, d_g0, d_g1, d_A, d_trace, d_Asum);
-}
-
-int alq_topk_merge(const double *h_keys, const int64_t *h_idx, int64_t n, int64_t B, int64_t *h_out_idx,
-                   int64_t *n_out) {
-    ALQ_REQUIRE(n >= 0 && B >= 0 && (n == 0 || (h_keys && h_idx)) && (B == 0 || h_out_idx) && n_out, ALQ_EINVAL,
-                "alq_topk_merge: bad argument");
-    // Keys are compared by BIT PATTERN, like the device top-B (topk.hip): |p - .5| is non-negative, so the unsigned
-    // order of the bits is the numeric order, and a NaN key (NaN posterior of a NaN / inf patch on some rank) sorts
-    // deterministically behind every number instead of breaking the strict weak ordering of operator<.
-    std::vector<std::pair<uint64_t, int64_t>> v;
-    v.reserve((size_t)n);
-    for (int64_t i = 0; i < n; ++i)
-        if (h_idx[i] >= 0) {
-            double k = h_keys[i] == 0.0 ? 0.0 : h_keys[i];      // -0.0 -> +0.0
-            uint64_t b;
-            std::memcpy(&b, &k, sizeof(b));
-            v.emplace_back(b, h_idx[i]);
-        }
-    std::sort(v.begin(), v.end());          // key bits, then global index
-    const int64_t m = std::min<int64_t>(B, (int64_t)v.size());
-    for (int64_t i = 0; i < m; ++i) h_out_idx[i] = v[(size_t)i].second;
-    *n_out = m;
-    return ALQ_OK;
-}
-
-static const char *kProfNames[PROF_NUM] = {"igemm_fwd", "igemm_bwd", "elementwise", "reduce", "fc_small",
-                                           "igemm3_fwd", "igemm3_bwd", "direct_conv", "igemm_f16x2", "gnorm",
-                                           "committee", "eval"};
-
-int alq_prof_enable(alq_ctx *ctx, int on) {
-    ALQ_REQUIRE(ctx != nullptr, ALQ_EINVAL, "null ctx");
-    ctx->prof_on = on != 0;
-    ctx->prof_every = on > 1 ? on : 1;
-    ctx->prof_pass = 0;
-    return ALQ_OK;
-}
-
-int alq_prof_reset(alq_ctx *ctx) {
-    ALQ_REQUIRE(ctx != nullptr, ALQ_EINVAL, "null ctx");
-    ALQ_TRY(ctx->prof_collect());
-    for (int c = 0; c < PROF_NUM; ++c) {
-        ctx->prof[c].ms = 0; ctx->prof[c].launches = 0; ctx->prof[c].flops = 0;
-    }
-    return ALQ_OK;
-}
-
-int alq_prof_num_classes(void) { return PROF_NUM; }
-const char *alq_prof_class_name(int cls) { return (cls >= 0 && cls < PROF_NUM) ? kProfNames[cls] : ""; }
-
-int alq_prof_read(alq_ctx *ctx, int cls, double *ms, int64_t *launches, double *flops) {
-    ALQ_REQUIRE(ctx && cls >= 0 && cls < PROF_NUM, ALQ_EINVAL, "alq_prof_read: bad class");
-    ALQ_TRY(ctx->prof_collect());
-    if (ms) *ms = ctx->prof[cls].ms;
-    if (launches) *launches = ctx->prof[cls].launches;
-    if (flops) *flops = ctx->prof[cls].flops;
-    return ALQ_OK;
 }
 
 int alq_model_debug_copy(alq_model *m, int layer_idx, int what, int N, float *d_out, int64_t *elems_out) {
@@ -2458,13 +1571,6 @@ int alq_debug_set(int key, int value) {
 int alq_debug_set_stamp_buffer(void *d_buf) {
     g_igemm2_dbg = reinterpret_cast<unsigned long long *>(d_buf);
     return ALQ_OK;
-}
-
-int alq_synth_patches(alq_ctx *ctx, uint64_t seed, int64_t first_id, int64_t n, int64_t epp, float *d_out) {
-    ALQ_REQUIRE(ctx && (n == 0 || d_out), ALQ_EINVAL, "alq_synth_patches: null argument");
-    if (n == 0) return ALQ_OK;
-    ALQ_HIP(hipSetDevice(ctx->device));
-    return synth_impl(ctx, seed, first_id, n, epp, d_out);
 }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-// The model plan of libalq.so: what model.hip (plans, passes, the C ABI) and weights.hip (weight setting) share.
+// The model plan of libalq.so: what model.hip (plans, forward and Fisher passes), grads.hip (general gradient path) and weights.hip (weight setting) share.
 #pragma once
 #include <algorithm>
 
@@ -210,3 +210,24 @@ int upload_release(alq_model *m, D **d, std::vector<T> *h) {
 }
 
 namespace alq { int refresh_fallback_forms(alq_model *m); }      // weights.hip
+
+// ---- model.hip, for the general gradient path (grads.hip)
+// dropout of a training / MC forward pass: layers whose OUTPUT is dropped (NN.py:169-171), one keep probability
+struct DropSpec {
+    unsigned long long layers = 0;     // bit i = layer i
+    float keep_prob = 1.f;
+    unsigned long long seed = 0;
+    long long first_sample = 0;        // id of patch 0 of this call: masks are keyed by sample id, not by batch position
+    bool on(int i) const { return keep_prob < 1.f && i < 64 && ((layers >> i) & 1ull); }
+};
+int make_drop(const alq_model *m, float keep_prob, uint64_t seed, int64_t first_sample, const int32_t *h_layers, int n_layers, DropSpec *d);
+int prepare_call(alq_model *m, bool fisher);
+int run_forward(alq_model *m, const float *d_x, int N, bool with_sums, bool keep_all = false, const DropSpec *drop = nullptr);
+int gemm_launch(alq_ctx *ctx, const alq::Gemm &g, const alq::View &in, const alq::View &out, const float *bias, int relu, int accumulate, int N,
+                int cls, const alq::Igemm2Fuse *fuse = nullptr, bool *fused = nullptr, float fc_in_bound = 0.f);
+alq::View flat_view(const alq::View &v);
+
+// ---- grads.hip, for the entry points of model.hip: the head of a fully-convolutional model, and the refusal of the fc-only calls
+int dense_forward_head(alq_model *m, const float *d_x, int N, float *d_post, int64_t *d_pred, bool want_logits);
+#define ALQ_REFUSE_DENSE(m, who)                                                                                                \
+    ALQ_REQUIRE(!(m) || !(m)->dense, ALQ_EUNSUPPORTED, "%s: not defined for a fully-convolutional model (1x1 conv head)", who)

@@ -1,5 +1,5 @@
 // Device-side weight packing for wide fully connected layers (alq_model_set_weights_device): everything the host packers of
-// model.hip / fcgemm.hip derive from an fc layer's TF weights W[o][f_tf], computed from a DEVICE copy with the same bits.
+// weights.hip / fcgemm.hip derive from an fc layer's TF weights W[o][f_tf], computed from a DEVICE copy with the same bits.
 //
 //   wpack_stats_kernel    bwd_l1 = max_f sum_o |W[o][f]| (fp64, rows in the host's order: one thread per column, which is also
 //                         the coalesced order) and max |W| (the fp16 pairs' scale exponent) in one pass over W
