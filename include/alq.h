@@ -368,6 +368,54 @@ int alq_param_grads_loss(alq_model *m, const float *d_x, int N, const int32_t *d
 int alq_rmsprop_step(alq_ctx *ctx, float *d_theta, const float *d_grad, float *d_ms, float *d_mom, int64_t n, float lr,
                      float decay, float momentum, float eps);
 
+/* ---- mean-teacher consistency training of a fully-convolutional model (NN_extended.py:913-926, :1337-1396, :1535-1560) ----
+ * The student's posteriors p and the teacher's q, both class-major planes [c, R] over R = N V voxels, 2 <= c <= 8.  Per voxel
+ *   div = mean_j (p_j - q_j)^2 (ALQ_MT_L2)   or   -sum_j p_j log q_j (ALQ_MT_CE; log as in alq_loss_t)
+ * and the row of  loss_scale * sum_v l_v + k' * sum_v div_v  at the logits, l the ALQ_LOSS_CE objective of `loss` (class, voxel
+ * and focal weights; targets and old logits must be NULL):
+ *   row_k = [the row alq_param_grads_loss writes at loss_scale] + cons_scale p_k (d_k - sum_j p_j d_j),  d = p - q,
+ * cons_scale = 2 k' / c, for ALQ_MT_L2 on every voxel, labelled or not; ALQ_MT_CE adds nothing to a row (TF 1.x's
+ * softmax_cross_entropy_with_logits does not differentiate its labels and the teacher sits behind stop_gradient).  The
+ * consistency term is formed in fp64 from the fp32 posteriors and is added before the one rounding to fp32; with
+ * cons_scale == 0 the rows have the bits alq_param_grads_loss writes.  Statistics d_stats3 (double [3], device): sum_v l_v
+ * unscaled, the number of voxels whose weight is not zero, sum_v div_v.  No atomics: bit-identical from run to run.        */
+enum { ALQ_MT_L2 = 0, ALQ_MT_CE = 1 };
+/* Voxels one sweep of the capped grid of the cotangent kernel covers on its 16-byte path (more: the lanes grid-stride). */
+int64_t alq_mt_trip_voxels(void);
+/* Replaces: tf.gradients of model.loss = L + cons_coeff * cons at the logits (get_FCN_loss with MT_SSL, NN_extended.py:1353-1396;
+ * measure_output_perturbation, :1535-1560), given both posteriors: d_rows [R, c] and the statistics.  For tests and tools (a
+ * training step goes through alq_param_grads_loss_mt).  ALQ_EINVAL before any launch: a null pointer (d_teacher_post included),
+ * c outside [2, 8], R < 1, an unknown measure, a loss that is not ALQ_LOSS_CE without targets / old logits.                      */
+int alq_mt_cotangent(alq_ctx *ctx, const float *d_post, const float *d_teacher_post, int c, int64_t R, const int32_t *d_labels,
+                     const alq_loss_t *loss, float loss_scale, float cons_scale, int measure, float *d_rows, double *d_stats3);
+/* Replaces: sess.run(model.loss / model.labeled_loss / model.cons_loss, ...) of such a model: the same pass, statistics only. */
+int alq_mt_stats(alq_ctx *ctx, const float *d_post, const float *d_teacher_post, int c, int64_t R, const int32_t *d_labels,
+                 const alq_loss_t *loss, int measure, double *d_stats3);
+/* Replaces: the gradient half of sess.run(model.train_step, ...) with MT_SSL (NN_extended.py:1006-1008, :1353-1396):
+ * alq_param_grads_loss for a fully-convolutional model with the cotangent above - same forward pass, dropout arguments, head
+ * backward, backward sweep, weight products and [P] layout.  d_teacher_post [c, N V]: the teacher's posteriors of its own
+ * (perturbed) input, constants of the step.  ALQ_EINVAL: as alq_mt_cotangent and alq_param_grads_loss; ALQ_EUNSUPPORTED: an
+ * fc-head model (the reference's axes need an output map).  Nothing is launched before the checks pass.                      */
+int alq_param_grads_loss_mt(alq_model *m, const float *d_x, int N, const int32_t *d_labels, const alq_loss_t *loss,
+                            float loss_scale, const float *d_teacher_post, int measure, float cons_scale, float keep_prob,
+                            uint64_t seed, int64_t first_sample, const int32_t *h_drop_layers, int n_drop_layers, float *d_grads,
+                            float *d_post, double *d_stats3);
+/* Replaces: sess.run(model.ema_apply) (tf.train.ExponentialMovingAverage.apply, NN_extended.py:913-926): per element
+ * shadow -= (shadow - theta) * (1 - decay), every operation rounded to fp32 (1 - decay included).  ALQ_EINVAL: null pointer
+ * with n > 0, n < 0, decay outside [0, 1].                                                                                  */
+int alq_ema_step(alq_ctx *ctx, float *d_shadow, const float *d_theta, int64_t n, float decay);
+/* Replaces: perturb_input (NN_extended.py:1337-1351) on a channels-last batch [N, H, W, C]: Gaussian noise of standard
+ * deviation noise_std, then - rotate != 0 - tf.contrib.image.rotate(x, angle): nearest neighbour about the image centre,
+ * counter-clockwise, zero outside.  One gather: out[n, y, x, ch] = in[n, ys, xs, ch] + noise_std * z(n, ys, xs, ch) with, in fp32,
+ *   xo = ((W-1) - (cos a (W-1) - sin a (H-1))) / 2,  yo = ((H-1) - (sin a (W-1) + cos a (H-1))) / 2,
+ *   ys = round(sin a x + cos a y + yo),  xs = round(cos a x - sin a y + xo)   (half away from zero; outside the image: 0).
+ * z: Box-Muller on two 24-bit uniforms of the dropout masks' counter-based generator keyed (seed, a tag no layer has, sample id
+ * first_sample + n, source element in memory order): independent of the batch split.  A 3-D batch [N, D, H, W, C] takes the
+ * call with H = D * H and rotate = 0.  d_out may be d_x when rotate == 0.  ALQ_EINVAL: null pointer, a size below 1,
+ * noise_std < 0, a rotation in place.                                                                                        */
+int alq_perturb_input(alq_ctx *ctx, const float *d_x, float *d_out, int N, int H, int W, int C, float noise_std, uint64_t seed,
+                      int64_t first_sample, int rotate, float angle);
+
 /* Replaces: the accumulation loop of model_utils.diagonal_Fisher (model_utils.py:294-330):
  * d_acc[i] += sum_n d_grads[n, i]^2 (fp64).                                                                    */
 int alq_sq_accum(alq_ctx *ctx, const float *d_grads, int64_t per_sample_len, int N, double *d_acc);

@@ -107,6 +107,14 @@ _SIGNATURES = {
     'alq_param_grads_loss': (C.c_int, [_P, _P, C.c_int, _P, C.POINTER(LossT), C.c_float, C.c_float, C.c_float, C.c_uint64, C.c_int64,
                                        C.POINTER(C.c_int32), C.c_int, _P, _P, _P]),
     'alq_rmsprop_step': (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float]),
+    'alq_mt_trip_voxels': (C.c_int64, []),
+    'alq_mt_cotangent': (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, C.POINTER(LossT), C.c_float, C.c_float, C.c_int, _P, _P]),
+    'alq_mt_stats': (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, C.POINTER(LossT), C.c_int, _P]),
+    'alq_param_grads_loss_mt': (C.c_int, [_P, _P, C.c_int, _P, C.POINTER(LossT), C.c_float, _P, C.c_int, C.c_float, C.c_float,
+                                          C.c_uint64, C.c_int64, C.POINTER(C.c_int32), C.c_int, _P, _P, _P]),
+    'alq_ema_step': (C.c_int, [_P, _P, _P, C.c_int64, C.c_float]),
+    'alq_perturb_input': (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_int64, C.c_int,
+                                    C.c_float]),
     'alq_sq_accum': (C.c_int, [_P, _P, C.c_int64, C.c_int, _P]),
     'alq_shrink_sum': (C.c_int, [_P, _P, C.c_int, C.c_int64, C.POINTER(C.c_int64), C.c_int, _P]),
     'alq_fisher_classes': (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),

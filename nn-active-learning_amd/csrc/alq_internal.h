@@ -94,6 +94,7 @@ struct ProfSlot {
 #define ALQ_PARAM_BLOCK_BYTES 512
 #define ALQ_LOSS_MAX_BLOCKS 64      // workgroups of loss_cotangent_kernel (grid-stride beyond 64 * 256 samples)
 #define ALQ_DENSE_MAX_BLOCKS 2048   // workgroups (= rows of fp64 partials) of dense_head_bwd_kernel (dense.hip)
+#define ALQ_MT_MAX_BLOCKS 2048      // workgroups of mt_cotangent_kernel (mteach.hip): 8 per compute unit, grid-stride beyond
 #define ALQ_PARAM_FLAG_OFFSET (ALQ_PARAM_BLOCK_BYTES - 8)   // last word of the block: the bad-index flag of alq_eval_counts
 
 struct alq_ctx {
@@ -113,6 +114,7 @@ struct alq_ctx {
     bool side_off = false;     // alq_ctx_use_side_stream(ctx, 0): statistics kernels stay on the main stream (a caller that overlaps whole passes on two contexts)
     void *param_block = nullptr;   // small device buffer for per-call parameters (gather)
     double *loss_part = nullptr;   // per-workgroup partials of the loss statistics (loss.hip), allocated by the first call
+    double *mt_part = nullptr;     // ... of the mean-teacher statistics (mteach.hip), likewise
     void *comm = nullptr;          // RCCL communicator of this rank (comm.hip), or null
     int comm_rank = 0, comm_world = 1;
     int f16_subnormal_mfma = -1;   // c3d_subnormals_ok: -1 not probed yet on this context's device, else 0 / 1
@@ -786,6 +788,20 @@ int debug_view_copy(alq_ctx *, const View &, int, float *);
 int debug_f64_copy(alq_ctx *, const double *, long long, float *);
 size_t topk_work_bytes_impl(int64_t n);
 int topk_impl(alq_ctx *, const double *, int64_t, int64_t, int64_t *, void *);
+// The cotangent rows [R, c] and the statistics of a mean-teacher step (mteach.hip): k_loss_cotangent's CE branch plus the
+// consistency term against the teacher's posteriors; dlogits null: statistics only.  mt_check: the argument checks, shared by
+// alq_mt_cotangent / alq_mt_stats (mteach.hip) and alq_param_grads_loss_mt (grads.hip).
+int mt_check(const char *who, const float *post, const float *tpost, int c, long long R, const int32_t *labels, const alq_loss_t *loss,
+             int measure);
+int k_mt_cotangent(alq_ctx *, const float *post_cR, const float *tpost_cR, int c, long long R, const int *labels, const alq_loss_t *loss,
+                   float loss_scale, float cons_scale, int measure, float *dlogits, double *d_stats3);
+// the counter-based generator of the dropout masks (train.hip) and of the teacher's input noise (mteach.hip)
+__device__ inline unsigned long long tr_splitmix64(unsigned long long x) {
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
 // the argument checks of an alq_loss_t, shared by alq_loss_stats (ctx.hip) and alq_param_grads_loss (grads.hip)
 int loss_check(const char *who, const float *d_post_or_x, int c, const int32_t *d_labels, const alq_loss_t *loss);
 // The device flag a kernel raises over values that live on the device (a class or an index out of range): the last word of the context's

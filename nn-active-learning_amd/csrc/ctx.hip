@@ -138,6 +138,7 @@ int alq_ctx_destroy(alq_ctx *ctx) {
     }
     (void)hipFree(ctx->param_block);
     if (ctx->loss_part) (void)hipFree(ctx->loss_part);
+    if (ctx->mt_part) (void)hipFree(ctx->mt_part);
     delete ctx;
     return ALQ_OK;
 }

@@ -499,4 +499,26 @@ int alq_param_grads_loss(alq_model *m, const float *d_x, int N, const int32_t *d
     return run_param_grads(m, d_x, N, 1, d_grads, P);
 }
 
+// alq_param_grads_loss of a dense model with the mean-teacher cotangent (mteach.hip) in place of k_loss_cotangent
+int alq_param_grads_loss_mt(alq_model *m, const float *d_x, int N, const int32_t *d_labels, const alq_loss_t *loss, float loss_scale,
+                            const float *d_teacher_post, int measure, float cons_scale, float keep_prob, uint64_t seed,
+                            int64_t first_sample, const int32_t *h_drop_layers, int n_drop_layers, float *d_grads, float *d_post,
+                            double *d_stats3) {
+    ALQ_REQUIRE(m && d_grads, ALQ_EINVAL, "alq_param_grads_loss_mt: null argument");
+    ALQ_REQUIRE(m->dense, ALQ_EUNSUPPORTED, "alq_param_grads_loss_mt: mean-teacher training is defined for a fully-convolutional model");
+    REQUIRE_BATCH(m, N, "alq_param_grads_loss_mt");
+    ALQ_TRY(mt_check("alq_param_grads_loss_mt", d_x, d_teacher_post, m->nclass, (long long)N * m->V, d_labels, loss, measure));
+    ALQ_HIP(hipSetDevice(m->ctx->device));
+    DropSpec ds;
+    float *post = d_post ? d_post : m->post;
+    ALQ_TRY(general_forward(m, d_x, N, nullptr, &ds, keep_prob, seed, first_sample, h_drop_layers, n_drop_layers));
+    const long long P = alq_model_num_params(m);
+    ALQ_TRY(dense_forward_head(m, d_x, N, post, nullptr, false));
+    ALQ_TRY(k_mt_cotangent(m->ctx, post, d_teacher_post, m->nclass, (long long)N * m->V, d_labels, loss, loss_scale, cons_scale, measure,
+                           m->dlogits, d_stats3));
+    ALQ_TRY(dense_backward_head(m, d_x, N, d_grads, P));
+    if (m->layers.back().pidx > 0) ALQ_TRY(run_backward_general(m, N, &ds));
+    return run_param_grads(m, d_x, N, 1, d_grads, P);
+}
+
 }  // extern "C"

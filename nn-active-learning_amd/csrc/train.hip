@@ -39,13 +39,6 @@ static DView dview(const View &v) {
     return d;
 }
 
-__device__ inline unsigned long long tr_splitmix64(unsigned long long x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
 // ------------------------------------------------------------------------------------------ dropout
 // out[n, e] *= keep(n, e) / keep_prob, keep ~ Bernoulli(keep_prob) from a counter-based generator keyed
 // (seed, layer, sample id, element): tf.nn.dropout's scaling (NN.py:169-171), its own reproducible mask (TF's RNG

@@ -480,6 +480,8 @@ class DeviceSession(object):
             return model.grad_log_post(x, j, keep_prob=kp)
         if model is None:
             raise KeyError('unknown fetch %r' % (fetch,))
+        if fetch.name == 'ema_apply':          # (NN_extended.py:1006-1008: run without a feed)
+            return model.apply_ema()
         x = feed_dict[model.x]
         kp = float(feed_dict.get(model.keep_prob, 1.))
         iw = None
@@ -827,6 +829,7 @@ class DeviceModel(object):
         self._pft_mask = None             # float32 device [P]
         self._pft_layers = None           # parameterised layers with a non-zero mask entry
         self._drop_calls = 0
+        self._mt = None                   # set_mean_teacher: the settings and state of mean-teacher training
         self.num_params = int(self.lib.alq_model_num_params(self._m))
         self._feature_perm = self._feature_permutation()
 
@@ -1118,6 +1121,175 @@ class DeviceModel(object):
         self._opt = dict(name=optimizer_name, lr=float(learning_rate), schedule=schedule, t=0, theta=None, m=None, v=None,
                          beta1=float(h.get('beta1', 0.9)), beta2=float(h.get('beta2', 0.999)), decay=float(h.get('decay', 0.9)),
                          momentum=float(h.get('momentum', 0.)), epsilon=float(h.get('epsilon', 1e-10)))
+        if self._mt is not None:
+            self._build_teacher()
+
+    # -- mean-teacher consistency training (NN_extended.py:913-926, :1337-1396) -------------
+    @property
+    def global_step(self):
+        """Optimiser steps taken so far (the reference's `global_step` variable)."""
+        return self._opt['t'] if self._opt is not None else 0
+
+    def set_mean_teacher(self, mt):
+        """MT_SSL of NN_extended.CNN: `mt` holds output_perturbation_measure, MT_ema_decay_schedule, Gaussian_noise_std,
+        rotation_angle, max_cons_coeff and rampup_length.  get_optimizer() then builds the teacher."""
+        from . import mteach
+        if not self.dense:
+            raise NotImplementedError('mean-teacher training is defined for fully-convolutional models')
+        if mt.get('rotation_angle') is not None and len(self.in_shape) != 3:
+            raise ValueError('rotation_angle on a 3-D model')
+        self._mt = dict(measure=mteach.MEASURES[mt['output_perturbation_measure']], decay=mt['MT_ema_decay_schedule'],
+                        std=float(mt['Gaussian_noise_std'] or 0.), angle=mt.get('rotation_angle'),
+                        max_coeff=float(mt['max_cons_coeff']), rampup=float(mt['rampup_length']), shadow=None, tver=0)
+        self.cons_coeff = mteach.cons_coeff(0, self._mt['rampup'], self._mt['max_coeff'])
+
+    def _build_teacher(self):
+        """get_FCN_loss with MT_SSL (NN_extended.py:1337-1396): a second model over the same layers on the same session whose
+        weights are the moving averages of this model's, its input `perturbed_x`, and the handles of the step."""
+        drop = [self.dropout_layers, self.dropout_rate] if len(self.dropout_layers) else None
+        if getattr(self, 'teacher', None) is not None:      # (a second get_optimizer(): a new teacher, as a new graph would hold)
+            self.teacher.close()
+        self.teacher = DeviceModel(self.sess, self.layer_dict, self.in_shape, self.skips, None, drop, self.max_batch,
+                                   self.name + '_teacher')
+        self.perturbed_x = Handle('perturbed_x')
+        for nme in ('ema_apply', 'labeled_loss', 'cons_loss'):
+            h = Handle(nme)
+            h.model = self
+            setattr(self, nme, h)
+        self._mt.update(shadow=None, tver=0)
+
+    def _student_theta(self):
+        """This model's weights as a flat device vector: the optimiser's own when it is current."""
+        o = self._opt
+        if o is not None and o['theta'] is not None and o.get('version') == self._weights_version:
+            return o['theta']
+        return self.sess.to_device(self.flat_params(), self.sess.torch.float32)
+
+    def _mt_shadow(self):
+        """The teacher's weights, flat fp32 on the device.  They start as a copy of this model's weights at the first use -
+        of the teacher's own when teacher.set_weights / load_weights was called (again after every later such call)."""
+        mt, T = self._mt, self.teacher
+        if mt['shadow'] is None or T._weights_version != mt['tver']:
+            src = self._student_theta() if T._weights_version == 0 else self.sess.to_device(T.flat_params(), self.sess.torch.float32)
+            mt['shadow'] = src.clone()
+            T.set_weights_device(mt['shadow'])
+            mt['tver'] = T._weights_version
+        return mt['shadow']
+
+    def apply_ema(self):
+        """`sess.run(model.ema_apply)`: shadow -= (shadow - theta) * (1 - decay) on the device (alq_ema_step), decay =
+        MT_ema_decay_schedule(global_step) evaluated on the host; the teacher is repacked from the shadow vector."""
+        if self._mt is None or self._opt is None:
+            raise RuntimeError('ema_apply needs MT_SSL and get_optimizer()')
+        mt = self._mt
+        shadow = self._mt_shadow()
+        theta = self._student_theta()
+        self.sess.bind_stream()
+        check(self.lib.alq_ema_step(self.sess.ctx, C.c_void_p(shadow.data_ptr()), C.c_void_p(theta.data_ptr()), self.num_params,
+                                    float(mt['decay'](self.global_step))))
+        self.teacher.set_weights_device(shadow)
+        mt['tver'] = self.teacher._weights_version
+
+    def perturb_device(self, t, n, seed, first_sample=0):
+        """`model.perturbed_x` of n device patches (alq_perturb_input): Gaussian noise, then the rotation."""
+        mt = self._mt
+        out = self.sess.empty((n, self.elems_per_patch), self.sess.torch.float32)
+        H, W, Cc = (self.in_shape if len(self.in_shape) == 3 else (self.in_shape[0] * self.in_shape[1],) + self.in_shape[2:])
+        self.sess.bind_stream()
+        check(self.lib.alq_perturb_input(self.sess.ctx, C.c_void_p(t.data_ptr()), C.c_void_p(out.data_ptr()), n, H, W, Cc, mt['std'],
+                                         int(seed), int(first_sample), int(mt['angle'] is not None), float(mt['angle'] or 0.)))
+        return out
+
+    def _mt_pass(self, t, n, y, keep_prob, seed, input_weights, want_grad, feed):
+        """_objective_pass of a mean-teacher model: loss = L + cons_coeff * cons read as the vector [n], so
+        the gradient is n grad L + cons_coeff sum_i grad cons_i.  Per cut of max_batch: perturb the cut, the teacher's forward
+        pass at its own keep_prob, alq_param_grads_loss_mt.  `feed`: dict(kp = the teacher's keep_prob, px = a fed
+        perturbed_x or None).  The labelled scale is n / (non-zero weights of the whole batch), the consistency scale
+        cons_coeff 2 / (c V) per voxel (L2; CE adds to the value only).  Returns (gradient or None, loss) and leaves
+        (L, mean_i cons_i, cons_coeff) in self._mt['last']."""
+        from . import losses, mteach
+        torch = self.sess.torch
+        self.sess.bind_stream()
+        mt, T = self._mt, self.teacher
+        obj = self._obj or dict(q=0.7, gamma=None, class_w=None)          # (no hypers: the plain voxel-wise cross-entropy)
+        c, V = self.nclass, self.out_voxels
+        ns = n * V
+        t = t.reshape(n, -1)
+        y = np.asarray(y)
+        if y.shape != (c, ns):
+            raise ValueError('labels must be [%d, %d] columns, got %r' % (c, ns, y.shape))
+        lab = np.where(y.sum(0) > 0, y.argmax(0), -1).astype(np.int32)
+        labd = self.sess.to_device(lab, torch.int32)
+        sw = None if input_weights is None else np.asarray(input_weights, dtype=np.float32).reshape(ns)
+        swd = None if sw is None else self.sess.to_device(sw, torch.float32)
+        cw = obj['class_w']
+        gamma = obj['gamma'] if (obj['gamma'] is not None and obj['gamma'] > 0) else None
+        kp, arr, nl, seed = self._drop_args(keep_prob, seed)
+        tkp, tarr, tnl, tseed = T._drop_args(feed.get('kp', 1.), None)            # the second draw of the seed stream
+        px = feed.get('px')
+        nseed = int(np.random.randint(0, 2 ** 31 - 1)) if (px is None and mt['std'] > 0) else 0      # ... and the third
+        if px is not None:
+            px, npx = self._as_device_batch(px)
+            if npx != n:
+                raise ValueError('perturbed_x holds %d patches, x %d' % (npx, n))
+            px = px.reshape(n, -1)
+        self._mt_shadow()
+        coeff = mteach.cons_coeff(self.global_step, mt['rampup'], mt['max_coeff'])
+        kscale = coeff * 2. / (c * V) if mt['measure'] == mteach.L2 else 0.
+        cuts = [(a, min(n, a + self.max_batch)) for a in range(0, n, self.max_batch)]
+        xb = lambda src, a: C.c_void_p(src.data_ptr() + a * self.elems_per_patch * 4)
+        spec = lambda a: LossT(losses.CE, -1. if gamma is None else gamma, obj['q'], 1., cw.data_ptr() if cw is not None else None,
+                               swd.data_ptr() + a * V * 4 if swd is not None else None, None, None)
+
+        def teacher_post(a, b):
+            pin = px[a:b] if px is not None else (self.perturb_device(t[a:b], b - a, nseed, a) if (mt['std'] > 0 or mt['angle'] is not None)
+                                                  else t[a:b])
+            tq = self.sess.empty((c, (b - a) * V), torch.float32)
+            check(self.lib.alq_forward_dropout(T._m, xb(pin, 0), b - a, tkp, tseed, a, tarr, tnl, C.c_void_p(tq.data_ptr()), None))
+            return tq
+
+        def student_post(a, b):
+            pb = self.sess.empty((c, (b - a) * V), torch.float32)
+            check(self.lib.alq_forward_dropout(self._m, xb(t, a), b - a, kp, seed, a, arr, nl, C.c_void_p(pb.data_ptr()), None))
+            return pb
+
+        stats = torch.zeros((len(cuts), 3), dtype=torch.float64, device=self.sess.device)
+        if want_grad:
+            if gamma is None:
+                w = (lab >= 0).astype(np.float64)
+                if cw is not None:
+                    w = w * np.asarray(self.hypers['bin_class_weights'], dtype=np.float32).reshape(2)[np.where(lab == 1, 1, 0)]
+                if sw is not None:
+                    w = w * sw
+                cnt = float(np.count_nonzero(w))
+            else:      # the focal weight can vanish (pt == 1): the count comes from a statistics pass first
+                for k, (a, b) in enumerate(cuts):
+                    pb, L = student_post(a, b), spec(a)
+                    check(self.lib.alq_loss_stats(self.sess.ctx, C.c_void_p(pb.data_ptr()), c, (b - a) * V,
+                                                  C.c_void_p(labd.data_ptr() + a * V * 4), C.byref(L), C.c_void_p(stats.data_ptr() + k * 24)))
+                cnt = float(stats[:, 1].sum().item())
+            s = n / cnt if cnt else 0.
+            gsum = torch.zeros((self.num_params,), dtype=torch.float32, device=self.sess.device)
+            for k, (a, b) in enumerate(cuts):
+                g = self.sess.empty((self.num_params,), torch.float32)
+                tq, L = teacher_post(a, b), spec(a)
+                check(self.lib.alq_param_grads_loss_mt(self._m, xb(t, a), b - a, C.c_void_p(labd.data_ptr() + a * V * 4), C.byref(L), float(s),
+                                                       C.c_void_p(tq.data_ptr()), mt['measure'], float(kscale), kp, seed, a, arr, nl,
+                                                       C.c_void_p(g.data_ptr()), None, C.c_void_p(stats.data_ptr() + k * 24)))
+                gsum += g
+        else:
+            gsum = None
+            for k, (a, b) in enumerate(cuts):
+                tq, pb, L = teacher_post(a, b), student_post(a, b), spec(a)
+                check(self.lib.alq_mt_stats(self.sess.ctx, C.c_void_p(pb.data_ptr()), C.c_void_p(tq.data_ptr()), c, (b - a) * V,
+                                            C.c_void_p(labd.data_ptr() + a * V * 4), C.byref(L), mt['measure'],
+                                            C.c_void_p(stats.data_ptr() + k * 24)))
+        st = stats.cpu().numpy()
+        cnt = st[:, 1].sum()
+        labelled = float(st[:, 0].sum() / cnt) if cnt else 0.
+        cons = float(st[:, 2].sum() / ns)
+        mt['last'] = (labelled, cons, coeff)
+        return gsum, labelled + coeff * cons
 
     def _train_mask(self):
         """1 on the parameters of `train_layers` (all when empty), flat order."""
@@ -1206,7 +1378,7 @@ class DeviceModel(object):
         y[lab[ok], np.nonzero(ok)[0]] = 1.
         return y
 
-    def _objective_pass(self, t, n, y, keep_prob, seed, input_weights, lwf, want_grad=True):
+    def _objective_pass(self, t, n, y, keep_prob, seed, input_weights, lwf, want_grad=True, mt_feed=None):
         """The model's objective (set_hypers; the batch-mean cross-entropy with divisor n when none is set) on n device patches
         over passes of max_batch: (gradient of the loss, float32 device [P] - None without `want_grad` - and the loss).
         y [c, n]: one-hot columns (all zero: unlabelled) or, for CE_softclasses / GCE, the soft targets; input_weights [n];
@@ -1216,6 +1388,10 @@ class DeviceModel(object):
         the summed gradient is divided by the count on the device (no read in between); focal with LwF - two terms with two
         divisors - takes the count from forward passes + alq_loss_stats first.  One read of the statistics at the end."""
         from . import losses
+        if self._mt is not None and getattr(self, 'teacher', None) is not None:      # (before get_optimizer(): the labelled loss alone)
+            if lwf is not None:
+                raise NotImplementedError('MT_SSL with learning without forgetting')
+            return self._mt_pass(t, n, y, keep_prob, seed, input_weights, want_grad, mt_feed or {})
         torch = self.sess.torch
         self.sess.bind_stream()
         # (a dense model: V samples per patch, always the non-zero-weight divisor of get_FCN_loss, NN_extended.py:1285-1335)
@@ -1315,7 +1491,7 @@ class DeviceModel(object):
         t, n = self._as_device_batch(x)
         return self._objective_pass(t, n, y_onehot, keep_prob, seed, input_weights, lwf, want_grad=False)[1]
 
-    def train_on_batch(self, x, y_onehot, keep_prob=1., seed=None, pft_mask=None, input_weights=None, lwf=None):
+    def train_on_batch(self, x, y_onehot, keep_prob=1., seed=None, pft_mask=None, input_weights=None, lwf=None, mt_feed=None):
         """One `sess.run(model.train_step, {x, y_, keep_prob})`: gradient of the batch-mean cross-entropy (summed over
         device passes of max_batch patches), one optimiser step on the device, weights repacked.  y_onehot: [c, n]
         like the reference's hot_labels (PW_AL.py:1064-1067); an all-zero column is an unlabelled sample.
@@ -1332,7 +1508,7 @@ class DeviceModel(object):
             raise ValueError('labels must be [%d, %d] one-hot columns, got %r' % (self.nclass, n * self.out_voxels, y.shape))
         self._check_input_weights(input_weights)
         if self._obj is not None or lwf is not None or self.dense:
-            gsum, loss = self._objective_pass(t, n, y, keep_prob, seed, input_weights, lwf)
+            gsum, loss = self._objective_pass(t, n, y, keep_prob, seed, input_weights, lwf, mt_feed=mt_feed)
         else:
             lab = np.where(y.sum(0) > 0, y.argmax(0), -1).astype(np.int32)
             kp, _, _, seed = self._drop_args(keep_prob, seed)
@@ -1404,6 +1580,9 @@ class DeviceModel(object):
                 only = [t for t in (range(self.L) if only is None else only) if t in players]
             self.set_weights_device(o['theta'], only=only)
         o['version'] = self._weights_version
+        if self._mt is not None:
+            from . import mteach
+            self.cons_coeff = mteach.cons_coeff(o['t'], self._mt['rampup'], self._mt['max_coeff'])
         return loss
 
     def diagonal_fisher_device(self, t, n, labels):
@@ -1780,7 +1959,8 @@ class DeviceModel(object):
             return (pred if name == 'prediction' else maps.contiguous()).cpu().numpy()
         if name == 'feature_layer':
             return self.forward(x, want=(name,), keep_prob=kp)[name]
-        if name not in ('loss', 'train_step'):
+        mt_on = self._mt is not None and getattr(self, 'teacher', None) is not None
+        if name not in ('loss', 'train_step') + (('labeled_loss', 'cons_loss') if mt_on else ()):
             raise NotImplementedError('sess.run(model.%s) is not defined for a fully-convolutional model (1x1 conv head)' % name)
         y = np.asarray(feed_dict[self.y_])
         n = int(np.asarray(x).shape[0]) if not isinstance(x, self.sess.torch.Tensor) else int(x.shape[0])
@@ -1792,14 +1972,17 @@ class DeviceModel(object):
             if tuple(iw.shape) != (n,) + self.out_map_shape:
                 raise ValueError('input_vox_weights must be %r, got %r' % ((n,) + self.out_map_shape, tuple(iw.shape)))
             iw = iw.reshape(-1)
-        if name == 'loss':
+        mt_feed = dict(kp=float(feed_dict.get(self.teacher.keep_prob, 1.)), px=feed_dict.get(self.perturbed_x)) if mt_on else None
+        if name in ('loss', 'labeled_loss', 'cons_loss'):
             t, n = self._as_device_batch(x)
-            return self._objective_pass(t, n, ycols, kp, None, iw, None, want_grad=False)[1]
+            loss = self._objective_pass(t, n, ycols, kp, None, iw, None, want_grad=False, mt_feed=mt_feed)[1]
+            return loss if name == 'loss' else self._mt['last'][name == 'cons_loss']
         ph = getattr(self, 'par_placeholders', None)
         fed = [h in feed_dict for h in ph] if ph else []
         if any(fed) and not all(fed):
             raise KeyError('a PFT step needs a mask for every entry of par_placeholders')
-        return self.train_on_batch(x, ycols, keep_prob=kp, pft_mask=[feed_dict[h] for h in ph] if any(fed) else None, input_weights=iw)
+        return self.train_on_batch(x, ycols, keep_prob=kp, pft_mask=[feed_dict[h] for h in ph] if any(fed) else None, input_weights=iw,
+                                   mt_feed=mt_feed)
 
     def forward(self, x, want=('posteriors',), keep_prob=1.):
         t, n = self._as_device_batch(x)
@@ -2092,6 +2275,8 @@ class DeviceModel(object):
             self.lib.alq_model_destroy(ln['m'])
             ln['sess'].close()
         self._xlanes = []
+        if getattr(self, 'teacher', None) is not None:
+            self.teacher.close()
         if self._m:
             self.lib.alq_model_destroy(self._m)
             self._m = C.c_void_p()
