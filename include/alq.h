@@ -96,6 +96,12 @@ int alq_dense_head_fwd(alq_ctx *ctx, const float *d_x, int64_t R, int Ci, int c,
                        int64_t *d_pred);
 int alq_dense_head_bwd(alq_ctx *ctx, const float *d_delta, const float *d_x, int64_t R, int Ci, int c, const float *d_W, float *d_dx,
                        void *d_work, float *d_dW_db);
+/* The launch arithmetic of alq_dense_head_bwd over R rows of Ci channels, as the launch itself computes it (no device call): the
+ * workgroups (at most 2048), the rows each of them owns, the rows one sweep of a workgroup covers (256 / (Ci / 4)) and the rows a
+ * lane sums in fp32 before they go into its fp64 sums.  A workgroup owning more than flush_rows * rows_per_sweep rows folds more
+ * than once.  For tests: a case asserts from these that it is in the regime it names.  ALQ_EINVAL: a null pointer or R < 1;
+ * ALQ_EUNSUPPORTED: Ci as for the launch.                                                                                         */
+int alq_dense_head_bwd_geometry(int64_t R, int Ci, int *blocks, int64_t *rows_per_block, int *rows_per_sweep, int *flush_rows);
 /* Number of parameterised layers L ( = len(grad_posts['1'])/2, PW_NNAL.py:751 ).             */
 int alq_model_num_param_layers(const alq_model *m);
 /* W/b element counts of parameterised layer t (creation order), i.e. prod(W.shape), len(b).  */

@@ -294,11 +294,16 @@ __global__ __launch_bounds__(DENSE_BLOCK) void dense_head_reduce_kernel(const do
 }
 
 // Workgroups of a backward launch over R rows: enough rows each to amortise the closing tree, never more than the partials hold
+static int dense_head_bwd_rpi(int Ci) { return DENSE_BLOCK / (Ci / 4); }      // the kernel's `rpi`
+
 int dense_head_bwd_blocks(long long R, int Ci) {
-    const int rpi = DENSE_BLOCK / (Ci / 4);
+    const int rpi = dense_head_bwd_rpi(Ci);
     const long long want = (R + (long long)rpi * 8 - 1) / ((long long)rpi * 8);
     return (int)std::max(1LL, std::min(want, (long long)ALQ_DENSE_MAX_BLOCKS));
 }
+
+// Rows per workgroup of that launch (the kernel's `per`)
+static long long dense_head_bwd_rows(long long R, int nblk) { return (R + nblk - 1) / nblk; }
 
 int k_dense_head_bwd(alq_ctx *ctx, const float *delta, const float *x, long long R, int Ci, int c, const float *W, float *dx,
                      int accumulate, double *part, float *d_dW_db) {
@@ -308,7 +313,7 @@ int k_dense_head_bwd(alq_ctx *ctx, const float *delta, const float *x, long long
     DenseBwdArgs a;
     a.delta = delta; a.x = x; a.W = W; a.dx = dx; a.part = part; a.R = R; a.Ci = Ci; a.accumulate = accumulate;
     const int nblk = dense_head_bwd_blocks(R, Ci);
-    a.per = (R + nblk - 1) / nblk;
+    a.per = dense_head_bwd_rows(R, nblk);
     {
         ProfScope ps(ctx, PROF_ELEMWISE, 4.0 * R * Ci * c);
 #define CALL(CC) hipLaunchKernelGGL(dense_head_bwd_kernel<CC>, dim3((unsigned)nblk), dim3(DENSE_BLOCK), 0, ctx->stream, a)
@@ -330,6 +335,18 @@ extern "C" {
 
 size_t alq_dense_head_work_bytes(int Ci, int c) {
     return (Ci > 0 && c > 0) ? (size_t)ALQ_DENSE_MAX_BLOCKS * ((size_t)Ci * c + c) * sizeof(double) : 0;
+}
+
+int alq_dense_head_bwd_geometry(int64_t R, int Ci, int *blocks, int64_t *rows_per_block, int *rows_per_sweep, int *flush_rows) {
+    ALQ_REQUIRE(blocks && rows_per_block && rows_per_sweep && flush_rows && R >= 1, ALQ_EINVAL,
+                "alq_dense_head_bwd_geometry: null argument or no voxels");
+    ALQ_REQUIRE(Ci >= 4 && Ci <= alq::DENSE_MAX_CI && Ci % 4 == 0, ALQ_EUNSUPPORTED,
+                "alq_dense_head_bwd_geometry: %d input channels (a multiple of 4, at most %d)", Ci, alq::DENSE_MAX_CI);
+    *blocks = alq::dense_head_bwd_blocks(R, Ci);
+    *rows_per_block = alq::dense_head_bwd_rows(R, *blocks);
+    *rows_per_sweep = alq::dense_head_bwd_rpi(Ci);
+    *flush_rows = alq::DENSE_FLUSH;
+    return ALQ_OK;
 }
 
 int alq_dense_head_fwd(alq_ctx *ctx, const float *d_x, int64_t R, int Ci, int c, const float *d_W, const float *d_b, float *d_post,

@@ -144,11 +144,13 @@ def _reproducible(sess, m, x, ycols):
 
 
 @pytest.mark.parametrize('c', [2, 3, 8])
-@pytest.mark.parametrize('ci', [4, 8, 16, 64])
+@pytest.mark.parametrize('ci', [4, 8, 12, 16, 20, 64])
 @pytest.mark.parametrize('shape', sorted(HEAD_SHAPES))
 def test_head_alone_vs_fp64(sess, shape, ci, c):
     """conv(Ci, 3x3, ReLU) + the 1x1 head.  5x7 with N = 3: 105 voxels, under one workgroup and no multiple of 4 (the guarded
-    one-voxel path); 12x20 with N = 5 at max_batch 4: 16-byte path, two passes; 3-D 4x6x5."""
+    one-voxel path); 12x20 with N = 5 at max_batch 4: 16-byte path, two passes; 3-D 4x6x5.  Ci = 12 and 20: 3 and 5 16-byte
+    pieces a row, so the backward workgroup sweeps 85 and 51 rows with lanes idle (the kernels on their own:
+    tests/test_gpu_dense_head.py)."""
     in_shape, N = HEAD_SHAPES[shape]
     ld, sk = _head_net(ci, c, len(in_shape) - 1)
     _check_case(sess, 'head %s Ci=%d c=%d' % (shape, ci, c), ld, sk, in_shape, N, c, seed=300 + ci + c, max_batch=4)

@@ -58,7 +58,7 @@ def main():
         worst = 0.
         for shape in sorted(T.HEAD_SHAPES):
             in_shape, N = T.HEAD_SHAPES[shape]
-            for ci in (4, 8, 16, 64):
+            for ci in (4, 8, 12, 16, 20, 64):
                 for c in (2, 3, 8):
                     ld, sk = T._head_net(ci, c, len(in_shape) - 1)
                     worst = max(worst, T._check_case(sess, 'head %s Ci=%d c=%d' % (shape, ci, c), ld, sk, in_shape, N, c, 300 + ci + c, 4))
