@@ -96,6 +96,13 @@ int alq_dense_head_fwd(alq_ctx *ctx, const float *d_x, int64_t R, int Ci, int c,
                        int64_t *d_pred);
 int alq_dense_head_bwd(alq_ctx *ctx, const float *d_delta, const float *d_x, int64_t R, int Ci, int c, const float *d_W, float *d_dx,
                        void *d_work, float *d_dW_db);
+/* The forward kernel for a head with an aleatoric-uncertainty channel (AU_4U, NN_extended.py:265-288): d_W [Ci, c + 1], d_b [c + 1],
+ * 2 <= c <= 7.  d_post [c, R] = softmax over the first c channels and d_pred (or NULL) their first maximum - the bits
+ * alq_dense_head_fwd writes for W[:, :c], b[:c] (every channel keeps its own chain of fused multiply-adds) -, d_au [R] =
+ * max(z_c, 0), the per-voxel log-variance, d_logits [R, c + 1] or NULL.  ALQ_EINVAL: a null pointer (d_au included);
+ * ALQ_EUNSUPPORTED: Ci or c outside the limits.                                                                                      */
+int alq_dense_head_fwd_au(alq_ctx *ctx, const float *d_x, int64_t R, int Ci, int c, const float *d_W, const float *d_b, float *d_post,
+                          int64_t *d_pred, float *d_au, float *d_logits);
 /* The launch arithmetic of alq_dense_head_bwd over R rows of Ci channels, as the launch itself computes it (no device call): the
  * workgroups (at most 2048), the rows each of them owns, the rows one sweep of a workgroup covers (256 / (Ci / 4)) and the rows a
  * lane sums in fp32 before they go into its fp64 sums.  A workgroup owning more than flush_rows * rows_per_sweep rows folds more
@@ -406,6 +413,43 @@ int alq_param_grads_loss_mt(alq_model *m, const float *d_x, int N, const int32_t
                             float loss_scale, const float *d_teacher_post, int measure, float cons_scale, float keep_prob,
                             uint64_t seed, int64_t first_sample, const int32_t *h_drop_layers, int n_drop_layers, float *d_grads,
                             float *d_post, double *d_stats3);
+/* ---- aleatoric uncertainty for unlabelled voxels (AU_4U, NN_extended.py:265-288, :1376-1383, :1551-1554) ----
+ * The head of a fully-convolutional model has c + 1 channels: c classes and, behind a ReLU, a per-voxel log-variance a >= 0.
+ * With e = exp(-a) the consistency value of a voxel is  cons = div e + kappa a / 2  (kappa = AU_log_rel_coeff; div as above,
+ * over the c posteriors; the teacher's own log-variance is not read), and the rows [R, c + 1] at the student's logits are
+ *   k < c:  [the labelled row, on the c clean logits] + cons_scale e p_k (d_k - sum_j p_j d_j)   (ALQ_MT_L2; ALQ_MT_CE: no term)
+ *   c:      a > 0 ? au_scale (kappa / 2 - div e) : 0                                               (TF's ReluGrad; both measures)
+ * formed in fp64 from the fp32 planes and rounded once.  With d_au all zero and kappa = 0 the columns below c and the statistics
+ * have the bits of alq_mt_cotangent at the same cons_scale and column c is 0.  Statistics: sum_v l_v, the non-zero weights,
+ * sum_v cons_v.  No atomics: bit-identical from run to run.
+ * alq_model_set_aleatoric(m, on): the model's head is read that way from here on: alq_forward and alq_forward_dropout write
+ * d_post [c, N V] and d_pred over the c classes, alq_param_grads_loss and alq_param_grads_loss_mt return ALQ_EUNSUPPORTED before
+ * any launch.  ALQ_EUNSUPPORTED unless the model has a 1x1 conv head of 3 .. 8 channels.                                        */
+int alq_model_set_aleatoric(alq_model *m, int on);
+/* Replaces: sess.run(model.posteriors / model.AU_vals / model.output, ...) of such a model (eval_utils.py:147-198): one forward
+ * pass - dropout arguments as alq_forward_dropout, keep_prob = 1: none - into d_post [c, N V] (or NULL), d_pred (or NULL),
+ * d_au [N V] and d_logits [N V, c + 1] (or NULL).  ALQ_EINVAL: a null m / d_x / d_au, N outside [0, max_batch];
+ * ALQ_EUNSUPPORTED: a model without alq_model_set_aleatoric.                                                                    */
+int alq_forward_au(alq_model *m, const float *d_x, int N, float keep_prob, uint64_t seed, int64_t first_sample,
+                   const int32_t *h_drop_layers, int n_drop_layers, float *d_post, int64_t *d_pred, float *d_au, float *d_logits);
+/* Voxels one sweep of the capped grid of the aleatoric cotangent kernel covers on its 16-byte path. */
+int64_t alq_mt_au_trip_voxels(void);
+/* alq_mt_cotangent / alq_mt_stats with the log-variance plane d_au [R]: d_rows [R, c + 1].  ALQ_EINVAL before any launch: a null
+ * d_au, c outside [2, 7], and the conditions of alq_mt_cotangent.  R % 4 != 0 or a base that is not 16-byte aligned (d_au
+ * included): the guarded one-voxel path.                                                                                        */
+int alq_mt_cotangent_au(alq_ctx *ctx, const float *d_post, const float *d_teacher_post, const float *d_au, int c, int64_t R,
+                        const int32_t *d_labels, const alq_loss_t *loss, float loss_scale, float cons_scale, float au_scale,
+                        float au_log_rel_coeff, int measure, float *d_rows, double *d_stats3);
+int alq_mt_stats_au(alq_ctx *ctx, const float *d_post, const float *d_teacher_post, const float *d_au, int c, int64_t R,
+                    const int32_t *d_labels, const alq_loss_t *loss, float au_log_rel_coeff, int measure, double *d_stats3);
+/* alq_param_grads_loss_mt for a model with alq_model_set_aleatoric: the head's forward launch writes the log-variances, the rows
+ * above go through the existing head backward with c + 1 columns.  d_teacher_post [c, N V]; d_post [c, N V] optional.  The caller
+ * passes cons_scale = coeff 2 / (c V) and au_scale = coeff / V.  ALQ_EINVAL: as alq_mt_cotangent_au and alq_param_grads_loss;
+ * ALQ_EUNSUPPORTED: a model without the flag.  Nothing is launched before the checks pass.                                      */
+int alq_param_grads_loss_mt_au(alq_model *m, const float *d_x, int N, const int32_t *d_labels, const alq_loss_t *loss,
+                               float loss_scale, const float *d_teacher_post, int measure, float cons_scale, float au_scale,
+                               float au_log_rel_coeff, float keep_prob, uint64_t seed, int64_t first_sample,
+                               const int32_t *h_drop_layers, int n_drop_layers, float *d_grads, float *d_post, double *d_stats3);
 /* Replaces: sess.run(model.ema_apply) (tf.train.ExponentialMovingAverage.apply, NN_extended.py:913-926): per element
  * shadow -= (shadow - theta) * (1 - decay), every operation rounded to fp32 (1 - decay included).  ALQ_EINVAL: null pointer
  * with n > 0, n < 0, decay outside [0, 1].                                                                                  */

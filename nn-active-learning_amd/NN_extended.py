@@ -6,7 +6,8 @@ voxel-wise objective of get_FCN_loss, :1285-1335, with `input_vox_weights`), and
 training hyper-parameters of `set_hypers` (NN_extended.py:24-63) that the device step knows:
 losses CE / CE_softclasses / GCE with class, focal and per-sample weights, optimisers SGD / Adam /
 RMSProp, learning-rate schedules; mean-teacher consistency training (`MT_SSL`, NN_extended.py:913-926, :1337-1396) of a
-fully-convolutional model, and the training loop `train` (:928-1009)."""
+fully-convolutional model, with the aleatoric-uncertainty head for unlabelled voxels (`AU_4U`, :265-288, :1376-1383,
+:1551-1554), and the training loop `train` (:928-1009)."""
 import os
 
 import numpy as np
@@ -73,13 +74,25 @@ class CNN(DeviceModel):
         'max_cons_coeff': 1e-3,
         'rampup_length': 5000,
     }
-    REFUSED_WITH_MT = ('AU_4U', 'AU_4L', 'regularizer')
+    # aleatoric uncertainty (NN_extended.py:42-45): AU_4U is built; AU_4L reads an undefined model.MC_probs in the reference
+    # (:1562-1578) and stays refused
+    AU_HYPERS = {'AU_4U': False, 'AU_4L': False, 'AU_log_rel_coeff': 0.1}
+    REFUSED_WITH_MT = ('AU_4L', 'regularizer')
 
     def __init__(self, in_shape, layer_dict, name, skips=[], feature_layer=None, dropout=None,
                  probes=[[], []], sess=None, max_batch=256, **kwargs):
         last = list(layer_dict.values())[-1]
         dense_head = isinstance(last[0], str) and last[0] == 'conv'
         mt = {k: kwargs.pop(k) for k in list(kwargs) if k in self.MT_HYPERS}
+        au = dict(self.AU_HYPERS, **{k: kwargs.pop(k) for k in list(kwargs) if k in self.AU_HYPERS})
+        if au['AU_4L']:
+            raise NotImplementedError('AU_4L: the reference\'s corrupt_output_wAU_4L_FCN reads an undefined model.MC_probs')
+        if au['AU_4U']:
+            if not dense_head:
+                raise NotImplementedError('AU_4U on an fc-head model: the log-variance is a channel of an output map')
+            if int(last[1][0]) < 3:
+                raise NotImplementedError('AU_4U on a head of %d channels: one is the log-variance, and the device head has 2 .. 7 '
+                                          'classes beside it' % int(last[1][0]))
         if mt.get('MT_SSL'):
             for key in self.REFUSED_WITH_MT:
                 if kwargs.get(key):
@@ -92,8 +105,7 @@ class CNN(DeviceModel):
                 if kwargs[key] != 'ReLU':
                     raise NotImplementedError('activation %r: the device layers are ReLU' % (kwargs[key],))
             elif key not in self.DEFAULT_HYPERS:
-                raise NotImplementedError('hyper-parameter %r (regularisers, batch-norm and aleatoric uncertainty are outside '
-                                          'the device step)' % key)
+                raise NotImplementedError('hyper-parameter %r (regularisers and batch-norm are outside the device step)' % key)
         hypers = dict(self.DEFAULT_HYPERS)
         hypers.update(kwargs)
         if mt.get('MT_SSL'):
@@ -122,6 +134,7 @@ class CNN(DeviceModel):
             raise ValueError('lr_schedule is a callable of the step count')
         training = [k for k in kwargs if k != 'activation']
         nclass = int(last[1][0]) if isinstance(last[0], str) else int(last[0])          # either layer-dict schema
+        nclass -= 1 if au['AU_4U'] else 0
         if dense_head and hypers['loss_name'] != 'CE':
             # a fully-convolutional model trains on get_FCN_loss (NN_extended.py:1285-1335), the only FCN loss the reference defines
             raise ValueError('loss_name %r on a fully-convolutional model: its objective is the voxel-wise cross-entropy (CE)'
@@ -130,7 +143,8 @@ class CNN(DeviceModel):
             raise ValueError('bin_class_weights / focal_gamma need a two-class net (where(labels == 1, .[1], .[0])), got %d classes'
                              % nclass)
         super(CNN, self).__init__(sess or default_session(), layer_dict, in_shape, skips, feature_layer,
-                                  dropout, max_batch, name)
+                                  dropout, max_batch, name, aleatoric=bool(au['AU_4U']), au_log_rel_coeff=float(au['AU_log_rel_coeff']))
+        self.AU_4L = False
         if training or self.dense:      # (a dense model always trains on get_FCN_loss: non-zero-weight divisor, voxel weights)
             self.set_hypers(hypers)
         self.MT_SSL = bool(mt.get('MT_SSL'))

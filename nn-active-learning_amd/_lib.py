@@ -114,6 +114,15 @@ _SIGNATURES = {
     'alq_mt_stats': (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, C.POINTER(LossT), C.c_int, _P]),
     'alq_param_grads_loss_mt': (C.c_int, [_P, _P, C.c_int, _P, C.POINTER(LossT), C.c_float, _P, C.c_int, C.c_float, C.c_float,
                                           C.c_uint64, C.c_int64, C.POINTER(C.c_int32), C.c_int, _P, _P, _P]),
+    'alq_dense_head_fwd_au': (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
+    'alq_model_set_aleatoric': (C.c_int, [_P, C.c_int]),
+    'alq_forward_au': (C.c_int, [_P, _P, C.c_int, C.c_float, C.c_uint64, C.c_int64, C.POINTER(C.c_int32), C.c_int, _P, _P, _P, _P]),
+    'alq_mt_au_trip_voxels': (C.c_int64, []),
+    'alq_mt_cotangent_au': (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int64, _P, C.POINTER(LossT), C.c_float, C.c_float, C.c_float, C.c_float,
+                                      C.c_int, _P, _P]),
+    'alq_mt_stats_au': (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int64, _P, C.POINTER(LossT), C.c_float, C.c_int, _P]),
+    'alq_param_grads_loss_mt_au': (C.c_int, [_P, _P, C.c_int, _P, C.POINTER(LossT), C.c_float, _P, C.c_int, C.c_float, C.c_float, C.c_float,
+                                             C.c_float, C.c_uint64, C.c_int64, C.POINTER(C.c_int32), C.c_int, _P, _P, _P]),
     'alq_ema_step': (C.c_int, [_P, _P, _P, C.c_int64, C.c_float]),
     'alq_perturb_input': (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_int64, C.c_int,
                                     C.c_float]),

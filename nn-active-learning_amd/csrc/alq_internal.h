@@ -681,6 +681,10 @@ int k_loss_cotangent(alq_ctx *, const float *post_cN, int c, int N, const int *l
 // added to what is there) and d_dW_db = [dW (Ci c), db (c)] through `part` (ALQ_DENSE_MAX_BLOCKS x (Ci c + c) doubles)
 int k_dense_head_fwd(alq_ctx *, const float *x, long long R, int Ci, int c, const float *W, const float *b, float *post_cR, int64_t *pred,
                      float *z);
+// ... with a log-variance channel behind the c classes (AU_4U): W [Ci, c + 1], b [c + 1], c <= 7; post [c, R] and pred over the classes,
+// au [R] = max(z_c, 0) or null, z [R, c + 1] or null
+int k_dense_head_fwd_au(alq_ctx *, const float *x, long long R, int Ci, int c, const float *W, const float *b, float *post_cR,
+                        int64_t *pred, float *au, float *z);
 int k_dense_head_bwd(alq_ctx *, const float *delta, const float *x, long long R, int Ci, int c, const float *W, float *dx, int accumulate,
                      double *part, float *d_dW_db);
 int k_rmsprop(alq_ctx *, float *theta, const float *g, float *ms, float *mom, long long n, float lr, float decay, float momentum,
@@ -795,6 +799,13 @@ int mt_check(const char *who, const float *post, const float *tpost, int c, long
              int measure);
 int k_mt_cotangent(alq_ctx *, const float *post_cR, const float *tpost_cR, int c, long long R, const int *labels, const alq_loss_t *loss,
                    float loss_scale, float cons_scale, int measure, float *dlogits, double *d_stats3);
+// ... of a head with a log-variance channel behind its c classes (AU_4U): au [R], rows [R, c + 1], the third statistic
+// sum_v (div_v exp(-a_v) + kappa a_v / 2).  mt_check_au: mt_check, a null au and c outside [2, 7].
+int mt_check_au(const char *who, const float *post, const float *tpost, const float *au, int c, long long R, const int32_t *labels,
+                const alq_loss_t *loss, int measure);
+int k_mt_cotangent_au(alq_ctx *, const float *post_cR, const float *tpost_cR, const float *au, int c, long long R, const int *labels,
+                      const alq_loss_t *loss, float loss_scale, float cons_scale, float au_scale, float kappa, int measure, float *dlogits,
+                      double *d_stats3);
 // the counter-based generator of the dropout masks (train.hip) and of the teacher's input noise (mteach.hip)
 __device__ inline unsigned long long tr_splitmix64(unsigned long long x) {
     x += 0x9E3779B97F4A7C15ull;

@@ -4,6 +4,10 @@
 //     pieces, every plane goes out as 16-byte stores; W / b sit in LDS, read as broadcasts.  Voxels past the last whole group
 //     of 4 - or all of them when the planes cannot be stored 16 bytes at a time (R % 4 != 0 or an unaligned buffer: plane j
 //     starts at float j R) - take the guarded one-voxel path.
+//   * dense_head_fwd_au_kernel: the same body for a head of c + 1 channels whose last one is a log-variance (AU_4U,
+//     NN_extended.py:265-288): softmax and first maximum over the first c accumulators, au [R] = max(z_c, 0) as one more plane,
+//     logits [R, c + 1].  Every channel keeps its own chain of fused multiply-adds: the posterior planes carry the bits
+//     dense_head_fwd_kernel writes for W[:, :c], b[:c].
 //   * dense_head_bwd_kernel: one pass over delta [R, c] and x [R, Ci]: dX = delta W^T (16-byte stores, optionally added to
 //     what a skip consumer wrote) and per-workgroup partials of dW = x^T delta, db = sum delta.  A lane owns one 4-channel
 //     piece of a row (consecutive lanes = consecutive 16-byte pieces of x and dX); it takes 4 rows per trip (their loads issued together), sums 64 of its rows in fp32, folds
@@ -30,13 +34,15 @@ struct DenseFwdArgs {
     const float *b;      // [c]
     float *post;         // [c, R]
     long long *pred;     // [R] or null
-    float *z;            // [R, c] or null
+    float *z;            // [R, c] (aleatoric: [R, c + 1]) or null
+    float *au;           // aleatoric: [R] or null
     long long R, groups; // groups of 4 voxels on the 16-byte path
     int Ci;
 };
 
-template <int C>
-__device__ inline void dense_softmax(const float (&zv)[C], float (&p)[C], int *best) {
+// softmax and first maximum over the first C of the CT logits of a voxel
+template <int C, int CT>
+__device__ inline void dense_softmax(const float (&zv)[CT], float (&p)[C], int *best) {
     float mx = zv[0];
 #pragma unroll
     for (int j = 1; j < C; ++j) mx = fmaxf(mx, zv[j]);
@@ -53,30 +59,32 @@ __device__ inline void dense_softmax(const float (&zv)[C], float (&p)[C], int *b
     *best = bj;
 }
 
-template <int C>
-__global__ __launch_bounds__(DENSE_BLOCK) void dense_head_fwd_kernel(DenseFwdArgs a) {
-    __shared__ float sW[DENSE_MAX_CI * C + C];
+// AU = 1: one accumulator more a voxel, the log-variance channel; W [Ci, CT], b [CT]
+template <int C, int AU>
+__device__ __forceinline__ void dense_head_fwd_body(const DenseFwdArgs &a) {
+    constexpr int CT = C + AU;
+    __shared__ float sW[DENSE_MAX_CI * CT + CT];
     const int Ci = a.Ci, nq = Ci / 4;
-    for (int i = threadIdx.x; i < Ci * C + C; i += DENSE_BLOCK) sW[i] = i < Ci * C ? a.W[i] : a.b[i - Ci * C];
+    for (int i = threadIdx.x; i < Ci * CT + CT; i += DENSE_BLOCK) sW[i] = i < Ci * CT ? a.W[i] : a.b[i - Ci * CT];
     __syncthreads();
-    const float *sb = sW + Ci * C;
+    const float *sb = sW + Ci * CT;
     const long long R = a.R, stride = (long long)gridDim.x * DENSE_BLOCK, t0 = blockIdx.x * (long long)DENSE_BLOCK + threadIdx.x;
     const float4 *x4 = reinterpret_cast<const float4 *>(a.x);
     for (long long g = t0; g < a.groups; g += stride) {
         const long long r0 = 4 * g;
-        float acc[4][C];
+        float acc[4][CT];
 #pragma unroll
         for (int v = 0; v < 4; ++v)
 #pragma unroll
-            for (int j = 0; j < C; ++j) acc[v][j] = sb[j];
+            for (int j = 0; j < CT; ++j) acc[v][j] = sb[j];
         for (int q = 0; q < nq; ++q) {
             float4 xv[4];
 #pragma unroll
             for (int v = 0; v < 4; ++v) xv[v] = x4[(r0 + v) * nq + q];
-            const float *w = sW + 4 * q * C;
+            const float *w = sW + 4 * q * CT;
 #pragma unroll
-            for (int j = 0; j < C; ++j) {
-                const float w0 = w[j], w1 = w[C + j], w2 = w[2 * C + j], w3 = w[3 * C + j];
+            for (int j = 0; j < CT; ++j) {
+                const float w0 = w[j], w1 = w[CT + j], w2 = w[2 * CT + j], w3 = w[3 * CT + j];
 #pragma unroll
                 for (int v = 0; v < 4; ++v)
                     acc[v][j] = fmaf(xv[v].w, w3, fmaf(xv[v].z, w2, fmaf(xv[v].y, w1, fmaf(xv[v].x, w0, acc[v][j]))));
@@ -85,10 +93,14 @@ __global__ __launch_bounds__(DENSE_BLOCK) void dense_head_fwd_kernel(DenseFwdArg
         float p[4][C];
         int best[4];
 #pragma unroll
-        for (int v = 0; v < 4; ++v) dense_softmax<C>(acc[v], p[v], &best[v]);
+        for (int v = 0; v < 4; ++v) dense_softmax<C, CT>(acc[v], p[v], &best[v]);
 #pragma unroll
         for (int j = 0; j < C; ++j)
             *reinterpret_cast<float4 *>(a.post + (long long)j * R + r0) = make_float4(p[0][j], p[1][j], p[2][j], p[3][j]);
+        if constexpr (AU != 0)
+            if (a.au)
+                *reinterpret_cast<float4 *>(a.au + r0) = make_float4(fmaxf(acc[0][C], 0.f), fmaxf(acc[1][C], 0.f), fmaxf(acc[2][C], 0.f),
+                                                                     fmaxf(acc[3][C], 0.f));
         if (a.pred) {
             longlong2 *pp = reinterpret_cast<longlong2 *>(a.pred + r0);
             pp[0] = make_longlong2(best[0], best[1]);
@@ -98,32 +110,40 @@ __global__ __launch_bounds__(DENSE_BLOCK) void dense_head_fwd_kernel(DenseFwdArg
 #pragma unroll
             for (int v = 0; v < 4; ++v)
 #pragma unroll
-                for (int j = 0; j < C; ++j) a.z[(r0 + v) * C + j] = acc[v][j];
+                for (int j = 0; j < CT; ++j) a.z[(r0 + v) * CT + j] = acc[v][j];
         }
     }
     // the voxels the groups do not cover, one per lane
     for (long long r = 4 * a.groups + t0; r < R; r += stride) {
-        float zv[C], p[C];
+        float zv[CT], p[C];
 #pragma unroll
-        for (int j = 0; j < C; ++j) zv[j] = sb[j];
+        for (int j = 0; j < CT; ++j) zv[j] = sb[j];
         for (int q = 0; q < nq; ++q) {
             const float4 xv = x4[r * nq + q];
-            const float *w = sW + 4 * q * C;
+            const float *w = sW + 4 * q * CT;
 #pragma unroll
-            for (int j = 0; j < C; ++j)
-                zv[j] = fmaf(xv.w, w[3 * C + j], fmaf(xv.z, w[2 * C + j], fmaf(xv.y, w[C + j], fmaf(xv.x, w[j], zv[j]))));
+            for (int j = 0; j < CT; ++j)
+                zv[j] = fmaf(xv.w, w[3 * CT + j], fmaf(xv.z, w[2 * CT + j], fmaf(xv.y, w[CT + j], fmaf(xv.x, w[j], zv[j]))));
         }
         int best;
-        dense_softmax<C>(zv, p, &best);
+        dense_softmax<C, CT>(zv, p, &best);
 #pragma unroll
         for (int j = 0; j < C; ++j) a.post[(long long)j * R + r] = p[j];
+        if constexpr (AU != 0)
+            if (a.au) a.au[r] = fmaxf(zv[C], 0.f);
         if (a.pred) a.pred[r] = best;
         if (a.z) {
 #pragma unroll
-            for (int j = 0; j < C; ++j) a.z[r * C + j] = zv[j];
+            for (int j = 0; j < CT; ++j) a.z[r * CT + j] = zv[j];
         }
     }
 }
+
+template <int C>
+__global__ __launch_bounds__(DENSE_BLOCK) void dense_head_fwd_kernel(DenseFwdArgs a) { dense_head_fwd_body<C, 0>(a); }
+
+template <int C>
+__global__ __launch_bounds__(DENSE_BLOCK) void dense_head_fwd_au_kernel(DenseFwdArgs a) { dense_head_fwd_body<C, 1>(a); }
 
 static bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
@@ -148,22 +168,48 @@ static int dense_check(const char *who, const float *x, long long R, int Ci, int
     return ALQ_OK;
 }
 
-int k_dense_head_fwd(alq_ctx *ctx, const float *x, long long R, int Ci, int c, const float *W, const float *b, float *post_cR,
-                     int64_t *pred, float *z) {
-    ALQ_TRY(dense_check("dense_head_fwd", x, R, Ci, c));
-    ALQ_REQUIRE(W && b && post_cR, ALQ_EINVAL, "dense_head_fwd: null argument");
+// au_head: W [Ci, c + 1], b [c + 1], the log-variance channel behind the c classes (c <= 7): au [R] or null, z [R, c + 1] or null
+static int dense_fwd_launch(alq_ctx *ctx, bool au_head, const float *x, long long R, int Ci, int c, const float *W, const float *b,
+                            float *post_cR, int64_t *pred, float *au, float *z) {
+    const char *who = au_head ? "dense_head_fwd_au" : "dense_head_fwd";
+    ALQ_TRY(dense_check(who, x, R, Ci, c + (au_head ? 1 : 0)));
+    ALQ_REQUIRE(!au_head || c >= 2, ALQ_EUNSUPPORTED, "%s: %d classes beside the log-variance channel (2 .. %d)", who, c, DENSE_MAX_C - 1);
+    ALQ_REQUIRE(W && b && post_cR, ALQ_EINVAL, "%s: null argument", who);
     DenseFwdArgs a;
-    a.x = x; a.W = W; a.b = b; a.post = post_cR; a.pred = reinterpret_cast<long long *>(pred); a.z = z; a.R = R; a.Ci = Ci;
-    const bool vec = R % 4 == 0 && aligned16(post_cR) && (!pred || aligned16(pred));
+    a.x = x; a.W = W; a.b = b; a.post = post_cR; a.pred = reinterpret_cast<long long *>(pred); a.z = z; a.au = au; a.R = R; a.Ci = Ci;
+    const bool vec = R % 4 == 0 && aligned16(post_cR) && (!pred || aligned16(pred)) && aligned16(au);
     a.groups = vec ? R / 4 : 0;
     const long long lanes = std::max(a.groups, R - 4 * a.groups);
     const unsigned nblk = (unsigned)std::max(1LL, std::min((lanes + DENSE_BLOCK - 1) / DENSE_BLOCK, 65535LL * 16));
-    ProfScope ps(ctx, PROF_ELEMWISE, 2.0 * R * Ci * c);
-#define CALL(CC) hipLaunchKernelGGL(dense_head_fwd_kernel<CC>, dim3(nblk), dim3(DENSE_BLOCK), 0, ctx->stream, a)
-    DENSE_DISPATCH(c, CALL)
+    ProfScope ps(ctx, PROF_ELEMWISE, 2.0 * R * Ci * (c + (au_head ? 1 : 0)));
+    if (au_head) {
+#define CALL(CC) hipLaunchKernelGGL(dense_head_fwd_au_kernel<CC>, dim3(nblk), dim3(DENSE_BLOCK), 0, ctx->stream, a)
+        switch (c) {
+            case 2: CALL(2); break;
+            case 3: CALL(3); break;
+            case 4: CALL(4); break;
+            case 5: CALL(5); break;
+            case 6: CALL(6); break;
+            default: CALL(7); break;
+        }
 #undef CALL
+    } else {
+#define CALL(CC) hipLaunchKernelGGL(dense_head_fwd_kernel<CC>, dim3(nblk), dim3(DENSE_BLOCK), 0, ctx->stream, a)
+        DENSE_DISPATCH(c, CALL)
+#undef CALL
+    }
     ALQ_LAUNCH_CHECK();
     return ALQ_OK;
+}
+
+int k_dense_head_fwd(alq_ctx *ctx, const float *x, long long R, int Ci, int c, const float *W, const float *b, float *post_cR,
+                     int64_t *pred, float *z) {
+    return dense_fwd_launch(ctx, false, x, R, Ci, c, W, b, post_cR, pred, nullptr, z);
+}
+
+int k_dense_head_fwd_au(alq_ctx *ctx, const float *x, long long R, int Ci, int c, const float *W, const float *b, float *post_cR,
+                        int64_t *pred, float *au, float *z) {
+    return dense_fwd_launch(ctx, true, x, R, Ci, c, W, b, post_cR, pred, au, z);
 }
 
 // ------------------------------------------------------------------------------------------ backward
@@ -354,6 +400,13 @@ int alq_dense_head_fwd(alq_ctx *ctx, const float *d_x, int64_t R, int Ci, int c,
     ALQ_REQUIRE(ctx, ALQ_EINVAL, "alq_dense_head_fwd: null context");
     ALQ_HIP(hipSetDevice(ctx->device));
     return alq::k_dense_head_fwd(ctx, d_x, R, Ci, c, d_W, d_b, d_post, d_pred, nullptr);
+}
+
+int alq_dense_head_fwd_au(alq_ctx *ctx, const float *d_x, int64_t R, int Ci, int c, const float *d_W, const float *d_b, float *d_post,
+                          int64_t *d_pred, float *d_au, float *d_logits) {
+    ALQ_REQUIRE(ctx && d_au, ALQ_EINVAL, "alq_dense_head_fwd_au: null context or log-variance plane");
+    ALQ_HIP(hipSetDevice(ctx->device));
+    return alq::k_dense_head_fwd_au(ctx, d_x, R, Ci, c, d_W, d_b, d_post, d_pred, d_au, d_logits);
 }
 
 int alq_dense_head_bwd(alq_ctx *ctx, const float *d_delta, const float *d_x, int64_t R, int Ci, int c, const float *d_W, float *d_dx,

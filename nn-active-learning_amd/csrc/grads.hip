@@ -333,11 +333,15 @@ static int run_hess_vecp(alq_model *m, const float *d_x, int N, const int32_t *d
 }
 
 // posteriors [c, N V] (and predictions, and the logits into the head's output buffer) from the head's input, after run_forward
-int dense_forward_head(alq_model *m, const float *d_x, int N, float *d_post, int64_t *d_pred, bool want_logits) {
+int dense_forward_head(alq_model *m, const float *d_x, int N, float *d_post, int64_t *d_pred, bool want_logits, float *d_au,
+                       float *d_logits) {
     Layer &h = m->layers.back();
     const float *x = m->layers.size() == 1 ? d_x : h.in.p;
-    return k_dense_head_fwd(m->ctx, x, (long long)N * m->V, h.in.C, m->nclass, h.d_W32, h.d_bias, d_post ? d_post : m->post, d_pred,
-                            want_logits ? h.out.p : nullptr);
+    float *z = d_logits ? d_logits : (want_logits ? h.out.p : nullptr);
+    if (m->aleatoric)
+        return k_dense_head_fwd_au(m->ctx, x, (long long)N * m->V, h.in.C, m->nclass - 1, h.d_W32, h.d_bias, d_post ? d_post : m->post, d_pred,
+                                   d_au, z);
+    return k_dense_head_fwd(m->ctx, x, (long long)N * m->V, h.in.C, m->nclass, h.d_W32, h.d_bias, d_post ? d_post : m->post, d_pred, z);
 }
 
 // the head's cotangent rows (m->dlogits) -> the cotangent of its input and its own slice [dW, db] of the flat gradient
@@ -479,6 +483,7 @@ int alq_param_grads_loss(alq_model *m, const float *d_x, int N, const int32_t *d
                          float lwf_scale, float keep_prob, uint64_t seed, int64_t first_sample, const int32_t *h_drop_layers,
                          int n_drop_layers, float *d_grads, float *d_post, double *d_stats3) {
     ALQ_REQUIRE(m && d_grads, ALQ_EINVAL, "alq_param_grads_loss: null argument");
+    ALQ_REFUSE_ALEATORIC(m, "alq_param_grads_loss");
     REQUIRE_BATCH(m, N, "alq_param_grads_loss");
     ALQ_TRY(loss_check("alq_param_grads_loss", d_x, m->nclass, d_labels, loss));
     ALQ_HIP(hipSetDevice(m->ctx->device));
@@ -505,6 +510,7 @@ int alq_param_grads_loss_mt(alq_model *m, const float *d_x, int N, const int32_t
                             int64_t first_sample, const int32_t *h_drop_layers, int n_drop_layers, float *d_grads, float *d_post,
                             double *d_stats3) {
     ALQ_REQUIRE(m && d_grads, ALQ_EINVAL, "alq_param_grads_loss_mt: null argument");
+    ALQ_REFUSE_ALEATORIC(m, "alq_param_grads_loss_mt");
     ALQ_REQUIRE(m->dense, ALQ_EUNSUPPORTED, "alq_param_grads_loss_mt: mean-teacher training is defined for a fully-convolutional model");
     REQUIRE_BATCH(m, N, "alq_param_grads_loss_mt");
     ALQ_TRY(mt_check("alq_param_grads_loss_mt", d_x, d_teacher_post, m->nclass, (long long)N * m->V, d_labels, loss, measure));
@@ -516,6 +522,30 @@ int alq_param_grads_loss_mt(alq_model *m, const float *d_x, int N, const int32_t
     ALQ_TRY(dense_forward_head(m, d_x, N, post, nullptr, false));
     ALQ_TRY(k_mt_cotangent(m->ctx, post, d_teacher_post, m->nclass, (long long)N * m->V, d_labels, loss, loss_scale, cons_scale, measure,
                            m->dlogits, d_stats3));
+    ALQ_TRY(dense_backward_head(m, d_x, N, d_grads, P));
+    if (m->layers.back().pidx > 0) ALQ_TRY(run_backward_general(m, N, &ds));
+    return run_param_grads(m, d_x, N, 1, d_grads, P);
+}
+
+// alq_param_grads_loss_mt of an aleatoric model: the head writes the log-variances beside the posteriors, the cotangent rows have
+// nclass = c + 1 columns, and the head's backward launch takes them as they are
+int alq_param_grads_loss_mt_au(alq_model *m, const float *d_x, int N, const int32_t *d_labels, const alq_loss_t *loss, float loss_scale,
+                               const float *d_teacher_post, int measure, float cons_scale, float au_scale, float au_log_rel_coeff,
+                               float keep_prob, uint64_t seed, int64_t first_sample, const int32_t *h_drop_layers, int n_drop_layers,
+                               float *d_grads, float *d_post, double *d_stats3) {
+    ALQ_REQUIRE(m && d_grads, ALQ_EINVAL, "alq_param_grads_loss_mt_au: null argument");
+    ALQ_REQUIRE(m->aleatoric, ALQ_EUNSUPPORTED, "alq_param_grads_loss_mt_au: the model has no log-variance channel (alq_model_set_aleatoric)");
+    REQUIRE_BATCH(m, N, "alq_param_grads_loss_mt_au");
+    const int c = m->nclass - 1;
+    ALQ_TRY(mt_check_au("alq_param_grads_loss_mt_au", d_x, d_teacher_post, m->au, c, (long long)N * m->V, d_labels, loss, measure));
+    ALQ_HIP(hipSetDevice(m->ctx->device));
+    DropSpec ds;
+    float *post = d_post ? d_post : m->post;
+    ALQ_TRY(general_forward(m, d_x, N, nullptr, &ds, keep_prob, seed, first_sample, h_drop_layers, n_drop_layers));
+    const long long P = alq_model_num_params(m);
+    ALQ_TRY(dense_forward_head(m, d_x, N, post, nullptr, false, m->au));
+    ALQ_TRY(k_mt_cotangent_au(m->ctx, post, d_teacher_post, m->au, c, (long long)N * m->V, d_labels, loss, loss_scale, cons_scale, au_scale,
+                              au_log_rel_coeff, measure, m->dlogits, d_stats3));
     ALQ_TRY(dense_backward_head(m, d_x, N, d_grads, P));
     if (m->layers.back().pidx > 0) ALQ_TRY(run_backward_general(m, N, &ds));
     return run_param_grads(m, d_x, N, 1, d_grads, P);

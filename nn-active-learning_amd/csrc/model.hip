@@ -1281,6 +1281,32 @@ extern "C" {
 
 int alq_model_out_voxels(const alq_model *m) { return m ? (int)m->V : ALQ_EINVAL; }
 
+int alq_model_set_aleatoric(alq_model *m, int on) {
+    ALQ_REQUIRE(m, ALQ_EINVAL, "alq_model_set_aleatoric: null model");
+    ALQ_REQUIRE(m->dense && m->nclass >= 3, ALQ_EUNSUPPORTED,
+                "alq_model_set_aleatoric: a log-variance channel needs a 1x1 conv head of 3 .. 8 channels (2 .. 7 classes beside it)");
+    if (on && !m->au) {
+        ALQ_HIP(hipSetDevice(m->ctx->device));
+        ALQ_TRY(m->dalloc(&m->au, (size_t)m->max_batch * m->V));
+    }
+    m->aleatoric = on != 0;
+    return ALQ_OK;
+}
+
+int alq_forward_au(alq_model *m, const float *d_x, int N, float keep_prob, uint64_t seed, int64_t first_sample,
+                   const int32_t *h_drop_layers, int n_drop_layers, float *d_post, int64_t *d_pred, float *d_au, float *d_logits) {
+    ALQ_REQUIRE(m && d_x && d_au, ALQ_EINVAL, "alq_forward_au: null argument");
+    ALQ_REQUIRE(m->aleatoric, ALQ_EUNSUPPORTED, "alq_forward_au: the model has no log-variance channel (alq_model_set_aleatoric)");
+    ALQ_REQUIRE(N >= 0 && N <= m->max_batch, ALQ_EINVAL, "alq_forward_au: N=%d exceeds max_batch=%d", N, m->max_batch);
+    if (N == 0) return ALQ_OK;
+    ALQ_HIP(hipSetDevice(m->ctx->device));
+    DropSpec ds;
+    ALQ_TRY(make_drop(m, keep_prob, seed, first_sample, h_drop_layers, n_drop_layers, &ds));
+    ALQ_TRY(prepare_call(m, /*fisher=*/false));
+    ALQ_TRY(run_forward(m, d_x, N, false, /*keep_all=*/true, &ds));
+    return dense_forward_head(m, d_x, N, d_post, d_pred, false, d_au, d_logits);
+}
+
 int alq_forward_dropout(alq_model *m, const float *d_x, int N, float keep_prob, uint64_t seed, int64_t first_sample,
                         const int32_t *h_drop_layers, int n_drop_layers, float *d_post, int64_t *d_pred) {
     ALQ_REQUIRE(m && d_x, ALQ_EINVAL, "alq_forward_dropout: null argument");

@@ -140,6 +140,8 @@ struct alq_model {
     int nclass = 0;
     bool dense = false;            // fully-convolutional: the last layer is a 1x1 conv head, every voxel of its output is a sample
     int64_t V = 1;                 // samples (voxels of the head's output) per patch; 1 for an fc head
+    bool aleatoric = false;        // alq_model_set_aleatoric: the head's last channel is a log-variance (AU_4U), nclass - 1 classes
+    float *au = nullptr;           // ... [max_batch V]: its ReLU of the running pass
     double *dh_part = nullptr;     // dense head backward: per-workgroup partials of dW and db (dense.hip)
     int L = 0;
     std::vector<alq::Layer> layers;
@@ -228,6 +230,11 @@ int gemm_launch(alq_ctx *ctx, const alq::Gemm &g, const alq::View &in, const alq
 alq::View flat_view(const alq::View &v);
 
 // ---- grads.hip, for the entry points of model.hip: the head of a fully-convolutional model, and the refusal of the fc-only calls
-int dense_forward_head(alq_model *m, const float *d_x, int N, float *d_post, int64_t *d_pred, bool want_logits);
+// (an aleatoric model: posteriors [nclass - 1, N V] and predictions over the classes; d_au [N V] and d_logits [N V, nclass] optional)
+int dense_forward_head(alq_model *m, const float *d_x, int N, float *d_post, int64_t *d_pred, bool want_logits, float *d_au = nullptr,
+                       float *d_logits = nullptr);
+#define ALQ_REFUSE_ALEATORIC(m, who)                                                                                           \
+    ALQ_REQUIRE(!(m) || !(m)->aleatoric, ALQ_EUNSUPPORTED,                                                                      \
+                "%s: the model's head has a log-variance channel (alq_model_set_aleatoric): alq_param_grads_loss_mt_au", who)
 #define ALQ_REFUSE_DENSE(m, who)                                                                                                \
     ALQ_REQUIRE(!(m) || !(m)->dense, ALQ_EUNSUPPORTED, "%s: not defined for a fully-convolutional model (1x1 conv head)", who)

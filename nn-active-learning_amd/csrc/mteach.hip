@@ -8,6 +8,13 @@
 //     come in as 16-byte pieces, the 4 c floats of its rows go out as c plain 16-byte stores (global stores through a pointer:
 //     not the register-offset buffer stores of alq_internal.h's hazard note).  R % 4 != 0 or an unaligned base: every voxel
 //     takes the guarded one-voxel path, as in dense_head_fwd_kernel.  At most ALQ_MT_MAX_BLOCKS workgroups, grid-stride beyond.
+//   * mt_cotangent_au_kernel<C>: the same pass for a head of c + 1 channels whose last one, through a ReLU, is a per-voxel
+//     log-variance a (AU_4U, NN_extended.py:265-288, :1376-1383, :1551-1554): one plane more comes in (a [R]), the consistency
+//     value of a voxel is div e + kappa a / 2 with e = exp(-a), its rows [R, c + 1] are
+//         k < c:  [labelled row] + k e p_k (d_k - sum_j p_j d_j)  (L2; CE: the labelled row alone)
+//         c:      a > 0 ? k_au (kappa / 2 - div e) : 0            (TF's ReluGrad; both measures)
+//     and go out as c + 1 16-byte stores a lane.  Both kernels are one body (mt_body<C, AU>): with a = 0 and kappa = 0 the
+//     columns below c and the statistics are mt_cotangent_kernel's, operation for operation.
 //   * mt_finish_kernel: the partials into the three statistics: lane t adds partials t, t + 256, ... in that order, the lanes
 //     fold in a fixed tree.  No atomics anywhere: bit-identical from run to run.
 //   * ema_step_kernel: tf.train.ExponentialMovingAverage's update, shadow -= (shadow - theta) * (1 - decay), in fp32.
@@ -38,15 +45,18 @@ struct MtArgs {
     long long R, groups;      // groups of 4 voxels on the 16-byte path
     float gamma, s, k;
     int measure;
+    const float *au;          // aleatoric kernel: the student's log-variances [R], >= 0
+    float kau, kappa;         // ... the scale of their column and AU_log_rel_coeff
 };
 
 __device__ inline double mt_logp(float p) { return log((double)fmaxf(p, 1e-38f)); }
 
 // One voxel: its row (when wanted) and its three statistics.  The labelled part is loss_cotangent_kernel's CE branch operation
 // for operation; with a.k == 0 the row is that kernel's, bit for bit.
-template <int C>
-__device__ inline void mt_voxel(const MtArgs &a, const float (&p)[C], const float (&q)[C], int y, float swv, float (&row)[C], double &sl,
-                                double &sc, double &sd) {
+// AU: `av` is the voxel's log-variance, row has the column C of it, and the third statistic is the consistency value div e + kappa av / 2.
+template <int C, int AU>
+__device__ inline void mt_voxel(const MtArgs &a, const float (&p)[C], const float (&q)[C], int y, float swv, float av, float (&row)[C + AU],
+                                double &sl, double &sc, double &sd) {
     const bool lab = y >= 0 && y < C;
     double mul = 0;
     if (lab) {
@@ -80,21 +90,25 @@ __device__ inline void mt_voxel(const MtArgs &a, const float (&p)[C], const floa
 #pragma unroll
         for (int j = 0; j < C; ++j) div -= (double)p[j] * mt_logp(q[j]);
     }
-    sd += div;
+    const double e = AU ? exp(-(double)av) : 1.0;
+    sd += AU ? div * e + (0.5 * (double)a.kappa) * (double)av : div;
     if (!a.dl) return;
     const bool cons = a.k != 0.f && a.measure == ALQ_MT_L2;
+    const double ke = AU ? (double)a.k * e : (double)a.k;
 #pragma unroll
     for (int j = 0; j < C; ++j) {
         const float base = lab ? (p[j] - (j == y ? 1.f : 0.f)) * a.s : 0.f;
         float d;
-        if (cons) d = (float)((double)base * mul + (double)a.k * (double)p[j] * (((double)p[j] - (double)q[j]) - dot));      // one rounding of both terms
+        if (cons) d = (float)((double)base * mul + ke * (double)p[j] * (((double)p[j] - (double)q[j]) - dot));      // one rounding of both terms
         else d = (lab && mul != 1.0) ? (float)((double)base * mul) : base;
         row[j] = d;
     }
+    if constexpr (AU != 0) row[C] = av > 0.f ? (float)((double)a.kau * (0.5 * (double)a.kappa - div * e)) : 0.f;      // ReluGrad: g * (x > 0)
 }
 
-template <int C>
-__global__ __launch_bounds__(MT_BLOCK) void mt_cotangent_kernel(MtArgs a) {
+template <int C, int AU>
+__device__ __forceinline__ void mt_body(const MtArgs &a) {
+    constexpr int CT = C + AU;      // floats of a row
     __shared__ double sh[3][MT_BLOCK];
     const long long R = a.R, stride = (long long)gridDim.x * MT_BLOCK, t0 = blockIdx.x * (long long)MT_BLOCK + threadIdx.x;
     double sl = 0, sc = 0, sd = 0;
@@ -108,9 +122,11 @@ __global__ __launch_bounds__(MT_BLOCK) void mt_cotangent_kernel(MtArgs a) {
         }
         const int4 yv = *reinterpret_cast<const int4 *>(a.labels + r0);
         const float4 wv = a.sw ? *reinterpret_cast<const float4 *>(a.sw + r0) : make_float4(1.f, 1.f, 1.f, 1.f);
+        const float4 uv = AU ? *reinterpret_cast<const float4 *>(a.au + r0) : make_float4(0.f, 0.f, 0.f, 0.f);
         const int ys[MT_VOX] = {yv.x, yv.y, yv.z, yv.w};
         const float ws[MT_VOX] = {wv.x, wv.y, wv.z, wv.w};
-        float rows[MT_VOX][C];
+        const float us[MT_VOX] = {uv.x, uv.y, uv.z, uv.w};
+        float rows[MT_VOX][CT];
 #pragma unroll
         for (int v = 0; v < MT_VOX; ++v) {
             float p[C], q[C];
@@ -119,28 +135,28 @@ __global__ __launch_bounds__(MT_BLOCK) void mt_cotangent_kernel(MtArgs a) {
                 p[j] = v == 0 ? pv[j].x : (v == 1 ? pv[j].y : (v == 2 ? pv[j].z : pv[j].w));
                 q[j] = v == 0 ? qv[j].x : (v == 1 ? qv[j].y : (v == 2 ? qv[j].z : qv[j].w));
             }
-            mt_voxel<C>(a, p, q, ys[v], ws[v], rows[v], sl, sc, sd);
+            mt_voxel<C, AU>(a, p, q, ys[v], ws[v], us[v], rows[v], sl, sc, sd);
         }
-        if (a.dl) {      // the rows of voxels r0 .. r0 + 3 are 4 C consecutive floats
-            float4 *out = reinterpret_cast<float4 *>(a.dl + r0 * C);
+        if (a.dl) {      // the rows of voxels r0 .. r0 + 3 are 4 CT consecutive floats
+            float4 *out = reinterpret_cast<float4 *>(a.dl + r0 * CT);
 #pragma unroll
-            for (int i = 0; i < C; ++i)      // flat element f = v C + j of the lane's 4 rows
-                out[i] = make_float4(rows[(4 * i) / C][(4 * i) % C], rows[(4 * i + 1) / C][(4 * i + 1) % C], rows[(4 * i + 2) / C][(4 * i + 2) % C],
-                                     rows[(4 * i + 3) / C][(4 * i + 3) % C]);
+            for (int i = 0; i < CT; ++i)      // flat element f = v CT + j of the lane's 4 rows
+                out[i] = make_float4(rows[(4 * i) / CT][(4 * i) % CT], rows[(4 * i + 1) / CT][(4 * i + 1) % CT],
+                                     rows[(4 * i + 2) / CT][(4 * i + 2) % CT], rows[(4 * i + 3) / CT][(4 * i + 3) % CT]);
         }
     }
     // the voxels the groups do not cover, one per lane
     for (long long r = MT_VOX * a.groups + t0; r < R; r += stride) {
-        float p[C], q[C], row[C];
+        float p[C], q[C], row[CT];
 #pragma unroll
         for (int j = 0; j < C; ++j) {
             p[j] = a.p[(long long)j * R + r];
             q[j] = a.q[(long long)j * R + r];
         }
-        mt_voxel<C>(a, p, q, a.labels[r], a.sw ? a.sw[r] : 1.f, row, sl, sc, sd);
+        mt_voxel<C, AU>(a, p, q, a.labels[r], a.sw ? a.sw[r] : 1.f, AU ? a.au[r] : 0.f, row, sl, sc, sd);
         if (a.dl) {
 #pragma unroll
-            for (int j = 0; j < C; ++j) a.dl[r * C + j] = row[j];
+            for (int j = 0; j < CT; ++j) a.dl[r * CT + j] = row[j];
         }
     }
     sh[0][threadIdx.x] = sl; sh[1][threadIdx.x] = sc; sh[2][threadIdx.x] = sd;
@@ -155,6 +171,12 @@ __global__ __launch_bounds__(MT_BLOCK) void mt_cotangent_kernel(MtArgs a) {
     }
     if (threadIdx.x < 3) a.part[blockIdx.x * 3 + threadIdx.x] = sh[threadIdx.x][0];
 }
+
+template <int C>
+__global__ __launch_bounds__(MT_BLOCK) void mt_cotangent_kernel(MtArgs a) { mt_body<C, 0>(a); }
+
+template <int C>
+__global__ __launch_bounds__(MT_BLOCK) void mt_cotangent_au_kernel(MtArgs a) { mt_body<C, 1>(a); }
 
 __global__ __launch_bounds__(MT_BLOCK) void mt_finish_kernel(const double *part, int nblk, double *stats) {
     __shared__ double sh[3][MT_BLOCK];
@@ -189,30 +211,46 @@ int mt_check(const char *who, const float *post, const float *tpost, int c, long
     return ALQ_OK;
 }
 
-int k_mt_cotangent(alq_ctx *ctx, const float *post_cR, const float *tpost_cR, int c, long long R, const int *labels,
-                   const alq_loss_t *loss, float loss_scale, float cons_scale, int measure, float *dlogits, double *d_stats3) {
+// au null: mt_cotangent_kernel, rows [R, c]; else mt_cotangent_au_kernel, rows [R, c + 1] (c <= 7)
+static int mt_launch(alq_ctx *ctx, const float *post_cR, const float *tpost_cR, const float *au, int c, long long R, const int *labels,
+                     const alq_loss_t *loss, float loss_scale, float cons_scale, float au_scale, float kappa, int measure, float *dlogits,
+                     double *d_stats3) {
     if (!ctx->mt_part) ALQ_HIP(hipMalloc(&ctx->mt_part, (size_t)ALQ_MT_MAX_BLOCKS * 3 * sizeof(double)));
     MtArgs a;
     a.p = post_cR; a.q = tpost_cR; a.labels = labels; a.sw = loss->d_sample_w; a.cw = loss->d_class_w; a.dl = dlogits;
     a.part = ctx->mt_part; a.R = R; a.gamma = loss->focal_gamma; a.s = loss_scale; a.k = cons_scale; a.measure = measure;
+    a.au = au; a.kau = au_scale; a.kappa = kappa;
     const bool vec = R % MT_VOX == 0 && aligned16(post_cR) && aligned16(tpost_cR) && aligned16(labels) && aligned16(loss->d_sample_w) &&
-                     aligned16(dlogits);
+                     aligned16(dlogits) && aligned16(au);
     a.groups = vec ? R / MT_VOX : 0;
     const long long lanes = std::max(a.groups, R - MT_VOX * a.groups);
     const int nblk = (int)std::max(1LL, std::min((lanes + MT_BLOCK - 1) / MT_BLOCK, (long long)ALQ_MT_MAX_BLOCKS));
     {
         ProfScope ps(ctx, PROF_ELEMWISE, 0);
 #define CALL(CC) hipLaunchKernelGGL(mt_cotangent_kernel<CC>, dim3((unsigned)nblk), dim3(MT_BLOCK), 0, ctx->stream, a)
-        switch (c) {
-            case 2: CALL(2); break;
-            case 3: CALL(3); break;
-            case 4: CALL(4); break;
-            case 5: CALL(5); break;
-            case 6: CALL(6); break;
-            case 7: CALL(7); break;
-            default: CALL(8); break;
+#define CALL_AU(CC) hipLaunchKernelGGL(mt_cotangent_au_kernel<CC>, dim3((unsigned)nblk), dim3(MT_BLOCK), 0, ctx->stream, a)
+        if (au) {
+            switch (c) {
+                case 2: CALL_AU(2); break;
+                case 3: CALL_AU(3); break;
+                case 4: CALL_AU(4); break;
+                case 5: CALL_AU(5); break;
+                case 6: CALL_AU(6); break;
+                default: CALL_AU(7); break;
+            }
+        } else {
+            switch (c) {
+                case 2: CALL(2); break;
+                case 3: CALL(3); break;
+                case 4: CALL(4); break;
+                case 5: CALL(5); break;
+                case 6: CALL(6); break;
+                case 7: CALL(7); break;
+                default: CALL(8); break;
+            }
         }
 #undef CALL
+#undef CALL_AU
         ALQ_LAUNCH_CHECK();
     }
     if (d_stats3) {
@@ -221,6 +259,24 @@ int k_mt_cotangent(alq_ctx *ctx, const float *post_cR, const float *tpost_cR, in
         ALQ_LAUNCH_CHECK();
     }
     return ALQ_OK;
+}
+
+int k_mt_cotangent(alq_ctx *ctx, const float *post_cR, const float *tpost_cR, int c, long long R, const int *labels,
+                   const alq_loss_t *loss, float loss_scale, float cons_scale, int measure, float *dlogits, double *d_stats3) {
+    return mt_launch(ctx, post_cR, tpost_cR, nullptr, c, R, labels, loss, loss_scale, cons_scale, 0.f, 0.f, measure, dlogits, d_stats3);
+}
+
+int mt_check_au(const char *who, const float *post, const float *tpost, const float *au, int c, long long R, const int32_t *labels,
+                const alq_loss_t *loss, int measure) {
+    ALQ_REQUIRE(au, ALQ_EINVAL, "%s: the log-variance plane is missing", who);
+    ALQ_REQUIRE(c >= 2 && c <= 7, ALQ_EINVAL, "%s: %d classes beside the log-variance channel (2 .. 7)", who, c);
+    return mt_check(who, post, tpost, c, R, labels, loss, measure);
+}
+
+int k_mt_cotangent_au(alq_ctx *ctx, const float *post_cR, const float *tpost_cR, const float *au, int c, long long R, const int *labels,
+                      const alq_loss_t *loss, float loss_scale, float cons_scale, float au_scale, float kappa, int measure, float *dlogits,
+                      double *d_stats3) {
+    return mt_launch(ctx, post_cR, tpost_cR, au, c, R, labels, loss, loss_scale, cons_scale, au_scale, kappa, measure, dlogits, d_stats3);
 }
 
 // ------------------------------------------------------------------------------------------ the teacher's weights
@@ -304,6 +360,27 @@ int alq_mt_stats(alq_ctx *ctx, const float *d_post, const float *d_teacher_post,
     ALQ_TRY(alq::mt_check("alq_mt_stats", d_post, d_teacher_post, c, R, d_labels, loss, measure));
     ALQ_HIP(hipSetDevice(ctx->device));
     return alq::k_mt_cotangent(ctx, d_post, d_teacher_post, c, R, d_labels, loss, 1.f, 0.f, measure, nullptr, d_stats3);
+}
+
+int64_t alq_mt_au_trip_voxels(void) { return alq_mt_trip_voxels(); }
+
+int alq_mt_cotangent_au(alq_ctx *ctx, const float *d_post, const float *d_teacher_post, const float *d_au, int c, int64_t R,
+                        const int32_t *d_labels, const alq_loss_t *loss, float loss_scale, float cons_scale, float au_scale,
+                        float au_log_rel_coeff, int measure, float *d_rows, double *d_stats3) {
+    ALQ_REQUIRE(ctx && d_rows && d_stats3, ALQ_EINVAL, "alq_mt_cotangent_au: null argument");
+    ALQ_TRY(alq::mt_check_au("alq_mt_cotangent_au", d_post, d_teacher_post, d_au, c, R, d_labels, loss, measure));
+    ALQ_HIP(hipSetDevice(ctx->device));
+    return alq::k_mt_cotangent_au(ctx, d_post, d_teacher_post, d_au, c, R, d_labels, loss, loss_scale, cons_scale, au_scale, au_log_rel_coeff,
+                                  measure, d_rows, d_stats3);
+}
+
+int alq_mt_stats_au(alq_ctx *ctx, const float *d_post, const float *d_teacher_post, const float *d_au, int c, int64_t R,
+                    const int32_t *d_labels, const alq_loss_t *loss, float au_log_rel_coeff, int measure, double *d_stats3) {
+    ALQ_REQUIRE(ctx && d_stats3, ALQ_EINVAL, "alq_mt_stats_au: null argument");
+    ALQ_TRY(alq::mt_check_au("alq_mt_stats_au", d_post, d_teacher_post, d_au, c, R, d_labels, loss, measure));
+    ALQ_HIP(hipSetDevice(ctx->device));
+    return alq::k_mt_cotangent_au(ctx, d_post, d_teacher_post, d_au, c, R, d_labels, loss, 1.f, 0.f, 0.f, au_log_rel_coeff, measure, nullptr,
+                                  d_stats3);
 }
 
 int alq_ema_step(alq_ctx *ctx, float *d_shadow, const float *d_theta, int64_t n, float decay) {

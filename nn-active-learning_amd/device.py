@@ -740,7 +740,7 @@ class DeviceModel(object):
     grad_posts, var_dict, dropout_rate`) over a libalq model."""
 
     def __init__(self, sess, layer_dict, in_shape, skips=(), feature_layer=None, dropout=None,
-                 max_batch=256, name='model'):
+                 max_batch=256, name='model', aleatoric=False, au_log_rel_coeff=0.1):
         self.sess = sess
         self.lib = sess.lib
         self.name = name
@@ -775,6 +775,13 @@ class DeviceModel(object):
         self._create_env = {k: v for k, v in os.environ.items() if k.startswith('ALQ_')}     # engine switches are read at creation
         self.L = self.lib.alq_model_num_param_layers(self._m)
         self.nclass = self.layers[-1]['cout']
+        # AU_4U (NN_extended.py:265-288): the head's last channel, through a ReLU, is a per-voxel log-variance; class_num = cout - 1
+        self.AU_4U = bool(aleatoric)
+        self.AU_log_rel_coeff = float(au_log_rel_coeff)
+        if self.AU_4U:
+            check(self.lib.alq_model_set_aleatoric(self._m, 1))
+            self.nclass -= 1
+        self.class_num = self.nclass
         # a fully-convolutional model (1x1 conv head, csrc/dense.hip): every voxel of the head's output map is a sample
         self.dense = self.layers[-1]['type'] == ALQ_CONV
         self.out_voxels = int(self.lib.alq_model_out_voxels(self._m))
@@ -801,6 +808,9 @@ class DeviceModel(object):
         self.feature_layer = Handle('feature_layer', (fdim,))
         for h in (self.posteriors, self.prediction, self.feature_layer):
             h.model = self
+        if self.AU_4U:
+            self.AU_vals, self.output = Handle('AU_vals'), Handle('output')          # [n, *spatial] and [n, *spatial, c + 1]
+            self.AU_vals.model = self.output.model = self
         # 2L opaque entries per class, so that len(model.grad_posts['1'])/2 == L (PW_NNAL.py:751)
         self.var_dict = LazyVarDict((n, None) for n in self.var_names)
         # Weights that are already in device memory are packed there (alq_model_set_weights_device): per parameterised layer,
@@ -1104,6 +1114,9 @@ class DeviceModel(object):
             optimizer_name = h.get('optimizer_name', 'SGD')
         if optimizer_name not in ('SGD', 'Adam', 'RMSProp'):
             raise NotImplementedError('optimizer %r (SGD, Adam and RMSProp are known)' % (optimizer_name,))
+        if self.AU_4U and self._mt is None:
+            raise NotImplementedError('an AU_4U model trains with MT_SSL: its log-variance channel has a gradient only under the '
+                                      'consistency term')
         schedule = None
         if learning_rate is None:
             learning_rate = h.get('learning_rate')
@@ -1150,7 +1163,7 @@ class DeviceModel(object):
         if getattr(self, 'teacher', None) is not None:      # (a second get_optimizer(): a new teacher, as a new graph would hold)
             self.teacher.close()
         self.teacher = DeviceModel(self.sess, self.layer_dict, self.in_shape, self.skips, None, drop, self.max_batch,
-                                   self.name + '_teacher')
+                                   self.name + '_teacher', aleatoric=self.AU_4U, au_log_rel_coeff=self.AU_log_rel_coeff)
         self.perturbed_x = Handle('perturbed_x')
         for nme in ('ema_apply', 'labeled_loss', 'cons_loss'):
             h = Handle(nme)
@@ -1205,8 +1218,10 @@ class DeviceModel(object):
         the gradient is n grad L + cons_coeff sum_i grad cons_i.  Per cut of max_batch: perturb the cut, the teacher's forward
         pass at its own keep_prob, alq_param_grads_loss_mt.  `feed`: dict(kp = the teacher's keep_prob, px = a fed
         perturbed_x or None).  The labelled scale is n / (non-zero weights of the whole batch), the consistency scale
-        cons_coeff 2 / (c V) per voxel (L2; CE adds to the value only).  Returns (gradient or None, loss) and leaves
-        (L, mean_i cons_i, cons_coeff) in self._mt['last']."""
+        cons_coeff 2 / (c V) per voxel (L2; CE adds to the value only).  An AU_4U model takes the _au entry points: the
+        consistency value of a voxel is div exp(-a) + AU_log_rel_coeff a / 2 and its log-variance column has the scale
+        cons_coeff / V under both measures.  Returns (gradient or None, loss) and leaves (L, mean_i cons_i, cons_coeff) in
+        self._mt['last']."""
         from . import losses, mteach
         torch = self.sess.torch
         self.sess.bind_stream()
@@ -1236,6 +1251,7 @@ class DeviceModel(object):
         self._mt_shadow()
         coeff = mteach.cons_coeff(self.global_step, mt['rampup'], mt['max_coeff'])
         kscale = coeff * 2. / (c * V) if mt['measure'] == mteach.L2 else 0.
+        au_on, kappa = self.AU_4U, self.AU_log_rel_coeff
         cuts = [(a, min(n, a + self.max_batch)) for a in range(0, n, self.max_batch)]
         xb = lambda src, a: C.c_void_p(src.data_ptr() + a * self.elems_per_patch * 4)
         spec = lambda a: LossT(losses.CE, -1. if gamma is None else gamma, obj['q'], 1., cw.data_ptr() if cw is not None else None,
@@ -1248,8 +1264,13 @@ class DeviceModel(object):
             check(self.lib.alq_forward_dropout(T._m, xb(pin, 0), b - a, tkp, tseed, a, tarr, tnl, C.c_void_p(tq.data_ptr()), None))
             return tq
 
-        def student_post(a, b):
+        def student_post(a, b, want_au=False):
             pb = self.sess.empty((c, (b - a) * V), torch.float32)
+            if want_au:
+                au = self.sess.empty(((b - a) * V,), torch.float32)
+                check(self.lib.alq_forward_au(self._m, xb(t, a), b - a, kp, seed, a, arr, nl, C.c_void_p(pb.data_ptr()), None,
+                                              C.c_void_p(au.data_ptr()), None))
+                return pb, au
             check(self.lib.alq_forward_dropout(self._m, xb(t, a), b - a, kp, seed, a, arr, nl, C.c_void_p(pb.data_ptr()), None))
             return pb
 
@@ -1273,14 +1294,27 @@ class DeviceModel(object):
             for k, (a, b) in enumerate(cuts):
                 g = self.sess.empty((self.num_params,), torch.float32)
                 tq, L = teacher_post(a, b), spec(a)
-                check(self.lib.alq_param_grads_loss_mt(self._m, xb(t, a), b - a, C.c_void_p(labd.data_ptr() + a * V * 4), C.byref(L), float(s),
-                                                       C.c_void_p(tq.data_ptr()), mt['measure'], float(kscale), kp, seed, a, arr, nl,
-                                                       C.c_void_p(g.data_ptr()), None, C.c_void_p(stats.data_ptr() + k * 24)))
+                if au_on:
+                    check(self.lib.alq_param_grads_loss_mt_au(self._m, xb(t, a), b - a, C.c_void_p(labd.data_ptr() + a * V * 4), C.byref(L),
+                                                              float(s), C.c_void_p(tq.data_ptr()), mt['measure'], float(kscale),
+                                                              float(coeff / V), kappa, kp, seed, a, arr, nl, C.c_void_p(g.data_ptr()), None,
+                                                              C.c_void_p(stats.data_ptr() + k * 24)))
+                else:
+                    check(self.lib.alq_param_grads_loss_mt(self._m, xb(t, a), b - a, C.c_void_p(labd.data_ptr() + a * V * 4), C.byref(L),
+                                                           float(s), C.c_void_p(tq.data_ptr()), mt['measure'], float(kscale), kp, seed, a, arr,
+                                                           nl, C.c_void_p(g.data_ptr()), None, C.c_void_p(stats.data_ptr() + k * 24)))
                 gsum += g
         else:
             gsum = None
             for k, (a, b) in enumerate(cuts):
-                tq, pb, L = teacher_post(a, b), student_post(a, b), spec(a)
+                tq, L = teacher_post(a, b), spec(a)
+                if au_on:
+                    pb, au = student_post(a, b, True)
+                    check(self.lib.alq_mt_stats_au(self.sess.ctx, C.c_void_p(pb.data_ptr()), C.c_void_p(tq.data_ptr()), C.c_void_p(au.data_ptr()),
+                                                   c, (b - a) * V, C.c_void_p(labd.data_ptr() + a * V * 4), C.byref(L), kappa, mt['measure'],
+                                                   C.c_void_p(stats.data_ptr() + k * 24)))
+                    continue
+                pb = student_post(a, b)
                 check(self.lib.alq_mt_stats(self.sess.ctx, C.c_void_p(pb.data_ptr()), C.c_void_p(tq.data_ptr()), c, (b - a) * V,
                                             C.c_void_p(labd.data_ptr() + a * V * 4), C.byref(L), mt['measure'],
                                             C.c_void_p(stats.data_ptr() + k * 24)))
@@ -1948,6 +1982,24 @@ class DeviceModel(object):
         maps = post.reshape((self.nclass, n) + self.out_map_shape).movedim(0, -1)
         return maps, (pred.reshape((n,) + self.out_map_shape) if pred is not None else None)
 
+    def forward_au_device(self, t, n, keep_prob=1., seed=None, want_output=True):
+        """An AU_4U model's `AU_vals` [n, *spatial] and `output` [n, *spatial, c + 1] (or None) on the device: alq_forward_au over
+        passes of max_batch; keep_prob < 1 drops as forward_dropout_device does ('MC-sigma')."""
+        if not self.AU_4U:
+            raise NotImplementedError('forward_au_device: the model has no aleatoric-uncertainty head (AU_4U)')
+        torch = self.sess.torch
+        self.sess.bind_stream()
+        kp, arr, nl, seed = self._drop_args(keep_prob, seed)
+        V, ct = self.out_voxels, self.nclass + 1
+        au = self.sess.empty((n * V,), torch.float32)
+        out = self.sess.empty((n * V, ct), torch.float32) if want_output else None
+        for a in range(0, n, self.max_batch):
+            b = min(n, a + self.max_batch)
+            check(self.lib.alq_forward_au(self._m, C.c_void_p(t.data_ptr() + a * self.elems_per_patch * 4), b - a, kp, seed, a, arr, nl,
+                                          None, None, C.c_void_p(au.data_ptr() + a * V * 4),
+                                          C.c_void_p(out.data_ptr() + a * V * ct * 4) if want_output else None))
+        return au.reshape((n,) + self.out_map_shape), (out.reshape((n,) + self.out_map_shape + (ct,)) if want_output else None)
+
     def _run_dense(self, fetch, feed_dict, x, kp, iw):
         """sess.run of a dense model: `posteriors` [n, *spatial, c], `prediction` [n, *spatial], `feature_layer`, `loss` and
         `train_step` with `y_` one-hot [n, *spatial, c] (an all-zero row: unlabelled voxel, NN_extended.py:1291-1293) and
@@ -1959,6 +2011,10 @@ class DeviceModel(object):
             return (pred if name == 'prediction' else maps.contiguous()).cpu().numpy()
         if name == 'feature_layer':
             return self.forward(x, want=(name,), keep_prob=kp)[name]
+        if name in ('AU_vals', 'output') and self.AU_4U:
+            t, n = self._as_device_batch(x)
+            au, out = self.forward_au_device(t, n, kp, want_output=name == 'output')
+            return (au if name == 'AU_vals' else out).cpu().numpy()
         mt_on = self._mt is not None and getattr(self, 'teacher', None) is not None
         if name not in ('loss', 'train_step') + (('labeled_loss', 'cons_loss') if mt_on else ()):
             raise NotImplementedError('sess.run(model.%s) is not defined for a fully-convolutional model (1x1 conv head)' % name)

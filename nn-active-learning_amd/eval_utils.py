@@ -42,10 +42,14 @@ def full_slice_segment(model, sess, img_paths_or_mats, data_reader, op='predicti
     op: 'prediction' -> (h, w, z) argmax of the posteriors; 'posterior' -> (c, h, w, z); 'MC-posterior' -> (c, h, w, z), the
     running mean of MC_PASSES passes at keep_prob = 1 - model.dropout_rate; 'loss' -> the slice-weighted running mean of
     model.loss (needs `mask`: the (h, w, z) label volume, fed one-hot under model.y_; a model whose loss takes no labels may
-    leave it out).  The aleatoric-uncertainty ops of the reference ('output', 'AU_vals', 'sigma', 'MC-sigma') are not built."""
-    if op in ('output', 'AU_vals', 'sigma', 'MC-sigma'):
-        raise NotImplementedError('op %r: aleatoric-uncertainty outputs are outside the device model' % (op,))
-    if op not in ('prediction', 'posterior', 'MC-posterior', 'loss'):
+    leave it out).  A model with AU_4U true (eval_utils.py:147-198): 'AU_vals' -> (h, w, z), the log-variance map; 'output' ->
+    (c + 1, h, w, z), the head's raw channels; 'sigma' -> (c, h, w, z), the raw log-variance channel broadcast over c as the
+    reference's assignment does; 'MC-sigma' -> the same of its running mean over MC_PASSES dropout passes.  These four run
+    through sess.run and are assembled on the host; any other model: NotImplementedError."""
+    au_op = op in ('output', 'AU_vals', 'sigma', 'MC-sigma')
+    if au_op and not getattr(model, 'AU_4U', False):
+        raise NotImplementedError('op %r needs a model with AU_4U (an aleatoric-uncertainty head)' % (op,))
+    if not au_op and op not in ('prediction', 'posterior', 'MC-posterior', 'loss'):
         raise ValueError('unknown op %r' % (op,))
     imgs = _load_volumes(img_paths_or_mats, data_reader)
     m = len(imgs)
@@ -53,14 +57,16 @@ def full_slice_segment(model, sess, img_paths_or_mats, data_reader, op='predicti
     hx, wx = int(model.in_shape[0]), int(model.in_shape[1])
     assert h == hx and w == wx, 'Shape of data and model.x should match.'
     c = int(getattr(model, 'class_num', getattr(model, 'nclass', 0)))
-    dev = _on_device(model) and op != 'loss'
+    dev = _on_device(model) and op != 'loss' and not au_op
     if dev:
         torch = sess.torch
         vols = sess.to_device(np.stack([np.asarray(v, dtype=np.float32) for v in imgs], axis=-1), torch.float32)      # (h, w, z, m)
         out = torch.zeros((h, w, z), dtype=torch.int64, device=vols.device) if op == 'prediction' else \
             torch.zeros((c, h, w, z), dtype=torch.float32, device=vols.device)
-    elif op == 'prediction':
+    elif op in ('prediction', 'AU_vals'):
         out = np.zeros((h, w, z))
+    elif op == 'output':
+        out = np.zeros((c + 1, h, w, z))
     elif op == 'loss':
         out, seen = 0., 0
     else:
@@ -89,6 +95,20 @@ def full_slice_segment(model, sess, img_paths_or_mats, data_reader, op='predicti
             val = float(sess.run(model.loss, feed_dict=feed))
             out = (len(inds) * val + seen * out) / (seen + len(inds))
             seen += len(inds)
+            continue
+        if au_op:
+            kp = 1. - float(model.dropout_rate) if op == 'MC-sigma' else 1.
+            fetch = model.AU_vals if op == 'AU_vals' else model.output
+            run = lambda: np.asarray(sess.run(fetch, feed_dict={model.x: batch_X, model.keep_prob: kp}))
+            if op == 'AU_vals':
+                out[:, :, inds] = np.transpose(run(), (1, 2, 0))
+                continue
+            P = run()
+            if op != 'output':          # the one raw channel behind the classes, [b, h, w, 1]
+                P = P[..., c:]
+                for i in range(1, MC_PASSES if op == 'MC-sigma' else 1):
+                    P = (i * P + run()[..., c:]) / (i + 1)
+            out[:, :, :, inds] = np.transpose(P, (3, 1, 2, 0))          # ('sigma': broadcast over the c planes)
             continue
         if op == 'MC-posterior':
             kp = 1. - float(model.dropout_rate)

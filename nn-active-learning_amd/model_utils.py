@@ -20,6 +20,34 @@ def diagonal_Fisher(model, sess, batch_dat):
     return model.diagonal_fisher(np.asarray(x), labels)
 
 
+def extend_weights_to_aleatoric_mode(weights_path, out_channels, last_layer_name='last'):
+    """model_utils.extend_weights_to_aleatoric_mode (model_utils.py:14-48): a copy of the weight file whose last layer has
+    `out_channels` output channels, the new ones zero, every other layer as it was; written next to the file as
+    '<name>_extended' + its suffix (.npz, or .h5 with h5py) and its path returned.  A last layer that already has that many:
+    nothing is written, None.  The reference always doubles the channels (the AU_4L layout) and reads `out_channels` only
+    for that check; for out_channels = 2 c the files agree.  The added log-variance channel sits at x == 0, where ReluGrad
+    is 0: it trains only once its bias is made positive, in the reference as here."""
+    import os
+    from . import weights_io
+    pars = weights_io.read_weights(weights_path, weights_io.layer_names(weights_path))
+    W, b = (np.asarray(v) for v in pars[last_layer_name])
+    c = W.shape[-1]
+    if c == int(out_channels):
+        print('The weights already match the extended shape.')
+        return None
+    if int(out_channels) < c:
+        raise ValueError('the last layer has %d output channels, more than %d' % (c, out_channels))
+    ext_W = np.zeros(W.shape[:-1] + (int(out_channels),), dtype=W.dtype)
+    ext_W[..., :c] = W
+    ext_b = np.zeros((int(out_channels),) + b.shape[1:], dtype=b.dtype)
+    ext_b[:c] = b
+    pars[last_layer_name] = [ext_W, ext_b]
+    root, ext = os.path.splitext(str(weights_path))
+    new_path = root + '_extended' + ext
+    weights_io.write_weights(new_path, pars)
+    return new_path
+
+
 def keep_k_largest_from_LoV(LoV, k):
     """model_utils.keep_k_largest_from_LoV (model_utils.py:54-83): a binary mask with the structure of the list of
     variables `LoV`, 1 on the k largest values over all of them, and the positions in the list that hold a 1.

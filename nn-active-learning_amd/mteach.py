@@ -46,6 +46,37 @@ def evaluate(post, tpost, labels, measure, loss_scale=1., cons_scale=0., class_w
                 stats=(lab['stats'][0], lab['stats'][1], float(div.sum())))
 
 
+def consistency_au(post, tpost, au, measure, cons_scale=0., au_scale=0., kappa=0.1):
+    """The consistency term of a head with an aleatoric-uncertainty channel (AU_4U, NN_extended.py:265-288, :1551-1554): au [R]
+    is the student's log-variance a = relu(z_c) >= 0 and, with e = exp(-a), a voxel's value is cons = div e + kappa a / 2.
+    (div [R], cons [R], rows [R, c + 1]) in fp64: columns k < c are consistency's rows times e (CE: zero), column c is
+    au_scale (kappa / 2 - div e) where a > 0 and 0 elsewhere (TF's ReluGrad is g * (x > 0))."""
+    a = np.asarray(au)
+    a64 = a.astype(np.float64)
+    e = np.exp(-a64)
+    div, _ = consistency(post, tpost, measure)
+    kap = float(np.float32(kappa))
+    p64 = np.asarray(post).astype(np.float64)
+    rows = np.zeros((a.shape[0], p64.shape[0] + 1))
+    if measure == L2:          # the order of the products is the device's: ((cons_scale e) p_k) (d_k - sum_j p_j d_j)
+        d = p64 - np.asarray(tpost).astype(np.float64)
+        rows[:, :-1] = (float(cons_scale) * e * p64 * (d - (p64 * d).sum(0, keepdims=True))).T
+    rows[:, -1] = np.where(a > 0, float(au_scale) * (0.5 * kap - div * e), 0.)
+    return div, div * e + (0.5 * kap) * a64, rows
+
+
+def evaluate_au(post, tpost, au, labels, measure, loss_scale=1., cons_scale=0., au_scale=0., kappa=0.1, class_w=None, sample_w=None,
+                focal_gamma=None):
+    """The rows [R, c + 1] and statistics alq_mt_cotangent_au writes: the labelled rows of `evaluate` on the c clean logits (the
+    log-variance column gets none) plus consistency_au's.  dict(rows, labelled_rows, cons_rows, div [R], cons [R], stats = (sum l,
+    number of non-zero weights, sum cons))."""
+    lab = losses.evaluate(post, labels, losses.CE, class_w=class_w, sample_w=sample_w, focal_gamma=focal_gamma, loss_scale=loss_scale)
+    div, cons, crow = consistency_au(post, tpost, au, measure, cons_scale, au_scale, kappa)
+    lrow = np.concatenate([lab['rows'], np.zeros((crow.shape[0], 1))], axis=1)
+    return dict(rows=lrow + crow, labelled_rows=lrow, cons_rows=crow, div=div, cons=cons,
+                stats=(lab['stats'][0], lab['stats'][1], float(cons.sum())))
+
+
 def ema_step(shadow, theta, decay):
     """tf.train.ExponentialMovingAverage's update in fp32, every operation rounded: shadow - (shadow - theta) * (1 - decay)."""
     s, t = np.asarray(shadow, dtype=np.float32), np.asarray(theta, dtype=np.float32)

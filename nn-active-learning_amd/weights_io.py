@@ -49,6 +49,20 @@ def _pick(group, want, layer, path):
     raise KeyError('%s: layer group %r has no dataset %r (found %s)' % (path, layer, want, sorted(group.keys())))
 
 
+def layer_names(path):
+    """The layers a weight file holds, in the file's order."""
+    if is_h5(path):
+        h5py = _need_h5py(path)
+        with h5py.File(path, 'r') as f:
+            return list(f.keys())
+    names = []
+    for k in np.load(path).files:
+        n = k.rsplit('/', 1)[0]
+        if n not in names:
+            names.append(n)
+    return names
+
+
 def read_weights(path, layer_names):
     """{layer: [W, b]} for `layer_names` from an HDF5 file of the reference or its .npz twin."""
     if is_h5(path):

@@ -8,10 +8,15 @@
      (32 bytes per voxel: two posteriors of each model, label, weight, two row entries), its statistics-only form, the
      existing loss_cotangent_kernel in ITS statistics-only form on the same columns (alq_loss_stats: it reads half the planes
      and writes no rows), and a device-to-device copy of the kernel's bytes in the same process.
+  2b. The aleatoric-uncertainty kernels (AU_4U): mt_cotangent_au_kernel against the fp64 statement on the first 2^18 voxels, and
+     in `--rounds` alternating rounds its time against mt_cotangent_kernel at the same R and c (40 against 32 bytes per voxel at
+     c = 2: 4 (2c + 1) + 8 read and 4 (c + 1) written against 8c + 8 and 4c), dense_head_fwd_au_kernel at c classes against
+     dense_head_fwd_kernel at c + 1 outputs (the same bytes), and device copies of each kernel's bytes.  The spread max / min of
+     the parent kernel's round medians is the noise floor the ratios are read against.
   3. One mean-teacher step (train_step + ema_apply) of net_c_dense at 32^3, N = `--batch`, against the plain dense step of a
      model built without MT_SSL, alternating, host clock around a device synchronise.
 
-    python tools/gpu_mteach.py [--reps 20] [--warmup 5] [--batch 64] [--skip-step] [--out mteach.json]
+    python tools/gpu_mteach.py [--reps 20] [--warmup 5] [--rounds 5] [--batch 64] [--skip-step] [--out mteach.json]
 
 Prints one JSON line at the end."""
 import argparse
@@ -33,6 +38,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--rounds', type=int, default=5)
     ap.add_argument('--batch', type=int, default=64)
     ap.add_argument('--skip-step', action='store_true')
     ap.add_argument('--out', default=None)
@@ -104,7 +110,60 @@ def main():
                                ratio_to_old_stats=res['mt_cotangent']['us_median'] / res['loss_stats_old_kernel']['us_median'])
     print('mt_cotangent: %.1f MB = %.0f GB/s; kernel / copy = %.2f; kernel / old statistics-only kernel = %.2f'
           % (nbytes / 1e6, res['mt_cotangent']['gbps_median'], res['mt_cotangent']['ratio_to_copy'], res['mt_cotangent']['ratio_to_old_stats']))
-    del src, dst, p, q, rows
+    del src, dst
+
+    # ---- the aleatoric-uncertainty kernels
+    kappa, kau, Ci = 0.1, float(np.float32(1. / 32 ** 3)), 16
+    au = (torch.clamp(torch.randn((R,), generator=g), min=0.) * 2.).to(dev)
+    rows_au = torch.empty((R, c + 1), dtype=torch.float32, device=dev)
+    xh = torch.randn((R, Ci), generator=g).to(dev)
+    Wh, bh = (0.5 * torch.randn((Ci, c + 1), generator=g)).to(dev), torch.randn((c + 1,), generator=g).to(dev)
+    post_h = torch.empty((c + 1, R), dtype=torch.float32, device=dev)
+    au_h = torch.empty((R,), dtype=torch.float32, device=dev)
+
+    def cot_au():
+        check(sess.lib.alq_mt_cotangent_au(sess.ctx, P(p), P(q), P(au), c, R, P(lab), C.byref(L), s, k, kau, kappa, mteach.L2, P(rows_au), P(st)))
+
+    def head_au():
+        check(sess.lib.alq_dense_head_fwd_au(sess.ctx, P(xh), R, Ci, c, P(Wh), P(bh), P(post_h), None, P(au_h), None))
+
+    def head():
+        check(sess.lib.alq_dense_head_fwd(sess.ctx, P(xh), R, Ci, c + 1, P(Wh), P(bh), P(post_h), None))
+
+    cot_au()
+    torch.cuda.synchronize()
+    ref = mteach.evaluate_au(p[:, :n].cpu().numpy(), q[:, :n].cpu().numpy(), au[:n].cpu().numpy(), lab[:n].cpu().numpy(), mteach.L2, s, k, kau,
+                             kappa, cw32, sw[:n].cpu().numpy(), 2.)
+    mag = np.abs(ref['labelled_rows']) + np.abs(ref['cons_rows'])
+    mag[:, c] = kau * (0.5 * float(np.float32(kappa)) + ref['div'] * np.exp(-au[:n].cpu().numpy().astype(np.float64)))
+    err = np.abs(rows_au[:n].cpu().numpy().astype(np.float64) - ref['rows'])
+    res['au_row_err_over_bound'] = float((err / np.maximum(4 * 2. ** -24 * mag, 1e-300)).max())
+    print('aleatoric cotangent: worst row error / bound %.3f' % res['au_row_err_over_bound'])
+    nb = {'mt_cotangent': (8 * c + 8 + 4 * c) * R, 'mt_cotangent_au': (4 * (2 * c + 1) + 8 + 4 * (c + 1)) * R,
+          'dense_head_fwd': (4 * Ci + 4 * (c + 1)) * R}
+    nb['dense_head_fwd_au'] = nb['dense_head_fwd']
+    bufs = {kk: (torch.empty((v // 8,), dtype=torch.float32, device=dev).normal_(), torch.empty((v // 8,), dtype=torch.float32, device=dev))
+            for kk, v in nb.items() if kk != 'dense_head_fwd_au'}
+    bufs['dense_head_fwd_au'] = bufs['dense_head_fwd']
+    fns = {'mt_cotangent': cot, 'mt_cotangent_au': cot_au, 'dense_head_fwd': head, 'dense_head_fwd_au': head_au}
+    meds = {kk: [] for kk in list(fns) + ['copy_' + kk for kk in fns]}
+    for _ in range(a.rounds):          # alternating rounds: drift of a shared machine falls on every kernel alike
+        for kk, fn in fns.items():
+            meds[kk].append(timed(torch, fn, a.warmup, a.reps)[0])
+            meds['copy_' + kk].append(timed(torch, lambda: bufs[kk][1].copy_(bufs[kk][0]), a.warmup, a.reps)[0])
+    au_res = {kk: dict(us_median=float(np.median(v)), us_rounds=[float(t) for t in v], spread=float(max(v) / min(v))) for kk, v in meds.items()}
+    for kk in fns:
+        au_res[kk].update(bytes=nb[kk], gbps_median=nb[kk] / au_res[kk]['us_median'] / 1e3,
+                          ratio_to_copy=au_res[kk]['us_median'] / au_res['copy_' + kk]['us_median'])
+    for new, old in (('mt_cotangent_au', 'mt_cotangent'), ('dense_head_fwd_au', 'dense_head_fwd')):
+        au_res[new].update(ratio_to_parent=au_res[new]['us_median'] / au_res[old]['us_median'], byte_ratio=nb[new] / nb[old],
+                           parent_spread=au_res[old]['spread'])
+        print('%s: %.1f us median = %.0f GB/s, kernel / copy %.2f; parent %s %.1f us (kernel / copy %.2f); time ratio %.3f, byte ratio '
+              '%.3f, spread of the parent\'s %d round medians %.3f'
+              % (new, au_res[new]['us_median'], au_res[new]['gbps_median'], au_res[new]['ratio_to_copy'], old, au_res[old]['us_median'],
+                 au_res[old]['ratio_to_copy'], au_res[new]['ratio_to_parent'], au_res[new]['byte_ratio'], a.rounds, au_res[old]['spread']))
+    res['aleatoric'] = au_res
+    del bufs, p, q, rows, rows_au, xh, post_h, au_h, au
 
     if not a.skip_step:
         N, in_shape = a.batch, (32, 32, 32, 1)
