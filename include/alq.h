@@ -802,6 +802,33 @@ int alq_model_engine_info(alq_model *m, int what);
 int alq_synth_patches(alq_ctx *ctx, uint64_t seed, int64_t first_id, int64_t n,
                       int64_t elems_per_patch, float *d_out);
 
+/* ---- resident volumes and the batches cut from them (csrc/volbatch.hip) ---------------------------------------------------- */
+/* Replaces: the per-sample, per-plane, per-modality loop of datasets/utils.prepare_batch_BrVol and the strided slice reads
+ * `img[:, :, s]` behind it.  A subject is uploaded once, packed once, and a batch is one launch (per 64 samples).
+ *
+ * alq_vol_pack: m device arrays [H, W, Z] in C order (z fastest) of `src_type` -> d_out [Z, H, W, m] floats; dims = {H, W, Z}.
+ * double rounds to nearest even once, the integer types are exact.  alq_mask_pack: a class-id volume of bytes [H, W, Z] ->
+ * [Z, H, W] (255: no class).  ALQ_EINVAL: a null pointer, an axis below 1, another src_type; ALQ_EUNSUPPORTED: m above 8.   */
+enum { ALQ_SRC_F32 = 0, ALQ_SRC_F64 = 1, ALQ_SRC_I16 = 2, ALQ_SRC_U8 = 3 };
+int alq_vol_pack(alq_ctx *ctx, const void *const *d_src, int m, int src_type, const int32_t *dims, float *d_out);
+int alq_mask_pack(alq_ctx *ctx, const uint8_t *d_src, const int32_t *dims, uint8_t *d_out);
+/* alq_slice_batch: b windows of crop = {z, h, w} voxels out of nvol packed subjects.  h_vols / h_masks: HOST arrays [nvol] of the
+ * device pointers alq_vol_pack / alq_mask_pack filled (a mask may be NULL for a subject no labelled sample names), h_dims host
+ * [nvol][3] = {H, W, Z} of each, h_desc host [b][5] = (subject, zc, h0, w0, labelled 0 / 1).  Outputs:
+ *   d_X [b, z, h, w, m] floats, X[i, jz, r, s, j] = vol[zc - z/2 + jz, h0 + r, w0 + s, j];
+ *   d_lab [b, z, h, w] int32: the mask byte, or -1 where the sample is unlabelled or the byte is >= C;
+ *   d_counts int64 [C + 1]: the voxels of every class, the -1 voxels last (zeroed by the call).
+ * Every descriptor is checked on the host before anything is launched or written (alq_slice_batch_check, the same check without
+ * a device): subject in range, 0 <= zc - z/2, zc - z/2 + z <= Z, 0 <= h0, h0 + h <= H, 0 <= w0, w0 + w <= W, the flag 0 or 1,
+ * 1 <= C <= 254, a crop axis below 1: ALQ_EINVAL.  Stream-ordered, no synchronisation; the host arrays are read before return.
+ * alq_slice_batch_trip_rows: the output rows (i, jz, r) one sweep of the capped grid covers; alq_slice_batch_launch_samples: the
+ * samples of one launch (for tests: a case asserts from these that it passes them).                                             */
+int alq_slice_batch_check(const int32_t *h_dims, int nvol, const int32_t *h_desc, int b, const int32_t *crop, int C);
+int alq_slice_batch(alq_ctx *ctx, const float *const *h_vols, const uint8_t *const *h_masks, const int32_t *h_dims, int nvol, int m,
+                    const int32_t *h_desc, int b, const int32_t *crop, int C, float *d_X, int32_t *d_lab, int64_t *d_counts);
+int64_t alq_slice_batch_trip_rows(void);
+int alq_slice_batch_launch_samples(void);
+
 #ifdef __cplusplus
 }
 #endif

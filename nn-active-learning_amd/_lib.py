@@ -158,6 +158,13 @@ _SIGNATURES = {
     'alq_aopt_direction': (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P, _P, _P, _P, C.c_double, C.c_double, C.c_double, _P, _P, _P]),
     'alq_aopt_linesearch': (C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_int, _P, _P]),
     'alq_aopt_update': (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int, C.c_double, _P, _P]),
+    'alq_vol_pack': (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.POINTER(C.c_int32), _P]),
+    'alq_mask_pack': (C.c_int, [_P, _P, C.POINTER(C.c_int32), _P]),
+    'alq_slice_batch_check': (C.c_int, [C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.c_int]),
+    'alq_slice_batch': (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int,
+                                  C.POINTER(C.c_int32), C.c_int, _P, _P, _P]),
+    'alq_slice_batch_trip_rows': (C.c_int64, []),
+    'alq_slice_batch_launch_samples': (C.c_int, []),
     'alq_comm_unique_id': (C.c_int, [_P]),
     'alq_comm_init': (C.c_int, [_P, _P, C.c_int, C.c_int]),
     'alq_comm_destroy': (C.c_int, [_P]),

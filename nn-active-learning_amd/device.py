@@ -1230,11 +1230,15 @@ class DeviceModel(object):
         c, V = self.nclass, self.out_voxels
         ns = n * V
         t = t.reshape(n, -1)
-        y = np.asarray(y)
-        if y.shape != (c, ns):
-            raise ValueError('labels must be [%d, %d] columns, got %r' % (c, ns, y.shape))
-        lab = np.where(y.sum(0) > 0, y.argmax(0), -1).astype(np.int32)
-        labd = self.sess.to_device(lab, torch.int32)
+        counts = None
+        if self._is_device_labels(y):
+            lab, labd, counts = self._device_label_feed(y, ns, input_weights is not None)
+        else:
+            y = np.asarray(y)
+            if y.shape != (c, ns):
+                raise ValueError('labels must be [%d, %d] columns, got %r' % (c, ns, y.shape))
+            lab = np.where(y.sum(0) > 0, y.argmax(0), -1).astype(np.int32)
+            labd = self.sess.to_device(lab, torch.int32)
         sw = None if input_weights is None else np.asarray(input_weights, dtype=np.float32).reshape(ns)
         swd = None if sw is None else self.sess.to_device(sw, torch.float32)
         cw = obj['class_w']
@@ -1276,7 +1280,9 @@ class DeviceModel(object):
 
         stats = torch.zeros((len(cuts), 3), dtype=torch.float64, device=self.sess.device)
         if want_grad:
-            if gamma is None:
+            if gamma is None and lab is None:
+                cnt = float(self._count_from_class_counts(counts, cw))
+            elif gamma is None:
                 w = (lab >= 0).astype(np.float64)
                 if cw is not None:
                     w = w * np.asarray(self.hypers['bin_class_weights'], dtype=np.float32).reshape(2)[np.where(lab == 1, 1, 0)]
@@ -1412,6 +1418,30 @@ class DeviceModel(object):
         y[lab[ok], np.nonzero(ok)[0]] = 1.
         return y
 
+    @staticmethod
+    def _is_device_labels(y):
+        from .datasets.utils import DeviceLabels
+        return isinstance(y, DeviceLabels)
+
+    def _device_label_feed(self, dl, ns, want_host):
+        """The label feed of a dense objective from a datasets.DeviceLabels: (host labels [ns] - only when per-voxel weights
+        need them -, the int32 device labels [ns], the class counts).  No one-hot, no argmax, no upload."""
+        torch = self.sess.torch
+        if not self.dense:
+            raise TypeError('DeviceLabels feed a fully-convolutional model; an fc-head model takes one-hot columns')
+        if dl.C != self.nclass or int(dl.labels.numel()) != ns:
+            raise ValueError('labels must be [%d, %d] columns, got DeviceLabels of %r' % (self.nclass, ns, dl.shape))
+        labd = dl.labels.to(device=self.sess.device, dtype=torch.int32).contiguous().reshape(ns)
+        return (labd.cpu().numpy() if want_host else None), labd, dl.counts
+
+    def _count_from_class_counts(self, counts, cw):
+        """The non-zero weights of a batch from its voxels per class: every labelled voxel, or - with bin_class_weights - those
+        of the classes whose weight is not zero (the integer the host path counts voxel by voxel)."""
+        if cw is None:
+            return int(counts[:self.nclass].sum())
+        bw = np.asarray(self.hypers['bin_class_weights'], dtype=np.float32).reshape(2)
+        return int(counts[0]) * int(bw[0] != 0) + int(counts[1]) * int(bw[1] != 0)
+
     def _objective_pass(self, t, n, y, keep_prob, seed, input_weights, lwf, want_grad=True, mt_feed=None):
         """The model's objective (set_hypers; the batch-mean cross-entropy with divisor n when none is set) on n device patches
         over passes of max_batch: (gradient of the loss, float32 device [P] - None without `want_grad` - and the loss).
@@ -1432,12 +1462,19 @@ class DeviceModel(object):
         obj = self._obj or dict(kind=losses.CE, divisor='nonzero' if self.dense else 'N', q=0.7, gamma=None, class_w=None)
         kind, c, V = obj['kind'], self.nclass, self.out_voxels
         ns = n * V
-        y = np.asarray(y)
-        if y.shape != (c, ns):
-            raise ValueError('labels must be [%d, %d] columns, got %r' % (c, ns, y.shape))
-        lab = np.where(y.sum(0) > 0, y.argmax(0), -1).astype(np.int32)
-        labd = self.sess.to_device(lab, torch.int32)
-        tgd = self.sess.to_device(y.astype(np.float32), torch.float32) if kind != losses.CE else None
+        counts = None
+        if self._is_device_labels(y):
+            if kind != losses.CE:
+                raise TypeError('DeviceLabels are class ids: the objective reads soft targets')
+            lab, labd, counts = self._device_label_feed(y, ns, input_weights is not None)
+            tgd = None
+        else:
+            y = np.asarray(y)
+            if y.shape != (c, ns):
+                raise ValueError('labels must be [%d, %d] columns, got %r' % (c, ns, y.shape))
+            lab = np.where(y.sum(0) > 0, y.argmax(0), -1).astype(np.int32)
+            labd = self.sess.to_device(lab, torch.int32)
+            tgd = self.sess.to_device(y.astype(np.float32), torch.float32) if kind != losses.CE else None
         sw = None if input_weights is None else np.asarray(input_weights, dtype=np.float32).reshape(ns)
         swd = None if sw is None else self.sess.to_device(sw, torch.float32)
         cw = obj['class_w']
@@ -1474,6 +1511,9 @@ class DeviceModel(object):
             s = 1.           # reduce_mean over the classes leaves a vector over samples: the optimiser differentiates its sum
         elif obj['divisor'] == 'N':
             s = 1. / ns
+        elif gamma is None and lab is None:
+            cnt = self._count_from_class_counts(counts, cw)
+            s = 1. / cnt if cnt else 0.
         elif gamma is None:
             w = (lab >= 0).astype(np.float64)
             if cw is not None:
@@ -1537,9 +1577,14 @@ class DeviceModel(object):
             raise RuntimeError('get_optimizer() has not been called (NN.py:1354)')
         torch = self.sess.torch
         t, n = self._as_device_batch(x)
-        y = np.asarray(y_onehot)
-        if y.shape != (self.nclass, n * self.out_voxels):
-            raise ValueError('labels must be [%d, %d] one-hot columns, got %r' % (self.nclass, n * self.out_voxels, y.shape))
+        if self._is_device_labels(y_onehot):          # (a dense model's labels from datasets: checked where they are read)
+            if not self.dense:
+                raise TypeError('DeviceLabels feed a fully-convolutional model; an fc-head model takes one-hot columns')
+            y = y_onehot
+        else:
+            y = np.asarray(y_onehot)
+            if y.shape != (self.nclass, n * self.out_voxels):
+                raise ValueError('labels must be [%d, %d] one-hot columns, got %r' % (self.nclass, n * self.out_voxels, y.shape))
         self._check_input_weights(input_weights)
         if self._obj is not None or lwf is not None or self.dense:
             gsum, loss = self._objective_pass(t, n, y, keep_prob, seed, input_weights, lwf, mt_feed=mt_feed)
@@ -2003,7 +2048,8 @@ class DeviceModel(object):
     def _run_dense(self, fetch, feed_dict, x, kp, iw):
         """sess.run of a dense model: `posteriors` [n, *spatial, c], `prediction` [n, *spatial], `feature_layer`, `loss` and
         `train_step` with `y_` one-hot [n, *spatial, c] (an all-zero row: unlabelled voxel, NN_extended.py:1291-1293) and
-        `input_vox_weights` [n, *spatial]."""
+        `input_vox_weights` [n, *spatial].  A datasets.DeviceLabels under `y_` (labels [n, *spatial] built on the device) is read in
+        place: no one-hot, no argmax, no upload; the non-zero-weight count comes from its class counts."""
         name = fetch.name
         if name in ('posteriors', 'prediction'):
             t, n = self._as_device_batch(x)
@@ -2018,11 +2064,13 @@ class DeviceModel(object):
         mt_on = self._mt is not None and getattr(self, 'teacher', None) is not None
         if name not in ('loss', 'train_step') + (('labeled_loss', 'cons_loss') if mt_on else ()):
             raise NotImplementedError('sess.run(model.%s) is not defined for a fully-convolutional model (1x1 conv head)' % name)
-        y = np.asarray(feed_dict[self.y_])
+        y = feed_dict[self.y_]
+        on_device = self._is_device_labels(y)          # datasets.DeviceLabels: the labels stay where they are
+        y = y if on_device else np.asarray(y)
         n = int(np.asarray(x).shape[0]) if not isinstance(x, self.sess.torch.Tensor) else int(x.shape[0])
         if tuple(y.shape) != (n,) + self.out_map_shape + (self.nclass,):
             raise ValueError('y_ must be one-hot %r, got %r' % ((n,) + self.out_map_shape + (self.nclass,), tuple(y.shape)))
-        ycols = np.ascontiguousarray(y.reshape(-1, self.nclass).T)
+        ycols = y if on_device else np.ascontiguousarray(y.reshape(-1, self.nclass).T)
         if iw is not None:
             iw = np.asarray(iw)
             if tuple(iw.shape) != (n,) + self.out_map_shape:
