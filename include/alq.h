@@ -217,6 +217,25 @@ int alq_committee_update(alq_ctx *ctx, const float *d_p1, int64_t n, int member,
 int alq_eval_counts(alq_ctx *ctx, const int64_t *d_pred, const int64_t *d_inds, int64_t n, const void *d_mask,
                     int mask_is_f64, int64_t mask_elems, int64_t *d_counts, uint8_t *d_seg);
 
+/* Multi-class confusion counts over resident label maps (csrc/confusion.hip).
+ * Replaces: the two np.argmax, the concatenation and the NumPy counting of eval_utils.eval_metrics (eval_utils.py:55-98) and the
+ * per-partition np.sum(preds*labels) of eval_utils.eval_full_segs_explicit_partitions / _label_percentage (:240-363).
+ * d_pred, d_lab: n ids each, uint8, int32 or int64 (the ALQ_IDS_* of their own).  For element i, with j = first + i and
+ * g = (j / inner) % groups: t = lab[i], replaced by `fill` when t lies outside [0, C) and 0 <= fill < C; the element is
+ * skipped when t (after that) or p = pred[i] lies outside [0, C); otherwise d_counts[g][t][p] += 1.
+ * d_counts: int64 [groups, C, C]; the call ADDS (the caller zeroes).  d_skipped (optional): int64 [1], += skipped elements.
+ *   whole batch: inner = n, groups = 1;  per sample of [b, h, w]: inner = h w, groups = b;
+ *   per axial slice of an [H, W, Z] volume in C order: inner = 1, groups = Z;  per slice of a packed [Z, H, W]: inner = H W,
+ *   groups = Z.  `first` makes a chunked sequence of calls equal to one call.
+ * 1 <= C <= 16, inner >= 1, groups >= 1, first >= 0, n >= 0 (n = 0: nothing is done).  Integer sums: exact and bit-identical
+ * whatever the chunking, the grid or the launch order.  groups C^2 cells beyond the kernel's histogram: one launch per window of
+ * alq_confusion_window(C) groups (0 for a C out of range).  Stream-ordered, no synchronisation.  ALQ_EINVAL before any launch:
+ * a null pointer (d_skipped aside), an unknown type, a bound broken, a pointer not aligned to its element.                    */
+enum { ALQ_IDS_U8 = 0, ALQ_IDS_I32 = 1, ALQ_IDS_I64 = 2 };
+int alq_confusion_counts(alq_ctx *ctx, const void *d_pred, int pred_type, const void *d_lab, int lab_type, int64_t n, int64_t first,
+                         int64_t inner, int64_t groups, int C, int fill, int64_t *d_counts, int64_t *d_skipped);
+int alq_confusion_window(int C);
+
 /* Multi-GPU top-B merge step (no reference counterpart: the reference is one process).
  * Host function: merges the candidate (key, GLOBAL index) pairs gathered from all ranks
  * (torch.distributed all_gather over RCCL in pool_shard.merge_topB; entries with index < 0 are padding)
@@ -586,6 +605,17 @@ int alq_cc_label(alq_ctx *ctx, const uint8_t *d_seg, const int64_t dims[3], int 
 int alq_cc_keep_largest(alq_ctx *ctx, const uint8_t *d_seg, const int64_t dims[3], int connectivity, int skip_origin, uint8_t *d_out,
                         int64_t *d_info, void *d_work);
 int alq_fill_holes(alq_ctx *ctx, const uint8_t *d_seg, const int64_t dims[3], uint8_t *d_out, int64_t *d_info, void *d_work);
+/* Sizes of every component and relabelling by a table (datasets/lesion_utils.py: find_lesion_components,
+ * drop_lesions_with_threshold).  d_labels: int32 [n] as alq_cc_label wrote it (the root of the voxel's component, or -1).
+ *   alq_cc_sizes    d_sizes int32 [n]: at every root voxel the size of its component, 0 elsewhere (the call zeroes it).  One
+ *                   atomic per run of equal labels inside a wave, the runs of one root summed in the wave first: exact.
+ *   alq_cc_relabel  exactly one output: d_out_i32[v] = label < 0 ? 0 : d_table[label] (d_table int32 [n], e.g. ranks), or
+ *                   d_out_u8[v] = label >= 0 && d_sizes[label] >= min_size.  A label of n or above reads nothing and gives 0.
+ * 0 <= n < 2^31 (n = 0: nothing is done).  ALQ_EINVAL: a null pointer, both or neither outputs, the table its output needs
+ * missing, n out of range.  Stream-ordered, no synchronisation.                                                              */
+int alq_cc_sizes(alq_ctx *ctx, const int32_t *d_labels, int64_t n, int32_t *d_sizes);
+int alq_cc_relabel(alq_ctx *ctx, const int32_t *d_labels, int64_t n, const int32_t *d_table, const int32_t *d_sizes, int32_t min_size,
+                   int32_t *d_out_i32, uint8_t *d_out_u8);
 
 /* ---- dense CRF on a two-class posterior map: exact mean-field inference (csrc/dcrf.hip) --------------------------------- */
 /* Replaces: PW_analyze_results.DCRF_postprocess_2D (PW_analyze_results.py:539-591), pydensecrf's DenseCRF2D with 2 labels, a

@@ -141,6 +141,10 @@ _SIGNATURES = {
     'alq_cc_label': (C.c_int, [_P, _P, C.POINTER(C.c_int64), C.c_int, C.c_int, _P]),
     'alq_cc_keep_largest': (C.c_int, [_P, _P, C.POINTER(C.c_int64), C.c_int, C.c_int, _P, _P, _P]),
     'alq_fill_holes': (C.c_int, [_P, _P, C.POINTER(C.c_int64), _P, _P, _P]),
+    'alq_cc_sizes': (C.c_int, [_P, _P, C.c_int64, _P]),
+    'alq_cc_relabel': (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32, _P, _P]),
+    'alq_confusion_counts': (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, _P, _P]),
+    'alq_confusion_window': (C.c_int, [C.c_int]),
     'alq_dcrf_work_bytes': (C.c_size_t, [C.POINTER(C.c_int64)]),
     'alq_dcrf2d': (C.c_int, [_P, _P, _P, C.POINTER(C.c_int64), C.POINTER(DcrfParams), _P, _P, _P]),
     'alq_llfc_grads': (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),

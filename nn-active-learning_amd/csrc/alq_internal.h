@@ -62,7 +62,7 @@ enum ProfClass { PROF_IGEMM_FWD = 0, PROF_IGEMM_BWD = 1, PROF_ELEMWISE = 2, PROF
                  PROF_IGEMM_F16 = 8 /* igemm4 launches on the fp16x2 split (3 products) */,
                  PROF_GNORM = 9 /* per-sample weight-gradient norms on fp32 MFMA (gnorm.hip) */,
                  PROF_COMMITTEE = 10 /* committee running means and keys (committee.hip) */,
-                 PROF_EVAL = 11 /* confusion counts of a test-set evaluation (evalcounts.hip) */, PROF_NUM = 12 };
+                 PROF_EVAL = 11 /* confusion counts of an evaluation (evalcounts.hip, confusion.hip) */, PROF_NUM = 12 };
 
 struct ProfSlot {
     double ms = 0;

@@ -4,6 +4,8 @@
 //   alq_cc_label          labels[v] = the smallest raveled index of the component that holds v (selected voxels), -1 elsewhere
 //   alq_cc_keep_largest   out[v] = [v lies in the largest component], ties -> the component whose first voxel comes first
 //   alq_fill_holes        out[v] = seg[v] != 0 or v lies in a 6-connected background component that touches no face
+//   alq_cc_sizes          sizes[root] = voxels of the component, 0 at every other voxel (labels of alq_cc_label in)
+//   alq_cc_relabel        out[v] = table[labels[v]] (0 outside), or out[v] = sizes[labels[v]] >= min_size
 //
 // Volumes are [H, W, S] in C order, z contiguous.  The labelling is the atomic-min union-find of Komura / Playne & Hawick in
 // three launches:
@@ -177,6 +179,50 @@ __global__ __launch_bounds__(CC_THREADS) void cc_merge_kernel(const unsigned cha
     }
 }
 
+// The size pass of one wave step.  r.mask: the selected lanes, r.brk: lanes at which a run starts whatever came before; a
+// selected lane's `root` is its component.  The first lane of every run adds the run length to size[root]; a wave sums what
+// the runs of a step give to one root before it issues the atomic, and the root that holds most of the step's selected
+// voxels goes into a wave-uniform (root, sum) pair kept across the steps: it reaches memory when another root takes its
+// place and at the end (cc_flush_held).  Integer sums: the same totals whatever is held back.  Every lane of the wave calls.
+struct CcHeld {
+    int root = -1;
+    unsigned sum = 0;
+};
+
+__device__ inline void cc_add_runs(const CcRuns &r, bool sel, int root, int lane, unsigned *size, CcHeld &h) {
+    const bool lead = sel && cc_run_start(r, lane) == lane;
+    const unsigned len = lead ? (unsigned)cc_run_len(r, lane) : 0u;
+    const unsigned nsel = __popcll(r.mask);
+    u64 todo = __ballot(lead);      // wave-uniform: the loop below is too
+    while (todo) {
+        const int l0 = __ffsll((long long)todo) - 1;
+        const int r0 = __shfl(root, l0);
+        const bool same = lead && root == r0;
+        const u64 sm = __ballot(same);
+        unsigned s = same ? len : 0u;
+        if (sm & (sm - 1)) {      // more than one run of that root in this step
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+        } else {
+            s = __shfl(s, l0);
+        }
+        if (r0 == h.root) {
+            h.sum += s;
+        } else if (2 * s > nsel) {
+            if (h.sum && lane == 0) atomicAdd(size + h.root, h.sum);
+            h.root = r0;
+            h.sum = s;
+        } else if (lane == l0) {
+            atomicAdd(size + r0, s);
+        }
+        todo &= ~sm;
+    }
+}
+
+__device__ inline void cc_flush_held(unsigned *size, const CcHeld &h, int lane) {
+    if (h.sum && lane == 0) atomicAdd(size + h.root, h.sum);
+}
+
 // labels[v] = find(v) (in place over parent[]: a concurrent reader meets either the old parent or the root, both ancestors).
 // MODE 1: the first lane of every z-run adds the run length to size[root]; MODE 2: a selected voxel on a face of the volume
 // raises flag[root]
@@ -187,8 +233,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_compress_kernel(CcGeo g, int *l
     // 256 x 256 x 128).  So a wave first sums the runs of a step per root, and the root that holds most of the step's
     // selected voxels goes into a wave-uniform (root, sum) pair kept across the steps; it reaches memory when another root
     // takes its place and at the end.  Integer sums: the same totals whatever is held back
-    int croot = -1;
-    unsigned csum = 0;
+    CcHeld held;
     for (long long base = blockIdx.x * (long long)CC_THREADS; base < g.nvox; base += (long long)gridDim.x * CC_THREADS) {
         const long long vl = base + threadIdx.x;
         const bool in = vl < g.nvox;
@@ -203,33 +248,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_compress_kernel(CcGeo g, int *l
             CcRuns r;
             r.mask = __ballot(sel);
             r.brk = __ballot(in && v % g.S == 0);
-            const bool lead = sel && cc_run_start(r, lane) == lane;
-            const unsigned len = lead ? (unsigned)cc_run_len(r, lane) : 0u;
-            const unsigned nsel = __popcll(r.mask);
-            u64 todo = __ballot(lead);      // wave-uniform: the loop below is too
-            while (todo) {
-                const int l0 = __ffsll((long long)todo) - 1;
-                const int r0 = __shfl(root, l0);
-                const bool same = lead && root == r0;
-                const u64 sm = __ballot(same);
-                unsigned s = same ? len : 0u;
-                if (sm & (sm - 1)) {      // more than one run of that root in this step
-#pragma unroll
-                    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
-                } else {
-                    s = __shfl(s, l0);
-                }
-                if (r0 == croot) {
-                    csum += s;
-                } else if (2 * s > nsel) {
-                    if (csum && lane == 0) atomicAdd(aux + croot, csum);
-                    croot = r0;
-                    csum = s;
-                } else if (lane == l0) {
-                    atomicAdd(aux + r0, s);
-                }
-                todo &= ~sm;
-            }
+            cc_add_runs(r, sel, root, lane, aux, held);
         }
         if (MODE == 2 && sel) {
             const int z = v % g.S;
@@ -238,7 +257,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_compress_kernel(CcGeo g, int *l
             if (z == 0 || z == g.S - 1 || j == 0 || j == g.W - 1 || i == 0 || i == g.H - 1) aux[root] = 1;
         }
     }
-    if (MODE == 1 && csum && lane == 0) atomicAdd(aux + croot, csum);
+    if (MODE == 1) cc_flush_held(aux, held, lane);
 }
 
 // the maximum of (size << 32) | ~root over the candidate roots -> header[0]; their number -> info[0]
@@ -318,6 +337,38 @@ __global__ __launch_bounds__(CC_THREADS) void cc_fill_kernel(const unsigned char
         u64 s = 0;
         for (int w = 0; w < CC_WAVES; ++w) s += part[w][threadIdx.x];
         if (s) atomicAdd(info + threadIdx.x, s);
+    }
+}
+
+// size[root] += the voxels of every run of equal labels (alq_cc_sizes: labels as alq_cc_label left them, size zeroed before)
+__global__ __launch_bounds__(CC_THREADS) void cc_sizes_kernel(const int *__restrict__ labels, long long n, unsigned *size) {
+    const int lane = threadIdx.x & 63;
+    CcHeld held;
+    // every lane of a block walks the same number of steps, so each ballot sees the whole wave
+    for (long long base = blockIdx.x * (long long)CC_THREADS; base < n; base += (long long)gridDim.x * CC_THREADS) {
+        const long long vl = base + threadIdx.x;
+        const int lab = vl < n ? labels[vl] : -1;
+        const bool sel = lab >= 0 && lab < n;
+        const int before = __shfl_up(lab, 1);
+        CcRuns r;
+        r.mask = __ballot(sel);
+        r.brk = __ballot(sel && (lane == 0 || before != lab));      // a run ends where the label changes
+        cc_add_runs(r, sel, lab, lane, size, held);
+    }
+    cc_flush_held(size, held, lane);
+}
+
+// out_i32[v] = label < 0 ? 0 : table[label], or out_u8[v] = label >= 0 && sizes[label] >= min_size
+__global__ __launch_bounds__(CC_THREADS) void cc_relabel_kernel(const int *__restrict__ labels, long long n, const int *__restrict__ table,
+                                                                const int *__restrict__ sizes, int min_size, int *__restrict__ out_i32,
+                                                                unsigned char *__restrict__ out_u8) {
+    for (long long vl = blockIdx.x * (long long)CC_THREADS + threadIdx.x; vl < n; vl += (long long)gridDim.x * CC_THREADS) {
+        const int lab = labels[vl];
+        const bool sel = lab >= 0 && lab < n;
+        if (out_i32)
+            out_i32[vl] = sel ? table[lab] : 0;
+        else
+            out_u8[vl] = (unsigned char)(sel && sizes[lab] >= min_size);
     }
 }
 
@@ -424,6 +475,34 @@ int alq_cc_keep_largest(alq_ctx *ctx, const uint8_t *d_seg, const int64_t dims[3
     ProfScope ps(ctx, PROF_ELEMWISE, 0);
     hipLaunchKernelGGL(cc_select_kernel, grid, dim3(CC_THREADS), 0, ctx->stream, g, (const int *)w.parent, (const u64 *)w.header, d_out,
                        reinterpret_cast<long long *>(d_info));
+    ALQ_HIP(hipGetLastError());
+    return ALQ_OK;
+}
+
+int alq_cc_sizes(alq_ctx *ctx, const int32_t *d_labels, int64_t n, int32_t *d_sizes) {
+    ALQ_REQUIRE(ctx && d_labels && d_sizes, ALQ_EINVAL, "alq_cc_sizes: null argument");
+    ALQ_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), ALQ_EINVAL, "alq_cc_sizes: n = %lld (0 .. 2^31 - 1)", (long long)n);
+    if (n == 0) return ALQ_OK;
+    ALQ_HIP(hipSetDevice(ctx->device));
+    ALQ_HIP(hipMemsetAsync(d_sizes, 0, (size_t)n * sizeof(int32_t), ctx->stream));
+    ProfScope ps(ctx, PROF_REDUCE, 0);
+    hipLaunchKernelGGL(cc_sizes_kernel, dim3(cc_grid(ctx, n)), dim3(CC_THREADS), 0, ctx->stream, (const int *)d_labels, (long long)n,
+                       reinterpret_cast<unsigned *>(d_sizes));
+    ALQ_HIP(hipGetLastError());
+    return ALQ_OK;
+}
+
+int alq_cc_relabel(alq_ctx *ctx, const int32_t *d_labels, int64_t n, const int32_t *d_table, const int32_t *d_sizes, int32_t min_size,
+                   int32_t *d_out_i32, uint8_t *d_out_u8) {
+    ALQ_REQUIRE(ctx && d_labels, ALQ_EINVAL, "alq_cc_relabel: null argument");
+    ALQ_REQUIRE((d_out_i32 != nullptr) != (d_out_u8 != nullptr), ALQ_EINVAL, "alq_cc_relabel: exactly one of d_out_i32 / d_out_u8");
+    ALQ_REQUIRE(d_out_i32 ? d_table != nullptr : d_sizes != nullptr, ALQ_EINVAL, "alq_cc_relabel: null %s", d_out_i32 ? "d_table" : "d_sizes");
+    ALQ_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), ALQ_EINVAL, "alq_cc_relabel: n = %lld (0 .. 2^31 - 1)", (long long)n);
+    if (n == 0) return ALQ_OK;
+    ALQ_HIP(hipSetDevice(ctx->device));
+    ProfScope ps(ctx, PROF_ELEMWISE, 0);
+    hipLaunchKernelGGL(cc_relabel_kernel, dim3(cc_grid(ctx, n)), dim3(CC_THREADS), 0, ctx->stream, (const int *)d_labels, (long long)n,
+                       (const int *)d_table, (const int *)d_sizes, (int)min_size, (int *)d_out_i32, (unsigned char *)d_out_u8);
     ALQ_HIP(hipGetLastError());
     return ALQ_OK;
 }

@@ -164,6 +164,57 @@ class DeviceSession(object):
         check(self.lib.alq_eval_counts(self._ctx, ptr(pred), ptr(inds), n, ptr(mask), 1 if mask.dtype == torch.float64 else 0,
                                        elems, ptr(counts), ptr(seg)))
 
+    def confusion_counts(self, pred, labels, C, inner=None, groups=1, first=0, fill=-1, counts=None, want_skipped=False):
+        """alq_confusion_counts: adds counts[g][t][p] over the n elements of the device id tensors `pred` and `labels` (uint8,
+        int32 or int64 each, contiguous, the same number of elements), g = ((first + i) // inner) % groups, to the int64 device
+        tensor `counts` [groups, C, C] (None: a new zeroed one).  A label outside [0, C) reads as `fill` when 0 <= fill < C; an
+        element whose label (after that) or prediction lies outside [0, C) is skipped.  inner None: the whole call is one group
+        run (inner = n).  Returns counts, or (counts, skipped int64 device [1]) with want_skipped.  Nothing is copied back."""
+        torch = self.torch
+        self.bind_stream()
+        types = {torch.uint8: 0, torch.int32: 1, torch.int64: 2}
+        n = int(pred.numel())
+        for t in (pred, labels):
+            assert t.dtype in types and t.is_contiguous() and t.device == self.device and int(t.numel()) == n
+        C, groups = int(C), int(groups)          # (the argument hides the module's ctypes alias here: _lib.C)
+        inner = max(n, 1) if inner is None else int(inner)
+        if counts is None:
+            counts = torch.zeros((max(groups, 0), max(C, 0), max(C, 0)), dtype=torch.int64, device=self.device)
+        assert counts.dtype == torch.int64 and counts.is_contiguous() and counts.device == self.device and \
+            int(counts.numel()) == groups * C * C
+        skipped = torch.zeros((1,), dtype=torch.int64, device=self.device) if want_skipped else None
+        check(self.lib.alq_confusion_counts(self._ctx, _lib.C.c_void_p(pred.data_ptr()), types[pred.dtype], _lib.C.c_void_p(labels.data_ptr()),
+                                            types[labels.dtype], n, int(first), inner, groups, C, int(fill), _lib.C.c_void_p(counts.data_ptr()),
+                                            _lib.C.c_void_p(skipped.data_ptr()) if want_skipped else None))
+        return (counts, skipped) if want_skipped else counts
+
+    def cc_sizes(self, labels):
+        """alq_cc_sizes: `labels` int32 device tensor as cc_label returns it -> int32 device tensor of its shape, the size of the
+        component at every root voxel (the smallest raveled index of the component), 0 elsewhere."""
+        torch = self.torch
+        self.bind_stream()
+        assert labels.dtype == torch.int32 and labels.is_contiguous() and labels.device == self.device
+        sizes = self.empty(tuple(labels.shape), torch.int32)
+        check(self.lib.alq_cc_sizes(self._ctx, C.c_void_p(labels.data_ptr()), int(labels.numel()), C.c_void_p(sizes.data_ptr())))
+        return sizes
+
+    def cc_relabel(self, labels, table=None, sizes=None, min_size=0):
+        """alq_cc_relabel: with `table` (int32 device, one entry per voxel, read at the roots) the int32 image
+        table[labels[v]] (0 where labels is -1); with `sizes` (cc_sizes) the uint8 mask sizes[labels[v]] >= min_size."""
+        torch = self.torch
+        self.bind_stream()
+        if (table is None) == (sizes is None):
+            raise ValueError('cc_relabel takes exactly one of table / sizes')
+        n = int(labels.numel())
+        for t in (labels, table, sizes):
+            assert t is None or (t.dtype == torch.int32 and t.is_contiguous() and t.device == self.device and int(t.numel()) == n)
+        out = self.empty(tuple(labels.shape), torch.int32 if table is not None else torch.uint8)
+        check(self.lib.alq_cc_relabel(self._ctx, C.c_void_p(labels.data_ptr()), n, C.c_void_p(table.data_ptr()) if table is not None else None,
+                                      C.c_void_p(sizes.data_ptr()) if sizes is not None else None, int(min_size),
+                                      C.c_void_p(out.data_ptr()) if table is not None else None,
+                                      C.c_void_p(out.data_ptr()) if table is None else None))
+        return out
+
     # -- connected components, largest component, hole filling (csrc/ccl.hip) ---------------
     def _cc_args(self, seg, shape, out=None):
         torch = self.torch

@@ -139,9 +139,77 @@ def confusion_matrix(preds, labels, C):
     return np.bincount(t[ok] * C + p[ok], minlength=C * C).reshape(C, C)
 
 
+MAX_DEVICE_CLASSES = 16       # alq_confusion_counts: 1 <= C <= 16
+
+
+def confusion_counts_host(pred, labels, C, inner=None, groups=1, first=0, fill=-1, want_skipped=False):
+    """alq_confusion_counts in NumPy: np.int64 [groups, C, C], counts[g][t][p] over the flattened id arrays with
+    g = ((first + i) // inner) % groups (inner None: one run, inner = n).  A label outside [0, C) reads as `fill` when
+    0 <= fill < C; an element whose label (after that) or prediction lies outside [0, C) is skipped.  want_skipped:
+    (counts, number of skipped elements)."""
+    p = np.ravel(np.asarray(pred)).astype(np.int64)
+    t = np.ravel(np.asarray(labels)).astype(np.int64)
+    C, groups = int(C), int(groups)
+    n = p.size
+    inner = max(n, 1) if inner is None else int(inner)
+    g = ((int(first) + np.arange(n, dtype=np.int64)) // inner) % groups
+    if 0 <= int(fill) < C:
+        t = np.where((t < 0) | (t >= C), int(fill), t)
+    ok = (p >= 0) & (p < C) & (t >= 0) & (t < C)
+    counts = np.bincount((g[ok] * C + t[ok]) * C + p[ok], minlength=groups * C * C).reshape(groups, C, C).astype(np.int64)
+    return (counts, int(n - np.count_nonzero(ok))) if want_skipped else counts
+
+
+def F1_from_confusion(M, C=None):
+    """The F1 arithmetic of binary_F1_score and multi_F1_score on a confusion matrix M[t, p] (any square integer matrix that
+    spans the values present) -> (binary, scores, average):
+      binary   2 TP / (P + TPFP) with TP = sum t p M[t, p], P = sum t M[t, p], TPFP = sum p M[t, p] - np.sum(preds * labels),
+               np.sum(labels) and np.sum(preds) of the maps M counts, for any integer values; 0. when P + TPFP is 0;
+      scores   per-class F1 of the classes 1 .. C-1 (C None: the matrix' size), 0 for a class with no true and no predicted voxel;
+      average  their support-weighted mean, 0 without support."""
+    M = np.asarray(M, dtype=np.int64)
+    span = M.shape[0]
+    vals = np.arange(span, dtype=np.int64)
+    TP = np.sum(np.outer(vals, vals) * M)
+    den = np.sum(vals * M.sum(axis=1)) + np.sum(vals * M.sum(axis=0))
+    binary = 2 * TP / den if den != 0 else 0.
+    C = span if C is None else int(C)
+    scores = np.zeros(max(C - 1, 0))
+    support = np.zeros(max(C - 1, 0))
+    for j in range(1, min(C, span)):
+        d = M[j, :].sum() + M[:, j].sum()
+        scores[j - 1] = 2. * M[j, j] / d if d else 0.
+        support[j - 1] = M[j, :].sum()
+    av = float(np.sum(scores * support) / support.sum()) if support.sum() else 0.
+    return binary, scores, av
+
+
+def _countable(preds, labels):
+    """True when both maps hold integers in [0, 2^16) and np.sum(preds * labels) cannot wrap in their common dtype: their
+    products and sums can then be read off a confusion matrix.  (A product of two uint8 maps with values above 15 wraps in the
+    reference's np.sum(preds * labels); such maps keep that statement.)"""
+    for a in (preds, labels):
+        if a.size == 0 or a.dtype.kind == 'b':
+            continue
+        if a.dtype.kind not in 'iu' and (a.dtype.kind != 'f' or not np.all(a == np.floor(a))):
+            return False
+        if a.min() < 0 or a.max() >= 65536:
+            return False
+    dt = np.result_type(preds, labels)
+    if dt.kind in 'iu' and preds.size and labels.size and int(preds.max()) * int(labels.max()) > np.iinfo(dt).max:
+        return False
+    return True
+
+
 def binary_F1_score(preds, labels):
-    """2 TP / (P + TPFP) of two 0/1 maps; 0 when neither holds a positive."""
+    """2 TP / (P + TPFP) of two 0/1 maps; 0 when neither holds a positive.  TP = np.sum(preds * labels), P = np.sum(labels),
+    TPFP = np.sum(preds), as the reference states it: integer maps are counted into a confusion matrix and scored by
+    F1_from_confusion (the same doubles), anything else takes the three sums themselves."""
     preds, labels = np.asarray(preds), np.asarray(labels)
+    if preds.shape == labels.shape and _countable(preds, labels):
+        span = 1 + int(max(preds.max() if preds.size else 0, labels.max() if labels.size else 0))
+        if span * span <= 4096:
+            return F1_from_confusion(confusion_matrix(preds, labels, span))[0]
     TP = np.sum(preds * labels)
     den = np.sum(labels) + np.sum(preds)
     return 2 * TP / den if den != 0 else 0.
@@ -158,22 +226,61 @@ def multi_F1_score(preds, labels, C=None):
     t = np.ravel(np.asarray(labels)).astype(np.int64)
     # every voxel counts, whatever its other value is: the matrix spans all values present, the scores read classes 1 .. C-1
     span = max(C, int(p.max()) + 1 if p.size else 0, int(t.max()) + 1 if t.size else 0)
-    M = confusion_matrix(p, t, span)
-    scores = np.zeros(max(C - 1, 0))
-    support = np.zeros(max(C - 1, 0))
-    for j in range(1, C):
-        den = M[j, :].sum() + M[:, j].sum()
-        scores[j - 1] = 2. * M[j, j] / den if den else 0.
-        support[j - 1] = M[j, :].sum()
-    av = float(np.sum(scores * support) / support.sum()) if support.sum() else 0.
+    _, scores, av = F1_from_confusion(confusion_matrix(p, t, span), C)
     return scores, av
+
+
+def _confusion_pass(model, sess, dat_gen, iters, want_loss, want_counts):
+    """`iters` batches through a dense device model: (np.int64 [C, C] confusion matrix [true, predicted] or None, the batch-size-
+    weighted mean of model.loss or None).  Predictions come from forward_maps_device(want_pred=True) and never leave the
+    device; labels are DeviceLabels.labels in place, or a host one-hot reduced to int32 ids once and uploaded; an unlabelled
+    voxel (-1, or an all-zero one-hot row) is class 0, np.argmax's reading of it.  One confusion_counts call per batch into one
+    resident matrix, one download of 8 C^2 bytes at the end."""
+    torch = sess.torch
+    C = int(getattr(model, 'class_num', getattr(model, 'nclass', 0)))
+    counts = torch.zeros((1, C, C), dtype=torch.int64, device=sess.device) if want_counts else None
+    av_loss, vol = (0. if want_loss else None), 0
+    for _ in range(iters):
+        batch_X, batch_mask = dat_gen()
+        b = batch_X.shape[0]
+        if want_loss:
+            val = float(sess.run(model.loss, feed_dict={model.x: batch_X, model.y_: batch_mask, model.keep_prob: 1.}))
+            av_loss = (vol * av_loss + val * b) / (vol + b)
+        if want_counts:
+            t, n = model._as_device_batch(batch_X)
+            pred = model.forward_maps_device(t, n, 1., want_pred=True)[1]
+            if model._is_device_labels(batch_mask):
+                lab = batch_mask.labels.to(device=sess.device, dtype=torch.int32).contiguous()
+            else:
+                lab = sess.to_device(np.argmax(np.asarray(batch_mask), axis=-1).astype(np.int32), torch.int32)
+            sess.confusion_counts(pred.contiguous(), lab, C, fill=0, counts=counts)
+        vol += b
+    return (counts.cpu().numpy().reshape(C, C) if want_counts else None), av_loss
+
+
+def eval_confusion(model, sess, dat_gen, iters=50):
+    """The confusion matrix of `iters` batches of `dat_gen()` -> (batch_X, batch_mask): np.int64 [C, C], indexed
+    [true, predicted].  A dense device model counts on the device (_confusion_pass); any other model runs model.posteriors
+    through sess.run and counts with NumPy - the same matrix."""
+    C = int(getattr(model, 'class_num', getattr(model, 'nclass', 0)))
+    if _on_device(model):
+        return _confusion_pass(model, sess, dat_gen, iters, False, True)[0]
+    M = np.zeros((C, C), dtype=np.int64)
+    for _ in range(iters):
+        batch_X, batch_mask = dat_gen()
+        feed = {model.x: batch_X, model.y_: batch_mask, model.keep_prob: 1.}
+        preds = np.argmax(np.asarray(sess.run(model.posteriors, feed_dict=feed)), axis=-1)
+        M += confusion_matrix(preds, np.argmax(np.asarray(batch_mask), axis=-1), C)
+    return M
 
 
 def eval_metrics(model, sess, dat_gen, iters=50, update=True, alt_attr=None):
     """`iters` batches of `dat_gen()` -> (batch_X, one-hot batch_mask [b, *spatial, c]) through the model; the metrics named
     by the keys of `model.valid_metrics` (or of the attribute `alt_attr`): 'acc' / 'av_acc' (voxel accuracy), 'F1' (binary, or
     the weighted multi-class score) and 'av_loss' (batch-size-weighted mean of model.loss).  update=True appends one value
-    per metric to its list; otherwise the running results are returned."""
+    per metric to its list; otherwise the running results are returned.  A dense device model counts on the device
+    (eval_confusion's matrix: no posterior map and no label crosses to the host); both paths score the matrix with
+    F1_from_confusion."""
     if alt_attr is not None:
         assert hasattr(model, alt_attr), 'The alternative attribute does not exist.'
         valid_metrics = getattr(model, alt_attr)
@@ -186,23 +293,33 @@ def eval_metrics(model, sess, dat_gen, iters=50, update=True, alt_attr=None):
     results = {}
     if want_loss:
         results['av_loss'] = 0.
-    all_preds, all_masks = [], []
-    vol = 0
-    for _ in range(iters):
-        batch_X, batch_mask = dat_gen()
-        b = batch_X.shape[0]
-        feed = {model.x: batch_X, model.y_: batch_mask, model.keep_prob: 1.}
+    if _on_device(model) and hasattr(sess, 'confusion_counts') and 1 <= C <= MAX_DEVICE_CLASSES:
+        M, av_loss = _confusion_pass(model, sess, dat_gen, iters, want_loss, want_post)
         if want_loss:
-            val = float(sess.run(model.loss, feed_dict=feed))
-            results['av_loss'] = (vol * results['av_loss'] + val * b) / (vol + b)
+            results['av_loss'] = av_loss
+    else:
+        M = None
+        all_preds, all_masks = [], []
+        vol = 0
+        for _ in range(iters):
+            batch_X, batch_mask = dat_gen()
+            b = batch_X.shape[0]
+            feed = {model.x: batch_X, model.y_: batch_mask, model.keep_prob: 1.}
+            if want_loss:
+                val = float(sess.run(model.loss, feed_dict=feed))
+                results['av_loss'] = (vol * results['av_loss'] + val * b) / (vol + b)
+            if want_post:
+                all_preds.append(np.argmax(np.asarray(sess.run(model.posteriors, feed_dict=feed)), axis=-1))
+                all_masks.append(np.argmax(batch_mask, axis=-1))
+            vol += b
         if want_post:
-            all_preds.append(np.argmax(np.asarray(sess.run(model.posteriors, feed_dict=feed)), axis=-1))
-            all_masks.append(np.argmax(batch_mask, axis=-1))
-        vol += b
+            preds, masks = np.concatenate(all_preds, axis=0), np.concatenate(all_masks, axis=0)
+            # the matrix spans every value present, as multi_F1_score's does; the scores read classes 1 .. C-1
+            M = confusion_matrix(preds, masks, max(C, int(preds.max()) + 1 if preds.size else 0, int(masks.max()) + 1 if masks.size else 0))
     if want_post:
-        preds, masks = np.concatenate(all_preds, axis=0), np.concatenate(all_masks, axis=0)
-        results['accs'] = float(np.sum(preds == masks)) / preds.size
-        results['F1s'] = binary_F1_score(preds, masks) if C == 2 else multi_F1_score(preds, masks, C)[1]
+        total = int(M.sum())
+        results['accs'] = float(np.trace(M)) / total if total else 0.
+        results['F1s'] = F1_from_confusion(M, C)[0] if C == 2 else F1_from_confusion(M, C)[2]
     if not update:
         return results
     for name in names:
@@ -239,3 +356,143 @@ def get_full_segs(models_dict, sess, dat, post_process=False, save_path=None, da
         for i, seg in enumerate(segs):
             dat_writer(os.path.join(save_path, 'seg_{}.nrrd'.format(i)), seg)
     return segs
+
+
+# ---- whole-volume scores by axial partitions (eval_utils.py:240-363) --------------------------------------------------------
+def _load_list(paths_or_mats, reader):
+    if isinstance(paths_or_mats[0], str):
+        return [reader(path) for path in paths_or_mats]
+    return paths_or_mats
+
+
+def _readers(kwargs):
+    from . import nrrd_io
+    kwargs.setdefault('dat_reader', lambda x: nrrd_io.read(x)[0])
+    kwargs.setdefault('mask_reader', lambda x: nrrd_io.read(x)[0])
+    return kwargs['dat_reader'], kwargs['mask_reader'], kwargs.get('sess')
+
+
+class _SliceScores(object):
+    """binary_F1_score of any range of axial slices of one (seg, mask) pair, and the per-slice count of a mask label, from the
+    per-slice confusion counts [Z, C, C] (counts[z][mask value][seg value], C = the largest value + 1): with a session one
+    alq_confusion_counts launch over the two uint8 volumes (inner = 1, groups = Z: z is the fastest axis), else
+    confusion_counts_host; values above 15 count with NumPy too.  Maps that hold anything but non-negative integers keep the
+    reference's own sums on the slices."""
+
+    def __init__(self, seg, mask, sess):
+        self.seg, self.mask = np.asarray(seg), np.asarray(mask)
+        self.counts = None
+        if self.seg.shape != self.mask.shape or self.seg.ndim != 3 or not self.seg.size or not _countable(self.seg, self.mask):
+            return
+        Z = self.seg.shape[2]
+        C = 1 + int(max(self.seg.max(), self.mask.max()))
+        if C > 256:
+            return
+        if sess is not None and C <= MAX_DEVICE_CLASSES:
+            torch = sess.torch
+            d_seg = sess.to_device(self.seg.astype(np.uint8), torch.uint8)
+            d_mask = sess.to_device(self.mask.astype(np.uint8), torch.uint8)
+            self.counts = sess.confusion_counts(d_seg, d_mask, C, inner=1, groups=Z).cpu().numpy()
+        else:
+            self.counts = confusion_counts_host(self.seg, self.mask, C, inner=1, groups=Z)
+
+    def score(self, lo=None, hi=None):
+        """binary_F1_score(seg[:, :, lo:hi], mask[:, :, lo:hi])"""
+        if self.counts is None:
+            return binary_F1_score(self.seg[:, :, lo:hi], self.mask[:, :, lo:hi])
+        return F1_from_confusion(self.counts[lo:hi].sum(axis=0))[0]
+
+    def label_num(self, label):
+        """np.sum(mask == label, axis=(0, 1))"""
+        if self.counts is None:
+            return np.sum(self.mask == label, axis=(0, 1))
+        C = self.counts.shape[1]
+        if label != int(label) or not 0 <= int(label) < C:
+            return np.zeros(self.counts.shape[0], dtype=np.int64)
+        return self.counts[:, int(label), :].sum(axis=1)
+
+
+def eval_full_segs_explicit_partitions(seg_paths_or_mats, mask_paths_or_mats, slice_partitions, **kwargs):
+    """(overall F1 [n], partition F1 [n, M]) of n whole-volume segmentations against their masks: binary_F1_score of each volume
+    and of the M = (cut points + 1) ranges of axial slices that `slice_partitions` cuts it into - an int array [n, M - 1], or a
+    list, which is np.repeat(np.array(list), n, axis=0) as in the reference (so the list is nested: [[c0, c1, ..]]).
+    Keywords: dat_reader / mask_reader for paths (default nrrd_io.read) and sess - with a session the counting runs on the
+    device (_SliceScores)."""
+    dat_reader, mask_reader, sess = _readers(kwargs)
+    segs = _load_list(seg_paths_or_mats, dat_reader)
+    masks = _load_list(mask_paths_or_mats, mask_reader)
+    if isinstance(slice_partitions, list):
+        slice_partitions = np.repeat(np.array(slice_partitions), len(segs), axis=0)
+    M = slice_partitions.shape[1] + 1
+    part_Fscores = np.zeros((len(segs), M))
+    overall_Fscores = np.zeros(len(segs))
+    for i in range(len(segs)):
+        sc = _SliceScores(segs[i], masks[i], sess)
+        overall_Fscores[i] = sc.score()
+        part_Fscores[i, 0] = sc.score(None, slice_partitions[i, 0])
+        for j in range(slice_partitions.shape[1] - 1):
+            part_Fscores[i, j + 1] = sc.score(slice_partitions[i, j], slice_partitions[i, j + 1])
+        part_Fscores[i, -1] = sc.score(slice_partitions[i, -1], None)
+    return overall_Fscores, part_Fscores
+
+
+def eval_full_segs_label_percentage(seg_paths_or_mats, mask_paths_or_mats, label, percentage, **kwargs):
+    """(overall F1 [n], partition F1 [n, 3]): the three-fold partition of the axial slices at the one gap of the set of slices
+    whose share of `label` voxels lies below `percentage` (top, middle, bottom).  As in the reference: more than one gap
+    prints its message and leaves the subject's row zero; no gap at all is its IndexError.  Keywords as above."""
+    dat_reader, mask_reader, sess = _readers(kwargs)
+    segs = _load_list(seg_paths_or_mats, dat_reader)
+    masks = _load_list(mask_paths_or_mats, mask_reader)
+    M = 3
+    part_Fscores = np.zeros((len(segs), M))
+    overall_Fscores = np.zeros(len(segs))
+    for i in range(len(segs)):
+        sc = _SliceScores(segs[i], masks[i], sess)
+        overall_Fscores[i] = sc.score()
+        label_num = sc.label_num(label)
+        thr_slices = np.where(label_num / np.prod(np.asarray(masks[i]).shape[:2]) < percentage)[0]
+        gap_loc = np.where((thr_slices[1:] - thr_slices[:-1]) > 1)[0]
+        if len(gap_loc) > 1:
+            print('There are more than one gap for slice-wise label volume' + ' of image {}'.format(i))
+            continue
+        edge_1 = thr_slices[gap_loc[0]]
+        edge_2 = thr_slices[gap_loc[0] + 1]
+        part_Fscores[i, 0] = sc.score(None, edge_1)
+        part_Fscores[i, 1] = sc.score(edge_1, edge_2)
+        part_Fscores[i, 2] = sc.score(edge_2, None)
+    return overall_Fscores, part_Fscores
+
+
+def simple_eval_model(model, sess, dat_gen):
+    """(accuracy, predictions) over the batches (Xb, Yb, _) of the iterable `dat_gen` (eval_utils.py:391-409): model.prediction
+    at keep_prob 1 (no keep_prob in the feed when model.dropout_rate is None), the ground truth np.argmax(Yb, axis=0) - class
+    scores along the first axis."""
+    preds, grounds = [], []
+    feed_dict = {} if model.dropout_rate is None else {model.keep_prob: 1.}
+    for Xb, Yb, _ in dat_gen:
+        feed_dict.update({model.x: Xb})
+        preds += [sess.run(model.prediction, feed_dict=feed_dict)]
+        grounds += [np.argmax(Yb, axis=0)]
+    preds = np.concatenate(preds)
+    grounds = np.concatenate(grounds)
+    acc = np.sum(preds == grounds) / len(preds)
+    return acc, preds
+
+
+def models_dict_for_different_sizes(model_builder, dat):
+    """{str((h, w)): model_builder([h, w], '<h>x<w>')} with one model per distinct in-plane image size of `dat` (read through
+    dat.reader from dat.img_addrs[dat.mods[0]]): the dictionary get_full_segs looks its models up in.  The reference's
+    np.unique(set(shapes))[0] is read as "the set of distinct shapes", here in sorted order; add_assign_ops() is called where the
+    model has it."""
+    shapes = []
+    for i in range(len(dat.img_addrs[dat.mods[0]])):
+        img = dat.reader(dat.img_addrs[dat.mods[0]][i])
+        shapes += [tuple(int(v) for v in img.shape[:2])]
+    models_dict = {}
+    for shape in sorted(set(shapes)):
+        key = str(shape)
+        model_name = '{}x{}'.format(shape[0], shape[1])
+        models_dict[key] = model_builder(list(shape), model_name)
+        if hasattr(models_dict[key], 'add_assign_ops'):
+            models_dict[key].add_assign_ops()
+    return models_dict
