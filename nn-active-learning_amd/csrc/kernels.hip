@@ -406,7 +406,7 @@ int k_pool_bwd(alq_ctx *ctx, const View &dout, const View &din, const uint8_t *a
     hipLaunchKernelGGL(pool_bwd_vox_kernel<CV>, dim3(grid_for(nvox)), dim3(256), 0, ctx->stream, dout.p, dout.cs,   \
                        dout.c0, dout.D, dout.H, dout.W, din.p, din.cs, din.c0, din.D, din.H, din.W, argmax, w[0], w[1], \
                        w[2], lo[0], lo[1], lo[2], accumulate, nvox, ap, acs, ac0, dsum, st)
-        switch (din.C) { case 4: ALQ_PBV(1); break; case 8: ALQ_PBV(2); break; case 16: ALQ_PBV(4); break; default: ALQ_PBV(8); }
+        if (din.C == 4) ALQ_PBV(1); else ALQ_PBV(2);      // (the guard above admits 4 and 8 channels only)
 #undef ALQ_PBV
         ALQ_LAUNCH_CHECK();
         if (fused) *fused = dsum != nullptr;

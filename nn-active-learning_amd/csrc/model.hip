@@ -1091,6 +1091,7 @@ static int run_backward_main(alq_model *m, const float *d_x, int N) {
         // wrote its slice earlier), so it can finish that tensor: ReLU-grad mask + channel sums.
         Layer *prev = i > 0 ? &m->layers[i - 1] : nullptr;
         const bool prev_param = prev && prev->pidx >= 0 && prev->spec.type != ALQ_FC;
+        if (ly.spec.type == ALQ_POOL && i == 0) break;      // a pool on the network input: nothing below takes a cotangent (as in grads.hip)
         if (ly.spec.type == ALQ_POOL && prev_param && pool_first_ok(ly, *prev) && (prev->dsum_partial || !prev_is_src)) {
             ALQ_TRY(k_pool_bwd_first(ctx, ly.dout, ly.out, ly.argmax, ly.spec.k, prev->out.D, prev->out.H, prev->out.W, N,
                                      prev->dsum, prev->dsum_partial ? 1 : 0, ly.signs_ready ? 1 : 0));
