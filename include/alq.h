@@ -236,6 +236,38 @@ int alq_confusion_counts(alq_ctx *ctx, const void *d_pred, int pred_type, const 
                          int64_t inner, int64_t groups, int C, int fill, int64_t *d_counts, int64_t *d_skipped);
 int alq_confusion_window(int C);
 
+/* Slice queries of a fully-convolutional model (csrc/sliceq.hip).  No reference counterpart: the reference stops at the
+ * (c, h, w, z) uncertainty volumes of eval_utils.full_slice_segment (eval_utils.py:176-198) and takes the queried slices in
+ * datasets/data_holders.py:360; its slice selection was never published.
+ * Posteriors as the library writes them: d_post [c, R] fp32, class-major, R = n_slices * V rows; 2 <= c <= 8.
+ * h(p) = -sum_j p_j log p_j, evaluated in fp64 by ONE device function, a term with p_j <= 0 exactly 0.
+ *
+ * alq_unc_accumulate folds one dropout pass into the running sums: d_sum_p [c, R] fp64 (+)= p, d_sum_h [R] fp64 (+)= h(p)
+ * (d_sum_h NULL: not kept, MC-entropy needs none).  first != 0 assigns, so the sums need no memset.  The fp64 sum of T fp32
+ * values is exact.
+ *
+ * alq_slice_scores writes, per slice, the SUM of a per-voxel value over the slice's ROI voxels (d_scores fp64 [n_slices]) and
+ * their number (d_counts int64 [n_slices]); the caller divides.  d_roi: uint8 [n_slices * V], a voxel counts when its byte is
+ * non-zero; NULL: every voxel.  An empty slice: 0.0 and 0.  The value:
+ *   ALQ_UNC_ENTROPY     h of the fp32 posteriors d_f32 [c, R] (no sums read)
+ *   ALQ_UNC_MC_ENTROPY  h(sum_p / T)
+ *   ALQ_UNC_BALD        h(sum_p / T) - sum_h / T      (exactly 0 for T = 1)
+ *   ALQ_UNC_MEAN        d_f32 [R] itself (the AU_vals log-variance map)
+ * Two stages: a workgroup sweeps rows_per_sweep consecutive rows at a time (whatever V is: a sweep may hold parts of two slices,
+ * or many whole ones) and stores one partial per (slice, sweep) at a place of its own, then a thread per slice adds the slice's
+ * partials in ascending order.  No float or double atomics; the order of every addition depends on (n_slices, V) alone, so
+ * results are bit-identical from run to run.  The partials live in the context (grown by the call that needs more).
+ * alq_slice_scores_geometry: out[4] = workgroup size, rows per workgroup sweep, the grid cap, partials per slice - the launch
+ * arithmetic, for tests that assert the regime they name (no device call).
+ * Stream-ordered, no synchronisation.  Before any launch - outputs untouched - ALQ_EINVAL: a null required pointer (ctx, the
+ * outputs, the inputs of the kind), T < 1, n_slices < 1, V < 1 (R < 1), an unknown kind, a pointer not aligned to its element;
+ * ALQ_EUNSUPPORTED: c outside 2 .. 8, n_slices * V (R) >= 2^31.                                                                   */
+enum { ALQ_UNC_ENTROPY = 0, ALQ_UNC_MC_ENTROPY = 1, ALQ_UNC_BALD = 2, ALQ_UNC_MEAN = 3 };
+int alq_unc_accumulate(alq_ctx *ctx, const float *d_post, int c, int64_t R, int first, double *d_sum_p, double *d_sum_h);
+int alq_slice_scores(alq_ctx *ctx, int kind, int T, int c, int64_t n_slices, int64_t V, const double *d_sum_p, const double *d_sum_h,
+                     const float *d_f32, const uint8_t *d_roi, double *d_scores, int64_t *d_counts);
+int alq_slice_scores_geometry(int c, int64_t n_slices, int64_t V, int64_t *out);
+
 /* Multi-GPU top-B merge step (no reference counterpart: the reference is one process).
  * Host function: merges the candidate (key, GLOBAL index) pairs gathered from all ranks
  * (torch.distributed all_gather over RCCL in pool_shard.merge_topB; entries with index < 0 are padding)

@@ -145,6 +145,9 @@ _SIGNATURES = {
     'alq_cc_relabel': (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32, _P, _P]),
     'alq_confusion_counts': (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, _P, _P]),
     'alq_confusion_window': (C.c_int, [C.c_int]),
+    'alq_unc_accumulate': (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, _P, _P]),
+    'alq_slice_scores': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, _P]),
+    'alq_slice_scores_geometry': (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
     'alq_dcrf_work_bytes': (C.c_size_t, [C.POINTER(C.c_int64)]),
     'alq_dcrf2d': (C.c_int, [_P, _P, _P, C.POINTER(C.c_int64), C.POINTER(DcrfParams), _P, _P, _P]),
     'alq_llfc_grads': (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),

@@ -95,6 +95,7 @@ struct ProfSlot {
 #define ALQ_LOSS_MAX_BLOCKS 64      // workgroups of loss_cotangent_kernel (grid-stride beyond 64 * 256 samples)
 #define ALQ_DENSE_MAX_BLOCKS 2048   // workgroups (= rows of fp64 partials) of dense_head_bwd_kernel (dense.hip)
 #define ALQ_MT_MAX_BLOCKS 2048      // workgroups of mt_cotangent_kernel (mteach.hip): 8 per compute unit, grid-stride beyond
+#define ALQ_SQ_MAX_BLOCKS 2048      // workgroups of the slice-query kernels (sliceq.hip): 8 per compute unit, grid-stride beyond
 #define ALQ_PARAM_FLAG_OFFSET (ALQ_PARAM_BLOCK_BYTES - 8)   // last word of the block: the bad-index flag of alq_eval_counts
 
 struct alq_ctx {
@@ -115,6 +116,9 @@ struct alq_ctx {
     void *param_block = nullptr;   // small device buffer for per-call parameters (gather)
     double *loss_part = nullptr;   // per-workgroup partials of the loss statistics (loss.hip), allocated by the first call
     double *mt_part = nullptr;     // ... of the mean-teacher statistics (mteach.hip), likewise
+    void *sq_part = nullptr;       // per-sweep partials of alq_slice_scores (sliceq.hip), grown by the call that needs more;
+    size_t sq_part_bytes = 0;      // outgrown buffers (a queued launch may still read one) are freed with the context
+    std::vector<void *> sq_retired;
     void *comm = nullptr;          // RCCL communicator of this rank (comm.hip), or null
     int comm_rank = 0, comm_world = 1;
     int f16_subnormal_mfma = -1;   // c3d_subnormals_ok: -1 not probed yet on this context's device, else 0 / 1

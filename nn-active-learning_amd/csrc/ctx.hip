@@ -139,6 +139,8 @@ int alq_ctx_destroy(alq_ctx *ctx) {
     (void)hipFree(ctx->param_block);
     if (ctx->loss_part) (void)hipFree(ctx->loss_part);
     if (ctx->mt_part) (void)hipFree(ctx->mt_part);
+    if (ctx->sq_part) (void)hipFree(ctx->sq_part);
+    for (void *p : ctx->sq_retired) (void)hipFree(p);
     delete ctx;
     return ALQ_OK;
 }

@@ -188,6 +188,42 @@ class DeviceSession(object):
                                             _lib.C.c_void_p(skipped.data_ptr()) if want_skipped else None))
         return (counts, skipped) if want_skipped else counts
 
+    def unc_accumulate(self, post, sum_p, sum_h=None, first=False):
+        """alq_unc_accumulate: one dropout pass `post` (float32 device [c, R], as the forward calls return it) into the float64
+        device sums sum_p [c, R] (+= p) and sum_h [R] (+= -sum_j p_j log p_j; None: not kept).  first: assign instead of add."""
+        torch = self.torch
+        self.bind_stream()
+        c, R = (int(v) for v in post.shape)
+        assert post.dtype == torch.float32 and post.is_contiguous() and post.device == self.device
+        for t, numel in ((sum_p, c * R), (sum_h, R)):
+            assert t is None or (t.dtype == torch.float64 and t.is_contiguous() and t.device == self.device and int(t.numel()) == numel)
+        check(self.lib.alq_unc_accumulate(self._ctx, C.c_void_p(post.data_ptr()), c, R, 1 if first else 0, C.c_void_p(sum_p.data_ptr()),
+                                          C.c_void_p(sum_h.data_ptr()) if sum_h is not None else None))
+
+    def slice_scores(self, kind, n_slices, V, c, T=1, sum_p=None, sum_h=None, f32=None, roi=None, scores=None, counts=None):
+        """alq_slice_scores: per slice the SUM of the per-voxel value of `kind` (slice_query.KINDS: entropy of the float32
+        posteriors f32 [c, R]; MC-entropy / BALD of the float64 sums of T passes; the float32 map f32 [R] itself) over the
+        voxels whose `roi` byte (uint8 device [R], None: all) is non-zero, and their number: (scores float64, counts int64)
+        device tensors [n_slices] (written into the ones given).  R = n_slices * V.  Nothing is copied back."""
+        torch = self.torch
+        self.bind_stream()
+        n_slices, V, c = int(n_slices), int(V), int(c)
+        R = n_slices * V
+        if scores is None:
+            scores = self.empty((max(n_slices, 0),), torch.float64)
+        if counts is None:
+            counts = self.empty((max(n_slices, 0),), torch.int64)
+        for t, dt, numel in ((sum_p, torch.float64, c * R), (sum_h, torch.float64, R), (roi, torch.uint8, R), (scores, torch.float64, n_slices),
+                             (counts, torch.int64, n_slices), (f32, torch.float32, None)):
+            assert t is None or (t.dtype == dt and t.is_contiguous() and t.device == self.device and numel in (None, int(t.numel())))
+        assert f32 is None or int(f32.numel()) in (R, c * R)
+
+        def ptr(t):
+            return C.c_void_p(t.data_ptr()) if t is not None else None
+        check(self.lib.alq_slice_scores(self._ctx, int(kind), int(T), c, n_slices, V, ptr(sum_p), ptr(sum_h), ptr(f32), ptr(roi), ptr(scores),
+                                        ptr(counts)))
+        return scores, counts
+
     def cc_sizes(self, labels):
         """alq_cc_sizes: `labels` int32 device tensor as cc_label returns it -> int32 device tensor of its shape, the size of the
         component at every root voxel (the smallest raveled index of the component), 0 elsewhere."""
