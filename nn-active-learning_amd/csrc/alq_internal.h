@@ -10,10 +10,9 @@
 
 #include "alq.h"
 #include "engine_switches.h"      // enum Knob, EngineSwitches
+#include "model_plan.h"           // set_error, ALQ_REQUIRE / ALQ_TRY, ConvDesc, G4Geom, the shape pass and the descriptor builders
 
 namespace alq {
-
-void set_error(const char *fmt, ...);
 
 #define ALQ_HIP(expr)                                                                     \
     do {                                                                                  \
@@ -23,20 +22,6 @@ void set_error(const char *fmt, ...);
                              hipGetErrorString(e_));                                      \
             return ALQ_EHIP;                                                              \
         }                                                                                 \
-    } while (0)
-
-#define ALQ_REQUIRE(cond, code, ...)                                                      \
-    do {                                                                                  \
-        if (!(cond)) {                                                                    \
-            ::alq::set_error(__VA_ARGS__);                                                \
-            return (code);                                                                \
-        }                                                                                 \
-    } while (0)
-
-#define ALQ_TRY(expr)                                                                     \
-    do {                                                                                  \
-        int rc_ = (expr);                                                                 \
-        if (rc_ != ALQ_OK) return rc_;                                                    \
     } while (0)
 
 // A channels-last activation tensor [N, D, H, W, cs] of which channels c0 .. c0+C-1 are "ours"
@@ -185,15 +170,6 @@ struct IgemmPlan {
     float *d_W = nullptr;
     std::vector<int> h_koff;     // SMALLC tap/channel offset table, uploaded to d_koff
     int *d_koff = nullptr;
-};
-
-struct ConvDesc {
-    // geometry of one GEMM: taps are INPUT offsets relative to m*sm
-    int ID, IH, IW, Ci;
-    int OD, OH, OW, Co;
-    int MD, MH, MW;
-    int sm = 1, so = 1, ooff[3] = {0, 0, 0};
-    std::vector<int> tz, ty, tx;  // tap offsets
 };
 
 int igemm_build_plan(const ConvDesc &d, int max_batch, IgemmPlan *plan);
@@ -392,18 +368,6 @@ struct Igemm4Args {
     // is not read), and the sign field of the output written after the ReLU of a forward launch (sign_out)
     const unsigned char *mask_bits;
     unsigned char *sign_out;
-};
-
-struct G4Geom {
-    int kind = 0;             // 0 stride-1 conv (fwd, or bwd-data when flipped), 1 conv_transpose bwd-data, 2 conv_transpose fwd (all classes),
-                              // 3 conv_transpose fwd, the one output parity class `cls`,
-                              // 4 conv_transpose fwd, every class as its own tiles of one launch (input restaged per class)
-    int cls[3] = {0, 0, 0};
-    int ID = 1, IH = 1, IW = 1, Ci = 0;     // GEMM input tensor
-    int OD = 1, OH = 1, OW = 1, Co = 0;     // GEMM output tensor
-    int k[3] = {1, 1, 1}, s[3] = {1, 1, 1}, lo[3] = {0, 0, 0};
-    bool flipped = false;
-    double flops_per_patch = 0;
 };
 
 struct Igemm4Plan {

@@ -9,17 +9,6 @@
 
 #include "model_types.h"
 
-namespace alq {
-
-static void same_pads(int in, int k, int s, int *out, int *lo) {
-    *out = (in + s - 1) / s;
-    int total = (*out - 1) * s + k - in;
-    if (total < 0) total = 0;
-    *lo = total / 2;
-}
-
-}  // namespace alq
-
 using namespace alq;
 
 // ------------------------------------------------------------------------------------------
@@ -92,155 +81,26 @@ int gemm_launch(alq_ctx *ctx, const Gemm &g, const View &in, const View &out, co
     return igemm_launch(ctx, g.p1, in, out, bias, relu, accumulate, N, cls);
 }
 
-static void enum_taps(const int k[3], std::vector<int> *tz, std::vector<int> *ty, std::vector<int> *tx) {
-    for (int z = 0; z < k[0]; ++z)
-        for (int y = 0; y < k[1]; ++y)
-            for (int x = 0; x < k[2]; ++x) {
-                tz->push_back(z); ty->push_back(y); tx->push_back(x);
-            }
+// ---- model creation: the shapes and every geometry descriptor come from model_plan.h; what follows allocates and plans --------
+static View mkview(float *p, const Shp &s, int cs, int c0, int C) {
+    View v; v.p = p; v.D = s.D; v.H = s.H; v.W = s.W; v.cs = cs; v.c0 = c0; v.C = C; return v;
 }
 
-static int build_model(alq_model *m, const alq_layer_t *specs, int n_layers) {
-    const EngineSwitches &sw = m->sw;
-    m->layers.resize(n_layers);
-    // ---- pass 1: shapes ------------------------------------------------------------------
-    struct Shp { int D, H, W, C; };
-    std::vector<Shp> outs(n_layers);
-    Shp cur = {m->in_dims[0], m->in_dims[1], m->in_dims[2], m->in_dims[3]};
-    bool flat = false;
-    int pidx = 0;
-    std::vector<int> src_of(n_layers, -1);   // dest layer -> src layer
-    std::vector<int> dest_of(n_layers, -1);  // src layer -> dest layer
-    for (int i = 0; i < n_layers; ++i) {
-        Layer &ly = m->layers[i];
-        ly.spec = specs[i];
-        const alq_layer_t &sp = ly.spec;
-        Shp in = cur;
-        if (sp.skip_src >= 0) {
-            ALQ_REQUIRE(sp.skip_src < i - 1, ALQ_EUNSUPPORTED, "layer %d: skip source %d must be an earlier, non-adjacent layer", i, sp.skip_src);
-            ALQ_REQUIRE(dest_of[sp.skip_src] < 0, ALQ_EUNSUPPORTED, "layer %d feeds more than one concat", sp.skip_src);
-            const Shp &s = outs[sp.skip_src];
-            ALQ_REQUIRE(!flat && s.D == cur.D && s.H == cur.H && s.W == cur.W, ALQ_EUNSUPPORTED,
-                        "layer %d: concat of maps of different size (resize_image_with_crop_or_pad) is outside the scored path", i);
-            in.C = cur.C + s.C;
-            src_of[i] = sp.skip_src;
-            dest_of[sp.skip_src] = i;
-        }
-        Shp o = in;
-        switch (sp.type) {
-            case ALQ_CONV: {
-                ALQ_REQUIRE(!flat, ALQ_EINVAL, "layer %d: conv after fc", i);
-                ALQ_REQUIRE(sp.s[0] == 1 && sp.s[1] == 1 && sp.s[2] == 1, ALQ_EUNSUPPORTED, "layer %d: strided conv", i);
-                for (int d = 0; d < 3; ++d) {
-                    int od;
-                    same_pads((&in.D)[d], sp.k[d], 1, &od, &ly.lo[d]);
-                }
-                o.C = sp.cout;
-                ly.pidx = pidx++;
-                ly.w_elems = (int64_t)sp.k[0] * sp.k[1] * sp.k[2] * in.C * sp.cout;
-                ly.b_elems = sp.cout;
-                break;
-            }
-            case ALQ_CONVT: {
-                ALQ_REQUIRE(!flat, ALQ_EINVAL, "layer %d: conv_transpose after fc", i);
-                for (int d = 0; d < 3; ++d) {
-                    ALQ_REQUIRE(sp.k[d] >= sp.s[d], ALQ_EUNSUPPORTED, "layer %d: conv_transpose kernel < stride", i);
-                    int od;
-                    same_pads((&in.D)[d] * sp.s[d], sp.k[d], sp.s[d], &od, &ly.lo[d]);
-                }
-                ALQ_REQUIRE(sp.s[0] == sp.s[1] || in.D == 1, ALQ_EUNSUPPORTED, "layer %d: anisotropic stride", i);
-                ALQ_REQUIRE(sp.s[1] == sp.s[2], ALQ_EUNSUPPORTED, "layer %d: anisotropic stride", i);
-                o.D = in.D * sp.s[0]; o.H = in.H * sp.s[1]; o.W = in.W * sp.s[2];
-                o.C = sp.cout;
-                ly.pidx = pidx++;
-                ly.w_elems = (int64_t)sp.k[0] * sp.k[1] * sp.k[2] * in.C * sp.cout;
-                ly.b_elems = sp.cout;
-                break;
-            }
-            case ALQ_POOL: {
-                ALQ_REQUIRE(!flat, ALQ_EINVAL, "layer %d: pool after fc", i);
-                for (int d = 0; d < 3; ++d) {
-                    ALQ_REQUIRE(sp.k[d] == sp.s[d], ALQ_EUNSUPPORTED, "layer %d: pool window != stride", i);
-                    ALQ_REQUIRE(sp.k[0] * sp.k[1] * sp.k[2] <= 255, ALQ_EUNSUPPORTED, "layer %d: pool window too large", i);
-                    same_pads((&in.D)[d], sp.k[d], sp.s[d], &(&o.D)[d], &ly.lo[d]);
-                }
-                break;
-            }
-            case ALQ_FC: {
-                ly.F = (int64_t)in.D * in.H * in.W * in.C;
-                o = {1, 1, 1, sp.cout};
-                ly.pidx = pidx++;
-                ly.w_elems = ly.F * sp.cout;
-                ly.b_elems = sp.cout;
-                flat = true;
-                break;
-            }
-            default:
-                ALQ_REQUIRE(false, ALQ_EINVAL, "layer %d: unknown type %d", i, sp.type);
-        }
-        outs[i] = o;
-        cur = o;
-    }
-    m->L = pidx;
-    if (n_layers > 0 && specs[n_layers - 1].type == ALQ_CONV) {
-        // a fully-convolutional model: the head is a 1x1 conv without ReLU on a dense tensor (dense.hip); anything else that is not an
-        // fc layer stays outside the library
-        const int hl = n_layers - 1;
-        const alq_layer_t &hs = specs[hl];
-        const int Cin = hl > 0 ? outs[hl - 1].C : m->in_dims[3];
-        ALQ_REQUIRE(hs.k[0] == 1 && hs.k[1] == 1 && hs.k[2] == 1, ALQ_EUNSUPPORTED,
-                    "a conv head must be 1x1 (found %dx%dx%d): the scored path needs an fc head or a 1x1 conv head", hs.k[0], hs.k[1], hs.k[2]);
-        ALQ_REQUIRE(!hs.relu, ALQ_EUNSUPPORTED, "a conv head takes no ReLU: its outputs are the logits");
-        ALQ_REQUIRE(hs.skip_src < 0, ALQ_EUNSUPPORTED, "a conv head on a concat (skip source %d) is unsupported", hs.skip_src);
-        ALQ_REQUIRE(hs.cout >= 2 && hs.cout <= 8, ALQ_EUNSUPPORTED, "a conv head of %d classes is unsupported (2 .. 8)", hs.cout);
-        ALQ_REQUIRE(dest_of[hl] < 0, ALQ_EUNSUPPORTED, "a conv head cannot be a skip source");
-        ALQ_REQUIRE(Cin % 4 == 0 && Cin <= 64, ALQ_EUNSUPPORTED, "a conv head on %d channels is unsupported (a multiple of 4, at most 64)", Cin);
-        ALQ_REQUIRE(hl == 0 || dest_of[hl - 1] < 0, ALQ_EUNSUPPORTED, "a conv head whose input is also a skip source is unsupported");
-        m->dense = true;
-        m->V = (int64_t)outs[hl].D * outs[hl].H * outs[hl].W;
-    } else {
-        ALQ_REQUIRE(n_layers > 0 && specs[n_layers - 1].type == ALQ_FC, ALQ_EUNSUPPORTED,
-                    "the scored path needs an fc head (get_gradients, NN_extended.py:1025) or a 1x1 conv head");
-    }
-    m->nclass = outs[n_layers - 1].C;
-    ALQ_REQUIRE(m->nclass >= 2 && m->nclass <= 64, ALQ_EUNSUPPORTED, "%d classes unsupported", m->nclass);
-    {   // The GEMM engines address a tensor with unsigned 32-bit BYTE offsets from its base, and the two halves of a split
-        // concat are one allocation: the workspace batch is the largest one every allocation stays below 2^30 floats with
-        // (NET-C at 32^3: 2047 patches).  A caller that asks for more gets this many per device pass - alq_model_max_batch
-        // reports it and the host walks a larger batch in passes (per-patch results do not depend on the split) - instead
-        // of an error at the first launch.
-        long long worst = m->epp;                                           // floats per patch of the largest allocation
-        for (int i = 0; i < n_layers; ++i) {
-            long long e = (long long)outs[i].D * outs[i].H * outs[i].W * outs[i].C;
-            if (src_of[i] >= 0) {                                           // consumer of a concat: source + direct producer share one
-                const Shp &sh = outs[src_of[i]];
-                e = std::max(e, (long long)sh.D * sh.H * sh.W * (outs[src_of[i]].C + outs[i - 1].C));
-            }
-            worst = std::max(worst, e);
-        }
-        const long long limit = std::max(1LL, ((1LL << 30) - 64) / std::max(worst, 1LL));
-        if (m->max_batch > limit) m->max_batch = (int)limit;
-        if (m->dense) {      // the posterior planes [c, NB V] and the cotangent rows [NB V, c] are allocations of the head's output size
-                             // (in `worst` already); the voxels of one pass are indexed in 32 bits
-            const long long lim2 = std::max(1LL, ((1LL << 31) - 1) / (long long)m->V);
-            if (m->max_batch > lim2) m->max_batch = (int)lim2;
-        }
-    }
-    const int NB = m->max_batch;
-    ALQ_REQUIRE(m->L <= 16, ALQ_EUNSUPPORTED, "%d parameterised layers > 16", m->L);
+struct ActViews { std::vector<View> act, dact, catv, dcatv; };      // per layer: output and its cotangent; a concat consumer's input likewise
 
-    // ---- pass 2: buffers (concat = two producers writing channel slices of one buffer) ----
-    auto mkview = [](float *p, const Shp &s, int cs, int c0, int C) {
-        View v; v.p = p; v.D = s.D; v.H = s.H; v.W = s.W; v.cs = cs; v.c0 = c0; v.C = C; return v;
-    };
-    std::vector<View> act(n_layers), dact(n_layers);
-    std::vector<View> catv(n_layers), dcatv(n_layers);
+// buffers (concat = two producers writing channel slices of one buffer), then the model's own result buffers
+static int alloc_activations(alq_model *m, const ModelShape &ms, ActViews *av) {
+    const EngineSwitches &sw = m->sw;
+    const int n_layers = (int)ms.layers.size(), NB = m->max_batch;
+    std::vector<View> &act = av->act, &dact = av->dact, &catv = av->catv, &dcatv = av->dcatv;
+    act.resize(n_layers); dact.resize(n_layers); catv.resize(n_layers); dcatv.resize(n_layers);
     for (int d = 0; d < n_layers; ++d) {
-        if (src_of[d] < 0) continue;
-        const int s = src_of[d];
-        ALQ_REQUIRE(dest_of[d - 1] < 0 && src_of[d] != d - 1, ALQ_EUNSUPPORTED, "layer %d: unsupported skip topology", d);
-        const int Cs = outs[s].C, Cp = outs[d - 1].C;
-        const Shp &sh = outs[s];
+        if (ms.src_of[d] < 0) continue;
+        const int s = ms.src_of[d];
+        const LayerShape &dl = ms.layers[d];
+        const alq_layer_t &dsp = m->layers[d].spec;
+        const Shp &sh = ms.layers[s].out;
+        const int Cs = sh.C, Cp = ms.layers[d - 1].out.C;
         float *buf, *dbuf;
         const size_t el = (size_t)NB * sh.D * sh.H * sh.W * (Cs + Cp);
         ALQ_TRY(m->dalloc(&buf, el));
@@ -252,22 +112,13 @@ static int build_model(alq_model *m, const alq_layer_t *specs, int n_layers) {
         // two channel groups.  Interleaved slices cost twice the cache lines per staged or stored row (32 of 64
         // bytes used), and the engine's staging and store parts are bound by lines touched.
         bool split_ok = false;
-        if (Cs == Cp && Cs % 8 == 0 && specs[d].type == ALQ_CONV && !sw.disable_v4 && !sw.no_split) {
-            const Layer &dl = m->layers[d];
-            G4Geom gf;
-            gf.kind = 0;
-            gf.ID = sh.D; gf.IH = sh.H; gf.IW = sh.W; gf.Ci = Cs + Cp;
-            gf.OD = outs[d].D; gf.OH = outs[d].H; gf.OW = outs[d].W; gf.Co = specs[d].cout;
-            for (int q = 0; q < 3; ++q) { gf.k[q] = specs[d].k[q]; gf.s[q] = specs[d].s[q]; gf.lo[q] = dl.lo[q]; }
-            G4Geom gb = gf;
-            gb.flipped = true;
-            gb.ID = outs[d].D; gb.IH = outs[d].H; gb.IW = outs[d].W; gb.Ci = specs[d].cout;
-            gb.OD = sh.D; gb.OH = sh.H; gb.OW = sh.W; gb.Co = Cs + Cp;
+        if (Cs == Cp && Cs % 8 == 0 && dsp.type == ALQ_CONV && !sw.disable_v4 && !sw.no_split) {
             Igemm4Plan tf, tb;
-            ALQ_TRY(igemm4_build_plan(gf, NB, &tf));
-            ALQ_TRY(igemm4_build_plan(gb, NB, &tb));
+            ALQ_TRY(igemm4_build_plan(conv_fwd_geom(dl.in, dl.out, dsp, dl.lo), NB, &tf));
+            ALQ_TRY(igemm4_build_plan(conv_bwd_geom(dl.in, dl.out, dsp, dl.lo), NB, &tb));
             split_ok = tf.ok && tb.ok && !tb.a.pair;
         }
+        m->layers[s].out_is_skip_src = true;
         if (split_ok) {
             const long long half = (long long)NB * sh.D * sh.H * sh.W * Cs;
             act[s] = mkview(buf, sh, Cs, 0, Cs);
@@ -279,7 +130,6 @@ static int build_model(alq_model *m, const alq_layer_t *specs, int n_layers) {
             if (sbuf) { act[s].sg = sbuf; act[d - 1].sg = sbuf + half / 4; catv[d].sg = sbuf; }
             dcatv[d] = mkview(dbuf, sh, Cs, 0, Cs + Cp);
             dcatv[d].split = Cs; dcatv[d].delta = half;
-            m->layers[s].out_is_skip_src = true;
             continue;
         }
         act[s] = mkview(buf, sh, Cs + Cp, 0, Cs);
@@ -289,18 +139,18 @@ static int build_model(alq_model *m, const alq_layer_t *specs, int n_layers) {
         catv[d] = mkview(buf, sh, Cs + Cp, 0, Cs + Cp);
         dcatv[d] = mkview(dbuf, sh, Cs + Cp, 0, Cs + Cp);
         if (sbuf) { act[s].sg = sbuf; act[d - 1].sg = sbuf; catv[d].sg = sbuf; }
-        m->layers[s].out_is_skip_src = true;
     }
     for (int i = 0; i < n_layers; ++i) {
         if (act[i].p) continue;
-        const Shp &sh = outs[i];
+        const Shp &sh = ms.layers[i].out;
+        const alq_layer_t &sp = m->layers[i].spec;
         float *buf, *dbuf;
         const size_t el = (size_t)NB * sh.D * sh.H * sh.W * sh.C;
         ALQ_TRY(m->dalloc(&buf, el));
         ALQ_TRY(m->dalloc(&dbuf, el));
         act[i] = mkview(buf, sh, sh.C, 0, sh.C);
         dact[i] = mkview(dbuf, sh, sh.C, 0, sh.C);
-        if (sh.C % 4 == 0 && specs[i].type != ALQ_FC && (specs[i].type == ALQ_POOL || specs[i].relu)) ALQ_TRY(m->dalloc(&act[i].sg, el / 4));
+        if (sh.C % 4 == 0 && sp.type != ALQ_FC && (sp.type == ALQ_POOL || sp.relu)) ALQ_TRY(m->dalloc(&act[i].sg, el / 4));
     }
     m->logits = act[n_layers - 1].p;
     m->dlogits = dact[n_layers - 1].p;
@@ -308,230 +158,193 @@ static int build_model(alq_model *m, const alq_layer_t *specs, int n_layers) {
     ALQ_TRY(m->dalloc(&m->S, (size_t)NB * m->L));
     ALQ_TRY(m->dalloc(&m->sizes, (size_t)m->L));
     ALQ_TRY(m->dalloc(&m->Apart, (size_t)((NB + 63) / 64) * m->L * m->L));
+    return ALQ_OK;
+}
 
-    // ---- pass 3: per-layer plans ---------------------------------------------------------
-    Shp inshape = {m->in_dims[0], m->in_dims[1], m->in_dims[2], m->in_dims[3]};
-    std::vector<double> h_sizes(m->L);
-    for (int i = 0; i < n_layers; ++i) {
-        Layer &ly = m->layers[i];
-        const alq_layer_t &sp = ly.spec;
-        if (src_of[i] >= 0) {
-            ly.in = catv[i];
-            ly.din = dcatv[i];
-        } else if (i == 0) {
-            ly.in = mkview(nullptr, inshape, inshape.C, 0, inshape.C);   // pointer bound per call
-            ly.din = View();
-        } else {
-            ly.in = act[i - 1];
-            ly.din = dact[i - 1];
+static int plan_conv(alq_model *m, const LayerShape &ls, Layer &ly) {
+    const EngineSwitches &sw = m->sw;
+    const int NB = m->max_batch;
+    const alq_layer_t &sp = ly.spec;
+    const bool first_param = (ly.pidx == 0);
+    const ConvDesc d = conv_fwd_desc(ls.in, ls.out, sp, ly.lo);
+    const G4Geom g4 = conv_fwd_geom(ls.in, ls.out, sp, ly.lo);
+    ly.fwd.resize(1);
+    ALQ_TRY(gemm_build(sw, d, NB, &ly.fwd[0], &g4));
+    // a 2-D window of 25 taps or more: the two-slot engine's tiles re-stage too much halo - NET-B's conv2 (24 -> 32 channels,
+    // 5 x 5 at 32^2) takes 673 us per 2048 patches there and ~390 on igemm3 (round 6; ALQ_NO_WIDE2D_RULE=1 = the other arm)
+    if (ly.fwd[0].p4.ok && ly.fwd[0].p3.ok && d.ID == 1 && d.tz.size() >= 25 && !sw.no_wide2d_rule) ly.fwd[0].p4.ok = false;
+    // a forward launch that stays on igemm3, tiles of one patch: the fp16-pair twin of its weights for Fisher / forward-only passes
+    // (run_forward, round 6; ALQ_NO_V3_F16_FWD=1: bf16 triples as before)
+    if (!ly.fwd[0].p4.ok && !ly.fwd[0].pd.ok && !ly.fwd[0].pfc.ok && ly.fwd[0].p3.ok && ly.fwd[0].p2.a.PT == 1 && sp.skip_src < 0 &&
+        !sw.no_v3_f16_fwd && !sw.no_v3_f16) {
+        ly.fwd[0].p3_f16 = true;
+        m->v3_fwd_f16 = true;
+    }
+    if (!ly.fwd[0].p4.ok && !ly.fwd[0].p3.ok && !ly.fwd[0].pd.ok && sp.cout > 32 && !sw.no_co_split) {
+        for (int w : {32, 48, 16}) {
+            if (sp.cout % w || sp.cout <= w) continue;
+            std::vector<Gemm> parts(sp.cout / w);
+            bool ok = true;
+            for (size_t j = 0; j < parts.size() && ok; ++j) {
+                ConvDesc dj = d;
+                dj.Co = w;
+                G4Geom gj = g4;
+                gj.Co = w;
+                ALQ_TRY(gemm_build(sw, dj, NB, &parts[j], &gj));
+                ok = parts[j].p4.ok || parts[j].p3.ok;
+            }
+            if (ok) { ly.fwd_co = std::move(parts); ly.fwd_co_w = w; break; }
         }
-        ly.out = act[i];
-        ly.dout = dact[i];
-        if (m->dense && i == n_layers - 1) {      // the 1x1 conv head: plain fp32 weights [Ci][c], no engine plans, no statistics buffers
-            ALQ_REQUIRE(ly.in.cs == ly.in.C && ly.in.c0 == 0 && !ly.in.split, ALQ_EUNSUPPORTED, "layer %d: conv head on a concat slice", i);
-            ly.dense_head = true;
-            h_sizes[ly.pidx] = (double)(ly.w_elems + ly.b_elems);
-            ALQ_TRY(m->dalloc(&ly.d_bias, (size_t)ly.b_elems));
-            ALQ_TRY(m->dalloc(&ly.d_W32, (size_t)ly.w_elems));
-            ALQ_TRY(m->dalloc(&m->dh_part, (size_t)ALQ_DENSE_MAX_BLOCKS * (ly.w_elems + ly.b_elems)));
-            continue;
+    }
+    if (!first_param && sp.relu) {
+        ALQ_TRY(c3d_fwd_build(ly.in, ly.out, sp.k, ly.lo, sp.s, &ly.c3f));
+        ALQ_TRY(c3d_bwd_build(ly.in, ly.out, sp.k, ly.lo, sp.s, &ly.c3b));
+        ALQ_TRY(e3d_build(ly.in, ly.out, sp.k, ly.lo, sp.s, &ly.e3b));
+        ALQ_TRY(d3d_build(ly.in, ly.out, sp.k, ly.lo, sp.s, &ly.d3f));
+        ALQ_TRY(f3d_build(ly.in, ly.out, sp.k, ly.lo, sp.s, &ly.f3f));
+    }
+    if (!first_param) {
+        const G4Geom gb = conv_bwd_geom(ls.in, ls.out, sp, ly.lo);
+        ALQ_TRY(gemm_build(sw, conv_bwd_desc(ls.in, ls.out, sp, ly.lo), NB, &ly.bwd, &gb));
+        ly.has_bwd = true;
+        // a backward launch that stays on igemm3 (no two-slot plan: NET-B's 5 x 5 and 96-channel convs) takes fp16 pairs under the
+        // cotangent bound of a Fisher pass like the two-slot launches do (round 6; ALQ_NO_V3_F16=1: bf16 triples as before)
+        ly.bwd.p3_f16 = !ly.bwd.p4.ok && ly.bwd.p3.ok && !sw.no_v3_f16;
+    }
+    return ALQ_OK;
+}
+
+static int plan_convt(alq_model *m, const LayerShape &ls, Layer &ly, int i) {
+    const EngineSwitches &sw = m->sw;
+    const int NB = m->max_batch;
+    const alq_layer_t &sp = ly.spec;
+    const bool first_param = (ly.pidx == 0);
+    const int nclsz = convt_classes_z(ls.in, sp);
+    for (int cz = 0; cz < nclsz; ++cz)
+        for (int cy = 0; cy < sp.s[1]; ++cy)
+            for (int cx = 0; cx < sp.s[2]; ++cx) {
+                std::vector<int> tl;
+                const ConvDesc d = convt_class_desc(ls.in, ls.out, sp, ly.lo, cz, cy, cx, &tl);
+                ALQ_REQUIRE(!tl.empty(), ALQ_EUNSUPPORTED, "layer %d: empty conv_transpose class", i);
+                ly.class_taps.push_back(tl);
+                ly.fwd.emplace_back();
+                const G4Geom gc = convt_class_geom(ls.in, ls.out, sp, ly.lo, cz, cy, cx);
+                ALQ_TRY(gemm_build(sw, d, NB, &ly.fwd.back(), &gc));
+            }
+    ALQ_REQUIRE(sp.s[0] == sp.s[2] || (ly.in.D == 1 && sp.s[0] == 1), ALQ_EUNSUPPORTED,
+                "layer %d: conv_transpose stride must be isotropic", i);
+    if (!sw.disable_v4) {
+        double flops = 0;
+        for (const Gemm &c : ly.fwd) flops += c.p1.flops_per_patch;
+        G4Geom gf = convt_all_geom(ls.in, ls.out, sp, ly.lo, 2);
+        gf.flops_per_patch = flops;
+        ALQ_TRY(igemm4_build_plan(gf, NB, &ly.fwd_all));
+        if (!ly.fwd_all.ok && !sw.no_class_tiles) {      // too large to stage once: the classes as tiles of one launch
+            gf = convt_all_geom(ls.in, ls.out, sp, ly.lo, 4);
+            gf.flops_per_patch = flops;
+            ALQ_TRY(igemm4_build_plan(gf, NB, &ly.fwd_all));
         }
-        if (ly.spec.type != ALQ_FC) ALQ_TRY(m->dalloc(&ly.osum, (size_t)NB * ly.out.vox()));
-        if (ly.pidx >= 0) {
-            h_sizes[ly.pidx] = (double)(ly.w_elems + ly.b_elems);
-            ALQ_TRY(m->dalloc(&ly.d_bias, (size_t)ly.b_elems));
-            ALQ_TRY(m->dalloc(&ly.asum, (size_t)NB * ly.in.vox()));
-            ALQ_TRY(m->dalloc(&ly.dsum, (size_t)NB * ly.out.vox()));
+    }
+    if (!sp.relu) ALQ_TRY(t3d_build(ly.in, ly.out, sp.k, ly.lo, sp.s, &ly.t3f, &ly.t3b));
+    if (first_param) ly.t3b.ok = false;
+    if (!first_param) {
+        const G4Geom gb = convt_bwd_geom(ls.in, ls.out, sp, ly.lo);
+        ALQ_TRY(gemm_build(sw, convt_bwd_desc(ls.in, ls.out, sp, ly.lo), NB, &ly.bwd, &gb));
+        ly.has_bwd = true;
+    }
+    return ALQ_OK;
+}
+
+static int plan_pool(alq_model *m, Layer &ly) {
+    uint8_t *am;
+    ALQ_TRY(m->dalloc(&am, (size_t)m->max_batch * ly.out.vox() * ly.out.C));
+    ly.argmax = am;
+    return ALQ_OK;
+}
+
+// `i`: the layer's index (the last layer under a ReLU conv of 8 channels may take the two-class head's workspaces)
+static int plan_fc(alq_model *m, Layer &ly, int i) {
+    const EngineSwitches &sw = m->sw;
+    const int NB = m->max_batch, n_layers = (int)m->layers.size();
+    const alq_layer_t &sp = ly.spec;
+    ALQ_REQUIRE(ly.in.cs == ly.in.C && ly.in.c0 == 0, ALQ_EUNSUPPORTED, "layer %d: fc on a concat slice", i);
+    if (sp.cout > 8) {
+        const ConvDesc d = fc_fwd_desc(ly.F, sp.cout);
+        ly.fwd.resize(1);
+        ALQ_TRY(gemm_build(sw, d, NB, &ly.fwd[0]));
+        if (ly.fwd[0].pfc.ok && !sw.no_fc_f16_fwd) {      // forward launch of a wide fc layer on fp16 pairs (measured per-patch maxima)
+            ly.fwd[0].pfc_f16 = true;
+            ALQ_TRY(m->dalloc(&ly.fwd[0].fc_row_amax, (size_t)m->max_batch));
         }
-        const bool first_param = (ly.pidx == 0);
-        if (sp.type == ALQ_CONV) {
-            ConvDesc d;
-            d.ID = ly.in.D; d.IH = ly.in.H; d.IW = ly.in.W; d.Ci = ly.in.C;
-            d.OD = ly.out.D; d.OH = ly.out.H; d.OW = ly.out.W; d.Co = sp.cout;
-            d.MD = d.OD; d.MH = d.OH; d.MW = d.OW;
-            enum_taps(sp.k, &d.tz, &d.ty, &d.tx);
-            for (size_t t = 0; t < d.tz.size(); ++t) { d.tz[t] -= ly.lo[0]; d.ty[t] -= ly.lo[1]; d.tx[t] -= ly.lo[2]; }
-            ly.fwd.resize(1);
-            G4Geom g4;
-            g4.kind = 0;
-            g4.ID = ly.in.D; g4.IH = ly.in.H; g4.IW = ly.in.W; g4.Ci = ly.in.C;
-            g4.OD = ly.out.D; g4.OH = ly.out.H; g4.OW = ly.out.W; g4.Co = sp.cout;
-            for (int q = 0; q < 3; ++q) { g4.k[q] = sp.k[q]; g4.s[q] = sp.s[q]; g4.lo[q] = ly.lo[q]; }
-            ALQ_TRY(gemm_build(sw, d, NB, &ly.fwd[0], &g4));
-            // a 2-D window of 25 taps or more: the two-slot engine's tiles re-stage too much halo - NET-B's conv2 (24 -> 32 channels,
-            // 5 x 5 at 32^2) takes 673 us per 2048 patches there and ~390 on igemm3 (round 6; ALQ_NO_WIDE2D_RULE=1 = the other arm)
-            if (ly.fwd[0].p4.ok && ly.fwd[0].p3.ok && d.ID == 1 && d.tz.size() >= 25 && !sw.no_wide2d_rule) ly.fwd[0].p4.ok = false;
-            // a forward launch that stays on igemm3, tiles of one patch: the fp16-pair twin of its weights for Fisher / forward-only passes
-            // (run_forward, round 6; ALQ_NO_V3_F16_FWD=1: bf16 triples as before)
-            if (!ly.fwd[0].p4.ok && !ly.fwd[0].pd.ok && !ly.fwd[0].pfc.ok && ly.fwd[0].p3.ok && ly.fwd[0].p2.a.PT == 1 && sp.skip_src < 0 &&
-                !sw.no_v3_f16_fwd && !sw.no_v3_f16) {
-                ly.fwd[0].p3_f16 = true;
-                m->v3_fwd_f16 = true;
-            }
-            if (!ly.fwd[0].p4.ok && !ly.fwd[0].p3.ok && !ly.fwd[0].pd.ok && sp.cout > 32 && !sw.no_co_split) {
-                for (int w : {32, 48, 16}) {
-                    if (sp.cout % w || sp.cout <= w) continue;
-                    std::vector<Gemm> parts(sp.cout / w);
-                    bool ok = true;
-                    for (size_t j = 0; j < parts.size() && ok; ++j) {
-                        ConvDesc dj = d;
-                        dj.Co = w;
-                        G4Geom gj = g4;
-                        gj.Co = w;
-                        ALQ_TRY(gemm_build(sw, dj, NB, &parts[j], &gj));
-                        ok = parts[j].p4.ok || parts[j].p3.ok;
-                    }
-                    if (ok) { ly.fwd_co = std::move(parts); ly.fwd_co_w = w; break; }
-                }
-            }
-            if (!first_param && sp.relu) {
-                ALQ_TRY(c3d_fwd_build(ly.in, ly.out, sp.k, ly.lo, sp.s, &ly.c3f));
-                ALQ_TRY(c3d_bwd_build(ly.in, ly.out, sp.k, ly.lo, sp.s, &ly.c3b));
-                ALQ_TRY(e3d_build(ly.in, ly.out, sp.k, ly.lo, sp.s, &ly.e3b));
-                ALQ_TRY(d3d_build(ly.in, ly.out, sp.k, ly.lo, sp.s, &ly.d3f));
-                ALQ_TRY(f3d_build(ly.in, ly.out, sp.k, ly.lo, sp.s, &ly.f3f));
-            }
-            if (!first_param) {
-                ConvDesc b;
-                b.ID = ly.out.D; b.IH = ly.out.H; b.IW = ly.out.W; b.Ci = sp.cout;
-                b.OD = ly.in.D; b.OH = ly.in.H; b.OW = ly.in.W; b.Co = ly.in.C;
-                b.MD = b.OD; b.MH = b.OH; b.MW = b.OW;
-                enum_taps(sp.k, &b.tz, &b.ty, &b.tx);
-                for (size_t t = 0; t < b.tz.size(); ++t) {
-                    b.tz[t] = ly.lo[0] - b.tz[t]; b.ty[t] = ly.lo[1] - b.ty[t]; b.tx[t] = ly.lo[2] - b.tx[t];
-                }
-                G4Geom gb = g4;
-                gb.flipped = true;
-                gb.ID = ly.out.D; gb.IH = ly.out.H; gb.IW = ly.out.W; gb.Ci = sp.cout;
-                gb.OD = ly.in.D; gb.OH = ly.in.H; gb.OW = ly.in.W; gb.Co = ly.in.C;
-                ALQ_TRY(gemm_build(sw, b, NB, &ly.bwd, &gb));
-                ly.has_bwd = true;
-                // a backward launch that stays on igemm3 (no two-slot plan: NET-B's 5 x 5 and 96-channel convs) takes fp16 pairs under the
-                // cotangent bound of a Fisher pass like the two-slot launches do (round 6; ALQ_NO_V3_F16=1: bf16 triples as before)
-                ly.bwd.p3_f16 = !ly.bwd.p4.ok && ly.bwd.p3.ok && !sw.no_v3_f16;
-            }
-        } else if (sp.type == ALQ_CONVT) {
-            // y[p] = sum_{q,t: s*q + t - lo = p} x[q] W[t]; output parity class c = p mod s uses the
-            // taps t == (c + lo) mod s at input offset (c + lo - t)/s   (<= 0)
-            std::vector<int> az, ay, ax;
-            enum_taps(sp.k, &az, &ay, &ax);
-            const int nclsz = ly.in.D == 1 && sp.s[0] == 1 ? 1 : sp.s[0];
-            for (int cz = 0; cz < nclsz; ++cz)
-                for (int cy = 0; cy < sp.s[1]; ++cy)
-                    for (int cx = 0; cx < sp.s[2]; ++cx) {
-                        ConvDesc d;
-                        d.ID = ly.in.D; d.IH = ly.in.H; d.IW = ly.in.W; d.Ci = ly.in.C;
-                        d.OD = ly.out.D; d.OH = ly.out.H; d.OW = ly.out.W; d.Co = sp.cout;
-                        d.MD = d.ID; d.MH = d.IH; d.MW = d.IW;
-                        d.so = sp.s[2];
-                        d.ooff[0] = cz; d.ooff[1] = cy; d.ooff[2] = cx;
-                        std::vector<int> tl;
-                        for (size_t t = 0; t < az.size(); ++t) {
-                            const int nz = cz + ly.lo[0] - az[t], ny = cy + ly.lo[1] - ay[t], nx = cx + ly.lo[2] - ax[t];
-                            if (nz % sp.s[0] || ny % sp.s[1] || nx % sp.s[2]) continue;
-                            d.tz.push_back(nz / sp.s[0]); d.ty.push_back(ny / sp.s[1]); d.tx.push_back(nx / sp.s[2]);
-                            tl.push_back((int)t);
-                        }
-                        ALQ_REQUIRE(!tl.empty(), ALQ_EUNSUPPORTED, "layer %d: empty conv_transpose class", i);
-                        ly.class_taps.push_back(tl);
-                        ly.fwd.emplace_back();
-                        G4Geom gc;                // this class alone on the two-slot engine (used when the fused form does not fit)
-                        gc.kind = 3;
-                        gc.ID = ly.in.D; gc.IH = ly.in.H; gc.IW = ly.in.W; gc.Ci = ly.in.C;
-                        gc.OD = ly.out.D; gc.OH = ly.out.H; gc.OW = ly.out.W; gc.Co = sp.cout;
-                        for (int q = 0; q < 3; ++q) { gc.k[q] = sp.k[q]; gc.s[q] = sp.s[q]; gc.lo[q] = ly.lo[q]; }
-                        gc.cls[0] = cz; gc.cls[1] = cy; gc.cls[2] = cx;
-                        ALQ_TRY(gemm_build(sw, d, NB, &ly.fwd.back(), &gc));
-                    }
-            ALQ_REQUIRE(sp.s[0] == sp.s[2] || (ly.in.D == 1 && sp.s[0] == 1), ALQ_EUNSUPPORTED,
-                        "layer %d: conv_transpose stride must be isotropic", i);
-            G4Geom g4;
-            g4.ID = ly.in.D; g4.IH = ly.in.H; g4.IW = ly.in.W; g4.Ci = ly.in.C;
-            g4.OD = ly.out.D; g4.OH = ly.out.H; g4.OW = ly.out.W; g4.Co = sp.cout;
-            for (int q = 0; q < 3; ++q) { g4.k[q] = sp.k[q]; g4.s[q] = sp.s[q]; g4.lo[q] = ly.lo[q]; }
-            if (!sw.disable_v4) {
-                G4Geom gf = g4;
-                gf.kind = 2;
-                gf.flops_per_patch = 0;
-                for (const Gemm &c : ly.fwd) gf.flops_per_patch += c.p1.flops_per_patch;
-                ALQ_TRY(igemm4_build_plan(gf, NB, &ly.fwd_all));
-                if (!ly.fwd_all.ok && !sw.no_class_tiles) {      // too large to stage once: the classes as tiles of one launch
-                    gf.kind = 4;
-                    ALQ_TRY(igemm4_build_plan(gf, NB, &ly.fwd_all));
-                }
-            }
-            if (!sp.relu) ALQ_TRY(t3d_build(ly.in, ly.out, sp.k, ly.lo, sp.s, &ly.t3f, &ly.t3b));
-            if (first_param) ly.t3b.ok = false;
-            if (!first_param) {
-                ConvDesc b;
-                b.ID = ly.out.D; b.IH = ly.out.H; b.IW = ly.out.W; b.Ci = sp.cout;
-                b.OD = ly.in.D; b.OH = ly.in.H; b.OW = ly.in.W; b.Co = ly.in.C;
-                b.MD = b.OD; b.MH = b.OH; b.MW = b.OW;
-                b.sm = sp.s[2];
-                enum_taps(sp.k, &b.tz, &b.ty, &b.tx);
-                for (size_t t = 0; t < b.tz.size(); ++t) { b.tz[t] -= ly.lo[0]; b.ty[t] -= ly.lo[1]; b.tx[t] -= ly.lo[2]; }
-                G4Geom gb = g4;
-                gb.kind = 1;
-                gb.ID = ly.out.D; gb.IH = ly.out.H; gb.IW = ly.out.W; gb.Ci = sp.cout;
-                gb.OD = ly.in.D; gb.OH = ly.in.H; gb.OW = ly.in.W; gb.Co = ly.in.C;
-                ALQ_TRY(gemm_build(sw, b, NB, &ly.bwd, &gb));
-                ly.has_bwd = true;
-            }
-        } else if (sp.type == ALQ_POOL) {
-            uint8_t *am;
-            ALQ_TRY(m->dalloc(&am, (size_t)NB * ly.out.vox() * ly.out.C));
-            ly.argmax = am;
-        } else {   // fc
-            ALQ_REQUIRE(ly.in.cs == ly.in.C && ly.in.c0 == 0, ALQ_EUNSUPPORTED, "layer %d: fc on a concat slice", i);
-            if (sp.cout <= 8) {
-                ly.dense_fc_small = true;
-                ly.fc_slices = fc_small_slices(ly.F);
-                ALQ_TRY(m->dalloc(&ly.d_Wp, (size_t)sp.cout * ly.F));
-                ALQ_TRY(m->dalloc(&ly.fc_partials, (size_t)NB * ly.fc_slices * sp.cout));
-                if (sp.cout == 2 && ly.F % 1024 == 0 && i == n_layers - 1 && i > 0 && m->layers[i - 1].spec.relu && m->layers[i - 1].pidx > 0 &&
-                    m->layers[i - 1].spec.type == ALQ_CONV && m->layers[i - 1].out.C == 8 && !sw.no_fc_bits) {
-                    ALQ_TRY(m->dalloc(&ly.fc_maskbits, (size_t)NB * (ly.F / 16)));      // one sign byte per 4 elements
-                    ALQ_TRY(m->dalloc(&ly.fc_wv, (size_t)ly.F));
-                    ALQ_TRY(m->dalloc(&ly.fc_wv16, (size_t)ly.F));
-                    const Layer &cv = m->layers[i - 1];
-                    const Igemm4Plan &fp = cv.fwd[0].p4;
-                    if (sp.cout == 2 && !sp.relu && fp.ok && fp.NTW == 1 && !fp.multi && fp.a.pair && fp.a.PT == 1 && cv.out.cs == 8 &&
-                        cv.out.c0 == 0 && !cv.out.split && cv.osum && !cv.out_is_skip_src && !sw.no_fc_fuse &&
-                        // the backward pass must be able to work from the bits alone (bits_ok in run_backward)
-                        cv.bwd.p4.ok && cv.bwd.p4.NTW == 1 && !cv.bwd.p4.multi && cv.bwd.p4.a.PT == 1 && !cv.dout.split) {
-                        ly.fc_slices2 = fp.a.tpg * 4;
-                        ALQ_TRY(m->dalloc(&ly.fc_part2, (size_t)NB * ly.fc_slices2));
-                        if (cv.c3f.ok && ly.F == (int64_t)cv.out.vox() * 8) {
-                            ALQ_TRY(m->dalloc(&ly.c3_part, (size_t)NB * 4));
-                            ALQ_TRY(m->dalloc(&ly.c3_asum, (size_t)NB * 4));
-                            if (cv.c3b.ok) ALQ_TRY(m->dalloc(&ly.fc_wv16c, (size_t)ly.F * 2));
-                        }
-                    }
-                }
-            } else {
-                ConvDesc d;
-                d.ID = d.IH = d.IW = 1; d.Ci = (int)ly.F;
-                d.OD = d.OH = d.OW = 1; d.Co = sp.cout;
-                d.MD = d.MH = d.MW = 1;
-                d.tz = {0}; d.ty = {0}; d.tx = {0};
-                ly.fwd.resize(1);
-                ALQ_TRY(gemm_build(sw, d, NB, &ly.fwd[0]));
-                if (ly.fwd[0].pfc.ok && !sw.no_fc_f16_fwd) {      // forward launch of a wide fc layer on fp16 pairs (measured per-patch maxima)
-                    ly.fwd[0].pfc_f16 = true;
-                    ALQ_TRY(m->dalloc(&ly.fwd[0].fc_row_amax, (size_t)m->max_batch));
-                }
-                if (!first_param) {
-                    ConvDesc b = d;
-                    b.Ci = sp.cout; b.Co = (int)ly.F;
-                    ALQ_TRY(gemm_build(sw, b, NB, &ly.bwd));
-                    ly.bwd.pfc_f16 = ly.bwd.pfc.ok && !sw.no_fc_f16;      // backward launch: fp16 pairs under the static cotangent bound
-                    ly.has_bwd = true;
-                }
+        if (ly.pidx != 0) {
+            ALQ_TRY(gemm_build(sw, fc_bwd_desc(ly.F, sp.cout), NB, &ly.bwd));
+            ly.bwd.pfc_f16 = ly.bwd.pfc.ok && !sw.no_fc_f16;      // backward launch: fp16 pairs under the static cotangent bound
+            ly.has_bwd = true;
+        }
+        return ALQ_OK;
+    }
+    ly.dense_fc_small = true;
+    ly.fc_slices = fc_small_slices(ly.F);
+    ALQ_TRY(m->dalloc(&ly.d_Wp, (size_t)sp.cout * ly.F));
+    ALQ_TRY(m->dalloc(&ly.fc_partials, (size_t)NB * ly.fc_slices * sp.cout));
+    if (sp.cout == 2 && ly.F % 1024 == 0 && i == n_layers - 1 && i > 0 && m->layers[i - 1].spec.relu && m->layers[i - 1].pidx > 0 &&
+        m->layers[i - 1].spec.type == ALQ_CONV && m->layers[i - 1].out.C == 8 && !sw.no_fc_bits) {
+        ALQ_TRY(m->dalloc(&ly.fc_maskbits, (size_t)NB * (ly.F / 16)));      // one sign byte per 4 elements
+        ALQ_TRY(m->dalloc(&ly.fc_wv, (size_t)ly.F));
+        ALQ_TRY(m->dalloc(&ly.fc_wv16, (size_t)ly.F));
+        const Layer &cv = m->layers[i - 1];
+        const Igemm4Plan &fp = cv.fwd[0].p4;
+        if (!sp.relu && fp.ok && fp.NTW == 1 && !fp.multi && fp.a.pair && fp.a.PT == 1 && cv.out.cs == 8 &&
+            cv.out.c0 == 0 && !cv.out.split && cv.osum && !cv.out_is_skip_src && !sw.no_fc_fuse &&
+            // the backward pass must be able to work from the bits alone (bits_ok in run_backward)
+            cv.bwd.p4.ok && cv.bwd.p4.NTW == 1 && !cv.bwd.p4.multi && cv.bwd.p4.a.PT == 1 && !cv.dout.split) {
+            ly.fc_slices2 = fp.a.tpg * 4;
+            ALQ_TRY(m->dalloc(&ly.fc_part2, (size_t)NB * ly.fc_slices2));
+            if (cv.c3f.ok && ly.F == (int64_t)cv.out.vox() * 8) {
+                ALQ_TRY(m->dalloc(&ly.c3_part, (size_t)NB * 4));
+                ALQ_TRY(m->dalloc(&ly.c3_asum, (size_t)NB * 4));
+                if (cv.c3b.ok) ALQ_TRY(m->dalloc(&ly.fc_wv16c, (size_t)ly.F * 2));
             }
         }
     }
-    ALQ_HIP(hipMemcpy(m->sizes, h_sizes.data(), m->L * sizeof(double), hipMemcpyHostToDevice));
-    // box-dot slab partials: conv / fc reduce over the OUTPUT grid, conv_transpose over the input grid
+    return ALQ_OK;
+}
+
+// layer i's views and the buffers every engine shares: the conv head's own (ly.dense_head: nothing else to plan), or the statistics buffers
+static int bind_layer(alq_model *m, const ModelShape &ms, const ActViews &av, int i) {
+    const int NB = m->max_batch, n_layers = (int)m->layers.size();
+    Layer &ly = m->layers[i];
+    if (ms.src_of[i] >= 0) {
+        ly.in = av.catv[i];
+        ly.din = av.dcatv[i];
+    } else if (i == 0) {
+        ly.in = mkview(nullptr, ms.layers[0].in, ms.layers[0].in.C, 0, ms.layers[0].in.C);   // pointer bound per call
+        ly.din = View();
+    } else {
+        ly.in = av.act[i - 1];
+        ly.din = av.dact[i - 1];
+    }
+    ly.out = av.act[i];
+    ly.dout = av.dact[i];
+    if (m->dense && i == n_layers - 1) {      // the 1x1 conv head: plain fp32 weights [Ci][c], no engine plans, no statistics buffers
+        ALQ_REQUIRE(ly.in.cs == ly.in.C && ly.in.c0 == 0 && !ly.in.split, ALQ_EUNSUPPORTED, "layer %d: conv head on a concat slice", i);
+        ly.dense_head = true;
+        ALQ_TRY(m->dalloc(&ly.d_bias, (size_t)ly.b_elems));
+        ALQ_TRY(m->dalloc(&ly.d_W32, (size_t)ly.w_elems));
+        ALQ_TRY(m->dalloc(&m->dh_part, (size_t)ALQ_DENSE_MAX_BLOCKS * (ly.w_elems + ly.b_elems)));
+        return ALQ_OK;
+    }
+    if (ly.spec.type != ALQ_FC) ALQ_TRY(m->dalloc(&ly.osum, (size_t)NB * ly.out.vox()));
+    if (ly.pidx >= 0) {
+        ALQ_TRY(m->dalloc(&ly.d_bias, (size_t)ly.b_elems));
+        ALQ_TRY(m->dalloc(&ly.asum, (size_t)NB * ly.in.vox()));
+        ALQ_TRY(m->dalloc(&ly.dsum, (size_t)NB * ly.out.vox()));
+    }
+    return ALQ_OK;
+}
+
+// box-dot slab partials: conv / fc reduce over the OUTPUT grid, conv_transpose over the input grid
+static int alloc_slabs(alq_model *m) {
     std::vector<int> h_nslab(m->L, 1);
     for (const Layer &ly : m->layers) {
         if (ly.pidx < 0) continue;
@@ -541,9 +354,40 @@ static int build_model(alq_model *m, const alq_layer_t *specs, int n_layers) {
         m->nslab_max = std::max(m->nslab_max, h_nslab[ly.pidx]);
     }
     ALQ_TRY(m->dalloc(&m->nslab, (size_t)m->L));
-    ALQ_TRY(m->dalloc(&m->Spart, (size_t)m->L * NB * m->nslab_max));
+    ALQ_TRY(m->dalloc(&m->Spart, (size_t)m->L * m->max_batch * m->nslab_max));
     ALQ_HIP(hipMemcpy(m->nslab, h_nslab.data(), m->L * sizeof(int), hipMemcpyHostToDevice));
     return ALQ_OK;
+}
+
+static int build_model(alq_model *m, const alq_layer_t *specs, int n_layers) {
+    ModelShape ms;
+    ALQ_TRY(plan_shapes(specs, n_layers, m->in_dims, m->epp, m->max_batch, &ms));
+    m->L = ms.L; m->dense = ms.dense; m->V = ms.V; m->nclass = ms.nclass; m->max_batch = ms.max_batch;
+    m->layers.resize(n_layers);
+    for (int i = 0; i < n_layers; ++i) {
+        Layer &ly = m->layers[i];
+        const LayerShape &ls = ms.layers[i];
+        ly.spec = specs[i];
+        for (int q = 0; q < 3; ++q) ly.lo[q] = ls.lo[q];
+        ly.pidx = ls.pidx; ly.w_elems = ls.w_elems; ly.b_elems = ls.b_elems; ly.F = ls.F;
+    }
+    ActViews av;
+    ALQ_TRY(alloc_activations(m, ms, &av));
+    std::vector<double> h_sizes(m->L);
+    for (int i = 0; i < n_layers; ++i) {
+        Layer &ly = m->layers[i];
+        ALQ_TRY(bind_layer(m, ms, av, i));
+        if (ly.pidx >= 0) h_sizes[ly.pidx] = (double)(ly.w_elems + ly.b_elems);
+        if (ly.dense_head) continue;
+        switch (ly.spec.type) {
+            case ALQ_CONV: ALQ_TRY(plan_conv(m, ms.layers[i], ly)); break;
+            case ALQ_CONVT: ALQ_TRY(plan_convt(m, ms.layers[i], ly, i)); break;
+            case ALQ_POOL: ALQ_TRY(plan_pool(m, ly)); break;
+            default: ALQ_TRY(plan_fc(m, ly, i)); break;
+        }
+    }
+    ALQ_HIP(hipMemcpy(m->sizes, h_sizes.data(), m->L * sizeof(double), hipMemcpyHostToDevice));
+    return alloc_slabs(m);
 }
 
 View flat_view(const View &v) {

@@ -1,4 +1,5 @@
 // The model plan of libalq.so: what model.hip (plans, forward and Fisher passes), grads.hip (general gradient path) and weights.hip (weight setting) share.
+// The shapes and geometry descriptors a plan is built from (plan_shapes, ConvDesc, G4Geom and their builders) are host arithmetic in model_plan.h.
 #pragma once
 #include <algorithm>
 
