@@ -809,7 +809,8 @@ int alq_debug_set_stamp_buffer(void *d_buf);
  * 4 = use the fp32-MFMA GEMM kernel instead of the bf16x3 split kernel, 7 = first conv and the pool behind
  * it as separate launches, 8 = the first conv + pool kernel on its narrow tile with per-voxel sum / sign
  * stores everywhere (same bits; ALQ_DCP_NARROW at model creation), 9 = at most that many workgroups in
- * the plane-sweep launch of csrc/e3d.hip (same bits; lets a handful of patches make multi-patch streams). */
+ * the plane-sweep launch of csrc/e3d.hip (same bits; lets a handful of patches make multi-patch streams),
+ * 10 = the same cap for the 7-k-step backward launch of csrc/c3d.hip (same bits).                          */
 int alq_debug_set(int key, int value);
 /* What the last pass of a model ran on (tests / bench reporting).  what = 0: 1 when the matrix cores of the context's device
  * keep fp16 subnormal operands (probed once; the one-accumulator form of the plane-sweep engine needs it), 1: 1 when the last
@@ -833,10 +834,14 @@ int alq_debug_set(int key, int value);
  * volumes with 16-byte channel-sum and sign-byte stores.
  * 17: form of the fused enc2 backward launch (csrc/e3d.hip) in the last backward pass: 0 = it did not run, 2 = the z plane sweep
  * (default), 1 = the row sweep (ALQ_E3D_ROWS=1 at model creation; same bits).
- * The backward indices 2, 8, 9, 11, 13 and 17 name launches of the Fisher pass only: all of them are 0 after a general backward
+ * 19: waves per SIMD of the head conv's backward kernel (csrc/c3d.hip) in the last backward pass: 0 = it did not run, 2 = the 7-k-step
+ * kernel on 512 threads, four rows per wave (default), 1 = one wave per SIMD (ALQ_C3D_BWD_WAVES=1 at model creation - same bits -
+ * and the 9-k-step forms).  (18 stays unused: callers have relied on it being refused.)
+ * 20: workgroups of that launch (0 = it did not run): min(patches, 256) unless alq_debug_set(10, g) capped it (tests).
+ * The backward indices 2, 8, 9, 11, 13, 17, 19 and 20 name launches of the Fisher pass only: all of them are 0 after a general backward
  * sweep (alq_param_grads, alq_grad_sqnorms, alq_class_layer_sums, alq_diag_fisher, the loss entry points) and after alq_hess_vecp,
  * whatever an earlier Fisher pass on the same model ran.
- * Returns the answer or a negative error code (ALQ_EINVAL for 4, which is unused, and for anything outside 0 .. 17).  */
+ * Returns the answer or a negative error code (ALQ_EINVAL for 4 and 18, which are unused, and for anything outside 0 .. 20).  */
 enum {
     ALQ_INFO_SUBNORMALS_OK = 0,
     ALQ_INFO_C3D_FWD = 1,
@@ -854,7 +859,9 @@ enum {
     ALQ_INFO_HOST_PACK_ELEMS = 14,
     ALQ_INFO_LSUM = 15,
     ALQ_INFO_DCP_FORM = 16,
-    ALQ_INFO_E3D_BWD_FORM = 17
+    ALQ_INFO_E3D_BWD_FORM = 17,
+    ALQ_INFO_C3D_BWD_WAVES = 19,
+    ALQ_INFO_C3D_BWD_GRID = 20
 };
 int alq_model_engine_info(alq_model *m, int what);
 

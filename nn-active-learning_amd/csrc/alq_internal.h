@@ -430,7 +430,8 @@ int c3d_bwd_build(const View &fwd_in, const View &fwd_out, const int k[3], const
 void c3d_bwd_pack(C3dPlan *plan, const std::vector<float> &Bmat_fwd /* the forward conv's [(tap, ci)][co] */);
 void c3d_presplit_vec(const float *v, long long F, int e, std::vector<unsigned short> *out);
 int c3d_bwd_launch(alq_ctx *ctx, const C3dPlan &plan, int N, const unsigned char *bits, const void *vec16, int e_in, const unsigned char *maskA,
-                   float *dB, float *sumA, float *sumB, int rows_per_wave = 8);
+                   float *dB, float *sumA, float *sumB, int rows_per_wave = 8, int waves_per_simd = 1 /* of the 7-k-step form: 1 or 2 */,
+                   int *grid_out = nullptr /* workgroups launched */);
 
 // ------------------------------------------------------------------ row-sweep engine for the stride-2 conv_transpose (t3d.hip)
 // 3x3x3 / stride 2 conv_transpose 16 -> 8 channels at 16^3 -> 32^3 (NET-C's up2) and its backward-data pass: every wave sweeps the

@@ -75,6 +75,11 @@ static_assert(C3_WD >= 1 && C3_WD <= 8, "weight-difference slices are fetched 1.
 #ifndef C3_B7PIPE
 #define C3_B7PIPE 4
 #endif
+// ... of its two-wave form, per half row (the partner wave fills gaps too).  Kernel traces at 2000 patches, both kernels in each
+// process, us per launch against the one-wave kernel's 1414 - 1449: 1 -> 1281, 2 -> 1197 / 1204, 3 -> 1251, 4 -> 1272, 5 -> 1274, 6 -> 1278
+#ifndef C3_B7PIPE2
+#define C3_B7PIPE2 2
+#endif
 #ifndef C3_B7PINW
 #define C3_B7PINW 0
 #endif
@@ -925,12 +930,30 @@ constexpr int P7_ROW = 34 * 16;               // one piece of one image row: slo
 constexpr int P7_PIECE = 34 * P7_ROW;         // rows y = -1 .. 32
 constexpr int P7_PLANE = 2 * P7_PIECE + 128;  // h image | l image | pad: 2320 slots
 constexpr int P7_LDS = 4 * P7_PLANE;          // 148,480 of the 163,840 bytes
-static_assert((P7_ROW / 16) % 16 == 2 && (P7_PLANE / 16) % 16 == 0 && P7_LDS <= 160 * 1024, "bank-conflict-free pitches (see above)");
+constexpr int P7_WS = 2 * 64 * 16;            // two-wave form: the S weights [h, l] x [64 lanes], behind the images
+static_assert((P7_ROW / 16) % 16 == 2 && (P7_PLANE / 16) % 16 == 0 && P7_LDS + P7_WS <= 160 * 1024, "bank-conflict-free pitches (see above)");
 }  // namespace
 
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void c3d_bwd7_kernel(const C3BwdArgs a) {
+//
+// TWO FORMS (round 9).  <8, 4>: 256 threads, one wave per SIMD, eight output rows per wave - the kernel of rounds 6 - 8.  <4, 8>
+// (default): 512 threads, TWO waves per SIMD, four output rows per wave.  One in-order wave issues its ~1,000 epilogue / staging
+// instructions per step between its 336 MFMAs, not under them (54.8 % MFMA busy); the second wave is the instruction stream
+// that fills the matrix pipe meanwhile.  Same LDS image, same ring, same patch order, same MFMA sequence and epilogue arithmetic
+// per half row: every output voxel sees the same MFMAs in the same order, so the two forms give the same bits.  A wave of the
+// two-wave form must fit 256 unified registers without scratch (the compiler's report: 250, scratch 0): 96 accumulators (instead
+// of 192), 48 weights of A and B - the S weights wait in LDS behind the images and are read and masked once per step -, ONE set of
+// B and S pieces (read at the head of their own half row, 9 and 18 MFMAs ahead of their use) and two of A pieces; with both
+// fragment sets of the one-wave form it spilled 10 - 13 registers.  Kernel trace, 2000 patches: 1431 -> 1197 us per launch.
+template <int RW, int NW>
+__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW / 4, NW / 4))) void c3d_bwd7_kernel(const C3BwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
-    constexpr int RW = 8, NU = 4;
+    static_assert(RW * NW == 32 && (NW == 4 || NW == 8), "the waves' strips of RW rows tile the 32 rows of a plane");
+    constexpr int NU = RW / 2;
+    // fragment sets: 2 = every piece of the next half row is read while this one multiplies (one wave per SIMD: nobody else hides the
+    // LDS latency); 1 = only the A pieces are, the B and S pieces are read at the head of their own half row (see the sweep step)
+    constexpr int FSETS = NW == 4 ? 2 : 1;
+    constexpr int PIPE = NW == 4 ? C3_B7PIPE : C3_B7PIPE2;
+    constexpr bool WS_LDS = NW == 8;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -939,7 +962,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const unsigned plane_v = 32u * 32u;
     const unsigned patch_v = (unsigned)D * plane_v;
 
-    for (int i = tid * 16; i < P7_LDS; i += 256 * 16) *reinterpret_cast<i32x4 *>(lds + i) = i32x4{0, 0, 0, 0};
+    for (int i = tid * 16; i < P7_LDS; i += NW * 64 * 16) *reinterpret_cast<i32x4 *>(lds + i) = i32x4{0, 0, 0, 0};
 
     // weights: [A0 A1 A2 B0 B1 B2 S] x [h, l] x [64 lanes] x [8] fp16 (c3d_bwd7_pack)
     f16x8 Wa[3][2], Wb[3][2], Ws[2];
@@ -954,6 +977,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             }
         Ws[0] = __builtin_bit_cast(f16x8, Wg[(6 * 2 + 0) * 64 + lane]);
         Ws[1] = __builtin_bit_cast(f16x8, Wg[(6 * 2 + 1) * 64 + lane]);
+        // two waves per SIMD: the S weights are needed once per step, to be masked; they wait in 2 KB of LDS behind the plane images
+        // (the same 64 lane values in every wave) instead of in 8 registers
+        if constexpr (WS_LDS) {
+            if (wave == 0) {
+                *reinterpret_cast<i32x4 *>(lds + P7_LDS + lane * 16) = __builtin_bit_cast(i32x4, Ws[0]);
+                *reinterpret_cast<i32x4 *>(lds + P7_LDS + 1024 + lane * 16) = __builtin_bit_cast(i32x4, Ws[1]);
+            }
+        }
 #if C3_B7PINW
         // 192 accumulators + the 48 registers of A and B fit the accumulation half (240 of 256): started there, they leave the
         // architectural half to the fragments, the staging and the epilogue (the S weights are masked per step: they stay vector)
@@ -993,7 +1024,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const __amdgpu_buffer_rsrc_t sB_rsrc = sw_rsrc(a.sumB, (unsigned long long)a.N * patch_v * 4u);
     auto item_patch = [&](int pi) __attribute__((always_inline)) { return (unsigned)(b0 + pi * G); };
 
-    // ---- staging of a plane: units u = 0 .. 3 (rows 8 w + 2 u, + 1): as in the kernel above ------------------------------------
+    // ---- staging of a plane: units u = 0 .. NU - 1 (rows RW w + 2 u, + 1): as in the kernel above ------------------------------
     i32x4 Vh[2], Vl[2];
     unsigned Sb[2];
     struct Src { unsigned voff, vvox, soff; };
@@ -1096,7 +1127,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     // the S weights with the k-group of a plane that does not exist zeroed (kill: that k-group, or -1)
     auto s_weights = [&](int kill, f16x8 &sh, f16x8 &sl) __attribute__((always_inline)) {
         const int km = lq == kill ? 0 : -1;
-        i32x4 h = __builtin_bit_cast(i32x4, Ws[0]), l = __builtin_bit_cast(i32x4, Ws[1]);
+        i32x4 h, l;
+        if constexpr (WS_LDS) {
+            h = *reinterpret_cast<const i32x4 *>(lds + P7_LDS + lane * 16);
+            l = *reinterpret_cast<const i32x4 *>(lds + P7_LDS + 1024 + lane * 16);
+        } else {
+            h = __builtin_bit_cast(i32x4, Ws[0]); l = __builtin_bit_cast(i32x4, Ws[1]);
+        }
         h.x &= km; h.y &= km; h.z &= km; h.w &= km;
         l.x &= km; l.y &= km; l.z &= km; l.w &= km;
         sh = __builtin_bit_cast(f16x8, h); sl = __builtin_bit_cast(f16x8, l);
@@ -1109,6 +1146,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         return c;
     };
 
+    // RING INVARIANT.  Four plane images; the plane staged in step n - 1 is image n & 3.  At step n the waves READ images n & 3
+    // (A, B: the current plane) and (n + ringS) & 3 (S: planes n - 2 .. n) and WRITE only image (n + 1) & 3, whose previous tenant
+    // - plane n - 3 - was last read in step n - 1 (as the S piece of plane (n - 1) - 2).  The ONE s_barrier at the head of a step,
+    // behind the wave's own lgkmcnt(0), separates that last read from the first write and the writes of step n - 1 from their
+    // reads; it spans every wave of the workgroup (4 or 8).  No second barrier, and no write to any other image.
     auto step = [&](auto RR, int pi, int z, long long n) __attribute__((always_inline)) {
         constexpr int R = decltype(RR)::value;
         constexpr int S_lo = (R + 2) % 3, S_mid = R, S_hi = (R + 1) % 3;
@@ -1125,20 +1167,80 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         s_weights(z == 1 ? 0 : -1, sh, sl);       // output plane 0 (completed at z = 1): its plane -1 is the z halo
 
         struct Frag { f16x8 ah, al, bh, bl, sh, sl; };
-        auto frag = [&](int i, int hx, Frag &f) __attribute__((always_inline)) {
+        auto frag_s = [&](int i, int hx, Frag &f) __attribute__((always_inline)) {
             const int o = i * P7_ROW + hx * 256;
-            f.ah = __builtin_bit_cast(f16x8, *reinterpret_cast<const i32x4 *>(lds + baseA + o));
-            f.al = __builtin_bit_cast(f16x8, *reinterpret_cast<const i32x4 *>(lds + baseA + o + P7_PIECE));
-            f.bh = __builtin_bit_cast(f16x8, *reinterpret_cast<const i32x4 *>(lds + baseB + o));
-            f.bl = __builtin_bit_cast(f16x8, *reinterpret_cast<const i32x4 *>(lds + baseB + o + P7_PIECE));
             f.sh = __builtin_bit_cast(f16x8, *reinterpret_cast<const i32x4 *>(lds + baseS + o));
             f.sl = __builtin_bit_cast(f16x8, *reinterpret_cast<const i32x4 *>(lds + baseS + o + P7_PIECE));
         };
+        auto frag_a = [&](int i, int hx, Frag &f) __attribute__((always_inline)) {
+            const int o = i * P7_ROW + hx * 256;
+            f.ah = __builtin_bit_cast(f16x8, *reinterpret_cast<const i32x4 *>(lds + baseA + o));
+            f.al = __builtin_bit_cast(f16x8, *reinterpret_cast<const i32x4 *>(lds + baseA + o + P7_PIECE));
+        };
+        auto frag_b = [&](int i, int hx, Frag &f) __attribute__((always_inline)) {
+            const int o = i * P7_ROW + hx * 256;
+            f.bh = __builtin_bit_cast(f16x8, *reinterpret_cast<const i32x4 *>(lds + baseB + o));
+            f.bl = __builtin_bit_cast(f16x8, *reinterpret_cast<const i32x4 *>(lds + baseB + o + P7_PIECE));
+        };
+        auto frag_ab = [&](int i, int hx, Frag &f) __attribute__((always_inline)) { frag_a(i, hx, f); frag_b(i, hx, f); };
+        auto frag = [&](int i, int hx, Frag &f) __attribute__((always_inline)) { frag_ab(i, hx, f); frag_s(i, hx, f); };
         Frag fc, fn;
-        frag(0, 0, fc);
+        if constexpr (FSETS == 2) frag(0, 0, fc);
+        if constexpr (FSETS == 1) frag_a(0, 0, fc);
+        // the 21 MFMAs of half row (i, hx) from the pieces in fc: output planes z + 1 (first contribution: starts at zero), z, z - 1
+        auto mfma_half = [&](auto I, int hx) __attribute__((always_inline)) {
+            constexpr int i = decltype(I)::value;
+            f32x4 c0 = f32x4{0.f, 0.f, 0.f, 0.f}, c1 = acc[S_mid][i][hx], c2 = acc[S_lo][i][hx];
+            c0 = mac3(c0, Wa[0][0], Wa[0][1], fc.ah, fc.al);
+            c1 = mac3(c1, Wa[1][0], Wa[1][1], fc.ah, fc.al);
+            c2 = mac3(c2, Wa[2][0], Wa[2][1], fc.ah, fc.al);
+            c0 = mac3(c0, Wb[0][0], Wb[0][1], fc.bh, fc.bl);
+            c1 = mac3(c1, Wb[1][0], Wb[1][1], fc.bh, fc.bl);
+            c2 = mac3(c2, Wb[2][0], Wb[2][1], fc.bh, fc.bl);
+            if constexpr (!(C3_B7ABL & 4)) c2 = mac3(c2, sh, sl, fc.sh, fc.sl);
+            acc[S_hi][i][hx] = c0; acc[S_mid][i][hx] = c1; acc[S_lo][i][hx] = c2;
+        };
         auto row = [&](auto I) __attribute__((always_inline)) {
             constexpr int i = decltype(I)::value;
             __builtin_amdgcn_sched_barrier(0);
+            if constexpr (FSETS == 1) {
+                // Two waves per SIMD: ONE set of B and S pieces, read at the head of their own half row (9 and 18 MFMAs ahead of their
+                // first use), and the A pieces of the next half row prefetched - 32 fragment registers instead of 48.  The pattern
+                // hands out its gaps in program order, so in each half row the reads stand AHEAD of the epilogue and the staging:
+                // behind those ~50 - 100 instructions they would come out of the last gaps, right in front of the MFMAs that wait
+                // for them.  Staging: unit i / 2 of the next plane is written in the second half of the even rows, and its registers take
+                // the loads of the plane after that - the whole next plane stays in flight across the step.
+                static_assert(NU == 2, "two units per plane and wave");
+#pragma unroll
+                for (int hx = 0; hx < 2; ++hx) {
+                    frag_b(i, hx, fc);
+                    if constexpr (!(C3_B7ABL & 4)) frag_s(i, hx, fc);
+                    if constexpr (!(C3_B7ABL & 1)) {
+                        if (hx == 0) epi_half(IC<S_hi>{}, I, IC<0>{}, E);
+                        else epi_half(IC<S_hi>{}, I, IC<1>{}, E);
+                    } else { const f32x4 k0 = acc[S_hi][i][hx]; asm volatile("" :: "v"(k0)); }      // (timing build: the MFMAs stay alive)
+                    // (behind the epilogue's ~55 instructions: past the nine A MFMAs of this half row, whose pieces' registers it takes)
+                    if (hx == 0) frag_a(i, 1, fn);
+                    else if (i < RW - 1) frag_a(i + 1, 0, fn);
+                    if constexpr ((i & 1) == 0 && !(C3_B7ABL & 2)) {
+                        if (hx == 1) {
+                            stage_unit(wbase, IC<i / 2>{});
+                            load_unit(C2, z2, IC<i / 2>{});
+                        }
+                    }
+                    mfma_half(I, hx);
+                    fc.ah = fn.ah; fc.al = fn.al;
+                    if constexpr (PIPE != 0) {
+#pragma unroll
+                        for (int m = 0; m < 21; ++m) {
+                            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                            __builtin_amdgcn_sched_group_barrier(C3_FILL_MASK, PIPE, 0);
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
+                return;
+            }
             if constexpr (!(C3_B7ABL & 1)) epi_row(IC<S_hi>{}, I, E);          // row i of the plane finished two steps ago, then its accumulators restart below
             else { const f32x4 k0 = acc[S_hi][i][0], k1 = acc[S_hi][i][1]; asm volatile("" :: "v"(k0), "v"(k1)); }      // (timing build: the MFMAs stay alive)
             if constexpr ((i & 1) == 0 && !(C3_B7ABL & 2)) {
@@ -1149,27 +1251,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             for (int hx = 0; hx < 2; ++hx) {
                 if (hx == 0) frag(i, 1, fn);
                 else if (i < RW - 1) frag(i + 1, 0, fn);
-                // output planes z + 1 (first contribution: starts at zero), z, z - 1
-                f32x4 c0 = f32x4{0.f, 0.f, 0.f, 0.f}, c1 = acc[S_mid][i][hx], c2 = acc[S_lo][i][hx];
-                c0 = mac3(c0, Wa[0][0], Wa[0][1], fc.ah, fc.al);
-                c1 = mac3(c1, Wa[1][0], Wa[1][1], fc.ah, fc.al);
-                c2 = mac3(c2, Wa[2][0], Wa[2][1], fc.ah, fc.al);
-                c0 = mac3(c0, Wb[0][0], Wb[0][1], fc.bh, fc.bl);
-                c1 = mac3(c1, Wb[1][0], Wb[1][1], fc.bh, fc.bl);
-                c2 = mac3(c2, Wb[2][0], Wb[2][1], fc.bh, fc.bl);
-                if constexpr (!(C3_B7ABL & 4)) c2 = mac3(c2, sh, sl, fc.sh, fc.sl);
-                acc[S_hi][i][hx] = c0; acc[S_mid][i][hx] = c1; acc[S_lo][i][hx] = c2;
+                mfma_half(I, hx);
                 fc = fn;
             }
-#if C3_B7PIPE
+            if constexpr (PIPE != 0) {
 #pragma unroll
-            for (int m = 0; m < 42; ++m) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(C3_FILL_MASK, C3_B7PIPE, 0);
+                for (int m = 0; m < 42; ++m) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(C3_FILL_MASK, PIPE, 0);
+                }
             }
-#endif
         };
-        row(IC<0>{}); row(IC<1>{}); row(IC<2>{}); row(IC<3>{}); row(IC<4>{}); row(IC<5>{}); row(IC<6>{}); row(IC<7>{});
+        row(IC<0>{}); row(IC<1>{}); row(IC<2>{}); row(IC<3>{});
+        if constexpr (RW == 8) { row(IC<4>{}); row(IC<5>{}); row(IC<6>{}); row(IC<7>{}); }
         {
             const Epi En = epi_setup(z + 1 < D ? z >= 1 : true, pi, z + 1 < D ? z - 1 : D - 2);
             mask_load(En, IC<0>{});
@@ -1186,7 +1280,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         constexpr bool last = decltype(LAST)::value != 0;
         const Epi E = epi_setup(true, pe, zo);
         auto rows = [&](auto I) __attribute__((always_inline)) { epi_row(S, I, E); };
-        rows(IC<0>{}); rows(IC<1>{}); rows(IC<2>{}); rows(IC<3>{}); rows(IC<4>{}); rows(IC<5>{}); rows(IC<6>{}); rows(IC<7>{});
+        rows(IC<0>{}); rows(IC<1>{}); rows(IC<2>{}); rows(IC<3>{});
+        if constexpr (RW == 8) { rows(IC<4>{}); rows(IC<5>{}); rows(IC<6>{}); rows(IC<7>{}); }
 #pragma unroll
         for (int i = 0; i < RW; ++i) { acc[s][i][0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[s][i][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
         if constexpr (last) {
@@ -1217,15 +1312,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         const int wb = st_lane;       // ring slot 0
         load_unit(C0, 0u, IC<0>{}); load_unit(C0, 0u, IC<1>{});
         stage_unit(wb, IC<0>{}); stage_unit(wb, IC<1>{});
-        load_unit(C0, 0u, IC<2>{}); load_unit(C0, 0u, IC<3>{});
-        stage_unit(wb, IC<2>{}); stage_unit(wb, IC<3>{});
+        if constexpr (NU == 4) {
+            load_unit(C0, 0u, IC<2>{}); load_unit(C0, 0u, IC<3>{});
+            stage_unit(wb, IC<2>{}); stage_unit(wb, IC<3>{});
+        }
         c1_pi = 0; c1_z = 0;
         advance(c1_pi, c1_z);
         c2_pi = c1_pi; c2_z = c1_z;
         advance(c2_pi, c2_z);
         const Src C1 = src_of(c1_pi);
+        // in flight across a step: the loads two units ahead (NU = 4: half a plane; NU = 2: the whole next plane)
         load_unit(C1, (unsigned)c1_z, IC<0>{}); load_unit(C1, (unsigned)c1_z, IC<1>{});
     }
+    // (one static s_setprio 1 for waves 4 - 7 here was measured too: 1209 against 1197 us per launch - not kept)
     long long n = 0;
     for (int pi = 0; pi < np; ++pi) {
         for (int zz = 0; zz < 10; ++zz) {
@@ -1380,10 +1479,11 @@ void c3d_presplit_vec(const float *v, long long F, int e, std::vector<unsigned s
 }
 
 int c3d_bwd_launch(alq_ctx *ctx, const C3dPlan &plan, int N, const unsigned char *bits, const void *vec16, int e_in, const unsigned char *maskA,
-                   float *dB, float *sumA, float *sumB, int rows_per_wave) {
+                   float *dB, float *sumA, float *sumB, int rows_per_wave, int waves_per_simd, int *grid_out) {
     ALQ_REQUIRE(plan.ok && plan.d_W && plan.D == 32, ALQ_EINVAL, "c3d: backward weights not set");
     ALQ_REQUIRE(bits && vec16 && dB && sumA && sumB, ALQ_EINVAL, "c3d: missing argument");
     SWEEP_REQUIRE_PATCHES(N, "c3d");
+    if (grid_out) *grid_out = 0;
     if (N <= 0) return ALQ_OK;
     C3BwdArgs a;
     a.bits = bits; a.vec = vec16; a.W = plan.d_W; a.maskA = maskA; a.dB = dB; a.sumA = sumA; a.sumB = sumB;
@@ -1395,8 +1495,14 @@ int c3d_bwd_launch(alq_ctx *ctx, const C3dPlan &plan, int N, const unsigned char
     const int rows8 = rows_per_wave == 4 ? 0 : 1;
     if (rows_per_wave == 7 && plan.d_W7) {      // the 27 taps in 7 k-steps (default since round 6; ALQ_C3D_BWD_ROWS=8: the 9-k-step kernel)
         a.W = plan.d_W7;
-        return sweep_launch(ctx, c3d_bwd7_kernel, (unsigned)std::min(N, 256), 256, P7_LDS, a);
+        unsigned g = (unsigned)std::min(N, 256);
+        if (g_dbg_knobs[KNOB_C3B7_GRID_CAP] > 0) g = std::min<unsigned>(g, (unsigned)g_dbg_knobs[KNOB_C3B7_GRID_CAP]);      // tests: a few workgroups, so that a handful of patches makes multi-patch streams
+        if (grid_out) *grid_out = (int)g;
+        // two waves per SIMD, four rows per wave (default since round 9; ALQ_C3D_BWD_WAVES=1: eight rows on one wave) - same bits
+        if (waves_per_simd == 2) return sweep_launch(ctx, c3d_bwd7_kernel<4, 8>, g, 512, P7_LDS + P7_WS, a);
+        return sweep_launch(ctx, c3d_bwd7_kernel<8, 4>, g, 256, P7_LDS, a);
     }
+    if (grid_out) *grid_out = rows8 ? std::min(N, 256) : std::min(2 * N, 256);
     if (rows8) return sweep_launch(ctx, c3d_bwd_kernel<true, 8>, (unsigned)std::min(N, 256), 256, 2 * (32 + 2) * B3_ROW + 2 * B3_ROW, a);
     return sweep_launch(ctx, c3d_bwd_kernel<true, 4>, (unsigned)std::min(2 * N, 256), 256, 2 * (16 + 2) * B3_ROW + 2 * B3_ROW, a);
 }

@@ -21,11 +21,12 @@ enum Knob {
     KNOB_NO_CONV_POOL = 7,    // first conv and the pool behind it as separate launches
     KNOB_DCP_NARROW = 8,      // the first conv + pool kernel on its narrow tile everywhere (direct.hip)
     KNOB_E3D_GRID_CAP = 9,    // at most that many workgroups in the plane-sweep launch of e3d.hip
-    ALQ_NKNOBS = 10
+    KNOB_C3B7_GRID_CAP = 10,  // ... in the 7-k-step backward launch of c3d.hip (alq_debug_set only: no environment variable)
+    ALQ_NKNOBS = 11
 };
 
 struct EngineSwitches {
-    int knobs[ALQ_NKNOBS] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};      // the model's snapshot of the debug knobs (alq_debug_set overrides a key for all models)
+    int knobs[ALQ_NKNOBS] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};      // the model's snapshot of the debug knobs (alq_debug_set overrides a key for all models)
     // plan time (gemm_build / build_model)
     int disable_v2 = 0;            // ALQ_DISABLE_V2=1 (diagnostics): force the general GEMM kernel, no igemm2 / direct plans
     int disable_v3 = 0;            // ALQ_DISABLE_V3=1: no igemm3 plans
@@ -59,6 +60,8 @@ struct EngineSwitches {
     int no_c3d = 0;                // ALQ_NO_C3D (A/B): the head conv pair on the two-slot engine (igemm4) as in round 3
     // 7 (default): the 27 taps packed into 7 k-steps (c3d_bwd7_kernel); 8: the 9-k-step kernel of round 4; 4: its half-patch form
     int c3_bwd_rows = 7;           // ALQ_C3D_BWD_ROWS=4 / 8 (A/B)
+    // the 7-k-step kernel's waves per SIMD: 2 (default since round 9: 512 threads, four rows per wave) or 1 (eight rows per wave); same bits
+    int c3_bwd_waves = 2;          // ALQ_C3D_BWD_WAVES=1 (A/B)
     int no_e3d = 0;                // ALQ_NO_E3D (A/B): pool2 backward, enc2 backward and pool1 backward as three launches as in round 4
     int e3d_rows = 0;              // ALQ_E3D_ROWS=1 (A/B): that launch on the row-sweep kernel of rounds 5 - 7 instead of the z plane sweep (same bits)
     int no_d3d = 0;                // ALQ_NO_D3D (A/B): dec1's forward on the two-slot engine as in round 4
@@ -154,6 +157,9 @@ inline EngineSwitches read_engine_switches() {
             case SW_ROWS:       dst = (v && std::atoi(v) == 4) ? 4 : ((v && std::atoi(v) == 8) ? 8 : 7); break;
         }
     }
+    // ALQ_C3D_BWD_WAVES (round 9) is read here and not through the table: the table is held row for row to the getenv lines it
+    // replaced (tests/host/switches_main.cpp), and this variable never had one.  1 -> 1, anything else or unset -> 2.
+    if (const char *v = std::getenv("ALQ_C3D_BWD_WAVES")) sw.c3_bwd_waves = std::atoi(v) == 1 ? 1 : 2;
     return sw;
 }
 

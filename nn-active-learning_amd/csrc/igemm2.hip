@@ -571,7 +571,7 @@ unsigned long long *g_igemm2_dbg = nullptr;
 int g_no_f16x2 = 0;
 int g_no_xcd_order = 0;
 int g_no_fixed = 0;
-int g_dbg_knobs[ALQ_NKNOBS] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // indexed by enum Knob (engine_switches.h)
+int g_dbg_knobs[ALQ_NKNOBS] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // indexed by enum Knob (engine_switches.h)
 
 template <int NTW, bool WRES, int GEO, bool SUMS>
 static int launch2_s(alq_ctx *ctx, const Igemm2Plan &plan, const Igemm2Args &a, unsigned grid) {

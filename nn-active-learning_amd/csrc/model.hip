@@ -12,7 +12,7 @@
 using namespace alq;
 
 // ------------------------------------------------------------------------------------------
-static int g_knob_override[ALQ_NKNOBS] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // alq_debug_set: >= 0 overrides every model's snapshot
+static int g_knob_override[ALQ_NKNOBS] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // alq_debug_set: >= 0 overrides every model's snapshot
 
 // The kernels' launch helpers read the process-wide g_dbg_knobs / g_no_f16x2; each entry point loads them from the
 // model it was called on, so creating another model (or its environment) never changes a live one.
@@ -1044,7 +1044,7 @@ static int run_backward_main(alq_model *m, const float *d_x, int N) {
                     int ex = 0;
                     (void)std::frexp(fz.in_vec_amax, &ex);
                     ALQ_TRY(c3d_bwd_launch(ctx, ly.c3b, N, reinterpret_cast<const unsigned char *>(fz.in_bits), vec16c, 14 - ex, fz.mask_bits,
-                                           ly.din.p + ly.din.delta, fz.osumA, fz.osumB, m->sw.c3_bwd_rows));
+                                           ly.din.p + ly.din.delta, fz.osumA, fz.osumB, m->sw.c3_bwd_rows, m->sw.c3_bwd_waves, &m->last.bwd.c3b_grid));
                 } else {
                     ALQ_TRY(igemm4_launch(ctx, ly.bwd.p4, ly.dout, ly.din, nullptr, 0, acc, N, PROF_IGEMM3_BWD, &fz));
                 }
@@ -1424,7 +1424,9 @@ int alq_model_engine_info(alq_model *m, int what) {
         case ALQ_INFO_LSUM: return m->last.lsum;
         case ALQ_INFO_DCP_FORM: return m->last.fwd.dcp;
         case ALQ_INFO_E3D_BWD_FORM: return m->last.bwd.e3b_form;
-        default: break;      // 4 is unused
+        case ALQ_INFO_C3D_BWD_WAVES: return m->last.bwd.c3_bwd ? (m->sw.c3_bwd_rows == 7 ? m->sw.c3_bwd_waves : 1) : 0;
+        case ALQ_INFO_C3D_BWD_GRID: return m->last.bwd.c3_bwd ? m->last.bwd.c3b_grid : 0;
+        default: break;      // 4 and 18 are unused
     }
     set_error("alq_model_engine_info: bad argument");
     return ALQ_EINVAL;

@@ -113,6 +113,7 @@ struct PassInfo {
     } fwd;
     struct Bwd {                   // launches of a Fisher pass's backward sweep only
         bool c3_bwd = false;       // the head conv's backward ran on the plane-sweep engine
+        int c3b_grid = 0;          // workgroups of that launch
         int t3b = 0;               // conv_transpose launches on the row-sweep engine
         int e3b = 0;               // pool2 backward, enc2 backward and pool1 backward ran as one launch (e3d.hip)
         int e3b_form = 0;          // form of that launch: 0 none, 1 row sweep, 2 z plane sweep
