@@ -287,7 +287,12 @@ def _descriptor_triples(c):
 
 
 TAP_CASES = [('conv_333', _ly(CONV, 3, (3, 3, 3)), (4, 5, 6, 2)), ('conv_155', _ly(CONV, 3, (1, 5, 5)), (4, 5, 6, 2)),
-             ('convt_k2s2', _ly(CONVT, 3, 2, 2), (3, 3, 3, 2)), ('convt_k3s2', _ly(CONVT, 3, 3, 2), (3, 3, 3, 2))]
+             ('convt_k2s2', _ly(CONVT, 3, 2, 2), (3, 3, 3, 2)), ('convt_k3s2', _ly(CONVT, 3, 3, 2), (3, 3, 3, 2)),
+             # the geometries tests/test_gpu_convt.py runs on the device: lo = 1 with two taps per class, three classes per
+             # dimension, another lo and tap count per dimension, stride 1 (one class), the 2-D schema (s[0] = 1, one z class)
+             ('convt_k4s2', _ly(CONVT, 3, 4, 2), (4, 3, 5, 2)), ('convt_k3s3', _ly(CONVT, 3, 3, 3), (2, 3, 4, 2)),
+             ('convt_k234s2', _ly(CONVT, 3, (2, 3, 4), 2), (3, 4, 5, 2)), ('convt_k3s1', _ly(CONVT, 3, 3, 1), (3, 4, 5, 2)),
+             ('convt_2d_k4s2', _ly(CONVT, 3, (1, 4, 4), (1, 2, 2)), (1, 5, 7, 2))]
 
 
 @pytest.mark.parametrize('name,layer,in_dims', TAP_CASES, ids=[c[0] for c in TAP_CASES])

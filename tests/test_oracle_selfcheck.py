@@ -7,7 +7,7 @@ import torch
 
 from oracle import alpath, netspec, tfops
 from oracle.model import OracleModel, OracleSession
-from tests import factored_ref
+from tests import convt_ref, factored_ref
 
 
 @pytest.mark.parametrize('shape,k,s', [((2, 7, 6, 3), (3, 3), None), ((1, 5, 5, 2), (5, 5), None),
@@ -29,8 +29,12 @@ def test_max_pool_same_vs_naive(shape, w):
     assert y.shape[1] == -(-shape[1] // 2)      # 25 -> 13: the odd unit of padding goes to the end
 
 
+# the geometries of tests/convt_ref.py (the table of tests/test_gpu_convt.py), two patches of three channels each
+_CONVT_TABLE = [((2,) + g['size'][3 - len(g['k']):] + (3,), tuple(g['k']), tuple(g['s'])) for g in convt_ref.GEOMETRIES.values()]
+
+
 @pytest.mark.parametrize('shape,k,s', [((2, 4, 3, 3), (3, 3), (2, 2)), ((1, 3, 2, 4, 2), (3, 3, 3), (2, 2, 2)),
-                                       ((1, 4, 4, 2), (2, 2), (2, 2))])
+                                       ((1, 4, 4, 2), (2, 2), (2, 2))] + _CONVT_TABLE)
 def test_conv_transpose_same_vs_naive(shape, k, s):
     rs = np.random.RandomState(2)
     x = rs.randn(*shape)
@@ -39,6 +43,30 @@ def test_conv_transpose_same_vs_naive(shape, k, s):
     y = tfops.conv_transpose_same(torch.tensor(x), torch.tensor(W), torch.tensor(b), s).numpy()
     assert y.shape[1] == shape[1] * s[0]
     np.testing.assert_allclose(y, tfops.naive_conv_transpose_same(x, W, b, s), rtol=1e-12, atol=1e-12)
+
+
+@pytest.mark.parametrize('tag', list(convt_ref.GEOMETRIES))
+def test_convt_ref_from_the_definition_vs_autograd(tag):
+    """tests/convt_ref.py states the layer's input and parameter gradients tap by tap from the definition (the truth of
+    tests/test_gpu_convt.py); torch autograd through tfops.conv_transpose_same in fp64 must give the same numbers."""
+    size, k3, s3, out, lo, _ = convt_ref.geometry(tag)
+    rs = np.random.RandomState(4)
+    a = rs.randn(2, *(size + (3,)))
+    W = rs.randn(*(tuple(k3) + (5, 3)))
+    dy = rs.randn(2, *(out + (5,)))
+    x = torch.tensor(a, requires_grad=True)
+    y = tfops.conv_transpose_same(x, torch.tensor(W), torch.zeros(5, dtype=torch.float64), s3)
+    assert tuple(y.shape[1:4]) == out
+    (y * torch.tensor(dy)).sum().backward()
+    np.testing.assert_allclose(convt_ref.bwd_data64(dy, W, s3, lo, size), x.grad.numpy(), rtol=1e-12, atol=1e-12)
+    np.testing.assert_allclose(convt_ref.bwd_data_torch(dy, W, s3, None, torch.float64), x.grad.numpy(), rtol=1e-12, atol=1e-12)
+    np.testing.assert_allclose(convt_ref.bwd_data64(dy, W, s3, lo, size, act=a), x.grad.numpy() * (a > 0), rtol=1e-12, atol=1e-12)
+    dW, db = convt_ref.wgrad64(a, dy, k3, s3, lo)
+    tW, tb = convt_ref.wgrad_torch(a, dy, W, s3, torch.float64)
+    np.testing.assert_allclose(dW, tW, rtol=1e-12, atol=1e-12)
+    np.testing.assert_allclose(db, tb, rtol=1e-12, atol=1e-12)
+    np.testing.assert_allclose(convt_ref.forward_torch(a, W, np.zeros(5), s3, torch.float64),
+                               convt_ref.forward_naive64(a, W, np.zeros(5), s3), rtol=1e-12, atol=1e-12)
 
 
 def test_conv_transpose_is_gradient_of_same_conv():
@@ -72,6 +100,13 @@ def _models():
     return out
 
 
+def _convt_models():
+    """A U-Net level at k = 4 and a conv_transpose below a conv at k = (2, 3, 4): the truth tests/test_gpu_convt.py judges with."""
+    ld, sk = convt_ref.unet_level([4, 4, 4], [2, 2, 2])
+    lb, _ = convt_ref.below_conv(8, 8, [2, 3, 4], [2, 2, 2], 'MA', 3)
+    return [('unet_k4s2', ld, (4, 6, 6, 1), sk), ('below_conv_k234s2', lb, (3, 4, 5, 1), ())]
+
+
 @pytest.mark.parametrize('name,ld,in_shape,skips', _models())
 def test_grad_finite_difference_fp64(name, ld, in_shape, skips):
     pars = netspec.he_init(ld, in_shape, seed=5, skips=skips, bias_std=0.1, dtype=np.float64)
@@ -95,7 +130,7 @@ def test_grad_finite_difference_fp64(name, ld, in_shape, skips):
                 assert abs(fd - gr[idx]) <= 1e-6 * max(1., abs(fd)), (name, lname, idx)
 
 
-@pytest.mark.parametrize('name,ld,in_shape,skips', _models())
+@pytest.mark.parametrize('name,ld,in_shape,skips', _models() + _convt_models())
 def test_factored_identity_fp64(name, ld, in_shape, skips):
     """One unit-cotangent backward + channel-sum/box-sum reductions == summed full gradients."""
     pars = netspec.he_init(ld, in_shape, seed=8, skips=skips, bias_std=0.1, dtype=np.float64)
