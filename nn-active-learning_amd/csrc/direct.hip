@@ -423,7 +423,7 @@ __global__ __launch_bounds__(256, 4) void direct_conv_pool_kernel(const DirectPo
     }
 }
 
-// eligibility is checked by the caller (model.hip): 3x3x3 SAME conv of one channel into 8, 2x2x2 pool, even dims
+// eligibility is checked by the caller (passes.hip): 3x3x3 SAME conv of one channel into 8, 2x2x2 pool, even dims
 int direct_conv_pool_launch(alq_ctx *ctx, const float *d_W, const View &in, const View &out, const View &pout,
                             const float *bias, int relu, uint8_t *argmax, float *osum, float *posum, int N,
                             double flops_per_patch, unsigned *amax, unsigned char *sg, unsigned char *psg) {

@@ -1,4 +1,4 @@
-// Engine-selection switches of a model: every ALQ_* environment variable model.hip understands, in ONE table, read ONCE when
+// Engine-selection switches of a model: every ALQ_* environment variable model.hip and passes.hip understand, in ONE table, read ONCE when
 // the model is created (alq_model_create -> read_engine_switches).  No HIP dependency: tests/host/switches_main.cpp compiles
 // this header with the host compiler alone.  (ALQ_G4_TUNE - a per-plan diagnostic string - and ALQ_NO_SIDE_STREAM - a switch
 // of the context - are not model switches and stay where they are read; the engines' own files read their own variables.)

@@ -15,7 +15,7 @@
 // F16 forward (round 6): fc1 / fc2 of a pass measure the per-patch maximum of their input (fc_rowmax_kernel: one read of [M x K]) and
 // contract with fp16 pairs scaled per patch; bias and ReLU ride in the epilogue.  ALQ_NO_FC_F16_FWD=1 at model creation: bf16 triples.
 // F16 (round 5): backward launches of a Fisher pass know a static bound on their input (the cotangent under the unit cotangent,
-// chained down from the head like the conv launches' - model.hip, run_backward_main): they contract with fp16 PAIRS at their true
+// chained down from the head like the conv launches' - passes.hip, bwd_bounds): they contract with fp16 PAIRS at their true
 // scale, x 2^e = h + l, three products in one accumulator instead of six (c3d.hip's one-accumulator form; needs fp16 subnormals
 // in the matrix cores: c3d_subnormals_ok), two LDS pieces per operand instead of three.
 #include "alq_internal.h"

@@ -42,8 +42,7 @@ static int run_backward_general(alq_model *m, int N, const DropSpec *drop, bool 
                 bool fused = false;
                 ALQ_TRY(k_fc_small_bwd(ctx, ly.dout.p, ly.spec.cout, ly.d_Wp, ly.F, N, ly.din.p, nullptr, nullptr, 0, &fused));
             } else {
-                // no bound: ly.dout_bound belongs to the unit cotangent of a Fisher pass (run_backward_main), this
-                // cotangent is arbitrary (loss scale, dropout factors) - the bf16-triple path, whatever ran before
+                // no bound (0): this cotangent is arbitrary (loss scale, dropout factors) - the bf16-triple path
                 ALQ_TRY(gemm_launch(ctx, ly.bwd, ly.dout, flat_view(ly.din), nullptr, 0, 0, N, PROF_IGEMM_BWD, nullptr, nullptr, 0.f));
             }
         } else {

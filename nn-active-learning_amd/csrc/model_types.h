@@ -1,4 +1,5 @@
-// The model plan of libalq.so: what model.hip (plans, forward and Fisher passes), grads.hip (general gradient path) and weights.hip (weight setting) share.
+// The model plan of libalq.so: what model.hip (plans, entry points), passes.hip (forward pass, Fisher backward sweep), grads.hip (general gradient
+// path) and weights.hip (weight setting) share.  A Layer describes the model and its weights: during a pass only device memory changes.
 // The shapes and geometry descriptors a plan is built from (plan_shapes, ConvDesc, G4Geom and their builders) are host arithmetic in model_plan.h.
 #pragma once
 #include <algorithm>
@@ -40,9 +41,6 @@ struct Layer {
     float *asum = nullptr, *dsum = nullptr;
     double *ls_field = nullptr; // [max_batch, out voxels] (fc: [max_batch]): field of alq_class_layer_sums, filled once per call
     float *osum = nullptr;     // channel sums of this layer's OUTPUT (spatial layers): next layers' asum
-    bool delta_ready = false;  // backward: the cotangent of our output is already masked and dsum is filled
-    bool signs_ready = false;  // Fisher pass: the forward launch wrote the sign field of our output (View::sg)
-    bool dsum_partial = false; // backward, first layer: the skip destination has written its share of dsum
     float *fc_partials = nullptr;
     // fc head of a Fisher pass on top of a ReLU conv: its input cotangent is [input > 0] * fc_wv for every patch; the
     // forward pass leaves the signs (one byte per 4 elements), the backward pass of the conv below contracts them
@@ -51,15 +49,11 @@ struct Layer {
     float *fc_wv = nullptr;
     unsigned *fc_wv16 = nullptr;       // fc_wv pre-split into fp16 pairs for the fp16x2 contraction of the conv below (BITSRC)
     float fc_wv_amax = 0.f;            // max |W0 - W1| of a two-output head (host side, set with the weights)
-    const unsigned *dout_amax = nullptr;   // per-patch max |cotangent of this layer's output| of the running backward pass, or null
     unsigned *amax_fwd = nullptr;          // [max_batch] per-patch max |output| of a forward pass that asked for it
-    float dout_vec_amax = 0.f;
     // Static bounds for the fp16x2 contraction of backward launches (no data pass needed): bwd_l1 = max over the input
     // channels of sum_{taps, output channels} |W| (set with the weights), i.e. |cotangent of the input| <= bwd_l1 * max
-    // |cotangent of the output|; dout_bound = the bound on this layer's output cotangent in the running Fisher pass
-    // (unit cotangent at the logits, chained down by run_backward_main).
+    // |cotangent of the output|; a Fisher pass chains them down from the unit cotangent at the logits (bwd_bounds, passes.hip).
     double bwd_l1 = 0;
-    float dout_bound = 0.f;
     // flip-safe fused head (the conv under a two-class head): plain fp32 copy of the weights in TF layout [tap][ci][co] for the
     // exact re-evaluation, and max over co of sum_{tap, ci} |W|
     float *d_W32 = nullptr;
@@ -77,10 +71,6 @@ struct Layer {
     T3dPlan t3f, t3b;                      // row-sweep engine for the stride-2 conv_transpose (t3d.hip), forward / backward-data
     float *c3_part = nullptr, *c3_asum = nullptr;
     unsigned short *fc_wv16c = nullptr;    // fc_wv as fp16 pairs at their true scale, [voxel][h8 | l8] (c3d_presplit_vec), for c3b
-    const unsigned short *dout_vec16c = nullptr;   // set on the conv below for one backward pass, like dout_vec16
-    const unsigned *dout_bits = nullptr;   // set on the conv below for the duration of one backward pass
-    const float *dout_vec = nullptr;
-    const unsigned *dout_vec16 = nullptr;
     int fc_slices = 0;
     bool out_is_skip_src = false;
     // convT class tap lists (indices into the k^3 tap enumeration)
@@ -110,6 +100,8 @@ struct PassInfo {
         int f3f = 0;               // enc2 and the pool behind it ran fused (f3d.hip)
         int dcp = 0;               // form of the first conv + pool kernel, 0 = it did not run (direct.hip: g_dcp_last_form)
         bool f16_derived = false;  // a launch ran on the fp16x2 split with derived input bounds
+        bool signs_ready[64] = {}; // per layer (alq_model_create: at most 64): a launch wrote the sign field of its output (View::sg); the
+                                   // backward sweep of the same Fisher pass and alq_model_debug_copy read it
     } fwd;
     struct Bwd {                   // launches of a Fisher pass's backward sweep only
         bool c3_bwd = false;       // the head conv's backward ran on the plane-sweep engine
@@ -215,7 +207,7 @@ int upload_release(alq_model *m, D **d, std::vector<T> *h) {
 
 namespace alq { int refresh_fallback_forms(alq_model *m); }      // weights.hip
 
-// ---- model.hip, for the general gradient path (grads.hip)
+// ---- model.hip and passes.hip, for each other and for the general gradient path (grads.hip)
 // dropout of a training / MC forward pass: layers whose OUTPUT is dropped (NN.py:169-171), one keep probability
 struct DropSpec {
     unsigned long long layers = 0;     // bit i = layer i
@@ -227,6 +219,10 @@ struct DropSpec {
 int make_drop(const alq_model *m, float keep_prob, uint64_t seed, int64_t first_sample, const int32_t *h_layers, int n_layers, DropSpec *d);
 int prepare_call(alq_model *m, bool fisher);
 int run_forward(alq_model *m, const float *d_x, int N, bool with_sums, bool keep_all = false, const DropSpec *drop = nullptr);
+int run_backward(alq_model *m, const float *d_x, int N);      // the backward sweep of a Fisher pass, behind run_forward(..., with_sums = true)
+// Which engine a gemm_launch call takes.
+enum GemmRoute { ROUTE_DIRECT, ROUTE_FCGEMM, ROUTE_IGEMM4, ROUTE_IGEMM3, ROUTE_IGEMM2, ROUTE_IGEMM };
+GemmRoute gemm_route(const alq::Gemm &g, const alq::View &in, const alq::View &out, int accumulate, const alq::Igemm2Fuse *fuse);
 int gemm_launch(alq_ctx *ctx, const alq::Gemm &g, const alq::View &in, const alq::View &out, const float *bias, int relu, int accumulate, int N,
                 int cls, const alq::Igemm2Fuse *fuse = nullptr, bool *fused = nullptr, float fc_in_bound = 0.f);
 alq::View flat_view(const alq::View &v);
