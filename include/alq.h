@@ -137,6 +137,14 @@ int alq_model_set_weights_device(alq_model *m, int t, const float *d_W, const fl
 /* 1 when alq_model_set_weights_device packs parameterised layer t with the device kernels, 0 when it takes the host packers;
  * negative error code for a bad t.                                                                                        */
 int alq_model_layer_packs_on_device(const alq_model *m, int t);
+/* The launch arithmetic of the streaming GEMM (csrc/fcgemm.hip) for a contraction of K inputs into N features over M rows, as
+ * the launches themselves compute it (no device call): out[6] = {wide (0 / 1: fcgemm_build_plan takes the shape - K a multiple of
+ * 32, N of 64, both >= 256), features per workgroup tile of the fp16-pair launches (64 / 128), tall wave tiles (0 / 1), grid.x,
+ * grid.y, k-steps}.  Reads ALQ_FC_BN64 / ALQ_FC_SQUARE as plan building does.  The bf16-triple launch of a wide shape always
+ * takes 64-feature tiles (grid.x = N / 64) over the same rows and k-steps.  A shape the plan declines: out = zeros, no error.
+ * A layer's backward Gemm is the same call with K and N swapped.  For tests: a case asserts from these that it is in the regime
+ * it names.  ALQ_EINVAL: null out or a non-positive size.                                                                   */
+int alq_fcgemm_geometry(int K, int N, int M, int *out);
 
 /* ---- patch gather + normalisation ------------------------------------------------------- */
 /* Replaces: patch_utils.get_patches (patch_utils.py:1087-1173) + the normalisation loops of

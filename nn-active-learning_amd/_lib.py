@@ -75,6 +75,7 @@ _SIGNATURES = {
     'alq_dense_head_bwd': (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P]),
     'alq_dense_head_bwd_geometry': (C.c_int, [C.c_int64, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int),
                                               C.POINTER(C.c_int)]),
+    'alq_fcgemm_geometry': (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     'alq_model_param_sizes': (C.c_int, [_P, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'alq_model_layer_out_elems': (C.c_int, [_P, C.c_int, C.POINTER(C.c_int64)]),
     'alq_model_set_weights': (C.c_int, [_P, C.c_int, _P, _P]),

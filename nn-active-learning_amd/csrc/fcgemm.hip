@@ -290,11 +290,29 @@ __global__ __launch_bounds__(256, 2) void fcgemm_kernel(const FcGemmArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------------
+// form of the fp16-pair launches, read when a plan is built: 0 = 128-wide tiles with tall wave tiles, 1 = 64 x 64 wave tiles, 2 = 64-wide tiles
+static int fc_form_from_env() { return getenv("ALQ_FC_BN64") ? 2 : (getenv("ALQ_FC_SQUARE") ? 1 : 0); }
+static bool fc_shape_ok(int K, int N) { return K % FC_BK == 0 && N % FC_BN == 0 && K >= 256 && N >= 256; }
+
+// Tile and grid of a launch over M rows - the one place they are computed (fc16_go, fcgemm_launch, alq_fcgemm_geometry).
+// f16: the fp16-pair kernels, 128 features per workgroup where the width allows; bf16 triples: the 64-wide kernel.
+struct FcTile { int BN; bool tall; unsigned gx, gy; int nks; };
+static FcTile fc_tile(int K, int N, int M, int form, bool f16) {
+    FcTile t;
+    const bool w128 = f16 && N % (2 * FC_BN) == 0 && form != 2;
+    t.BN = w128 ? 2 * FC_BN : FC_BN;
+    t.tall = w128 && form == 0;
+    t.gx = (unsigned)(N / t.BN);
+    t.gy = (unsigned)((M + FC_BM - 1) / FC_BM);
+    t.nks = K / FC_BK;
+    return t;
+}
+
 int fcgemm_build_plan(int K, int N, FcGemmPlan *plan) {
     plan->ok = false;
-    if (K % FC_BK != 0 || N % FC_BN != 0 || K < 256 || N < 256) return ALQ_OK;
+    if (!fc_shape_ok(K, N)) return ALQ_OK;
     plan->K = K; plan->N = N;
-    plan->form = getenv("ALQ_FC_BN64") ? 2 : (getenv("ALQ_FC_SQUARE") ? 1 : 0);
+    plan->form = fc_form_from_env();
     plan->ok = true;
     return ALQ_OK;
 }
@@ -364,20 +382,21 @@ void fcgemm_pack_weights_f16(FcGemmPlan *plan, const std::vector<float> &Bmat /*
 
 // the fp16-pair launch: 128-feature tiles where the layer's width allows (ALQ_FC_BN64=1: the 64-wide kernel, A/B)
 static int fc16_go(alq_ctx *ctx, const FcGemmPlan &plan, const FcGemmArgs &a, int M) {
-    const bool bn64 = plan.form == 2, tall = plan.form == 0;
+    const FcTile t = fc_tile(plan.K, plan.N, M, plan.form, true);
+    const dim3 grid(t.gx, t.gy);
     ProfScope ps16(ctx, PROF_IGEMM_F16, 2.0 * M * (double)plan.K * plan.N);
-    if (plan.N % (2 * FC_BN) == 0 && !bn64 && tall) {
+    if (t.tall) {
         const size_t lds = 2 * (2 * 4 * FC_BM * 16);
         ALQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fcgemm_kernel<true, 2 * FC_BN, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((fcgemm_kernel<true, 2 * FC_BN, true>), dim3(plan.N / (2 * FC_BN), (M + FC_BM - 1) / FC_BM), dim3(256), lds, ctx->stream, a);
-    } else if (plan.N % (2 * FC_BN) == 0 && !bn64) {
+        hipLaunchKernelGGL((fcgemm_kernel<true, 2 * FC_BN, true>), grid, dim3(256), lds, ctx->stream, a);
+    } else if (t.BN == 2 * FC_BN) {
         const size_t lds = 2 * (2 * 4 * FC_BM * 16);          // activations only: the weight fragments come from global memory
         ALQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fcgemm_kernel<true, 2 * FC_BN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((fcgemm_kernel<true, 2 * FC_BN>), dim3(plan.N / (2 * FC_BN), (M + FC_BM - 1) / FC_BM), dim3(256), lds, ctx->stream, a);
+        hipLaunchKernelGGL((fcgemm_kernel<true, 2 * FC_BN>), grid, dim3(256), lds, ctx->stream, a);
     } else {
         const size_t lds = 2 * (2 * 4 * FC_BM * 16 + 2 * 4 * FC_BN * 16);
         ALQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fcgemm_kernel<true, FC_BN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((fcgemm_kernel<true, FC_BN>), dim3(plan.N / FC_BN, (M + FC_BM - 1) / FC_BM), dim3(256), lds, ctx->stream, a);
+        hipLaunchKernelGGL((fcgemm_kernel<true, FC_BN>), grid, dim3(256), lds, ctx->stream, a);
     }
     ALQ_HIP(hipGetLastError());
     return ALQ_OK;
@@ -392,7 +411,6 @@ int fcgemm_launch(alq_ctx *ctx, const FcGemmPlan &plan, const View &in, const Vi
     a.A = in.p; a.Bp = plan.d_W; a.C = out.p; a.bias = bias;
     a.M = M; a.N = plan.N; a.K = plan.K; a.lda = in.cs; a.ldc = out.cs; a.relu = relu;
     a.scale = 1.f; a.inv = 1.f; a.row_amax = nullptr; a.e_w = plan.w_exp;
-    const dim3 grid(plan.N / FC_BN, (M + FC_BM - 1) / FC_BM);
     if (row_amax && plan.d_W16) {      // fp16 pairs under the MEASURED per-patch maximum of the input (a forward launch; bias + ReLU in the epilogue)
         hipLaunchKernelGGL(fc_rowmax_kernel, dim3((M + 3) / 4), dim3(256), 0, ctx->stream, in.p, M, plan.K, in.cs, row_amax);
         a.Bp = plan.d_W16;
@@ -409,6 +427,8 @@ int fcgemm_launch(alq_ctx *ctx, const FcGemmPlan &plan, const View &in, const Vi
         ALQ_TRY(fc16_go(ctx, plan, a, M));
         return ALQ_OK;
     }
+    const FcTile t = fc_tile(plan.K, plan.N, M, plan.form, false);
+    const dim3 grid(t.gx, t.gy);
     const size_t lds = 2 * (FC_XBYTES + FC_WBYTES);
     ALQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fcgemm_kernel<false, FC_BN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     ProfScope ps(ctx, prof_cls, 2.0 * M * (double)plan.K * plan.N);
@@ -418,3 +438,12 @@ int fcgemm_launch(alq_ctx *ctx, const FcGemmPlan &plan, const View &in, const Vi
 }
 
 }  // namespace alq
+
+extern "C" int alq_fcgemm_geometry(int K, int N, int M, int *out) {
+    ALQ_REQUIRE(out && K >= 1 && N >= 1 && M >= 1, ALQ_EINVAL, "alq_fcgemm_geometry: null argument or a non-positive size");
+    for (int j = 0; j < 6; ++j) out[j] = 0;
+    if (!alq::fc_shape_ok(K, N)) return ALQ_OK;
+    const alq::FcTile t = alq::fc_tile(K, N, M, alq::fc_form_from_env(), true);
+    out[0] = 1; out[1] = t.BN; out[2] = t.tall ? 1 : 0; out[3] = (int)t.gx; out[4] = (int)t.gy; out[5] = t.nks;
+    return ALQ_OK;
+}
