@@ -142,9 +142,10 @@ class _knob(object):
         self._set(0)
 
 
-def _make(sess, ld, in_shape, sk, pars, mb, route='default', extra_env=None, device_weights=False):
+def _make(sess, ld, in_shape, sk, pars, mb, route='default', extra_env=None, device_weights=False, routes=None):
+    """`routes`: another table of the form of ROUTES (tests/test_gpu_conv.py has its own)."""
     from nnal_amd import device
-    env = dict(ROUTES[route][0])
+    env = dict((routes or ROUTES)[route][0])
     env.update(extra_env or {})
     with _env(env):
         m = device.DeviceModel(sess, ld, in_shape, sk, max_batch=mb)
@@ -420,13 +421,20 @@ def whole(name):
     """Model, chosen patches, labels, a vector and both oracles' gradients: computed once, shared, never modified."""
     if name in _WHOLE:
         return _WHOLE[name]
-    import torch
     tag, Ci, Co, ku = WHOLE[name]
     if tag is None:
         (ld, sk), in_shape = convt_ref.unet_level([ku] * 3, [2] * 3), (4, 6, 6, 1)
     else:
         ld, sk, in_shape = _model_of(Case(tag, Ci, Co, 'MA', 4, True), 'below')
-    seed = 500 + list(WHOLE).index(name)
+    refused = _refusal([ku] * 3 if tag is None else GEOMETRIES[tag]['k'])
+    _WHOLE[name] = whole_record(name, ld, sk, in_shape, 500 + list(WHOLE).index(name), refused)
+    return _WHOLE[name]
+
+
+def whole_record(name, ld, sk, in_shape, seed, refused):
+    """What the whole-model checks share for one model: weights, both oracles, N patches without a fragile decision, labels, a
+    vector and both oracles' gradients."""
+    import torch
     pars = netspec.he_init(ld, in_shape, seed=seed, skips=sk, bias_std=0.05)
     om64 = OracleModel(ld, in_shape, pars, skips=sk, dtype=torch.float64)
     om32 = OracleModel(ld, in_shape, pars, skips=sk)
@@ -439,11 +447,8 @@ def whole(name):
     v = [rs.randn(*np.asarray(a).shape).astype(np.float32) for nme in names for a in pars[nme]]
     g64 = [[[np.asarray(a, np.float64) for a in om64.grad_log_post(j, x[[i]])] for j in (0, 1)] for i in range(N)]
     g32 = [[[np.asarray(a) for a in om32.grad_log_post(j, x[[i]])] for j in (0, 1)] for i in range(N)]
-    refused = _refusal([ku] * 3 if tag is None else GEOMETRIES[tag]['k'])
-    d = dict(refused=refused, name=name, ld=ld, sk=sk, in_shape=in_shape, n=N, pars=pars, x=x, labels=labels, v=v, names=names, om64=om64, om32=om32,
-             g64=g64, g32=g32, p64=om64.forward(x)['posteriors'].astype(np.float64), arrays=[nme + s for nme in names for s in ('/W', '/b')])
-    _WHOLE[name] = d
-    return d
+    return dict(refused=refused, name=name, ld=ld, sk=sk, in_shape=in_shape, n=N, pars=pars, x=x, labels=labels, v=v, names=names, om64=om64, om32=om32,
+                g64=g64, g32=g32, p64=om64.forward(x)['posteriors'].astype(np.float64), arrays=[nme + s for nme in names for s in ('/W', '/b')])
 
 
 def _refused(sess, d):
@@ -460,16 +465,23 @@ def _mk(sess, d, route='default', **kw):
 @pytest.mark.parametrize('name', list(WHOLE))
 def test_whole_model_param_grads_vs_fp64(sess, name):
     """tests/test_gpu_grads_fp64.test_param_grads_vs_fp64 on these models: every W and b array, modes 0 and 1, rows and sum."""
-    from tests.test_gpu_grads_fp64 import mode1_refs
     d = whole(name)
     if _refused(sess, d):
         return
+    check_param_grads(sess, d, _mk, ('default', 'no_v4_v3'))
+
+
+def check_param_grads(sess, d, mk, routes):
+    """The body of test_whole_model_param_grads_vs_fp64 on a model record of the form whole() builds (N patches, passes of 4);
+    mk(sess, d, route) creates the device model."""
+    from tests.test_gpu_grads_fp64 import mode1_refs
+    name = d['name']
     g64, g32, lab = d['g64'], d['g32'], d['labels']
     rows64, rows32, sum64, sum32 = mode1_refs(d)
     t = _dev(sess, d['x'])
     bad = []
-    for route in ('default', 'no_v4_v3'):
-        m = _mk(sess, d, route)
+    for route in routes:
+        m = mk(sess, d, route)
         got = {'mode 0 class 0': [], 'mode 0 class 1': [], 'mode 1 rows': []}
         total = np.zeros(m.num_params)
         for a, e in _passes(N, 4):
@@ -503,9 +515,15 @@ def test_whole_model_other_entry_points_vs_fp64(sess, name):
     d = whole(name)
     if _refused(sess, d):
         return
+    check_other_entry_points(sess, d, _mk)
+
+
+def check_other_entry_points(sess, d, mk):
+    """The body of test_whole_model_other_entry_points_vs_fp64 on a model record of the form whole() builds."""
+    name = d['name']
     g64, lab = d['g64'], d['labels']
     p1 = d['p64'][1]
-    m = _mk(sess, d)
+    m = mk(sess, d)
     t = _dev(sess, d['x'])
     L = m.L
     ref = {j: np.stack([_sq(g64[i][j]) for i in range(N)]) for j in (0, 1)}
@@ -547,11 +565,18 @@ def test_whole_model_fisher_pass_vs_fp64(sess, name):
     d = whole(name)
     if _refused(sess, d):
         return
+    check_fisher_pass(sess, d, _mk, ROUTES)
+
+
+def check_fisher_pass(sess, d, mk, routes):
+    """The body of test_whole_model_fisher_pass_vs_fp64 on a model record of the form whole() builds, on every route of the table
+    `routes` (of the form of ROUTES)."""
+    name = d['name']
     p64, S64, sizes = factored_ref.factored_unit_scores(d['om64'], d['x'].astype(np.float64))
     g64, h64, A64 = factored_ref.fisher_from_unit(p64[1], S64, sizes, 1e-3)
     t = _dev(sess, d['x'])
-    for route, (_, knob) in ROUTES.items():
-        m = _mk(sess, d, route)
+    for route, (_, knob) in routes.items():
+        m = mk(sess, d, route)
         with _knob(sess, knob):
             rs = [m.fisher_device(t[a:e], e - a, None, 1e-3, want=('p1', 'g0', 'g1', 'A')) for a, e in _passes(N, 4)]
             r = {k: np.concatenate([q[k].cpu().numpy() for q in rs]) for k in ('p1', 'g0', 'g1', 'A')}
@@ -574,10 +599,16 @@ def test_device_weight_packing_same_bits(sess, name):
     d = whole(name)
     if _refused(sess, d):
         return
+    check_packing(sess, d, _mk)
+
+
+def check_packing(sess, d, mk):
+    """The body of test_device_weight_packing_same_bits on a model record of the form whole() builds."""
+    name = d['name']
     t = _dev(sess, d['x'])
     outs = []
     for dw in (False, True):
-        m = _mk(sess, d, extra_env={} if dw else {'ALQ_HOST_REPACK': '1'}, device_weights=dw)
+        m = mk(sess, d, extra_env={} if dw else {'ALQ_HOST_REPACK': '1'}, device_weights=dw)
         assert m._host_repack == (not dw)
         o = OrderedDict()
         for a, e in _passes(N, 4):
