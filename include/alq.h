@@ -802,8 +802,10 @@ int alq_prof_read(alq_ctx *ctx, int cls, double *ms, int64_t *launches, double *
  * forward and the backward plan and the bits of the layer's fp64 L1 bound (N ignored); after a Fisher pass: 11 = channel-sum field of
  * the layer's OUTPUT [N, vox_out], 12 = the sign field of the rows its output lies in, as raw bytes in 4-byte words ([N, vox_out, cs / 4]
  * bytes, cs = channels of the allocation: the layer's own bytes are the C / 4 from byte c0 / 4 of a voxel; bit k of a byte = (channel
- * 4 b + k > 0)), 13 = a pool layer's arg-max field as raw bytes in 4-byte words ([N, vox_out, C] window indices).  *elems_out
- * receives the element count.  Tests only.  */
+ * 4 b + k > 0)), 13 = a pool layer's arg-max field as raw bytes in 4-byte words ([N, vox_out, C] window indices), 14 = the sign bytes a
+ * two-class fc head (layer_idx) keeps of its input, as raw bytes in 4-byte words ([N, F / 4] bytes in activation-memory order: bit k
+ * of byte j = (element 4 j + k > 0), bits 5 - 7 clear, bit 4 clear unless ALQ_NO_FLIPFIX=1 left a mark; ALQ_EUNSUPPORTED where the
+ * layer has no such field or the last pass was no Fisher pass).  *elems_out receives the element count.  Tests only.  */
 int alq_model_debug_copy(alq_model *m, int layer_idx, int what, int N, float *d_out,
                          int64_t *elems_out);
 

@@ -657,6 +657,13 @@ int alq_model_debug_copy(alq_model *m, int layer_idx, int what, int N, float *d_
         ALQ_HIP(hipMemcpyAsync(d_out, ly.argmax, (size_t)N * ly.out.vox() * ly.out.C, hipMemcpyDeviceToDevice, m->ctx->stream));
         return ALQ_OK;
     }
+    if (what == 14) {      // test hook: the sign bytes a two-class head keeps of its input in a Fisher pass, as raw bytes
+        ALQ_REQUIRE(ly.spec.type == ALQ_FC && ly.fc_maskbits && m->last.call_fisher && ((int64_t)N * ly.F) % 16 == 0, ALQ_EUNSUPPORTED,
+                    "layer %d: no sign bytes of its input in the last pass", layer_idx);
+        if (elems_out) *elems_out = (int64_t)N * ly.F / 16;
+        ALQ_HIP(hipMemcpyAsync(d_out, ly.fc_maskbits, (size_t)N * ly.F / 4, hipMemcpyDeviceToDevice, m->ctx->stream));
+        return ALQ_OK;
+    }
     if (what == 0 || what == 1) {
         // the last conv under a fused fc head: a Fisher pass stores neither its output nor the cotangent of it
         const Layer &head = m->layers.back();
