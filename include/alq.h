@@ -186,8 +186,10 @@ int alq_score_entropy(alq_ctx *ctx, const float *d_p1, int64_t n, double *d_absd
 
 /* Replaces: np.argsort(np.abs(posts - .5))[:B] (PW_NNAL.py:64,109-110,671-681,730).
  * Ascending keys, ties -> lower index first (the reference's tie order is unspecified).
- * Keys compare in numeric order for either sign (a NaN with the sign bit clear after +inf); -0.0 sorts before +0.0,
- * so a caller whose keys may be zero of either sign writes them as 0.0 - x, which is never -0.0.
+ * Keys compare in numeric order for either sign (a NaN with the sign bit clear after +inf, a NaN with the sign bit SET before
+ * -inf: the order is that of sign and magnitude bits, so such a key is picked FIRST - keep it out of the keys); -0.0 sorts
+ * immediately before +0.0, so a caller whose keys may be zero of either sign writes them as 0.0 - x, which is never -0.0.
+ * d_keys is only read; B = 0 touches neither d_out_idx nor d_work; B > n, B < 0 and n < 0 are ALQ_EINVAL.
  * d_out_idx: int64 [B].  d_work: device scratch of alq_topk_work_bytes(n) bytes.             */
 size_t alq_topk_work_bytes(int64_t n);
 int alq_topk_uncertain(alq_ctx *ctx, const double *d_keys, int64_t n, int64_t B,
@@ -280,7 +282,10 @@ int alq_slice_scores_geometry(int c, int64_t n_slices, int64_t V, int64_t *out);
  * Host function: merges the candidate (key, GLOBAL index) pairs gathered from all ranks
  * (torch.distributed all_gather over RCCL in pool_shard.merge_topB; entries with index < 0 are padding)
  * into the global top-B, ascending key (compared by bit pattern, so a NaN key sorts behind every number),
- * ties -> lower global index: the rule of alq_topk_uncertain, so the result is identical on every rank.
+ * ties -> lower global index, so the result is identical on every rank.  For NON-NEGATIVE keys (sign bit clear: +0.0, numbers,
+ * +inf, such NaNs - what |p - .5| and the other query keys are) this is the rule of alq_topk_uncertain.  It is not for the
+ * rest: the merge takes -0.0 for +0.0 (the index decides between them, where the device sorts -0.0 first) and a negative key
+ * sorts by its raw bits BEHIND every non-negative one, in reverse numeric order (tests/test_select_ref_host.py pins both).
  * out_idx: int64 [B]; returns the count in *n_out.                                               */
 int alq_topk_merge(const double *h_keys, const int64_t *h_idx, int64_t n, int64_t B, int64_t *h_out_idx,
                    int64_t *n_out);
@@ -587,7 +592,13 @@ int alq_fisher_classes(alq_ctx *ctx, const double *d_g, const double *d_w, const
  *                      the representativeness score of every candidate column in ONE pass (PW_NNAL.py:333-338 scores one
  *                      candidate per Python iteration); fixed summation order; d_work: alq_colsum_work_bytes(n, b) bytes
  *   alq_take_colmax    d_v[i] = max(d_v[i], S[i, j])  (first != 0: d_v[i] = S[i, j]): the running row maxima after a pick
- *   alq_fold_rowmax    d_v[j] = max(d_v[j], max_i S[i, j]) for a [t, n] block (core-set's labelled-set maxima, :420-425) */
+ *   alq_fold_rowmax    d_v[j] = max(d_v[j], max_i S[i, j]) for a [t, n] block (core-set's labelled-set maxima, :420-425)
+ * Non-finite values: a zero-norm row of A (of B) makes its row (its column) of d_C NaN, 0 / 0 as in the reference's NumPy.  The
+ * three max kernels take every maximum with fmax, which IGNORES a NaN operand (fmax(NaN, x) = x; NaN only when both are), where
+ * the reference's np.max / np.maximum propagate it: alq_colsum_max sums fmax(d_cmax[i], S[i, j]) (without d_cmax a NaN entry
+ * makes its column's sum NaN), alq_take_colmax with first != 0 copies the column, NaN included, and otherwise keeps d_v[i] over
+ * a NaN entry, alq_fold_rowmax skips NaN entries and replaces a NaN d_v[j] by the column's maximum.  DESIGN.md, "Zero feature
+ * vectors", says what that means for the two queries. */
 int alq_row_norms(alq_ctx *ctx, const float *d_A, int64_t n, int f, double *d_norms);
 int alq_cosine_sims(alq_ctx *ctx, const float *d_A, int64_t n, const float *d_B, int b, int f, const double *d_na,
                     const double *d_nb, double *d_C);

@@ -118,7 +118,8 @@ class DeviceSession(object):
 
     def topk_smallest(self, keys, B):
         """Positions of the B smallest entries of a float64 device vector, ascending, ties -> lower position (numeric order
-        for either sign, -0.0 before +0.0; +inf and a NaN with the sign bit clear come last)."""
+        for either sign, -0.0 immediately before +0.0; +inf and then a NaN with the sign bit clear come last, a NaN with the sign bit
+        set comes FIRST, before -inf - the order of sign and magnitude bits; include/alq.h, alq_topk_uncertain)."""
         torch = self.torch
         self.bind_stream()
         n = int(keys.numel())

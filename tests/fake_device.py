@@ -7,6 +7,7 @@ import torch
 
 from oracle import alpath
 from oracle.model import OracleModel, OracleSession
+from tests import select_ref
 
 
 class FakeSession(object):
@@ -30,8 +31,8 @@ class FakeSession(object):
         pass
 
     def topk_smallest(self, keys, B):
-        k = keys.numpy().view(np.uint64)                      # bit-pattern order like alq_topk_uncertain
-        return torch.as_tensor(np.lexsort((np.arange(len(k)), k))[:int(B)].astype(np.int64))
+        # numeric order for either sign, -0.0 before +0.0, ties -> lower position, like alq_topk_uncertain
+        return torch.as_tensor(select_ref.topk_ref(keys.numpy(), B))
 
     def run(self, fetch, feed_dict=None):
         assert fetch.name == 'train_step'

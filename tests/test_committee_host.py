@@ -11,6 +11,7 @@ import pytest
 import torch
 import torch.multiprocessing as mp
 
+from tests import select_ref
 from tests.fake_device import FakeModel, FakeSession, FakeVolumes
 
 
@@ -40,9 +41,7 @@ class CommitteeSession(FakeSession):
             keys.copy_(torch.as_tensor(np.abs(av - .5)))
 
     def topk_smallest(self, keys, B):
-        u = keys.numpy().view(np.uint64)
-        k = np.where(u >> np.uint64(63), ~u, u | np.uint64(1 << 63))
-        return torch.as_tensor(np.lexsort((np.arange(len(k)), k))[:int(B)].astype(np.int64))
+        return torch.as_tensor(select_ref.topk_ref(keys.numpy(), B))
 
     def run(self, fetch, feed_dict=None):
         m = fetch.model
