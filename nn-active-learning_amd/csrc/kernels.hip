@@ -1034,12 +1034,13 @@ __global__ __launch_bounds__(256) void boxdot_convT_out_kernel(const float *dsum
     if (threadIdx.x == 0) Spart[n * nslab_max + slab] = tot;
 }
 
-// window 3, stride 2 in y and x, and either the same in z or a flat (2-D) layer
+// window 3, stride 2 in y and x, and either the same in z or a flat (2-D) layer.  The kernel walks an output row in
+// groups of 4 points with 16-byte loads, so the output rows (2 * IW wide) must be a multiple of 4: IW even.
 static bool boxdot_convT_out_ok(int ID, int IH, int IW, const int k[3], const int s[3]) {
     const long long ivox = (long long)ID * IH * IW;
     const bool shape = k[1] == 3 && k[2] == 3 && s[1] == 2 && s[2] == 2 &&
                        ((k[0] == 3 && s[0] == 2) || (k[0] == 1 && s[0] == 1 && ID == 1));
-    return shape && ivox % 4 == 0 && ivox * 4 <= 48 * 1024;
+    return shape && IW % 2 == 0 && ivox % 4 == 0 && ivox * 4 <= 48 * 1024;
 }
 static int boxdot_convT_zs(int ID, int IH, int IW, const int s[3]) {
     int zs = 4096 / (IH * s[1] * IW * s[2]);
