@@ -816,9 +816,24 @@ int alq_prof_read(alq_ctx *ctx, int cls, double *ms, int64_t *launches, double *
  * 4 b + k > 0)), 13 = a pool layer's arg-max field as raw bytes in 4-byte words ([N, vox_out, C] window indices), 14 = the sign bytes a
  * two-class fc head (layer_idx) keeps of its input, as raw bytes in 4-byte words ([N, F / 4] bytes in activation-memory order: bit k
  * of byte j = (element 4 j + k > 0), bits 5 - 7 clear, bit 4 clear unless ALQ_NO_FLIPFIX=1 left a mark; ALQ_EUNSUPPORTED where the
- * layer has no such field or the last pass was no Fisher pass).  *elems_out receives the element count.  Tests only.  */
+ * layer has no such field or the last pass was no Fisher pass).
+ * The fp16-pair scales of the last pass, as the floats whose bits the launches read: 15 = the derived per-patch bounds on every layer's
+ * output [layers, N] (layer_idx ignored; ALQ_EUNSUPPORTED where the pass derived none), 16 = the measured per-patch maxima of the
+ * output of layer_idx [N] (ALQ_EUNSUPPORTED where the pass did not ask that layer's launch for them), 17 = the measured per-patch maxima
+ * of the network input [N] (layer_idx ignored; ALQ_EUNSUPPORTED unless the pass scaled the first launch by them), 18 = the static
+ * bounds on every layer's output cotangent in the backward sweep of the last Fisher pass [layers] (layer_idx and N ignored; -1 =
+ * unknown; ALQ_EUNSUPPORTED where the last call was no Fisher pass).
+ * *elems_out receives the element count.  Tests only.  */
 int alq_model_debug_copy(alq_model *m, int layer_idx, int what, int N, float *d_out,
                          int64_t *elems_out);
+/* Tests only: the two kernels behind the derived bounds on caller buffers (device pointers, the context's stream).
+ * alq_debug_rowmax_abs: d_out[n] = the bits of max_k |d_x[n * K + k]| (a NaN is dropped: the maximum of the rest).
+ * alq_debug_fwd_bounds: d_bound_all[k * stride + p] = the bits of bound_k(p) for k < nl <= 16 and p < N <= stride, where
+ * bound_0 = amax0 (from_input: amax0 * L[0] + B[0]) and bound_k = max(bound_{k-1}, bound_{src2[k]} if src2[k] >= 0) * L[k] + B[k];
+ * L, B and src2 are host arrays of nl entries, src2[k] in [-1, k).                                                          */
+int alq_debug_rowmax_abs(alq_ctx *ctx, const float *d_x, int N, int64_t K, uint32_t *d_out);
+int alq_debug_fwd_bounds(alq_ctx *ctx, const uint32_t *d_amax0, int N, int stride, const float *L, const float *B,
+                         const int32_t *src2, int nl, int from_input, uint32_t *d_bound_all);
 
 /* Diagnostic builds only (-DALQ_STAMPS): device buffer of 8 uint64 per workgroup that receives the
  * per-phase shader-clock ticks of the pipelined GEMM kernel's next launches; NULL switches it off.

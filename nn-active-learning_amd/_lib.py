@@ -183,6 +183,9 @@ _SIGNATURES = {
     'alq_prof_class_name': (C.c_char_p, [C.c_int]),
     'alq_prof_read': (C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     'alq_model_debug_copy': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_int64)]),
+    'alq_debug_rowmax_abs': (C.c_int, [_P, _P, C.c_int, C.c_int64, _P]),
+    'alq_debug_fwd_bounds': (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32),
+                                       C.c_int, C.c_int, _P]),
     'alq_debug_set_stamp_buffer': (C.c_int, [_P]),
     'alq_debug_set': (C.c_int, [C.c_int, C.c_int]),
     'alq_model_engine_info': (C.c_int, [_P, C.c_int]),

@@ -210,10 +210,17 @@ __global__ __launch_bounds__(256, 2) void igemm3_kernel(const Igemm2Args a) {
         f_cls = td.z;
         f_l = fl; f_g = fpg;
         if constexpr (F16) {
-            if (a.f16_bound) {      // bound = f 2^ex, f in [.5, 1): x 2^(14 - ex) < 2^14; the exponent field E = ex + 126 (clamped: no inf / denormal scale)
+            if (a.f16_bound) {      // bound = f 2^ex, f in [.5, 1): x 2^(14 - ex) < 2^14; the exponent field E = ex + 126
+                // Every bound from 2^-87 up keeps its own scale: E in [40, 254] gives f_t in [-114, 100].  Below, the scale stays 2^100:
+                // x 2^f_t < 2^14 still holds, such inputs are then simply small fp16 values, and the accumulator, which holds the OUTPUT
+                // times 2^(f_t + f16_wexp) - the bias too, however small the input - stays finite.  (The upper end was 200 once: a bound
+                // above 2^73 kept the scale of 2^73 and x 2^f_t left fp16's range.)  The product scale 2^(f_t + f16_wexp) and its inverse
+                // are exponent fields as well: where the sum leaves [-126, 126] the input scale gives way, never the field.
                 int E = (sload1(a.f16_bound + (fpg < a.N ? fpg : 0)) >> 23) & 255;
-                E = E < 40 ? 40 : (E > 200 ? 200 : E);
+                E = E < 40 ? 40 : (E > 254 ? 254 : E);
                 f_t = 140 - E;
+                if (f_t + a.f16_wexp > 126) f_t = 126 - a.f16_wexp;
+                if (f_t + a.f16_wexp < -126) f_t = -126 - a.f16_wexp;
             }
         }
         const int cls = f_cls & 63;

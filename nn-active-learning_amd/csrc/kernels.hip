@@ -1284,7 +1284,8 @@ int k_rowmax_u32(alq_ctx *ctx, const unsigned *in, int len, int N, unsigned *out
     return ALQ_OK;
 }
 
-// max |x| of every patch's input as float bits (one wave per patch; any element count)
+// max |x| of every patch's input as float bits (one wave per patch; any element count).  fmaxf drops a NaN: a row that holds one
+// yields the maximum of its other elements (0 for a row of NaN only); +-inf is kept.
 __global__ __launch_bounds__(256) void rowmax_abs_kernel(const float *x, int N, long long K, unsigned *out) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= N) return;

@@ -18,6 +18,9 @@ static int g_knob_override[ALQ_NKNOBS] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1
 static void apply_knobs(const alq_model *m) {
     for (int k = 0; k < ALQ_NKNOBS; ++k) g_dbg_knobs[k] = g_knob_override[k] >= 0 ? g_knob_override[k] : m->sw.knobs[k];
     g_no_f16x2 = m->sw.no_f16x2;
+    // a conv over a concat whose two weight slices no single fp16-pair exponent holds (set with the weights): the launches of this
+    // model stay on bf16 triples, which keep fp32's exponent range
+    for (const Layer &ly : m->layers) g_no_f16x2 |= ly.f16_slices_apart ? 1 : 0;
     g_no_xcd_order = m->sw.no_xcd_order;
     g_no_fixed = m->sw.no_fixed;
 }
@@ -613,8 +616,40 @@ int alq_model_debug_copy(alq_model *m, int layer_idx, int what, int N, float *d_
                                m->ctx->stream));
         return ALQ_OK;
     }
+    if (what == 15 || what == 17 || what == 18) {
+        // test hooks for the fp16-pair scales of the last pass (layer_idx ignored): 15 = the derived forward bounds [layers, N] (k_fwd_bounds),
+        // 17 = the measured maxima of the network input [N], both as the floats whose bits the launches read; 18 = the static cotangent
+        // bounds of the Fisher backward [layers] (bwd_bounds; -1 = unknown; N ignored)
+        const int nl = (int)m->layers.size();
+        if (what == 18) {
+            ALQ_REQUIRE(m->last.call_fisher && m->last.bwd.nbounds == nl, ALQ_EUNSUPPORTED, "the last pass ran no Fisher backward sweep");
+            float h[64];
+            for (int i = 0; i < nl; ++i) h[i] = m->last.bwd.dout_bound[i] > 0.f ? m->last.bwd.dout_bound[i] : -1.f;
+            if (elems_out) *elems_out = nl;
+            ALQ_HIP(hipMemcpyAsync(d_out, h, (size_t)nl * sizeof(float), hipMemcpyHostToDevice, m->ctx->stream));
+            ALQ_HIP(hipStreamSynchronize(m->ctx->stream));
+            return ALQ_OK;
+        }
+        if (what == 17) {
+            ALQ_REQUIRE(m->last.fwd.v3f16 && m->in_amax, ALQ_EUNSUPPORTED, "the last pass measured no input maxima");
+            if (elems_out) *elems_out = N;
+            ALQ_HIP(hipMemcpyAsync(d_out, m->in_amax, (size_t)N * sizeof(float), hipMemcpyDeviceToDevice, m->ctx->stream));
+            return ALQ_OK;
+        }
+        ALQ_REQUIRE((m->last.fwd.f16_derived || m->last.fwd.v3f16) && m->bound_all, ALQ_EUNSUPPORTED, "the last pass derived no forward bounds");
+        if (elems_out) *elems_out = (int64_t)nl * N;
+        ALQ_HIP(hipMemcpy2DAsync(d_out, (size_t)N * sizeof(float), m->bound_all, (size_t)m->max_batch * sizeof(float), (size_t)N * sizeof(float), nl,
+                                 hipMemcpyDeviceToDevice, m->ctx->stream));
+        return ALQ_OK;
+    }
     ALQ_REQUIRE(layer_idx >= 0 && layer_idx < (int)m->layers.size(), ALQ_EINVAL, "bad layer index");
     const Layer &ly = m->layers[layer_idx];
+    if (what == 16) {      // test hook: the per-patch maxima of the layer's output that the last forward pass asked its launch for [N]
+        ALQ_REQUIRE(layer_idx < 64 && m->last.fwd.amax_asked[layer_idx] && ly.amax_fwd, ALQ_EUNSUPPORTED, "layer %d: the last pass measured no output maxima", layer_idx);
+        if (elems_out) *elems_out = N;
+        ALQ_HIP(hipMemcpyAsync(d_out, ly.amax_fwd, (size_t)N * sizeof(float), hipMemcpyDeviceToDevice, m->ctx->stream));
+        return ALQ_OK;
+    }
     if (what >= 6 && what <= 10) {
         // packed weights of a wide fc layer as raw bytes (test hook): 6 / 7 = bf16 triples / fp16 pairs of the forward Gemm, 8 / 9 = of the
         // backward Gemm; 10 = 4 words: w_exp of the forward and the backward plan, then the bits of bwd_l1 (fp64)
@@ -683,6 +718,27 @@ int alq_model_debug_copy(alq_model *m, int layer_idx, int what, int N, float *d_
     ALQ_HIP(hipMemcpyAsync(d_out, what == 2 ? ly.asum : ly.dsum, e * sizeof(float), hipMemcpyDeviceToDevice,
                            m->ctx->stream));
     return ALQ_OK;
+}
+
+int alq_debug_rowmax_abs(alq_ctx *ctx, const float *d_x, int N, int64_t K, uint32_t *d_out) {
+    ALQ_REQUIRE(ctx && d_x && d_out && N >= 1 && K >= 1, ALQ_EINVAL, "alq_debug_rowmax_abs: bad argument");
+    ALQ_HIP(hipSetDevice(ctx->device));
+    return k_rowmax_abs(ctx, d_x, N, (long long)K, d_out);
+}
+
+int alq_debug_fwd_bounds(alq_ctx *ctx, const uint32_t *d_amax0, int N, int stride, const float *L, const float *B, const int32_t *src2,
+                         int nl, int from_input, uint32_t *d_bound_all) {
+    ALQ_REQUIRE(ctx && d_amax0 && d_bound_all && L && B && src2 && N >= 1 && stride >= N && nl >= 1 && nl <= 16, ALQ_EINVAL,
+                "alq_debug_fwd_bounds: bad argument");
+    FwdBoundsArgs a;
+    a.nl = nl;
+    a.from_input = from_input ? 1 : 0;
+    for (int k = 0; k < nl; ++k) {
+        ALQ_REQUIRE(src2[k] >= -1 && src2[k] < k, ALQ_EINVAL, "alq_debug_fwd_bounds: src2[%d] = %d names no earlier layer", k, src2[k]);
+        a.L[k] = L[k]; a.B[k] = B[k]; a.src2[k] = src2[k];
+    }
+    ALQ_HIP(hipSetDevice(ctx->device));
+    return k_fwd_bounds(ctx, d_amax0, N, stride, a, d_bound_all);
 }
 
 int alq_model_engine_info(alq_model *m, int what) {

@@ -54,6 +54,9 @@ struct Layer {
     // channels of sum_{taps, output channels} |W| (set with the weights), i.e. |cotangent of the input| <= bwd_l1 * max
     // |cotangent of the output|; a Fisher pass chains them down from the unit cotangent at the logits (bwd_bounds, passes.hip).
     double bwd_l1 = 0;
+    bool f16_slices_apart = false;     // ... and its two weight slices lie further apart than one fp16-pair exponent holds (slices_within_f16_range):
+                                       // every pass of the model then runs on bf16 triples (apply_knobs)
+    double bwd_l1_part[2] = {0, 0};    // a conv / conv_transpose over a concat: bwd_l1 of the skip source's channels and of the others (0: no concat)
     // flip-safe fused head (the conv under a two-class head): plain fp32 copy of the weights in TF layout [tap][ci][co] for the
     // exact re-evaluation, and max over co of sum_{tap, ci} |W|
     float *d_W32 = nullptr;
@@ -100,6 +103,8 @@ struct PassInfo {
         int f3f = 0;               // enc2 and the pool behind it ran fused (f3d.hip)
         int dcp = 0;               // form of the first conv + pool kernel, 0 = it did not run (direct.hip: g_dcp_last_form)
         bool f16_derived = false;  // a launch ran on the fp16x2 split with derived input bounds
+        bool v3f16 = false;        // igemm3's forward launches ran on fp16 pairs under bounds derived from the input maxima (in_amax)
+        bool amax_asked[64] = {};  // per layer: the pass asked its launch for the per-patch output maxima (amax_fwd; plan_input_scales)
         bool signs_ready[64] = {}; // per layer (alq_model_create: at most 64): a launch wrote the sign field of its output (View::sg); the
                                    // backward sweep of the same Fisher pass and alq_model_debug_copy read it
     } fwd;
@@ -110,6 +115,8 @@ struct PassInfo {
         int e3b = 0;               // pool2 backward, enc2 backward and pool1 backward ran as one launch (e3d.hip)
         int e3b_form = 0;          // form of that launch: 0 none, 1 row sweep, 2 z plane sweep
         int d3b = 0;               // dec1's backward-data launch ran on d3d.hip
+        int nbounds = 0;           // layers of dout_bound (0: no Fisher backward since)
+        float dout_bound[64] = {}; // per layer: the static cotangent bound of bwd_bounds (passes.hip); <= 0 = unknown
     } bwd;
     int lsum = 0;                  // the last GENERAL backward sweep ran the fused layer-sum kernels (set by run_backward_general only)
     bool call_fisher = false;      // the last entry point ran a Fisher pass (prepare_call)

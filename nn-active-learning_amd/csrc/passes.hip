@@ -215,12 +215,14 @@ static int plan_input_scales(FwdPass &P) {
     }
     for (int j = 0; j < nl; ++j) P.any_derived = P.any_derived || cons[j] == 2;
     m->last.fwd.f16_derived = P.any_derived;
+    for (int p = 0; p < nl && p < 64; ++p) m->last.fwd.amax_asked[p] = prod[p] != 0;
     if (P.any_derived) ALQ_TRY(ensure_bounds(m));
     // Forward launches that stay on igemm3 (no two-slot plan: NET-B's conv1 .. conv3) on fp16 pairs, one scale per patch: the
     // measured maximum of every patch of the network input, pushed through the layers' L1 norms, bounds every layer's input.
     // Fisher passes and forward-only passes; not the passes that keep every activation for training, not under dropout.
     P.v3f16 = m->v3_fwd_f16 && (P.with_sums || P.light) && !no16 && !drop && !P.any_derived && !P.dcp && nl <= 16 &&
               !g_dbg_knobs[KNOB_NO_FWD_FUSE] && two_slot_allowed() && m->layers[0].in.split == 0 && m->layers[0].in.cs == m->layers[0].in.C;
+    m->last.fwd.v3f16 = P.v3f16;
     if (P.v3f16) {
         if (!m->in_amax) ALQ_TRY(m->dalloc(&m->in_amax, (size_t)m->max_batch));
         ALQ_TRY(ensure_bounds(m));
@@ -651,9 +653,13 @@ static void bwd_bounds(BwdPass &B) {
             inb = (ly.spec.cout == 2 && ly.fc_wv_amax > 0.f && i == nl - 1) ? (double)ly.fc_wv_amax : (i < nl - 1 ? ly.bwd_l1 * bound : 0.0);
         else if (ly.spec.type != ALQ_POOL) inb = ly.bwd_l1 * bound;
         if (!(inb > 0.0) || bound <= 0.f) inb = 0.0;       // unknown upstream: no bound below either
-        auto add = [&](float &b) { b = (b < 0.f || inb <= 0.0) ? -1.f : b + (float)(inb * (1.0 + 1e-6)); };
-        add(B.st[i - 1].dout_bound);
-        if (ly.spec.skip_src >= 0) add(B.st[ly.spec.skip_src].dout_bound);
+        // a conv / conv_transpose over a concat: each producer's cotangent under the norm of its own channels (conv_bwd_l1_slices)
+        auto add = [&](float &b, double part_l1) {
+            const double v = (inb > 0.0 && part_l1 > 0.0 && ly.spec.type != ALQ_FC && ly.spec.type != ALQ_POOL) ? part_l1 * bound : inb;
+            b = (b < 0.f || v <= 0.0) ? -1.f : b + (float)(v * (1.0 + 1e-6));
+        };
+        add(B.st[i - 1].dout_bound, ly.bwd_l1_part[1]);
+        if (ly.spec.skip_src >= 0) add(B.st[ly.spec.skip_src].dout_bound, ly.bwd_l1_part[0]);
     }
 }
 
@@ -887,6 +893,8 @@ static int run_backward_main(alq_model *m, const float *d_x, int N) {
     BwdPass B{m, d_x, N};
     B.st.resize(nl);
     bwd_bounds(B);
+    m->last.bwd.nbounds = nl < 64 ? nl : 64;
+    for (int i = 0; i < m->last.bwd.nbounds; ++i) m->last.bwd.dout_bound[i] = B.st[i].dout_bound;
     for (int i = nl - 1; i >= 0; --i) {
         Layer &ly = m->layers[i];
         BwdStep s;

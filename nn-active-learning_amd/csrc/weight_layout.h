@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstdlib>
 #include <vector>
 
 #include "f16_pair.h"
@@ -35,6 +36,36 @@ inline void conv_norms(const float *W, const float *b, int ntaps, int Ci, int Co
     *bwd_l1 = best;
     *out_l1 = (float)(ob * (1.0 + 1e-6));
     *out_bmax = (float)(bm * (1.0 + 1e-6));
+}
+
+// bwd_l1 of conv_norms per slice of a concatenated input: part[0] over the input channels ci < split (the skip source's, which a concat
+// puts first), part[1] over the others.  The cotangent of either producer is bounded by its own slice's norm: one norm over all
+// channels is loose for the producer of the smaller slice by the ratio of the two, and the fp16 pairs of the launches below it
+// lose that many bits.
+// amax[s] = max |w| of slice s.  The fp16 pairs of a filter share ONE exponent (f16_pair_exp) and the launch ONE input scale per
+// patch: slices_within_f16_range says whether both slices keep their bits under that (the pairs sit at 2^14, fp16 ends 2^-24
+// below 1: a slice 2^20 below the other still has 18 bits of its hi piece; beyond, the model leaves the fp16-pair launches).
+inline void conv_bwd_l1_slices(const float *W, int ntaps, int Ci, int Co, bool transposed, int split, double part[2], float amax[2]) {
+    std::vector<double> in((size_t)Ci, 0.0);
+    amax[0] = amax[1] = 0.f;
+    for (int tp = 0; tp < ntaps; ++tp)
+        for (int ci = 0; ci < Ci; ++ci)
+            for (int co = 0; co < Co; ++co) {
+                const float w = std::fabs(transposed ? W[((size_t)tp * Co + co) * Ci + ci] : W[((size_t)tp * Ci + ci) * Co + co]);
+                in[(size_t)ci] += (double)w;
+                amax[ci < split ? 0 : 1] = std::max(amax[ci < split ? 0 : 1], w);
+            }
+    part[0] = part[1] = 0;
+    for (int ci = 0; ci < Ci; ++ci) part[ci < split ? 0 : 1] = std::max(part[ci < split ? 0 : 1], in[(size_t)ci]);
+}
+
+constexpr int F16_SLICE_BINADES = 20;
+inline bool slices_within_f16_range(const float amax[2]) {
+    if (!(amax[0] > 0.f) || !(amax[1] > 0.f)) return true;      // an all-zero slice has nothing to lose
+    int e0 = 0, e1 = 0;
+    (void)std::frexp(amax[0], &e0);
+    (void)std::frexp(amax[1], &e1);
+    return std::abs(e0 - e1) <= F16_SLICE_BINADES;
 }
 
 // fc W[o][f]: max over f of sum_o |W| - |cotangent of input f| <= sum_o |W[o][f]| * max |cotangent of the output|

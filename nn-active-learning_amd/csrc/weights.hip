@@ -106,6 +106,13 @@ static int set_conv(alq_model *m, Layer &ly, const float *W, const float *b) {
     const int Ci = ly.in.C, Co = ly.spec.cout;
     const int ntaps = ly.spec.k[0] * ly.spec.k[1] * ly.spec.k[2];
     conv_norms(W, b, ntaps, Ci, Co, false, &ly.bwd_l1, &ly.out_l1, &ly.out_bmax);
+    ly.bwd_l1_part[0] = ly.bwd_l1_part[1] = 0;
+    ly.f16_slices_apart = false;
+    if (ly.spec.skip_src >= 0 && m->layers[ly.spec.skip_src].out.C < Ci) {
+        float slice_amax[2];
+        conv_bwd_l1_slices(W, ntaps, Ci, Co, false, m->layers[ly.spec.skip_src].out.C, ly.bwd_l1_part, slice_amax);
+        ly.f16_slices_apart = !slices_within_f16_range(slice_amax);
+    }
     ly.fwd_l1 = ly.out_l1;
     const int li = (int)(&ly - &m->layers[0]);
     if (li + 2 == (int)m->layers.size() && m->layers[li + 1].fc_part2) {      // the conv under a fused two-class head
@@ -162,6 +169,13 @@ static int set_convt(alq_model *m, Layer &ly, const float *W, const float *b) {
     const int Ci = ly.in.C, Co = ly.spec.cout;
     const int ntaps = ly.spec.k[0] * ly.spec.k[1] * ly.spec.k[2];
     conv_norms(W, b, ntaps, Ci, Co, true, &ly.bwd_l1, &ly.out_l1, &ly.out_bmax);
+    ly.bwd_l1_part[0] = ly.bwd_l1_part[1] = 0;
+    ly.f16_slices_apart = false;
+    if (ly.spec.skip_src >= 0 && m->layers[ly.spec.skip_src].out.C < Ci) {
+        float slice_amax[2];
+        conv_bwd_l1_slices(W, ntaps, Ci, Co, true, m->layers[ly.spec.skip_src].out.C, ly.bwd_l1_part, slice_amax);
+        ly.f16_slices_apart = !slices_within_f16_range(slice_amax);
+    }
     // TF [tap][co][ci]; the two-slot plans index taps in the full k^3 enumeration, the older engines by class
     const std::vector<float> Bfull = transpose_taps(W, Co, Ci, ntaps);
     for (size_t c = 0; c < ly.fwd.size(); ++c) {
