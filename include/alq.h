@@ -668,6 +668,49 @@ int alq_cc_sizes(alq_ctx *ctx, const int32_t *d_labels, int64_t n, int32_t *d_si
 int alq_cc_relabel(alq_ctx *ctx, const int32_t *d_labels, int64_t n, const int32_t *d_table, const int32_t *d_sizes, int32_t min_size,
                    int32_t *d_out_i32, uint8_t *d_out_u8);
 
+/* ---- surface distances: surface voxels, exact distance transform, masked reductions (csrc/edt.hip) -------------------- */
+/* The primitives of the boundary metrics (Hausdorff, its percentile form, average symmetric surface distance, modified
+ * Hausdorff; surfdist.py states each of them in NumPy and builds the metrics).  Volumes are [H, W, S] = dims in C order (z
+ * contiguous; S = 1: a 2-D image).  Every call is stream-ordered, does not synchronise, and validates before any launch.
+ *   alq_surface_mask   d_out uint8 [H, W, S] = 1 on a foreground voxel that has a 6-neighbour which is background or outside the
+ *                      volume, 0 elsewhere.  Foreground: d_seg != 0 for label < 0, else d_seg == label (0 .. 255).  An axis of
+ *                      extent 1 has no neighbours and is ignored: a one-slice volume is the 4-neighbour 2-D case, a 1x1x1
+ *                      foreground voxel is no surface voxel.  d_out may NOT be d_seg.  H W S < 2^31.
+ *   alq_edt_sq         d_out double [H, W, S] = the exact squared Euclidean distance transform to the non-zero voxels of d_feat
+ *                      (uint8), +inf everywhere when there is none.  Defined as three line passes over g = 0 on a feature voxel,
+ *                      +inf elsewhere, in the order z, w, h: g[x] = min over x' of (g[x'] + spacing2 * (double)((x - x')^2)),
+ *                      the product rounded, then the sum rounded - equal to the minimum over the feature voxels of
+ *                      ((s2z dz^2 + s2w dw^2) + s2h dh^2) in that association, to the bit.  spacing2 = the SQUARED voxel
+ *                      spacings (h, w, z), host doubles, finite and > 0.  Every axis is 1 .. alq_edt_max_axis() = 1024 (a
+ *                      staged tile of 8 whole lines of the longest axis is 64 KiB of LDS).  d_work: alq_edt_work_bytes(dims)
+ *                      bytes (0 for dims the call refuses), d_out 8-byte aligned.  No atomics.
+ *   alq_edt_geometry   host arithmetic: out[4] = lines per tile of the z pass, z columns per tile of the strided (w, h) passes,
+ *                      workgroups of the z pass, workgroups of the larger strided pass.  No grid cap: one workgroup per tile.
+ *                      ALQ_EUNSUPPORTED and out = -1 for dims alq_edt_sq refuses.
+ *   alq_masked_dist_stats   d_out double [4] = over the elements i < n with d_mask[i] != 0: their number (exact), the sum of
+ *                      sqrt(d_d2[i]), the maximum and the minimum of d_d2[i]; an empty mask gives 0, 0, -inf, +inf.  Fixed-order
+ *                      reduction without float atomics: the same input gives the same bits on every run.
+ *   alq_masked_select  d_out double [R], 1 <= R <= 8: d_out[r] = the h_ranks[r]-th smallest (0-based) of the masked values;
+ *                      a rank at or above the masked count (which the host does not know) gives NaN.  h_ranks: host int64,
+ *                      each >= 0.  The values must be non-negative doubles or +inf (radix selection on the bit pattern, which
+ *                      orders those); NaN and negative values are outside the contract.  Integer atomics only: exact and
+ *                      run-independent.  No host round trip inside a selection.
+ * Both masked calls: 0 <= n < 2^31, d_work = alq_masked_work_bytes(n) bytes (0 for an n they refuse), 8-byte aligned like d_d2
+ * and d_out.  alq_masked_geometry: out[2] = elements a workgroup takes per grid-stride step, workgroups of the launch for n.
+ * ALQ_EINVAL: a null pointer, d_out == d_seg, a label above 255, a spacing that is 0, negative, infinite or NaN, R outside
+ * 1 .. 8, a negative rank, a misaligned pointer, an axis below 1 (surface mask).  ALQ_EUNSUPPORTED: an axis outside
+ * 1 .. alq_edt_max_axis() (distance transform), 2^31 voxels / elements or more.                                              */
+int alq_surface_mask(alq_ctx *ctx, const uint8_t *d_seg, const int64_t dims[3], int label, uint8_t *d_out);
+int alq_edt_max_axis(void);
+size_t alq_edt_work_bytes(const int64_t dims[3]);
+int alq_edt_geometry(const int64_t dims[3], int32_t out[4]);
+int alq_edt_sq(alq_ctx *ctx, const uint8_t *d_feat, const int64_t dims[3], const double spacing2[3], double *d_out, void *d_work);
+size_t alq_masked_work_bytes(int64_t n);
+int alq_masked_geometry(int64_t n, int32_t out[2]);
+int alq_masked_dist_stats(alq_ctx *ctx, const double *d_d2, const uint8_t *d_mask, int64_t n, double *d_out, void *d_work);
+int alq_masked_select(alq_ctx *ctx, const double *d_d2, const uint8_t *d_mask, int64_t n, const int64_t *h_ranks, int R, double *d_out,
+                      void *d_work);
+
 /* ---- dense CRF on a two-class posterior map: exact mean-field inference (csrc/dcrf.hip) --------------------------------- */
 /* Replaces: PW_analyze_results.DCRF_postprocess_2D (PW_analyze_results.py:539-591), pydensecrf's DenseCRF2D with 2 labels, a
  * smoothness kernel (create_pairwise_gaussian) and an appearance kernel (create_pairwise_bilateral), NORMALIZE_SYMMETRIC, Potts

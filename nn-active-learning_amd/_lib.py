@@ -144,6 +144,15 @@ _SIGNATURES = {
     'alq_fill_holes': (C.c_int, [_P, _P, C.POINTER(C.c_int64), _P, _P, _P]),
     'alq_cc_sizes': (C.c_int, [_P, _P, C.c_int64, _P]),
     'alq_cc_relabel': (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32, _P, _P]),
+    'alq_surface_mask': (C.c_int, [_P, _P, C.POINTER(C.c_int64), C.c_int, _P]),
+    'alq_edt_max_axis': (C.c_int, []),
+    'alq_edt_work_bytes': (C.c_size_t, [C.POINTER(C.c_int64)]),
+    'alq_edt_geometry': (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    'alq_edt_sq': (C.c_int, [_P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_double), _P, _P]),
+    'alq_masked_work_bytes': (C.c_size_t, [C.c_int64]),
+    'alq_masked_geometry': (C.c_int, [C.c_int64, C.POINTER(C.c_int32)]),
+    'alq_masked_dist_stats': (C.c_int, [_P, _P, _P, C.c_int64, _P, _P]),
+    'alq_masked_select': (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(C.c_int64), C.c_int, _P, _P]),
     'alq_confusion_counts': (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, _P, _P]),
     'alq_confusion_window': (C.c_int, [C.c_int]),
     'alq_unc_accumulate': (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, _P, _P]),

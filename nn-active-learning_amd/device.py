@@ -305,6 +305,67 @@ class DeviceSession(object):
                                       C.c_void_p(info.data_ptr()), C.c_void_p(work.data_ptr())))
         return out, info.cpu().numpy()
 
+    # -- surface distances: surface voxels, exact distance transform, masked reductions (csrc/edt.hip) ---
+    def surface_mask(self, seg, shape, label=None, out=None):
+        """alq_surface_mask: uint8 device mask (of `shape` [H, W, S] or [H, W]) of the foreground voxels of the uint8 device
+        volume `seg` that have a 6-neighbour which is background or outside the volume; foreground is seg != 0 (label None or
+        negative) or seg == label.  An axis of extent 1 is ignored.  `out` may not be `seg`."""
+        shape, nvox, dims = self._cc_args(seg, shape, out)
+        if out is None:
+            out = self.empty(shape, self.torch.uint8)
+        assert out.data_ptr() != seg.data_ptr() or nvox == 0
+        check(self.lib.alq_surface_mask(self._ctx, C.c_void_p(seg.data_ptr()), dims, -1 if label is None else int(label),
+                                        C.c_void_p(out.data_ptr())))
+        return out
+
+    def edt_sq(self, feat, shape, spacing=(1., 1., 1.), out=None):
+        """alq_edt_sq: float64 device tensor of `shape` [H, W, S] (or [H, W]) = the exact squared Euclidean distance from every
+        voxel to the nearest non-zero voxel of the uint8 device volume `feat` (+inf everywhere when there is none), voxel
+        spacings `spacing` (h, w, z; two values for an image).  Bit-equal to surfdist.edt_sq_host."""
+        torch = self.torch
+        shape, nvox, dims = self._cc_args(feat, shape)
+        sp = [np.float64(s) for s in spacing]
+        if len(sp) == 2:
+            sp.append(np.float64(1.))
+        assert len(sp) == 3
+        s2 = (C.c_double * 3)(*[float(s * s) for s in sp])
+        if out is None:
+            out = self.empty(shape, torch.float64)
+        assert out.dtype == torch.float64 and out.is_contiguous() and out.device == self.device and int(out.numel()) == nvox
+        work = self.empty((max(int(self.lib.alq_edt_work_bytes(dims)), 8),), torch.uint8)
+        check(self.lib.alq_edt_sq(self._ctx, C.c_void_p(feat.data_ptr()), dims, s2, C.c_void_p(out.data_ptr()), C.c_void_p(work.data_ptr())))
+        return out
+
+    def _masked_args(self, d2, mask):
+        torch = self.torch
+        self.bind_stream()
+        n = int(d2.numel())
+        assert d2.dtype == torch.float64 and d2.is_contiguous() and d2.device == self.device
+        assert mask.dtype == torch.uint8 and mask.is_contiguous() and mask.device == self.device and int(mask.numel()) == n
+        if n >= 2 ** 31:
+            raise ValueError('2^31 elements or more')
+        return n, self.empty((int(self.lib.alq_masked_work_bytes(n)),), torch.uint8)
+
+    def masked_dist_stats(self, d2, mask):
+        """alq_masked_dist_stats: np.float64 [4] = (count, sum of sqrt(d2), max of d2, min of d2) over the elements of the float64
+        device tensor `d2` whose byte of the uint8 device tensor `mask` is non-zero (empty: 0, 0, -inf, +inf); one copy of 32
+        bytes.  The same bits on every run."""
+        n, work = self._masked_args(d2, mask)
+        out = self.empty((4,), self.torch.float64)
+        check(self.lib.alq_masked_dist_stats(self._ctx, C.c_void_p(d2.data_ptr()), C.c_void_p(mask.data_ptr()), n, C.c_void_p(out.data_ptr()),
+                                             C.c_void_p(work.data_ptr())))
+        return out.cpu().numpy()
+
+    def masked_select(self, d2, mask, ranks):
+        """alq_masked_select: np.float64 [len(ranks)] (at most 8) = the ranks[r]-th smallest (0-based) of the masked entries of
+        `d2` (non-negative or +inf), NaN for a rank at or above the masked count; one copy of 8 bytes per rank."""
+        n, work = self._masked_args(d2, mask)
+        ranks = [int(r) for r in ranks]
+        out = self.empty((len(ranks),), self.torch.float64)
+        check(self.lib.alq_masked_select(self._ctx, C.c_void_p(d2.data_ptr()), C.c_void_p(mask.data_ptr()), n, (C.c_int64 * max(len(ranks), 1))(*ranks),
+                                         len(ranks), C.c_void_p(out.data_ptr()), C.c_void_p(work.data_ptr())))
+        return out.cpu().numpy()
+
     # -- dense CRF on a two-class posterior map (csrc/dcrf.hip) ------------------------------
     def dcrf2d(self, post, img, dims, params=None, want_q=False):
         """alq_dcrf2d: the dense CRF of DCRF_postprocess_2D (nnal_amd.dcrf states the model) on S independent slices,

@@ -463,6 +463,50 @@ def eval_full_segs_label_percentage(seg_paths_or_mats, mask_paths_or_mats, label
     return overall_Fscores, part_Fscores
 
 
+def eval_full_segs_surface_distances(seg_paths_or_mats, mask_paths_or_mats, spacings=None, labels=None, percentile=95., **kwargs):
+    """Boundary metrics (surfdist.surface_distances: HD, HD95, ASSD, MHD, surface voxel counts, directed values) of n whole-volume
+    segmentations against their masks: a dict of arrays [n], or [n, len(labels)] when `labels` lists the mask values to score
+    one by one (None: foreground is != 0).  `spacings`: one (h, w, z) for all, or one per subject; None: ones for arrays, and for
+    paths read with the default mask_reader the spacing of each mask file, nrrd_io.voxel_spacing(header).
+    Keywords: dat_reader / mask_reader for paths (default nrrd_io.read) and sess - with a session each volume is uploaded
+    once and every label is scored on the device (HD95 is the maximum of the directed percentiles, surfdist's module text)."""
+    from . import nrrd_io, surfdist
+    default_reader = 'mask_reader' not in kwargs
+    dat_reader, mask_reader, sess = _readers(kwargs)
+    segs = _load_list(seg_paths_or_mats, dat_reader)
+    masks = _load_list(mask_paths_or_mats, mask_reader)
+    n = len(segs)
+    if spacings is None:
+        spacings = [(1., 1., 1.)] * n
+        if default_reader and n and isinstance(mask_paths_or_mats[0], str):
+            spacings = []
+            for path in mask_paths_or_mats:
+                with open(path, 'rb') as f:
+                    spacings.append(nrrd_io.voxel_spacing(nrrd_io.read_header(f)))
+    elif np.ndim(spacings) == 1:
+        spacings = [tuple(spacings)] * n
+    labs = [None] if labels is None else list(labels)
+    out = {}
+    for i in range(n):
+        seg, mask = np.asarray(segs[i]), np.asarray(masks[i])
+        sp = tuple(spacings[i])[:seg.ndim]
+        if sess is not None:
+            # one upload per volume, every label reads it in place
+            shape = seg.shape
+            binary = labels is None
+            seg = sess.to_device((seg != 0) if binary else seg, sess.torch.uint8)
+            mask = sess.to_device((mask != 0) if binary else mask, sess.torch.uint8)
+        for j, lab in enumerate(labs):
+            res = surfdist.surface_distances(seg, mask, sp, lab, percentile, sess, shape if sess is not None else None)
+            for k, v in res.items():
+                if k not in out:
+                    out[k] = np.zeros((n, len(labs)), dtype=np.int64 if k.startswith('n_') else np.float64)
+                out[k][i, j] = v
+    if labels is None:
+        out = {k: v[:, 0] for k, v in out.items()}
+    return out
+
+
 def simple_eval_model(model, sess, dat_gen):
     """(accuracy, predictions) over the batches (Xb, Yb, _) of the iterable `dat_gen` (eval_utils.py:391-409): model.prediction
     at keep_prob 1 (no keep_prob in the feed when model.dropout_rate is None), the ground truth np.argmax(Yb, axis=0) - class

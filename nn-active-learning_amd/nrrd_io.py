@@ -80,8 +80,43 @@ def read(path):
     return np.array(data.astype(dt.newbyteorder('='), copy=False)), header
 
 
-def write(path, data, encoding='raw'):
-    """Attached-data NRRD0004 of `data` (first axis fastest), for fixtures and round trips."""
+def voxel_spacing(header):
+    """Voxel sizes per axis of a NRRD header (as read_header / read return it, or pynrrd's): the `spacings` field, else the
+    norms of the `space directions` vectors, else ones.  A `none` / `nan` entry (a non-spatial axis, an unknown spacing) gives
+    1.  A tuple of `dimension` floats (the length of what was found when the header has no dimension)."""
+    def number(v):
+        try:
+            v = float(v)
+        except (TypeError, ValueError):
+            return 1.
+        return v if np.isfinite(v) else 1.
+
+    out = None
+    sp = header.get('spacings')
+    if sp is not None:
+        out = [number(v) for v in (sp.split() if isinstance(sp, str) else np.asarray(sp).ravel())]
+    elif header.get('space directions') is not None:
+        sd = header['space directions']
+        out = []
+        for vec in (sd.split() if isinstance(sd, str) else sd):
+            if isinstance(vec, str):
+                vec = vec.strip()
+                if not vec.startswith('('):
+                    out.append(1.)      # none
+                    continue
+                vec = [number(v) for v in vec.strip('()').split(',')]
+            elif vec is None:
+                out.append(1.)
+                continue
+            out.append(number(np.sqrt(np.sum(np.asarray(vec, dtype=np.float64) ** 2))))
+    dim = int(header['dimension']) if 'dimension' in header else (len(out) if out else 3)
+    out = (out or [])[:dim]
+    return tuple(out + [1.] * (dim - len(out)))
+
+
+def write(path, data, encoding='raw', fields=None):
+    """Attached-data NRRD0004 of `data` (first axis fastest), for fixtures and round trips.  `fields`: further header lines as
+    a dict, e.g. {'spacings': '1 1 2.5'}."""
     data = np.asarray(data)
     inv = {v: k for k, v in (('float', 'f4'), ('double', 'f8'), ('uint8', 'u1'), ('int8', 'i1'), ('int16', 'i2'), ('uint16', 'u2'),
                              ('int32', 'i4'), ('uint32', 'u4'), ('int64', 'i8'), ('uint64', 'u8'))}
@@ -96,8 +131,9 @@ def write(path, data, encoding='raw'):
         payload = buf.getvalue()
     elif encoding != 'raw':
         raise NotImplementedError(encoding)
-    head = 'NRRD0004\ntype: %s\ndimension: %d\nsizes: %s\nendian: little\nencoding: %s\n\n' % (
-        inv[code], data.ndim, ' '.join(str(s) for s in data.shape), encoding)
+    extra = ''.join('%s: %s\n' % (k, v) for k, v in (fields or {}).items())
+    head = 'NRRD0004\ntype: %s\ndimension: %d\nsizes: %s\nendian: little\nencoding: %s\n%s\n' % (
+        inv[code], data.ndim, ' '.join(str(s) for s in data.shape), encoding, extra)
     with open(path, 'wb') as f:
         f.write(head.encode('ascii'))
         f.write(payload)
