@@ -977,6 +977,48 @@ int alq_slice_batch(alq_ctx *ctx, const float *const *h_vols, const uint8_t *con
 int64_t alq_slice_batch_trip_rows(void);
 int alq_slice_batch_launch_samples(void);
 
+/* ---- whole-volume inference of a dense model: tiles, blended on the device (csrc/tile.hip) ----------------------------------- */
+/* No reference counterpart (the reference builds one model per image size, eval_utils.models_dict_for_different_sizes); the NumPy
+ * statement of every function below is nnal_amd/tiled.py, and the device equals it bit for bit.
+ *
+ * The lattice, order Z, H, W.  Along an axis of length D with tile t and stride s (1 <= s <= t): D <= t gives one tile at origin 0,
+ * which overhangs the volume by t - D at the high end; otherwise there are ceil((D - t) / s) + 1 tiles at min(i s, D - t) - the last
+ * one is clamped so that it ends with the volume.  Tile (iz, ih, iw) has the index (iz nH + ih) nW + iw.  The three lattice functions
+ * are host arithmetic and make no device call.
+ *   alq_tile_lattice_check  ALQ_EINVAL: null, an axis or a tile below 1, a stride below 1 or above the tile.
+ *   alq_tile_count          the tiles per axis into counts (may be NULL); returns their product, or the check's error.
+ *   alq_tile_origin         the first voxel of tile idx; ALQ_EINVAL: idx outside 0 .. count - 1, null origin.
+ *
+ * alq_tile_gather: d_vol is a packed volume [Z, H, W, m] of floats (alq_vol_pack); writes d_X [n, tz, th, tw, m], the tiles
+ * first .. first + n - 1.  Voxels outside the volume - they occur only on an axis with D < t - are `fill`.  1 <= m <= 8.
+ *
+ * alq_tile_blend: d_post [c, n V] in class-major planes as alq_forward writes them for a dense model, V = tz th tw, sample j V + v
+ * is voxel v of tile first + j; d_wz [tz], d_wh [th], d_ww [tw] the window tables; d_acc [c + 1, Z, H, W], zeroed by the caller
+ * before the first call.  For every voxel and every tile of the call that covers it, in ascending tile index, with (lz, lh, lw) the
+ * voxel's place in the tile and every operation rounded to fp32 on its own:
+ *     w = (wz[lz] wh[lh]) ww[lw];    acc[k] += w p_k, k = 0 .. c - 1;    acc[c] += w.
+ * A voxel has one writer and its sum runs in tile order whatever the calls' ranges: calls over consecutive ranges of tiles leave
+ * the bytes of one call over all tiles.  The overhang of a tile is never written.  2 <= c <= 8.
+ * alq_tile_blend_trip_voxels: the voxels one sweep of the capped grid covers (for tests: a case asserts from it that the bounding
+ * box of its call passes them).
+ *
+ * alq_tile_finalize: dims = {Z, H, W}; q_k = acc[k] / acc[c], correctly rounded, into d_post_out [c, ...] (may be NULL); the first
+ * maximum of q over k into d_label bytes (may be NULL).  hwz = 0: both in [Z, H, W] order; hwz = 1: [H, W, Z] with z fastest, the
+ * layout alq_cc_*, alq_surface_mask and alq_confusion_counts read.  2 <= c <= 8.
+ *
+ * All three are stream-ordered with no synchronisation.  Refused before any launch - ALQ_EINVAL: a null pointer, a bad lattice,
+ * first < 0, n < 1, first + n beyond the tile count, m < 1, hwz outside {0, 1}, a misaligned pointer; ALQ_EUNSUPPORTED: m or c out
+ * of range, a volume or a call's tiles of 2^31 voxels (elements, for the gather) or more.                                          */
+typedef struct { int32_t dims[3], tile[3], stride[3]; } alq_tile_lattice_t;   /* order Z, H, W */
+int alq_tile_lattice_check(const alq_tile_lattice_t *lat);
+int64_t alq_tile_count(const alq_tile_lattice_t *lat, int32_t counts[3]);
+int alq_tile_origin(const alq_tile_lattice_t *lat, int64_t idx, int32_t origin[3]);
+int alq_tile_gather(alq_ctx *ctx, const float *d_vol, int m, const alq_tile_lattice_t *lat, int64_t first, int64_t n, float fill, float *d_X);
+int alq_tile_blend(alq_ctx *ctx, const float *d_post, int c, const alq_tile_lattice_t *lat, int64_t first, int64_t n, const float *d_wz,
+                   const float *d_wh, const float *d_ww, float *d_acc);
+int64_t alq_tile_blend_trip_voxels(void);
+int alq_tile_finalize(alq_ctx *ctx, const float *d_acc, int c, const int32_t dims[3], int hwz, float *d_post_out, uint8_t *d_label);
+
 #ifdef __cplusplus
 }
 #endif

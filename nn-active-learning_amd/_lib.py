@@ -50,6 +50,11 @@ class LossT(C.Structure):
                 ('d_class_w', C.c_void_p), ('d_sample_w', C.c_void_p), ('d_targets', C.c_void_p), ('d_old_logits', C.c_void_p)]
 
 
+class TileLattice(C.Structure):
+    """Mirror of alq_tile_lattice_t (order Z, H, W)."""
+    _fields_ = [('dims', C.c_int32 * 3), ('tile', C.c_int32 * 3), ('stride', C.c_int32 * 3)]
+
+
 class DcrfParams(C.Structure):
     """Mirror of alq_dcrf_params (defaults: the reference's DCRF_postprocess_2D call)."""
     _fields_ = [('sdims_smooth', C.c_float * 2), ('sdims_app', C.c_float * 2), ('schan', C.c_float), ('compat_smooth', C.c_float),
@@ -182,6 +187,13 @@ _SIGNATURES = {
                                   C.POINTER(C.c_int32), C.c_int, _P, _P, _P]),
     'alq_slice_batch_trip_rows': (C.c_int64, []),
     'alq_slice_batch_launch_samples': (C.c_int, []),
+    'alq_tile_lattice_check': (C.c_int, [C.POINTER(TileLattice)]),
+    'alq_tile_count': (C.c_int64, [C.POINTER(TileLattice), C.POINTER(C.c_int32)]),
+    'alq_tile_origin': (C.c_int, [C.POINTER(TileLattice), C.c_int64, C.POINTER(C.c_int32)]),
+    'alq_tile_gather': (C.c_int, [_P, _P, C.c_int, C.POINTER(TileLattice), C.c_int64, C.c_int64, C.c_float, _P]),
+    'alq_tile_blend': (C.c_int, [_P, _P, C.c_int, C.POINTER(TileLattice), C.c_int64, C.c_int64, _P, _P, _P, _P]),
+    'alq_tile_blend_trip_voxels': (C.c_int64, []),
+    'alq_tile_finalize': (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int32), C.c_int, _P, _P]),
     'alq_comm_unique_id': (C.c_int, [_P]),
     'alq_comm_init': (C.c_int, [_P, _P, C.c_int, C.c_int]),
     'alq_comm_destroy': (C.c_int, [_P]),

@@ -336,6 +336,69 @@ class DeviceSession(object):
         check(self.lib.alq_edt_sq(self._ctx, C.c_void_p(feat.data_ptr()), dims, s2, C.c_void_p(out.data_ptr()), C.c_void_p(work.data_ptr())))
         return out
 
+    # -- whole-volume inference by tiles: gather, blend, finalize (csrc/tile.hip; statement: tiled.py) ---
+    @staticmethod
+    def tile_lattice(dims, tile, stride):
+        """The alq_tile_lattice_t of a volume `dims`, `tile` and `stride`, each (Z, H, W); ValueError with the library's message for a
+        lattice it refuses."""
+        lat = _lib.TileLattice((C.c_int32 * 3)(*[int(v) for v in dims]), (C.c_int32 * 3)(*[int(v) for v in tile]),
+                               (C.c_int32 * 3)(*[int(v) for v in stride]))
+        if _lib.lib().alq_tile_lattice_check(C.byref(lat)) != 0:
+            raise ValueError(_lib.lib().alq_last_error().decode())
+        return lat
+
+    def tile_count(self, lat):
+        return int(self.lib.alq_tile_count(C.byref(lat), None))
+
+    def tile_gather(self, vol, lat, first, n, fill=0., out=None):
+        """alq_tile_gather: the tiles first .. first + n - 1 of the packed float32 device volume `vol` [Z, H, W, m] as a float32
+        device tensor [n, tz, th, tw, m] (`out` when given); what lies outside the volume is `fill`."""
+        torch = self.torch
+        self.bind_stream()
+        m = int(vol.shape[-1])
+        assert vol.dtype == torch.float32 and vol.is_contiguous() and vol.device == self.device
+        assert tuple(int(v) for v in vol.shape[:3]) == tuple(lat.dims)
+        shape = (max(int(n), 0),) + tuple(lat.tile) + (m,)
+        if out is None:
+            out = self.empty(shape, torch.float32)
+        assert out.dtype == torch.float32 and out.is_contiguous() and out.device == self.device and tuple(out.shape) == shape
+        check(self.lib.alq_tile_gather(self._ctx, C.c_void_p(vol.data_ptr()), m, C.byref(lat), int(first), int(n), float(fill),
+                                       C.c_void_p(out.data_ptr())))
+        return out
+
+    def tile_blend(self, post, lat, first, n, windows, acc):
+        """alq_tile_blend: adds the posteriors `post` (float32 device [c, n V], class-major planes as the forward calls return them)
+        of the tiles first .. first + n - 1, weighted by the float32 device window tables `windows` = (wz, wh, ww), into the
+        float32 device accumulator `acc` [c + 1, Z, H, W] (zeroed by the caller before the first call)."""
+        torch = self.torch
+        self.bind_stream()
+        c, V = int(acc.shape[0]) - 1, int(np.prod(tuple(lat.tile)))
+        for t, numel in ((post, c * int(n) * V), (acc, (c + 1) * int(np.prod(tuple(lat.dims))))) + tuple(zip(windows, tuple(lat.tile))):
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.device == self.device and int(t.numel()) == numel
+        check(self.lib.alq_tile_blend(self._ctx, C.c_void_p(post.data_ptr()), c, C.byref(lat), int(first), int(n),
+                                      *[C.c_void_p(t.data_ptr()) for t in windows], C.c_void_p(acc.data_ptr())))
+        return acc
+
+    def tile_finalize(self, acc, hwz=True, want_post=True, want_label=True, post=None, label=None):
+        """alq_tile_finalize of the accumulator `acc` [c + 1, Z, H, W]: (posteriors float32 [c, H, W, Z] or None, labels uint8
+        [H, W, Z] or None) with hwz, else [c, Z, H, W] / [Z, H, W]; written into `post` / `label` when given."""
+        torch = self.torch
+        self.bind_stream()
+        c = int(acc.shape[0]) - 1
+        Z, H, W = (int(v) for v in acc.shape[1:])
+        assert acc.dtype == torch.float32 and acc.is_contiguous() and acc.device == self.device
+        shape = (H, W, Z) if hwz else (Z, H, W)
+        if post is None and want_post:
+            post = self.empty((c,) + shape, torch.float32)
+        if label is None and want_label:
+            label = self.empty(shape, torch.uint8)
+        for t, dt, numel in ((post, torch.float32, c * Z * H * W), (label, torch.uint8, Z * H * W)):
+            assert t is None or (t.dtype == dt and t.is_contiguous() and t.device == self.device and int(t.numel()) == numel)
+        check(self.lib.alq_tile_finalize(self._ctx, C.c_void_p(acc.data_ptr()), c, (C.c_int32 * 3)(Z, H, W), 1 if hwz else 0,
+                                         C.c_void_p(post.data_ptr()) if post is not None else None,
+                                         C.c_void_p(label.data_ptr()) if label is not None else None))
+        return post, label
+
     def _masked_args(self, d2, mask):
         torch = self.torch
         self.bind_stream()
@@ -2164,13 +2227,15 @@ class DeviceModel(object):
             post[:, a * V:b * V] = pb
         return post, pred, feat
 
-    def forward_maps_device(self, t, n, keep_prob=1., want_pred=False, seed=None):
+    def forward_maps_device(self, t, n, keep_prob=1., want_pred=False, seed=None, first_sample=0):
         """A dense model's outputs as maps, on the device: (posteriors [n, *spatial, c] float32 - `model.posteriors` of the
-        reference's FCN branch, NN_extended.py:262-294 - and prediction [n, *spatial] int64 or None)."""
+        reference's FCN branch, NN_extended.py:262-294 - and prediction [n, *spatial] int64 or None).  The posteriors are a view of
+        the class-major planes [c, n V] the library wrote (`.movedim(-1, 0)` is that array again).  first_sample: the dropout keys
+        of the samples are first_sample .. first_sample + n - 1 (keep_prob < 1)."""
         if not self.dense:
             raise NotImplementedError('forward_maps_device: the model has an fc head (no output map)')
         if float(keep_prob) < 1. and len(self.dropout_layers):
-            post, pred = self.forward_dropout_device(t, n, keep_prob, seed=seed, want_pred=want_pred)
+            post, pred = self.forward_dropout_device(t, n, keep_prob, seed=seed, first_sample=first_sample, want_pred=want_pred)
         else:
             post, pred, _ = self.forward_device(t, n, want_pred)
         maps = post.reshape((self.nclass, n) + self.out_map_shape).movedim(0, -1)

@@ -358,6 +358,119 @@ def get_full_segs(models_dict, sess, dat, post_process=False, save_path=None, da
     return segs
 
 
+def _tile_geometry(model, stride):
+    """(tile, stride) of a dense model, each (Z, H, W): a 3-D model of in_shape (D, H, W, m) tiles the volume by (D, H, W) blocks, a
+    2-D one of (h, w, m) by (1, h, w) - every axial slice, stride 1 along z.  stride None: half a tile per axis (at least 1); an
+    int: that many voxels on every in-plane axis; a sequence: one value per spatial axis of the model."""
+    from . import tiled
+    spatial = tuple(int(v) for v in model.in_shape[:-1])
+    if len(spatial) not in (2, 3):
+        raise NotImplementedError('full_volume_segment: a model of input shape %r' % (tuple(model.in_shape),))
+    if stride is None:
+        st = tiled.default_stride(spatial)
+    elif np.ndim(stride) == 0:
+        st = (int(stride),) * len(spatial)
+    else:
+        st = tuple(int(v) for v in stride)
+        if len(st) != len(spatial):
+            raise ValueError('stride %r for a model with %d spatial axes' % (stride, len(spatial)))
+    if len(spatial) == 2:
+        return (1,) + spatial, (1,) + st
+    return spatial, st
+
+
+def full_volume_segment(model, sess, img_paths_or_mats, data_reader=None, op='prediction', stride=None, window='gaussian', fill=0.,
+                        keep_on_device=False):
+    """Runs a dense device model over a whole volume of ANY size by overlapping tiles of the model's input shape and blends the
+    tiles' posteriors on the device (tiled.py states every operation; csrc/tile.hip).
+
+    img_paths_or_mats: one (h, w, z) array or path, a list of m of them, or a datasets.utils.ResidentSubject (read in place).
+    op: 'prediction' -> (h, w, z), the first maximum of the blended posteriors; 'posterior' -> (c, h, w, z); 'MC-posterior' ->
+    (c, h, w, z) of the running mean of MC_PASSES dropout passes per tile at keep_prob = 1 - model.dropout_rate, the masks keyed by
+    (pass seed, tile index) - the MC_PASSES seeds are drawn from np.random once, so the result does not depend on model.max_batch.
+    stride: see _tile_geometry.  window: 'uniform', 'triangle' or 'gaussian' (tiled.window).  fill: the value of input voxels
+    outside the volume (only where the volume is smaller than the tile).  Float64 NumPy as full_slice_segment returns;
+    keep_on_device=True: the uint8 [h, w, z] / float32 [c, h, w, z] device tensors.  A model with AU_4U is served on its c clean
+    channels; an fc-head model raises NotImplementedError."""
+    from . import tiled
+    from .datasets.utils import ResidentSubject
+    if op not in ('prediction', 'posterior', 'MC-posterior'):
+        raise ValueError('unknown op %r' % (op,))
+    if not _on_device(model):
+        raise NotImplementedError('full_volume_segment needs a fully-convolutional device model (1x1 conv head)')
+    tile, st = _tile_geometry(model, stride)
+    if tuple(int(v) for v in model.out_map_shape) != tuple(int(v) for v in model.in_shape[:-1]):
+        raise NotImplementedError('full_volume_segment: the output map %r is not the input grid %r' % (model.out_map_shape, model.in_shape[:-1]))
+    torch = sess.torch
+    if isinstance(img_paths_or_mats, ResidentSubject):
+        subject = img_paths_or_mats
+    else:
+        subject = ResidentSubject.pack(sess, _load_volumes(img_paths_or_mats, data_reader))
+    h, w, z = subject.shape
+    if subject.m != int(model.in_shape[-1]):
+        raise ValueError('the subject has %d channels, the model takes %d' % (subject.m, int(model.in_shape[-1])))
+    c = int(model.class_num)
+    lat = sess.tile_lattice((z, h, w), tile, st)
+    ntiles = sess.tile_count(lat)
+    windows = tuple(sess.to_device(tiled.window(window, t), torch.float32) for t in tile)
+    acc = torch.zeros((c + 1, z, h, w), dtype=torch.float32, device=sess.device)
+    mc = op == 'MC-posterior'
+    kp = 1. - float(model.dropout_rate) if mc else 1.
+    seeds = [int(np.random.randint(0, 2 ** 31 - 1)) for _ in range(MC_PASSES)] if mc else [None]
+    nb = int(model.max_batch)
+    X = sess.empty((min(nb, ntiles),) + tuple(tile) + (subject.m,), torch.float32)
+    for first in range(0, ntiles, nb):
+        n = min(nb, ntiles - first)
+        Xn = sess.tile_gather(subject.vol, lat, first, n, fill, out=X[:n])
+        P = None
+        for i, seed in enumerate(seeds):
+            # [c, n V]: the class-major planes the library wrote, before forward_maps_device's movedim view
+            Pi = model.forward_maps_device(Xn, n, kp, seed=seed, first_sample=first)[0].movedim(-1, 0).reshape(c, -1)
+            P = Pi if P is None else (i * P + Pi) / (i + 1)
+        sess.tile_blend(P.contiguous(), lat, first, n, windows, acc)
+    want_post = op != 'prediction'
+    post, label = sess.tile_finalize(acc, hwz=True, want_post=want_post, want_label=not want_post)
+    out = post if want_post else label
+    if keep_on_device:
+        return out
+    return out.cpu().numpy().astype(np.float64)
+
+
+def get_full_segs_tiled(model, sess, dat, stride=None, window='gaussian', post_process=False, save_path=None, dat_writer=None):
+    """get_full_segs with ONE model for every subject size (full_volume_segment instead of a dictionary of models per size).
+    post_process=True keeps the largest connected component and fills its holes on the label volume where it lies (the uint8
+    [h, w, z] device tensor full_volume_segment leaves; post_processing.py); the segmentations are np.uint32 then, as
+    post_processing returns them."""
+    from .post_processing import connected_component_analysis_3d, fill_holes
+    n = len(dat.img_addrs[dat.mods[0]])
+    segs = []
+    for i in range(n):
+        seg = full_volume_segment(model, sess, [dat.img_addrs[mod][i] for mod in dat.mods], dat.reader, stride=stride, window=window,
+                                  keep_on_device=True)
+        if post_process:
+            shape = tuple(int(v) for v in seg.shape)
+            seg = fill_holes(connected_component_analysis_3d(seg, sess=sess, shape=shape), sess=sess, shape=shape)
+            segs.append(seg.cpu().numpy().astype(np.uint32))
+        else:
+            segs.append(seg.cpu().numpy().astype(np.float64))
+    _save_segs(segs, save_path, dat_writer)
+    return segs
+
+
+def _save_segs(segs, save_path, dat_writer):
+    """seg_<i>.nrrd under the existing directory `save_path` through `dat_writer(path, volume)` (default: nrrd_io.write)."""
+    if save_path is None:
+        return
+    if not os.path.exists(save_path):
+        print('The specified path for saving data does not exist.')
+        return
+    if dat_writer is None:
+        from . import nrrd_io
+        dat_writer = nrrd_io.write
+    for i, seg in enumerate(segs):
+        dat_writer(os.path.join(save_path, 'seg_{}.nrrd'.format(i)), seg)
+
+
 # ---- whole-volume scores by axial partitions (eval_utils.py:240-363) --------------------------------------------------------
 def _load_list(paths_or_mats, reader):
     if isinstance(paths_or_mats[0], str):
