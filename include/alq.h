@@ -1019,6 +1019,37 @@ int alq_tile_blend(alq_ctx *ctx, const float *d_post, int c, const alq_tile_latt
 int64_t alq_tile_blend_trip_voxels(void);
 int alq_tile_finalize(alq_ctx *ctx, const float *d_acc, int c, const int32_t dims[3], int hwz, float *d_post_out, uint8_t *d_label);
 
+/* ---- SLIC super-pixel over-segmentation of a resident subject (csrc/slic.hip) ---------------------------------------------- */
+/* Makes the over-segmentation alq_segment_min reads, where the reference calls skimage.segmentation.slic (PW_AL.py:2).  NOT
+ * skimage: there is no reference counterpart to match, the algorithm is defined by its NumPy statement nnal_amd/slic.py (a gSLIC
+ * per axial slice on values quantised to 16 bits, integer cluster sums, then enforced 4-connectivity), and the device equals that
+ * statement byte for byte whatever order its workgroups run in.  slic.py's docstring is the full definition; in short:
+ *   d_vol   packed subject [Z, H, W, m] floats (alq_vol_pack), d_mask packed bytes [Z, H, W] or NULL: byte 255 = out (the NO_CLASS
+ *           byte of alq_mask_pack), any other byte = in.  A pixel with a non-finite value in any channel is out as well.
+ *   dims    {H, W, S}, S = Z slices.  lo, scale: HOST arrays [m]; q_c = clamp(rint((double(v) - lo[c]) * scale[c]), 0, 65535).
+ *   gh, gw  cells per slice, 1 <= gh <= H, 1 <= gw <= W; w the spatial weight of d = sum_c (q_c - mu_c)^2 + w ((y - cy)^2 + (x - cx)^2);
+ *           T iterations of assign + update (0: the home cells); min_size: a cluster's largest component is kept only from that
+ *           size on (0: always), every other component is adopted by a kept region it touches or merged with its fellow orphans.
+ *   d_labels int32, [H, W, S] with hwz = 1 (what alq_segment_min reads), [S, H, W] with hwz = 0: 0 on out pixels, else 1 .. n_z in
+ *           the order of the regions' first pixels; d_nlabels int32 [S] = n_z.
+ *   d_work  alq_slic_work_bytes(dims, m, gh, gw) bytes (0 for arguments alq_slic refuses), 8-byte aligned: centres, cluster keys,
+ *           four int32 volumes and the uint16 pixels.
+ * One launch sequence for all slices: 2 + 2 T + 10 launches, no host round trip and no copy back - the adoption rounds loop inside a
+ * launch on a flag in LDS.  Measured (MI355X, 256 x 256 x 128, m = 1, a 32 x 32 grid, T = 10; DESIGN.md section 7 has the table):
+ * 4.68 ms the call, 0.31 ms an iteration - 24 times a device copy of the iteration's bytes, bound by latency, not by bytes -
+ * against 2.4 s for the statement on 16 host threads.  Stream-ordered, no synchronisation.  Refused before any launch - ALQ_EINVAL: a null pointer (d_mask may
+ * be NULL), an axis, m, gh or gw below 1, gh > H, gw > W, w negative or not finite, T or min_size below 0, hwz outside {0, 1}, a
+ * lo / scale that is not finite, a misaligned pointer; ALQ_EUNSUPPORTED: m above 8, 2^31 pixels or more.
+ * alq_slic_geometry (for tests: a case asserts from it that it is in the regime it names): out[0] = (slice, tile) pairs of the
+ * assign launch, out[1] = its workgroups, out[2] = clusters one update workgroup reduces per sweep, out[3] = update workgroups,
+ * out[4] = workgroups of the per-slice launches (one slice each per sweep), out[5] = the cap on every grid (8 per CU; the
+ * environment variable ALQ_SLIC_MAX_GROUPS overrides it, same bytes for every value), out[6] = workgroups of the per-pixel
+ * launches (256 pixels each per sweep), out[7] = the tile side.  A capped grid strides: workgroup b takes items b, b + grid, ...   */
+size_t alq_slic_work_bytes(const int64_t dims[3], int m, int gh, int gw);
+int alq_slic_geometry(alq_ctx *ctx, const int64_t dims[3], int m, int gh, int gw, int64_t out[8]);
+int alq_slic(alq_ctx *ctx, const float *d_vol, const uint8_t *d_mask, const int64_t dims[3], int m, const double *lo, const double *scale, int gh,
+             int gw, double w, int T, int min_size, int hwz, int32_t *d_labels, int32_t *d_nlabels, void *d_work);
+
 #ifdef __cplusplus
 }
 #endif

@@ -610,28 +610,39 @@ def stoch_approx_IF(model, sess, tr_patches, pool_patches, max_iter, scale=50):
     return V_t.cpu().numpy(), weak.cpu().numpy()
 
 
+def _is_device_tensor(x):
+    return hasattr(x, 'data_ptr') and hasattr(x, 'device')
+
+
 def _segment_min_device(sess, overseg_img, inds, scores, n_labels):
-    """alq_segment_min: float64 device table [S, n_labels] of an over-segmentation [H, W, S] (host array), the scored voxels
+    """alq_segment_min: float64 device table [S, n_labels] of an over-segmentation [H, W, S] (a host array, uploaded here, or an
+    int32 device tensor as regions.oversegment(..., keep_on_device=True) leaves it, read where it lies), the scored voxels
     `inds` (host) and their `scores` (float64 device tensor)."""
     import ctypes as C
     from ._lib import check
     torch = sess.torch
     sess.bind_stream()
-    seg = np.asarray(overseg_img)
+    on_device = _is_device_tensor(overseg_img)
+    seg = overseg_img if on_device else np.asarray(overseg_img)
     if seg.ndim != 3:
         raise ValueError('the over-segmentation must be a 3-D volume')
+    shape = tuple(int(v) for v in seg.shape)
+    nvox = shape[0] * shape[1] * shape[2]
     inds = np.ascontiguousarray(np.asarray(inds, dtype=np.int64)).reshape(-1)
     n = int(inds.shape[0])
     if int(scores.numel()) != n:
         raise ValueError('%d scores for %d voxels' % (int(scores.numel()), n))
-    if n and (inds.min() < 0 or inds.max() >= seg.size):
-        raise IndexError('voxel index outside the over-segmentation %r' % (seg.shape,))
+    if n and (inds.min() < 0 or inds.max() >= nvox):
+        raise IndexError('voxel index outside the over-segmentation %r' % (shape,))
     if len(np.unique(inds)) != n:
         raise ValueError('superpix_scoring: duplicate voxel indices (the reference keeps an arbitrary one of their scores)')
-    table = sess.empty((int(seg.shape[2]), int(n_labels)), torch.float64)
-    d_lab = sess.to_device(seg.astype(np.int32), torch.int32)
+    table = sess.empty((shape[2], int(n_labels)), torch.float64)
+    if on_device:
+        d_lab = seg if seg.dtype == torch.int32 and seg.is_contiguous() else seg.to(torch.int32).contiguous()
+    else:
+        d_lab = sess.to_device(seg.astype(np.int32), torch.int32)
     d_inds = sess.to_device(inds, torch.int64)
-    dims = (C.c_int64 * 3)(*[int(v) for v in seg.shape])
+    dims = (C.c_int64 * 3)(*shape)
     check(sess.lib.alq_segment_min(sess.ctx, C.c_void_p(d_lab.data_ptr()), dims, int(n_labels), C.c_void_p(d_inds.data_ptr()) if n else None,
                                    C.c_void_p(scores.data_ptr()) if n else None, n, C.c_void_p(table.data_ptr())))
     return table
@@ -642,15 +653,21 @@ def superpix_scoring(overseg_img, inds, scores):
     over-segmentation, unique) extended to super-pixels: float64 [S, overseg_img.max() + 1], entry (z, l) = the smallest score
     among the scored voxels of super-pixel l in slice z (regionprops' min_intensity of a score image that is inf elsewhere).
     inf where a (slice, label) got no scored voxel AND where the label is absent from the slice - the reference's code gives
-    inf in both cases, whatever its docstring says; column 0 (background) stays inf.  Device: alq_segment_min."""
+    inf in both cases, whatever its docstring says; column 0 (background) stays inf.  Device: alq_segment_min.  overseg_img may
+    be an int32 device tensor (regions.oversegment(..., keep_on_device=True)): it is read where it lies."""
     from . import device
     sess = device.default_session()
-    seg = np.asarray(overseg_img)
+    if _is_device_tensor(overseg_img):
+        seg, n_labels = overseg_img, int(overseg_img.max().item()) + 1
+    else:
+        seg = np.asarray(overseg_img)
+        n_labels = int(seg.max()) + 1
     sc = sess.to_device(np.asarray(scores, dtype=np.float64).reshape(-1), sess.torch.float64)
-    return _segment_min_device(sess, seg, inds, sc, int(seg.max()) + 1).cpu().numpy()
+    return _segment_min_device(sess, seg, inds, sc, n_labels).cpu().numpy()
 
 
-def SuPix_query(expr, model, sess, padded_imgs, pool_inds, overseg_img, method_name):
+def SuPix_query(expr, model, sess, padded_imgs, pool_inds, overseg_img, method_name, n_segments=100, compactness=0.1, T=10, min_size=0,
+                mask=None):
     """PW_NNAL.SuPix_query (PW_NNAL.py:883-941), `entropy`: the k super-pixels (slice, label) whose most uncertain scored
     voxel is the most uncertain.  Posteriors of the pool voxels as in batch_eval (kept on the device), keys |p - .5|
     (alq_score_entropy), their minimum per (slice, label) (alq_segment_min), and the k smallest finite entries of the table
@@ -658,7 +675,11 @@ def SuPix_query(expr, model, sess, padded_imgs, pool_inds, overseg_img, method_n
     PW_AL.get_SuPix_inds(overseg_img, qSuPix)).  Fewer than k scored super-pixels: ValueError (the reference's argsort would
     hand out unscored ones).  The reference's signature (expr, run, model, pool_lines, train_inds, overseg_img, method_name,
     sess) belongs to its per-run index-file API; here the pool is given as voxel indices, like CNN_query's.  `random` is not
-    defined by the reference (its `qSuPix` is never assigned there)."""
+    defined by the reference (its `qSuPix` is never assigned there).
+    overseg_img: a host array (uploaded for the table, as ever), an int32 device tensor [H, W, S], or None: then the un-padded
+    box of padded_imgs (every modality, padded by the patch radii) is over-segmented on the device - regions.oversegment with
+    n_segments, compactness, T, min_size, mask (bool over the un-padded box) - and the table is built from labels that never left
+    it; they are copied to the host once, at the end, for get_SuPix_inds."""
     import ctypes as C
     from . import PW_AL
     from ._lib import check
@@ -667,7 +688,19 @@ def SuPix_query(expr, model, sess, padded_imgs, pool_inds, overseg_img, method_n
                                   % (method_name,))
     torch = sess.torch
     k = int(expr.pars['k'])
-    seg = np.asarray(overseg_img)
+    if overseg_img is None:
+        from . import regions
+        r = patch_utils.patch_radii(expr.pars['patch_shape'])
+        box = [np.asarray(v)[r[0]:np.asarray(v).shape[0] - r[0], r[1]:np.asarray(v).shape[1] - r[1], r[2]:np.asarray(v).shape[2] - r[2]]
+               for v in padded_imgs]
+        seg, counts = regions.oversegment(box, n_segments=n_segments, compactness=compactness, T=T, min_size=min_size, mask=mask, sess=sess,
+                                          keep_on_device=True, with_counts=True)
+        n_labels = int(counts.max().item()) + 1
+    elif _is_device_tensor(overseg_img):
+        seg, n_labels = overseg_img, int(overseg_img.max().item()) + 1
+    else:
+        seg = np.asarray(overseg_img)
+        n_labels = int(seg.max()) + 1
     pool_inds = np.asarray(pool_inds, dtype=np.int64)
     vols = patch_utils.DeviceVolumes(sess, padded_imgs)
     p1 = PW_NN.posteriors_device(model, sess, padded_imgs, pool_inds, expr.pars['patch_shape'], expr.pars['ntb'], expr.pars['stats'],
@@ -677,14 +710,13 @@ def SuPix_query(expr, model, sess, padded_imgs, pool_inds, overseg_img, method_n
     keys = sess.empty((n,), torch.float64)
     if n:
         check(sess.lib.alq_score_entropy(sess.ctx, C.c_void_p(p1.data_ptr()), n, C.c_void_p(keys.data_ptr()), None))
-    n_labels = int(seg.max()) + 1
     table = _segment_min_device(sess, seg, pool_inds, keys, n_labels)
     nscored = int(torch.isfinite(table).sum().item())
     if nscored < k:
         raise ValueError('SuPix_query: %d super-pixels hold a scored voxel, k = %d' % (nscored, k))
     order = sess.topk_smallest(table.reshape(-1), k).cpu().numpy()
     qSuPix = np.array([order // n_labels, order % n_labels], dtype=np.int64)
-    return qSuPix, PW_AL.get_SuPix_inds(seg, qSuPix)
+    return qSuPix, PW_AL.get_SuPix_inds(seg.cpu().numpy() if _is_device_tensor(seg) else seg, qSuPix)
 
 
 def draw_queries(qdist, prior, k, replacement=False):

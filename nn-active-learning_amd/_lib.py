@@ -194,7 +194,11 @@ _SIGNATURES = {
     'alq_tile_blend': (C.c_int, [_P, _P, C.c_int, C.POINTER(TileLattice), C.c_int64, C.c_int64, _P, _P, _P, _P]),
     'alq_tile_blend_trip_voxels': (C.c_int64, []),
     'alq_tile_finalize': (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int32), C.c_int, _P, _P]),
-    'alq_comm_unique_id': (C.c_int, [_P]),
+    'alq_slic_work_bytes': (C.c_size_t, [C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int]),
+    'alq_slic_geometry': (C.c_int, [_P, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    'alq_slic': (C.c_int, [_P, _P, _P, C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_int,
+                           C.c_double, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    'alq_comm_unique_id':(C.c_int, [_P]),
     'alq_comm_init': (C.c_int, [_P, _P, C.c_int, C.c_int]),
     'alq_comm_destroy': (C.c_int, [_P]),
     'alq_allreduce_sum': (C.c_int, [_P, _P, C.c_int64]),

@@ -10,7 +10,7 @@ BUILD="$HERE/build${ALQ_BUILD_TAG:-}"
 mkdir -p "$BUILD"
 HAZARD_FILES="c3d d3d f3d t3d t3d8b e3d"
 pids=()
-for f in igemm igemm2 igemm3 igemm4 c3d t3d t3d8b e3d d3d f3d fcgemm direct kernels topk model passes grads ctx weights comm train gnorm lsum committee evalcounts confusion sim ref64 wpack hvp dfisher loss llfc aopt region ccl dcrf dense mteach volbatch sliceq edt tile; do
+for f in igemm igemm2 igemm3 igemm4 c3d t3d t3d8b e3d d3d f3d fcgemm direct kernels topk model passes grads ctx weights comm train gnorm lsum committee evalcounts confusion sim ref64 wpack hvp dfisher loss llfc aopt region ccl dcrf dense mteach volbatch sliceq edt tile slic; do
   # igemm4: no SLP vectorisation (a performance choice) - it turns neighbouring scalar f32 multiplies / adds of the staging and epilogue code into
   # v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32, which issue slower than the scalar pairs next to another wave's MFMAs on
   # the same SIMD (same-box A/B: 155.4 k -> 156.6 k patches/s); conversions still pack (v_cvt_pk_f16_f32 / _bf16_f32)
@@ -32,6 +32,8 @@ for f in igemm igemm2 igemm3 igemm4 c3d t3d t3d8b e3d d3d f3d fcgemm direct kern
   if [ "$f" = edt ]; then X="-ffp-contract=off"; fi
   # tile: the same - a blended voxel is acc + w * p with the window product, the product and the sum rounded one by one (tiled.py)
   if [ "$f" = tile ]; then X="-ffp-contract=off"; fi
+  # slic: the same - a pixel's distance to a centre is a sum of squares with every product and sum rounded one by one (slic.py)
+  if [ "$f" = slic ]; then X="-ffp-contract=off"; fi
   if [ "$f" = d3d ] || [ "$f" = f3d ]; then X="-fno-slp-vectorize ${ALQ_D3_FLAGS:-}"; fi      # (d3d: like c3d; same-box 523 -> 490 / 710 -> 675 us)
   # the sweep kernels leave their device assembly behind for the store-hazard gate below
   case " $HAZARD_FILES " in *" $f "*) X="$X --save-temps=obj";; esac
@@ -66,5 +68,5 @@ for f in $HAZARD_FILES; do
 done
 python3 "$ROOT/tools/isa_store_hazard.py" --min 2 "${HZ[@]}" > "$BUILD/store_hazard_report.txt" || { cat "$BUILD/store_hazard_report.txt" >&2; echo "build.sh: store-hazard gate failed" >&2; exit 1; }
 for f in $HAZARD_FILES; do rm -f "$BUILD"/$f-hip-*.bc "$BUILD"/$f-hip-*.hipi "$BUILD"/$f-hip-*.s "$BUILD"/$f-hip-*.o "$BUILD"/$f-hip-*.out "$BUILD"/$f-hip-*.hipfb "$BUILD"/$f-host-*.bc "$BUILD"/$f-host-*.hipi "$BUILD"/$f-host-*.s; done
-hipcc -shared -fPIC --offload-arch=gfx950 -o "$OUT" "$BUILD"/{igemm,igemm2,igemm3,igemm4,c3d,t3d,t3d8b,e3d,d3d,f3d,fcgemm,direct,kernels,topk,model,passes,grads,ctx,weights,comm,train,gnorm,lsum,committee,evalcounts,confusion,sim,ref64,wpack,hvp,dfisher,loss,llfc,aopt,region,ccl,dcrf,dense,mteach,volbatch,sliceq,edt,tile}.o -ldl
+hipcc -shared -fPIC --offload-arch=gfx950 -o "$OUT" "$BUILD"/{igemm,igemm2,igemm3,igemm4,c3d,t3d,t3d8b,e3d,d3d,f3d,fcgemm,direct,kernels,topk,model,passes,grads,ctx,weights,comm,train,gnorm,lsum,committee,evalcounts,confusion,sim,ref64,wpack,hvp,dfisher,loss,llfc,aopt,region,ccl,dcrf,dense,mteach,volbatch,sliceq,edt,tile,slic}.o -ldl
 echo "built $OUT"

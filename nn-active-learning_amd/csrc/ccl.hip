@@ -31,6 +31,7 @@
 #include <algorithm>
 
 #include "alq_internal.h"
+#include "unionfind.h"
 
 namespace alq {
 
@@ -50,47 +51,6 @@ struct CcGeo {
 };
 
 __device__ inline bool cc_sel(const unsigned char *seg, int v, int sel_zero) { return (seg[v] != 0) != (sel_zero != 0); }
-
-__device__ inline int cc_load(int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// the root of x while other workgroups hook trees (merge launch): every word through an agent-scope atomic load
-__device__ inline int cc_find_live(int *parent, int x) {
-    int p = cc_load(parent + x);
-    while (p != x) {
-        x = p;
-        p = cc_load(parent + x);
-    }
-    return x;
-}
-
-// the root of x in a forest nobody hooks any more (after the merge launch)
-__device__ inline int cc_find(const int *parent, int x) {
-    int p = parent[x];
-    while (p != x) {
-        x = p;
-        p = parent[x];
-    }
-    return x;
-}
-
-// -> a root-ward member of the united set (the next union of the same voxel starts there)
-__device__ inline int cc_unite(int *parent, int a, int b) {
-    for (;;) {
-        a = cc_find_live(parent, a);
-        b = cc_find_live(parent, b);
-        if (a == b) return a;
-        if (a > b) {
-            const int t = a;
-            a = b;
-            b = t;
-        }
-        // b is (was) a root above a: hook it.  old != b: someone hooked b under `old` first - the minimum now stands in
-        // parent[b], and the set of the other value still has to meet it: carry on with (a, old)
-        const int old = atomicMin(parent + b, a);
-        if (old == b) return a;
-        b = old;
-    }
-}
 
 // ballots of one wave step: which lanes are selected, which start a row (z == 0)
 struct CcRuns {

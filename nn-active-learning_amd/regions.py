@@ -3,7 +3,9 @@ patch_utils.get_vars_2d (patch_utils.py:794-826) and the per-(slice, label) scor
 (PW_NNAL.py:944-1021).  Host code: the reference of the kernel tests and of the tool, and the documentation of the formulas
 (include/alq.h).  No scipy in the first two: the box sums are integer prefix sums, which is what scipy's float64 convolution of
 the uint64 image equals wherever it is exact (check_variance_input).  The component functions at the end (cc_label_host,
-keep_largest_host, fill_holes_host) state alq_cc_label / alq_cc_keep_largest / alq_fill_holes through scipy.ndimage."""
+keep_largest_host, fill_holes_host) state alq_cc_label / alq_cc_keep_largest / alq_fill_holes through scipy.ndimage.  The
+SLIC over-segmentation has a module of its own for its statement (slic.py); oversegment / slic_device at the end of this one are
+its entry point and its device driver (alq_slic)."""
 import numpy as np
 
 MAX_D = 65
@@ -146,3 +148,92 @@ def fill_holes_host(seg, with_info=False):
         return out
     n = ndimage.label(filled)[1]                                   # default structure: face neighbours
     return out, np.array([n, int(filled.sum()), 0, 0], dtype=np.int64)
+
+
+# ---- SLIC over-segmentation: slic.py states it, csrc/slic.hip runs it -------------------------------------------------------
+def slic_device(sess, vol, gh, gw, w, T=10, min_size=0, mask=None, lo=None, scale=None, hwz=True, work=None):
+    """alq_slic on a packed subject: `vol` float32 device tensor [Z, H, W, m] (alq_vol_pack), `mask` uint8 device tensor
+    [Z, H, W] (255 = out) or None, lo / scale [m] host values.  -> (labels int32 device tensor, [H, W, S] with hwz else
+    [S, H, W]; n_per_slice int32 device tensor [S]).  Stream-ordered: nothing is read back."""
+    import ctypes as C
+    from ._lib import check
+    torch = sess.torch
+    Z, H, W, m = (int(v) for v in vol.shape)
+    dims = (C.c_int64 * 3)(H, W, Z)
+    lo = np.asarray(lo, dtype=np.float64).reshape(-1)
+    scale = np.asarray(scale, dtype=np.float64).reshape(-1)
+    if len(lo) != m or len(scale) != m:
+        raise ValueError('slic: %d / %d quantisation values for %d channels' % (len(lo), len(scale), m))
+    sess.bind_stream()
+    labels = sess.empty((H, W, Z) if hwz else (Z, H, W), torch.int32)
+    counts = sess.empty((Z,), torch.int32)
+    if work is None:
+        nbytes = int(sess.lib.alq_slic_work_bytes(dims, m, int(gh), int(gw)))
+        work = sess.empty((max(nbytes, 8) // 8,), torch.int64)
+    check(sess.lib.alq_slic(sess.ctx, C.c_void_p(vol.data_ptr()), C.c_void_p(mask.data_ptr()) if mask is not None else None, dims, m,
+                            (C.c_double * m)(*lo), (C.c_double * m)(*scale), int(gh), int(gw), float(w), int(T), int(min_size),
+                            1 if hwz else 0, C.c_void_p(labels.data_ptr()), C.c_void_p(counts.data_ptr()), C.c_void_p(work.data_ptr())))
+    return labels, counts
+
+
+def _device_quant_range(sess, vol, mask):
+    """slic.quant_range on a packed device subject (the minimum and maximum are float32 values: the same doubles)."""
+    torch = sess.torch
+    lo, scale = [], []
+    for c in range(int(vol.shape[3])):
+        a = vol[..., c]
+        ok = torch.isfinite(a) if mask is None else (torch.isfinite(a) & (mask != 255))
+        vals = a[ok]
+        if int(vals.numel()) == 0:
+            lo.append(0.0)
+            scale.append(0.0)
+            continue
+        mn, mx = float(vals.min().item()), float(vals.max().item())
+        lo.append(mn)
+        scale.append(65535 / (mx - mn) if mx > mn else 0.0)
+    return np.array(lo), np.array(scale)
+
+
+def oversegment(vols_or_array, n_segments=100, compactness=0.1, T=10, min_size=0, mask=None, sess=None, keep_on_device=False,
+                with_counts=False):
+    """The SLIC over-segmentation of a subject (slic.py: skimage-LIKE arguments, not skimage's algorithm): int32 labels
+    [H, W, S], 0 on out pixels and 1 .. n_z per slice; with_counts: (labels, n_per_slice int32 [S]).
+    vols_or_array: a datasets.utils.ResidentSubject (already on the device), one volume [H, W, S], an array [m, H, W, S] or a
+    list of m volumes; mask: bool [H, W, S], True = in.  gh, gw = slic.grid_for(H, W, n_segments), w =
+    slic.spatial_weight(compactness, H, W, gh, gw), the quantisation range = the subject's finite in-mask minimum and maximum per
+    channel.  Without a session this is slic.slic_host; with one the subject is packed (if it is not resident) and alq_slic runs
+    it.  keep_on_device=True (needs a session): device tensors, nothing is copied back."""
+    from . import slic
+    resident = hasattr(vols_or_array, 'vol') and hasattr(vols_or_array, 'shape')
+    if sess is None and resident:
+        sess = vols_or_array.sess
+    if sess is None:
+        if keep_on_device:
+            raise ValueError('oversegment: keep_on_device needs a session')
+        mods = slic.as_modalities(vols_or_array)
+        H, W, _ = mods[0].shape
+        gh, gw = slic.grid_for(H, W, n_segments)
+        out = slic.slic_host(mods, gh, gw, slic.spatial_weight(compactness, H, W, gh, gw), T, min_size, mask)
+        return out if with_counts else out[0]
+    torch = sess.torch
+    if resident:
+        vol = vols_or_array.vol
+    else:
+        from .datasets.utils import ResidentSubject
+        vol = ResidentSubject.pack(sess, slic.as_modalities(vols_or_array)).vol
+    Z, H, W, _ = (int(v) for v in vol.shape)
+    d_mask = None
+    if mask is not None:
+        if hasattr(mask, 'data_ptr'):
+            inm = mask.to(torch.bool)
+        else:
+            inm = torch.as_tensor(np.ascontiguousarray(np.asarray(mask, dtype=bool))).to(sess.device)
+        if tuple(int(v) for v in inm.shape) != (H, W, Z):
+            raise ValueError('oversegment: mask shape %r, subject %r' % (tuple(inm.shape), (H, W, Z)))
+        d_mask = torch.where(inm, 0, 255).to(torch.uint8).permute(2, 0, 1).contiguous()
+    gh, gw = slic.grid_for(H, W, n_segments)
+    lo, scale = _device_quant_range(sess, vol, d_mask)
+    labels, counts = slic_device(sess, vol, gh, gw, slic.spatial_weight(compactness, H, W, gh, gw), T, min_size, d_mask, lo, scale)
+    if not keep_on_device:
+        labels, counts = labels.cpu().numpy(), counts.cpu().numpy()
+    return (labels, counts) if with_counts else labels
