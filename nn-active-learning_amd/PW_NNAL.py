@@ -16,18 +16,14 @@ def device_uncertainty_filter(sess, posts, B, with_keys=False):
     """Same selection on the device (alq_score_entropy + alq_topk_uncertain) for posteriors that
     are already resident: `posts` float32 device tensor [n] -> int64 device tensor [B]
     (with_keys: also their keys |p - .5| as a float64 device tensor [B], ascending)."""
-    import ctypes as C
-    from ._lib import check
+    from ._lib import check, ptr
     torch = sess.torch
     sess.bind_stream()
     n = int(posts.numel())
     B = min(int(B), n)
     keys = sess.empty((n,), torch.float64)
-    check(sess.lib.alq_score_entropy(sess.ctx, C.c_void_p(posts.data_ptr()), n, C.c_void_p(keys.data_ptr()), None))
-    work = sess.empty((sess.lib.alq_topk_work_bytes(n),), torch.uint8)
-    out = sess.empty((B,), torch.int64)
-    check(sess.lib.alq_topk_uncertain(sess.ctx, C.c_void_p(keys.data_ptr()), n, B, C.c_void_p(out.data_ptr()),
-                                      C.c_void_p(work.data_ptr())))
+    check(sess.lib.alq_score_entropy(sess.ctx, ptr(posts), n, ptr(keys), None))
+    out = sess.topk_smallest(keys, B)
     if with_keys:
         return out, keys.index_select(0, out)
     return out
@@ -278,20 +274,17 @@ def _features_device(expr, model, sess, padded_mods, inds, stats):
 
 
 def _row_norms(sess, F):
-    import ctypes as C
-    from ._lib import check
+    from ._lib import check, ptr
     nrm = sess.empty((int(F.shape[0]),), sess.torch.float64)
-    check(sess.lib.alq_row_norms(sess.ctx, C.c_void_p(F.data_ptr()), int(F.shape[0]), int(F.shape[1]), C.c_void_p(nrm.data_ptr())))
+    check(sess.lib.alq_row_norms(sess.ctx, ptr(F), int(F.shape[0]), int(F.shape[1]), ptr(nrm)))
     return nrm
 
 
 def _cosine_sims(sess, A, na, Bm, nb):
     """[len(A), len(Bm)] float64 device tensor of cosine similarities (alq_cosine_sims)."""
-    import ctypes as C
-    from ._lib import check
+    from ._lib import check, ptr
     S = sess.empty((int(A.shape[0]), int(Bm.shape[0])), sess.torch.float64)
-    check(sess.lib.alq_cosine_sims(sess.ctx, C.c_void_p(A.data_ptr()), int(A.shape[0]), C.c_void_p(Bm.data_ptr()), int(Bm.shape[0]),
-                                   int(A.shape[1]), C.c_void_p(na.data_ptr()), C.c_void_p(nb.data_ptr()), C.c_void_p(S.data_ptr())))
+    check(sess.lib.alq_cosine_sims(sess.ctx, ptr(A), int(A.shape[0]), ptr(Bm), int(Bm.shape[0]), int(A.shape[1]), ptr(na), ptr(nb), ptr(S)))
     return S
 
 
@@ -306,8 +299,7 @@ def rep_entropy_query(expr, model, sess, all_padded_imgs, pool_inds):
     sum_r max_{c in Q + candidate} cos(f_r, f_c) over the remaining pool voxels r.  The similarity block is one device
     GEMM (alq_cosine_sims, fp64 accumulation like the reference's float64 NumPy), a greedy step one streaming pass that
     scores ALL candidates at once (alq_colsum_max) where the reference scores one candidate per Python iteration."""
-    import ctypes as C
-    from ._lib import check
+    from ._lib import check, ptr
     torch = sess.torch
     sess.bind_stream()
     k, B = expr.pars['k'], expr.pars['B']
@@ -329,14 +321,13 @@ def rep_entropy_query(expr, model, sess, all_padded_imgs, pool_inds):
     cmax = sess.empty((nR,), torch.float64)
     Q, taken = [], np.zeros(nB, bool)
     for it in range(min(k, nB)):
-        check(sess.lib.alq_colsum_max(sess.ctx, C.c_void_p(S.data_ptr()), nR, nB, C.c_void_p(cmax.data_ptr()) if it else None, None,
-                                      C.c_void_p(scores.data_ptr()), C.c_void_p(work.data_ptr())))
+        check(sess.lib.alq_colsum_max(sess.ctx, ptr(S), nR, nB, ptr(cmax) if it else None, None, ptr(scores), ptr(work)))
         sc = scores.cpu().numpy()
         sc[taken] = -np.inf
         j = int(np.argmax(sc))                      # first maximum among the candidates left, in their original order (:339-343)
         Q.append(j)
         taken[j] = True
-        check(sess.lib.alq_take_colmax(sess.ctx, C.c_void_p(S.data_ptr()), nR, nB, j, 0 if it else 1, C.c_void_p(cmax.data_ptr())))
+        check(sess.lib.alq_take_colmax(sess.ctx, ptr(S), nR, nB, j, 0 if it else 1, ptr(cmax)))
     local = patch_utils.global2local_inds(Q, [len(sel_inds[i]) for i in range(s)])
     return [np.array(sel_inds[i])[local[i]] for i in range(s)]
 
@@ -346,9 +337,8 @@ def core_set_query(expr, model, sess, all_padded_imgs, pool_inds, labeled_inds):
     largest similarity to the labelled set, then k times take the voxel LEAST similar to anything chosen or labelled.
     As in the reference the labelled side is the LAST subject of `labeled_inds` only (its loop variable `i` is read
     after the loop, :399-404), evaluated in batches of 1000 (NN.gen_batch_inds) with `expr.labeled_stats`."""
-    import ctypes as C
     from . import NN
-    from ._lib import check
+    from ._lib import check, ptr
     torch = sess.torch
     sess.bind_stream()
     k = expr.pars['k']
@@ -370,13 +360,13 @@ def core_set_query(expr, model, sess, all_padded_imgs, pool_inds, labeled_inds):
     for batch in NN.gen_batch_inds(nT, 1000):
         F_T = _features_device(expr, model, sess, lab_mods, np.array(labeled_inds[i])[batch], _subject_stats(expr, i, m, 'labeled_stats'))
         St = _cosine_sims(sess, F_T, _row_norms(sess, F_T), F_u, norms_u)                           # [labelled batch, pool]
-        check(sess.lib.alq_fold_rowmax(sess.ctx, C.c_void_p(St.data_ptr()), int(F_T.shape[0]), n, C.c_void_p(sims.data_ptr())))
+        check(sess.lib.alq_fold_rowmax(sess.ctx, ptr(St), int(F_T.shape[0]), n, ptr(sims)))
     Q = []
     for _ in range(min(k, n)):
         q_ind = int(np.argmin(sims.cpu().numpy()))
         Q.append(q_ind)
         Sq = _cosine_sims(sess, F_u[q_ind:q_ind + 1], norms_u[q_ind:q_ind + 1], F_u, norms_u)      # [1, pool]
-        check(sess.lib.alq_fold_rowmax(sess.ctx, C.c_void_p(Sq.data_ptr()), 1, n, C.c_void_p(sims.data_ptr())))
+        check(sess.lib.alq_fold_rowmax(sess.ctx, ptr(Sq), 1, n, ptr(sims)))
         sims[q_ind] = np.inf
     return patch_utils.global2local_inds(Q, sizes)
 
@@ -619,7 +609,7 @@ def _segment_min_device(sess, overseg_img, inds, scores, n_labels):
     int32 device tensor as regions.oversegment(..., keep_on_device=True) leaves it, read where it lies), the scored voxels
     `inds` (host) and their `scores` (float64 device tensor)."""
     import ctypes as C
-    from ._lib import check
+    from ._lib import check, ptr
     torch = sess.torch
     sess.bind_stream()
     on_device = _is_device_tensor(overseg_img)
@@ -643,8 +633,8 @@ def _segment_min_device(sess, overseg_img, inds, scores, n_labels):
         d_lab = sess.to_device(seg.astype(np.int32), torch.int32)
     d_inds = sess.to_device(inds, torch.int64)
     dims = (C.c_int64 * 3)(*shape)
-    check(sess.lib.alq_segment_min(sess.ctx, C.c_void_p(d_lab.data_ptr()), dims, int(n_labels), C.c_void_p(d_inds.data_ptr()) if n else None,
-                                   C.c_void_p(scores.data_ptr()) if n else None, n, C.c_void_p(table.data_ptr())))
+    check(sess.lib.alq_segment_min(sess.ctx, ptr(d_lab), dims, int(n_labels), ptr(d_inds) if n else None,
+                                   ptr(scores) if n else None, n, ptr(table)))
     return table
 
 
@@ -680,9 +670,8 @@ def SuPix_query(expr, model, sess, padded_imgs, pool_inds, overseg_img, method_n
     box of padded_imgs (every modality, padded by the patch radii) is over-segmented on the device - regions.oversegment with
     n_segments, compactness, T, min_size, mask (bool over the un-padded box) - and the table is built from labels that never left
     it; they are copied to the host once, at the end, for get_SuPix_inds."""
-    import ctypes as C
     from . import PW_AL
-    from ._lib import check
+    from ._lib import check, ptr
     if method_name != 'entropy':
         raise NotImplementedError("SuPix_query method %r: only 'entropy' is defined (the reference leaves qSuPix unset for 'random')"
                                   % (method_name,))
@@ -709,7 +698,7 @@ def SuPix_query(expr, model, sess, padded_imgs, pool_inds, overseg_img, method_n
     sess.bind_stream()
     keys = sess.empty((n,), torch.float64)
     if n:
-        check(sess.lib.alq_score_entropy(sess.ctx, C.c_void_p(p1.data_ptr()), n, C.c_void_p(keys.data_ptr()), None))
+        check(sess.lib.alq_score_entropy(sess.ctx, ptr(p1), n, ptr(keys), None))
     table = _segment_min_device(sess, seg, pool_inds, keys, n_labels)
     nscored = int(torch.isfinite(table).sum().item())
     if nscored < k:

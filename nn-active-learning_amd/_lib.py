@@ -262,3 +262,19 @@ def exported_names():
 def check(rc):
     if rc != 0:
         raise AlqError('libalq error %d: %s' % (rc, lib().alq_last_error().decode()))
+
+
+def ptr(t, byte_offset=0):
+    """The address of a tensor's memory, `byte_offset` bytes in, as the C ABI takes it; None (an argument left out) stays None."""
+    return None if t is None else C.c_void_p(t.data_ptr() + byte_offset)
+
+
+def check_tensor(t, dtype, numel=None, device=None, optional=False):
+    """What every entry point asks of a tensor it hands to the library: `dtype` (or one of a tuple of them), contiguous, on
+    `device` and of `numel` elements where those are given.  AssertionError otherwise; None passes only with `optional`."""
+    ok = optional if t is None else (
+        (t.dtype in dtype if isinstance(dtype, tuple) else t.dtype == dtype) and t.is_contiguous() and
+        (device is None or t.device == device) and (numel is None or int(t.numel()) == int(numel)))
+    if not ok:
+        raise AssertionError('expected a contiguous %s tensor (elements: %s, device: %s), got %s' % (
+            dtype, numel, device, t if t is None else (t.dtype, tuple(t.shape), t.stride(), t.device)))

@@ -192,10 +192,9 @@ def main():
     seed 15, per round entropy filter to B = 4096 -> Fisher -> SDP -> k = 100 draws -> fine-tune (SGD 1e-4, one epoch of
     batches of 50 over everything labelled so far; labels = sign of the patch's first 512 voxels' sum) -> weights saved.
     Under torch.distributed.run (WORLD_SIZE > 1) the pool is sharded over the ranks."""
-    import ctypes as C
     import sys
     from . import device, PW_AL
-    from ._lib import check
+    from ._lib import check, ptr
     from . import netspec
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 200000
     rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 5
@@ -223,7 +222,7 @@ def main():
     model.get_optimizer(1e-4, [], 'SGD')
     a, b = pool_shard.shard_bounds(n, ws, rank)
     pool = sess.empty((b - a, 32 ** 3), sess.torch.float32)
-    check(sess.lib.alq_synth_patches(sess.ctx, 1005, a, b - a, 32 ** 3, C.c_void_p(pool.data_ptr())))
+    check(sess.lib.alq_synth_patches(sess.ctx, 1005, a, b - a, 32 ** 3, ptr(pool)))
     lab_local = (pool[:, :512].sum(dim=1) > 0).cpu().numpy().astype(np.float64)
     labels = pool_shard.allgather_rows(n, np.arange(a, b), lab_local, sess).astype(np.int64)
     if ws > 1 and backend == 'nccl':

@@ -126,7 +126,7 @@ class ResidentSubject(object):
     def pack(cls, sess, imgs, mask_ids=None):
         """imgs: m host arrays [H, W, Z] of one shape (uploaded in their own dtype where the kernel reads it: float32, float64,
         int16, uint8; anything else as float64, which holds it exactly); mask_ids: uint8 [H, W, Z] class ids or None."""
-        from .._lib import check
+        from .._lib import check, ptr
         torch = sess.torch
         imgs = [np.asarray(a) for a in imgs]
         shape = imgs[0].shape
@@ -141,7 +141,7 @@ class ResidentSubject(object):
         vol = sess.empty((Z, H, W, len(imgs)), torch.float32)
         sess.bind_stream()
         check(sess.lib.alq_vol_pack(sess.ctx, (C.c_void_p * len(src))(*[t.data_ptr() for t in src]), len(src), _SRC_TYPES[dt], dims,
-                                    C.c_void_p(vol.data_ptr())))
+                                    ptr(vol)))
         mask = None
         if mask_ids is not None:
             mask_ids = np.asarray(mask_ids)
@@ -149,7 +149,7 @@ class ResidentSubject(object):
                 raise ValueError('class ids are uint8 %r, got %s %r' % (shape, mask_ids.dtype, mask_ids.shape))
             msrc = torch.as_tensor(np.ascontiguousarray(mask_ids)).to(sess.device)
             mask = sess.empty((Z, H, W), torch.uint8)
-            check(sess.lib.alq_mask_pack(sess.ctx, C.c_void_p(msrc.data_ptr()), dims, C.c_void_p(mask.data_ptr())))
+            check(sess.lib.alq_mask_pack(sess.ctx, ptr(msrc), dims, ptr(mask)))
         sess.synchronize()          # the unpacked copies go out of scope here
         return cls(sess, vol, mask)
 
@@ -234,7 +234,7 @@ def slice_batch(sess, subjects, desc, crop, nclass, out=None):
     """alq_slice_batch: `subjects` ResidentSubject list, desc int [b][5] = (subject, zc, h0, w0, labelled), crop (z, h, w).
     Returns (X float32 [b, z, h, w, m], labels int32 [b, z, h, w], counts int64 [C + 1] on the DEVICE); a bad window is a
     ValueError before anything is launched."""
-    from .._lib import ALQ_EINVAL, lib
+    from .._lib import ALQ_EINVAL, check, lib, ptr
     torch = sess.torch
     desc = np.ascontiguousarray(desc, dtype=np.int32).reshape(-1, 5)
     crop = np.ascontiguousarray(crop, dtype=np.int32).reshape(3)
@@ -251,13 +251,10 @@ def slice_batch(sess, subjects, desc, crop, nclass, out=None):
     masks = (C.c_void_p * len(subjects))(*[s.mask.data_ptr() if s.mask is not None else None for s in subjects])
     sess.bind_stream()
     rc = lib().alq_slice_batch(sess.ctx, vols, masks, dims.ctypes.data_as(C_i32), len(subjects), m, desc.ctypes.data_as(C_i32), b,
-                               crop.ctypes.data_as(C_i32), int(nclass), C.c_void_p(X.data_ptr()), C.c_void_p(lab.data_ptr()),
-                               C.c_void_p(counts.data_ptr()))
+                               crop.ctypes.data_as(C_i32), int(nclass), ptr(X), ptr(lab), ptr(counts))
     if rc == ALQ_EINVAL:
         raise ValueError(lib().alq_last_error().decode())
-    if rc != 0:
-        from .._lib import check
-        check(rc)
+    check(rc)
     return X, lab, counts
 
 

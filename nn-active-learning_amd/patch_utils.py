@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import device, regions
-from ._lib import check
+from ._lib import check, ptr
 
 
 def patch_radii(patch_shape):
@@ -50,11 +50,11 @@ class DeviceVolumes(object):
             self._var_checked.add((modality, d))
         pd = (C.c_int64 * 3)(*self.pad_dims)
         rd = (C.c_int32 * 3)(*r)
-        vol = C.c_void_p(self.tensors[modality].data_ptr())
+        vol = ptr(self.tensors[modality])
         sess.bind_stream()
         if inds is None:
             out = sess.empty(tuple(box), torch.float64)
-            check(sess.lib.alq_local_var2d(sess.ctx, vol, 1 if self.is_f64 else 0, pd, rd, d, None, 0, C.c_void_p(out.data_ptr())))
+            check(sess.lib.alq_local_var2d(sess.ctx, vol, 1 if self.is_f64 else 0, pd, rd, d, None, 0, ptr(out)))
             return out
         inds = np.ascontiguousarray(np.asarray(inds, dtype=np.int64)).reshape(-1)
         n = int(inds.shape[0])
@@ -64,8 +64,7 @@ class DeviceVolumes(object):
         if inds.min() < 0 or inds.max() >= box[0] * box[1] * box[2]:
             raise IndexError('voxel index outside the un-padded volume %r' % (box,))
         d_inds = sess.to_device(inds, torch.int64)
-        check(sess.lib.alq_local_var2d(sess.ctx, vol, 1 if self.is_f64 else 0, pd, rd, d, C.c_void_p(d_inds.data_ptr()), n,
-                                       C.c_void_p(out.data_ptr())))
+        check(sess.lib.alq_local_var2d(sess.ctx, vol, 1 if self.is_f64 else 0, pd, rd, d, ptr(d_inds), n, ptr(out)))
         return out
 
     def gather(self, inds, patch_shape, stats=None, quirk=2, out_f64=False):
@@ -91,8 +90,7 @@ class DeviceVolumes(object):
             flat = np.asarray(stats, dtype=np.float64).reshape(-1)[:2 * self.m]
             st = (C.c_double * (2 * self.m))(*flat)
         check(sess.lib.alq_gather_normalize(sess.ctx, ptrs, self.m, 1 if self.is_f64 else 0, pd,
-                                            C.c_void_p(d_inds.data_ptr()), n, ps, st, quirk,
-                                            1 if out_f64 else 0, C.c_void_p(out.data_ptr())))
+                                            ptr(d_inds), n, ps, st, quirk, 1 if out_f64 else 0, ptr(out)))
         return out
 
 

@@ -18,7 +18,7 @@ import itertools
 
 import numpy as np
 
-from ._lib import check
+from ._lib import check, ptr
 from .device import ALQ_CONV, ALQ_CONVT, ALQ_FC, ALQ_POOL
 
 
@@ -117,11 +117,8 @@ class Ref64(object):
                 ck = self.sess.empty((n, cand_cap), torch.float64)
                 cc = self.sess.empty((n,), torch.int32)
             check(self.lib.alq_ref64_scores(
-                self.sess.ctx, self._arr, self._nl, self._cd, self._pW, self._pb, C.c_void_p(pool.data_ptr()), C.c_void_p(r.data_ptr()), n,
-                C.c_void_p(fl.data_ptr()) if fl is not None else None, F, float(eps), int(cand_cap),
-                C.c_void_p(lg.data_ptr()), C.c_void_p(S.data_ptr()), C.c_void_p(rms.data_ptr()),
-                C.c_void_p(cd.data_ptr()) if cd is not None else None, C.c_void_p(ck.data_ptr()) if ck is not None else None,
-                C.c_void_p(cc.data_ptr()) if cc is not None else None))
+                self.sess.ctx, self._arr, self._nl, self._cd, self._pW, self._pb, ptr(pool), ptr(r), n,
+                ptr(fl), F, float(eps), int(cand_cap), ptr(lg), ptr(S), ptr(rms), ptr(cd), ptr(ck), ptr(cc)))
             out['logits'][a:b] = lg.cpu().numpy()
             out['S'][a:b] = S.cpu().numpy()
             out['rms'][:, a:b] = rms.cpu().numpy()

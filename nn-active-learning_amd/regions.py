@@ -156,7 +156,7 @@ def slic_device(sess, vol, gh, gw, w, T=10, min_size=0, mask=None, lo=None, scal
     [Z, H, W] (255 = out) or None, lo / scale [m] host values.  -> (labels int32 device tensor, [H, W, S] with hwz else
     [S, H, W]; n_per_slice int32 device tensor [S]).  Stream-ordered: nothing is read back."""
     import ctypes as C
-    from ._lib import check
+    from ._lib import check, ptr
     torch = sess.torch
     Z, H, W, m = (int(v) for v in vol.shape)
     dims = (C.c_int64 * 3)(H, W, Z)
@@ -170,9 +170,9 @@ def slic_device(sess, vol, gh, gw, w, T=10, min_size=0, mask=None, lo=None, scal
     if work is None:
         nbytes = int(sess.lib.alq_slic_work_bytes(dims, m, int(gh), int(gw)))
         work = sess.empty((max(nbytes, 8) // 8,), torch.int64)
-    check(sess.lib.alq_slic(sess.ctx, C.c_void_p(vol.data_ptr()), C.c_void_p(mask.data_ptr()) if mask is not None else None, dims, m,
+    check(sess.lib.alq_slic(sess.ctx, ptr(vol), ptr(mask), dims, m,
                             (C.c_double * m)(*lo), (C.c_double * m)(*scale), int(gh), int(gw), float(w), int(T), int(min_size),
-                            1 if hwz else 0, C.c_void_p(labels.data_ptr()), C.c_void_p(counts.data_ptr()), C.c_void_p(work.data_ptr())))
+                            1 if hwz else 0, ptr(labels), ptr(counts), ptr(work)))
     return labels, counts
 
 
