@@ -50,7 +50,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import alpath, netspec  # noqa: E402
 from oracle.model import OracleModel  # noqa: E402
-from tests import convt_ref, factored_ref  # noqa: E402
+from tests import convt_ref, factored_ref, hvp_cases  # noqa: E402
 from tests.convt_ref import GEOMETRIES, geometry  # noqa: E402
 from tests.test_gpu_grads_fp64 import smallest_key  # noqa: E402
 from tests.test_gpu_hvp import EPS, bars, fragile_units, oracle_hv  # noqa: E402
@@ -447,7 +447,7 @@ def whole_record(name, ld, sk, in_shape, seed, refused):
     v = [rs.randn(*np.asarray(a).shape).astype(np.float32) for nme in names for a in pars[nme]]
     g64 = [[[np.asarray(a, np.float64) for a in om64.grad_log_post(j, x[[i]])] for j in (0, 1)] for i in range(N)]
     g32 = [[[np.asarray(a) for a in om32.grad_log_post(j, x[[i]])] for j in (0, 1)] for i in range(N)]
-    return dict(refused=refused, name=name, ld=ld, sk=sk, in_shape=in_shape, n=N, pars=pars, x=x, labels=labels, v=v, names=names, om64=om64, om32=om32,
+    return dict(refused=refused, name=name, seed=seed, ld=ld, sk=sk, in_shape=in_shape, n=N, pars=pars, x=x, labels=labels, v=v, names=names, om64=om64, om32=om32,
                 g64=g64, g32=g32, p64=om64.forward(x)['posteriors'].astype(np.float64), arrays=[nme + s for nme in names for s in ('/W', '/b')])
 
 
@@ -511,7 +511,8 @@ def _sq(arrs):
 @pytest.mark.parametrize('name', list(WHOLE))
 def test_whole_model_other_entry_points_vs_fp64(sess, name):
     """alq_grad_sqnorms, alq_class_layer_sums, alq_diag_fisher and alq_hess_vecp under the bars tests/test_gpu_grads_fp64.py holds
-    NET-C to: 1e-4 r + 1e-12 row total; per layer 2 e(rows) + 6e-8 mean |entry|; 2e-3 ref + 1e-6 max ref; test_gpu_hvp.bars."""
+    NET-C to: 1e-4 r + 1e-12 row total; per layer 2 e(rows) + 6e-8 mean |entry|; 2e-3 ref + 1e-6 max ref; test_gpu_hvp.bars, and the product also under
+    the fp64 bar hvp_cases.bars64."""
     d = whole(name)
     if _refused(sess, d):
         return
@@ -551,11 +552,17 @@ def check_other_entry_points(sess, d, mk):
         assert np.all(err <= 2e-3 * r + 1e-6 * r.max()), (name, arr)
     hv64, hv32 = (oracle_hv(om, d['x'], lab, d['v'], d['names'], 1. / N) for om in (d['om64'], d['om32']))
     hv = m.hess_vecp(d['x'], lab, d['v'])
+    # the product is evaluated in fp64: also under the fp64 bar of tests/hvp_cases.py, on patches with its decision margin
+    # (tests/test_hvp_cases_host.py proves the bar's three conditions for every whole model that reaches this line)
+    tight = hvp_cases.whole_tight(d)
+    assert tight['bad'] == [], (name, tight['bad'])
+    hv_tight = hv if tight['chosen'] is None else m.hess_vecp(tight['x'], lab, d['v'])
     m.close()
     for arr, a, a64, a32, b in zip(d['arrays'], hv, hv64, hv32, bars(hv64, hv32)):
         e = np.abs(a - a64).max()
         print('%s Hv %s: e_dev %.3e  e_32 %.3e  bar %.3e' % (name, arr, e, np.abs(a32 - a64).max(), b))
         assert a.dtype == np.float64 and a.shape == a64.shape and e <= b, (name, arr, e, b)
+    hvp_cases.hold64('%s Hv (patches %r)' % (name, tight['chosen'] or 'of the other checks'), hv_tight, tight['y'], d['arrays'])
 
 
 @pytest.mark.parametrize('name', list(WHOLE))

@@ -326,7 +326,8 @@ def test_diag_fisher_vs_fp64(sess, name):
 def test_hess_vecp_vs_fp64(sess, name):
     """A random fp32 vector over all variables, random labels, loss_scale 1 / N against torch double-backward in fp64; the bar
     of test_gpu_hvp.test_hv_vs_fp64 (bars()): 2 e(fp32 oracle) + 6e-8 mean |Hv64|.  The device evaluates the product in fp64
-    on its own decisions, so with no fragile decision the bar holds as it stands."""
+    on its own decisions, so with no fragile decision the bar holds as it stands.
+    It keeps this fp32 bar, not hvp_cases.bars64: with about 1e5 units per sample no input has that bar's decision margin (2e-5)."""
     d = case(name)
     assert_no_fragile_decision(d)
     hv64, hv32 = hv_case(name)

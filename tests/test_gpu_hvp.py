@@ -11,6 +11,12 @@ seeds below were searched on the CPU so that the fp64 evaluation of every sample
 ref64.DEFAULT_EPS (rule of alq_ref64_scores restated on the oracle's pre-activations: |ReLU input| <= eps * rms of the
 layer's pre-activation of the sample; the two largest inputs of a pool window within eps * rms of the pool's input, maximum
 positive).  The tests assert that and skip no sample.
+
+The product is evaluated in fp64, so beside that fp32 bar every product is held to the fp64 bar of tests/hvp_cases.py,
+b64 = 2^-38 x (max over entries of sum_n |H_n v|) per array, on inputs for which tests/test_hvp_cases_host.py proves on the CPU
+that the bar lies 64 x above the truth's own fp64 noise, 1024 x below the fp32 oracle's error, and that no decision is fragile
+at hvp_cases.EPS_TIGHT = 2e-5.  The oracle, the bar and the table of cases live in tests/hvp_cases.py; tests 10 on run the
+cases that exist for one branch of csrc/hvp.hip or of run_hess_vecp (csrc/grads.hip) each.
 """
 import ctypes as C
 from collections import OrderedDict
@@ -22,21 +28,15 @@ pytestmark = pytest.mark.gpu
 
 from oracle import netspec  # noqa: E402
 from oracle.model import OracleModel  # noqa: E402
-from tests.test_gpu_lsum import net_3d_skip, net_wide_fc  # noqa: E402
-
-N = 5          # odd and below a wave
-EPS = 4e-6     # ref64.DEFAULT_EPS (asserted in test_hv_vs_fp64)
+from tests import hvp_cases  # noqa: E402
+from tests.hvp_cases import EPS, N, bars64, case, fragile_units, hold64, oracle_hv, symmetry_u, yard  # noqa: E402,F401  (other files import them here)
 
 
 def _hv_nets():
-    """(name, layer dict, input shape, skips, weight seed, input seed): the nets of test_gpu_lsum._nets() that the issue names
-    plus a two-class 3-D net (fused two-class head); seeds with no fragile unit in fp64 (module docstring)."""
-    ld4, sk4 = net_3d_skip(4)
-    ld2, sk2 = net_3d_skip(2)
-    return [('neta_c3', netspec.net_a(nclass=3), (20, 20, 1), (), 71, 17),
-            ('net3d_skip_c4', ld4, (8, 8, 8, 1), sk4, 73, 19),
-            ('wide_fc_c5', net_wide_fc(5), (8, 8, 1), (), 74, 20),
-            ('net3d_skip_c2', ld2, (8, 8, 8, 1), sk2, 77, 21)]
+    """(name, layer dict, input shape, skips, weight seed, input seed): the first four cases of tests/hvp_cases.TABLE - the nets
+    of test_gpu_lsum._nets() that the first issue named plus a two-class 3-D net (fused two-class head); seeds with no fragile
+    unit in fp64 at hvp_cases.EPS_TIGHT."""
+    return [(n,) + tuple(hvp_cases.TABLE[n][k] for k in ('ld', 'in_shape', 'sk', 'wseed', 'xseed')) for n in hvp_cases.FOUR_NETS]
 
 
 _NETS = {n[0]: n for n in _hv_nets()}
@@ -47,99 +47,6 @@ def sess():
     import nnal_amd  # noqa: F401
     from nnal_amd import device
     return device.default_session()
-
-
-# ------------------------------------------------------------------------------------------ oracle side (CPU)
-def fragile_units(om64, x, eps=EPS):
-    """Number of fragile ReLU / max-pool decisions of the fp64 evaluation of every sample (module docstring)."""
-    import torch
-    import torch.nn.functional as F
-    import oracle.model as omod
-    from oracle import tfops
-    count = [0]
-    real_relu, real_pool = torch.relu, tfops.max_pool_same
-
-    def per_sample_rms(t, sample_axis):
-        t2 = t.detach() ** 2
-        dims = [d for d in range(t.dim()) if d != sample_axis]
-        return torch.sqrt(t2.mean(dim=dims, keepdim=True))
-
-    def relu(t):
-        ax = 1 if t.dim() == 2 else 0                   # fc activations are [features, N]
-        count[0] += int((t.detach().abs() <= eps * per_sample_rms(t, ax)).sum())
-        return real_relu(t)
-
-    def pool(t, window, strides):
-        out = real_pool(t, window, strides)
-        nd = t.dim() - 2
-        xc = tfops._to_cf(t.detach())
-        flat = []
-        for d in reversed(range(nd)):
-            _, lo, hi = tfops.same_pads(t.shape[1 + d], list(window)[d], list(strides)[d])
-            flat += [lo, hi]
-        xp = F.pad(xc, flat, value=float('-inf'))
-        fn = F.max_pool2d if nd == 2 else F.max_pool3d
-        best, idx = fn(xp, list(window), list(strides), return_indices=True)
-        shp = xp.shape
-        x2 = xp.reshape(shp[0], shp[1], -1).clone()
-        x2.scatter_(2, idx.reshape(shp[0], shp[1], -1), float('-inf'))
-        second = fn(x2.reshape(shp), list(window), list(strides))
-        rms = per_sample_rms(t, 0).reshape(-1, *([1] * (nd + 1)))
-        count[0] += int(((best > 0) & ((best - second) <= eps * rms)).sum())
-        return out
-
-    torch.relu, tfops.max_pool_same = relu, pool
-    try:
-        with torch.no_grad():
-            om64._graph(om64._as_input(x))
-    finally:
-        torch.relu, tfops.max_pool_same = real_relu, real_pool
-    assert omod.torch.relu is real_relu
-    return count[0]
-
-
-def oracle_hv(om, x, labels, v_list, names, loss_scale):
-    """Double-backward through the oracle: H v over the variables of the layers `names`, H the Hessian of
-    loss_scale * sum_n CE (labels outside [0, c) add nothing); list [HW, Hb, ...] of float64 arrays."""
-    import torch
-    z = om._graph(om._as_input(x))['output']                 # [c, N]
-    c = z.shape[0]
-    lab = np.asarray(labels)
-    y = np.zeros((c, len(lab)))
-    for n, l in enumerate(lab):
-        if 0 <= l < c:
-            y[l, n] = 1.
-    logp = z - torch.logsumexp(z, dim=0, keepdim=True)
-    loss = -(torch.as_tensor(y).to(z.dtype) * logp).sum() * torch.tensor(float(np.float32(loss_scale))).to(z.dtype)
-    plist = [p for nme in names for p in om.params[nme]]
-    grads = torch.autograd.grad(loss, plist, create_graph=True)
-    dot = sum((g * torch.as_tensor(np.asarray(v, dtype=np.float32)).to(z.dtype).reshape(g.shape)).sum() for g, v in zip(grads, v_list))
-    hv = torch.autograd.grad(dot, plist, allow_unused=True)
-    return [np.zeros(tuple(p.shape)) if h is None else h.detach().numpy().astype(np.float64) for p, h in zip(plist, hv)]
-
-
-_CASES = {}
-
-
-def case(name):
-    """Weights, inputs, labels, a vector and both oracle products of one net: computed once, shared, never modified."""
-    if name in _CASES:
-        return _CASES[name]
-    import torch
-    _, ld, in_shape, sk, wseed, xseed = _NETS[name]
-    pars = netspec.he_init(ld, in_shape, seed=wseed, skips=sk, bias_std=0.05)
-    rs = np.random.RandomState(xseed)
-    x = rs.randn(N, *in_shape).astype(np.float32)
-    names = list(pars.keys())
-    c = np.asarray(pars[names[-1]][0]).shape[0]
-    labels = rs.randint(0, c, size=N).astype(np.int32)
-    v = [rs.randn(*np.asarray(a).shape).astype(np.float32) for nme in names for a in pars[nme]]
-    om64 = OracleModel(ld, in_shape, pars, skips=sk, dtype=torch.float64)
-    om32 = OracleModel(ld, in_shape, pars, skips=sk)
-    d = dict(ld=ld, in_shape=in_shape, sk=sk, pars=pars, x=x, labels=labels, v=v, names=names, om64=om64, om32=om32, c=c,
-             hv64=oracle_hv(om64, x, labels, v, names, 1. / N), hv32=oracle_hv(om32, x, labels, v, names, 1. / N))
-    _CASES[name] = d
-    return d
 
 
 def bars(hv64, hv32):
@@ -182,6 +89,7 @@ def test_hv_vs_fp64(sess, name):
             bad.append((k, e, b))
     m.close()
     assert not bad, (name, bad)
+    hold64(name, hv, yard(name), d['arrays'])
 
 
 # ------------------------------------------------------------------------------------------ 2. layer subsets
@@ -217,6 +125,8 @@ def test_layer_subsets(sess, which):
         e = np.abs(a - a64).max()
         print('%s array %d: e(device) %.3e  bar %.3e' % (which, k, e, b))
         assert e <= b, (which, k, e, b)
+    y = yard('net3d_skip_c4', chosen)
+    hold64(which, got, y, y['arrays'])
     # the list interface gives the same bits
     lst = m.hess_vecp(d['x'], d['labels'], vs, layers=chosen)
     for a, b in zip(lst, got):
@@ -289,15 +199,13 @@ def test_exact_properties(sess):
 
 # ------------------------------------------------------------------------------------------ 5. symmetry
 def test_symmetry(sess):
-    """u . Hv = v . Hu for the exact Hessian.  Each device product is within test 1's bar of the fp64 one, array by array,
-    and the fp64 products are symmetric to fp64 rounding, so |u . Hv - v . Hu| <= sum over arrays of bar(Hv) |u|_1 + bar(Hu) |v|_1."""
+    """u . Hv = v . Hu for the exact Hessian.  Each device product is within the fp64 bar of the fp64 one, array by array
+    (hvp_cases.bars64; the conditions for u as for v are proven in tests/test_hvp_cases_host.py), and the fp64 products are
+    symmetric to fp64 rounding, so |u . Hv - v . Hu| <= sum over arrays of b64(Hv) |u|_1 + b64(Hu) |v|_1."""
     d = case('net3d_skip_c4')
-    rs = np.random.RandomState(31)
-    u = [rs.randn(*a.shape).astype(np.float32) for a in d['v']]
+    u = symmetry_u(d)
     v = d['v']
-    hu64 = oracle_hv(d['om64'], d['x'], d['labels'], u, d['names'], 1. / N)
-    hu32 = oracle_hv(d['om32'], d['x'], d['labels'], u, d['names'], 1. / N)
-    bv, bu = bars(d['hv64'], d['hv32']), bars(hu64, hu32)
+    bv, bu = bars64(yard('net3d_skip_c4')), bars64(yard('net3d_skip_c4', v=u, key='u'))
     m = mk(sess, d)
     hv = m.hess_vecp(d['x'], d['labels'], v)
     hu = m.hess_vecp(d['x'], d['labels'], u)
@@ -308,6 +216,7 @@ def test_symmetry(sess):
     print('symmetry: u.Hv %.9e  v.Hu %.9e  |diff| %.3e  bound %.3e  (fp64 u.Hv %.9e)' % (lhs, rhs, abs(lhs - rhs), bound, ref))
     assert abs(lhs - rhs) <= bound
     m.close()
+    hold64('symmetry Hu', hu, yard('net3d_skip_c4', v=u, key='u'), d['arrays'])
 
 
 # ------------------------------------------------------------------------------------------ 6. batch cuts
@@ -453,6 +362,11 @@ def test_python_interface(sess):
         e = np.abs(a - a64).max()
         print('whole_set array %d: e(device) %.3e  bar %.3e' % (k, e, b))
         assert e <= b, (k, e, b)
+    # ... and to the fp64 bar.  The patches come out of the device gather, so its three conditions are asserted here, on the CPU
+    y = hvp_cases.yardsticks(s['om64'], s['om32'], x, lab, v, names, 1. / 7, h64, h32)
+    hvp_cases.figures('whole_set', y)
+    assert hvp_cases.conditions(y, s['om64'], x) == []
+    hold64('whole_set', [np.asarray(a) for a in ws], y)
     model.close()
 
 
@@ -489,3 +403,239 @@ def test_influence_end_to_end(sess):
     print('influence: |H t0 - g| %.6e -> |H t - g| %.6e after %d device calls' % (r0, r1, calls[0]))
     assert np.all(np.isfinite(t)) and r1 < r0
     model.close()
+
+
+# ------------------------------------------------------------------------------------------ 10. one case per branch (tests/hvp_cases.TABLE)
+# Every case: N = 5 under max_batch = 8 unless its row says otherwise, weights he_init(bias_std=0.05), the product under the fp64
+# bar; what a case claims about the net or the launch is asserted on the host from the layer table or the rule restated in
+# hvp_cases (tests/test_hvp_cases_host.py repeats those claims where no device is needed).
+def _held(sess, name, m=None):
+    """The whole product of a case on a fresh model (or on m), held to the fp64 bar; (the product, the flat device result)."""
+    d = case(name)
+    own = m is None
+    if own:
+        m = mk(sess, d, max_batch=hvp_cases.MAX_BATCH)
+    hv = m.hess_vecp(d['x'], d['labels'], d['v'])
+    if own:
+        m.close()
+    assert len(hv) == 2 * len(d['names'])
+    hold64(name, hv, yard(name), d['arrays'])
+    return hv
+
+
+def _layers_of(name):
+    from nnal_amd.device_host import translate_layers
+    d = case(name)
+    return translate_layers(d['ld'], d['in_shape'], d['sk'])
+
+
+@pytest.mark.parametrize('name', ['pool_route', 'pool_w3'])
+def test_pool_routing(sess, name):
+    """hvp_pool_fwd_kernel / hvp_pool_bwd_kernel: non-cubic windows (1, 2, 2) then (2, 2, 1) whose last window overhangs the
+    volume (pool_route), and a window 3 whose padding starts in front of it, lo = 1 on every axis (pool_w3)."""
+    from oracle import tfops
+    from nnal_amd._lib import ALQ_POOL
+    pools = [ly for ly in _layers_of(name) if ly['type'] == ALQ_POOL]
+    size = list(case(name)['in_shape'][:-1])
+    pads = []
+    for ly in pools:
+        pads.append([tfops.same_pads(n, k, k)[1:] for n, k in zip(size, ly['k'])])
+        size = [-(-n // k) for n, k in zip(size, ly['k'])]
+    if name == 'pool_route':
+        assert [ly['k'] for ly in pools] == [[1, 2, 2], [2, 2, 1]]
+        assert pads == [[(0, 0), (0, 1), (0, 0)], [(0, 1), (0, 0), (0, 0)]]      # H = 7 and then D = 5 end in half a window
+    else:
+        assert [ly['k'] for ly in pools] == [[3, 3, 3]] and pads == [[(1, 1), (1, 1), (1, 1)]]
+    _held(sess, name)
+
+
+@pytest.mark.parametrize('what', ['first', 'behind a concat'])
+def test_pool_refusal(sess, what):
+    """hvp_prepare's refusal of a pool layer that reads the network input or a concat, with its message."""
+    from nnal_amd import device
+    from nnal_amd._lib import AlqError
+    if what == 'first':
+        ld, sk = OrderedDict([('pool1', ['pool', [2, 2]]), ('conv1', ['conv', [4, [3, 3]], 'MA']), ('fc', ['fc', [2]])]), ()
+    else:
+        ld = OrderedDict([('conv1', ['conv', [4, [3, 3]], 'MA']), ('conv2', ['conv', [4, [3, 3]], 'MA']), ('pool1', ['pool', [2, 2]]),
+                          ('fc', ['fc', [2]])])
+        sk = [[0, [2], 'con']]
+    in_shape = (6, 6, 1)
+    pars = netspec.he_init(ld, in_shape, seed=91, skips=sk, bias_std=0.05)
+    m = device.DeviceModel(sess, ld, in_shape, sk, max_batch=4)
+    m.set_weights(pars)
+    rs = np.random.RandomState(92)
+    v = [rs.randn(*np.asarray(a).shape).astype(np.float32) for nme in pars for a in pars[nme]]
+    with pytest.raises(AlqError) as ei:
+        m.hess_vecp(rs.randn(3, *in_shape).astype(np.float32), np.zeros(3, np.int32), v)
+    print('refused: %s' % ei.value)
+    assert str(ei.value).endswith('alq_hess_vecp: pool layer first or behind a concat')
+    m.close()
+
+
+def test_layers_without_relu(sess):
+    """The `mask` off branches: HSrc() as mask in hvp_contract_kernel and hvp_fc_fwd_kernel and no k_hvp_mask on the way back, for a
+    conv and an fc layer without ReLU between ReLU layers."""
+    from nnal_amd._lib import ALQ_CONV, ALQ_FC
+    assert [(ly['type'], ly['relu']) for ly in _layers_of('no_relu')] == [(ALQ_CONV, 1), (ALQ_CONV, 0), (ALQ_CONV, 1), (ALQ_FC, 1), (ALQ_FC, 0),
+                                                                        (ALQ_FC, 1), (ALQ_FC, 0)]
+    _held(sess, 'no_relu')
+
+
+def test_fc_flatten_order(sess):
+    """hvp_ftf in hvp_fc_fwd / hvp_fc_bwd / hvp_fc_wgrad: the first fc reads an activation with D, H, W, C = 3, 4, 5, 2 all different,
+    the second reads (1, 1, 1, F)."""
+    d = case('fc_geom')
+    assert d['in_shape'][:-1] == (3, 4, 5) and d['pars']['conv1'][0].shape[-1] == 2
+    assert [d['pars'][n][0].shape for n in ('fc1', 'fc2', 'fc3')] == [(7, 3 * 4 * 5 * 2), (6, 7), (4, 6)]
+    _held(sess, 'fc_geom')
+
+
+def test_wide_fc_weight_sources(sess, monkeypatch):
+    """The TF-layout copy of a wide fc layer's weights: unpermuted on the device from the resident copy of a layer packed there
+    (hvp_unpermute_kernel, D, H, W, C = 2, 4, 8, 12), or uploaded from the host arrays of a layer set through the host.  Same bits."""
+    d = case('fc_wide')
+    assert d['pars']['fc1'][0].shape == (256, 2 * 4 * 8 * 12)
+    t = d['names'].index('fc1')
+    m = mk(sess, d, max_batch=hvp_cases.MAX_BATCH)
+    assert sess.lib.alq_model_layer_packs_on_device(m._m, t) == 1 and not m._host_repack and m._dev_w[t] is not None
+    dev = _held(sess, 'fc_wide', m)
+    m.close()
+    monkeypatch.setenv('ALQ_HOST_REPACK', '1')
+    mh = mk(sess, d, max_batch=hvp_cases.MAX_BATCH)
+    monkeypatch.delenv('ALQ_HOST_REPACK')
+    assert mh._host_repack and mh._dev_w[t] is None
+    host = _held(sess, 'fc_wide', mh)
+    mh.close()
+    for a, b in zip(dev, host):
+        np.testing.assert_array_equal(a, b)
+
+
+def _subset_call(sess, m, d, chosen, loss_scale):
+    """H v over the layers `chosen` through the flat interface, every other layer's entries of v NaN; the chosen layers' arrays."""
+    torch = sess.torch
+    names = d['names']
+    vs = sub(d['v'], names, chosen)
+    idx = m.hess_layer_idx(chosen)
+    full = np.full(m.num_params, np.nan, dtype=np.float32)
+    offs = m._param_offsets()
+    for t, (vw, vb) in zip(idx, zip(vs[0::2], vs[1::2])):
+        o, nw, nb = offs[t]
+        full[o:o + nw] = vw.ravel()
+        full[o + nw:o + nw + nb] = vb.ravel()
+    tx, n = m._as_device_batch(d['x'])
+    out, _ = m.hess_vecp_device(tx, n, sess.to_device(d['labels'], torch.int32), sess.to_device(full, torch.float32), idx, loss_scale)
+    flat = out.cpu().numpy()
+    assert np.all(np.isfinite(flat))
+    for t in range(m.L):
+        if t not in idx:
+            o, nw, nb = offs[t]
+            assert np.all(flat[o:o + nw + nb] == 0.0), t
+    return m.unflatten(flat, idx)
+
+
+_SUBSETS = [('only %d' % t, 'only', t) for t in range(5)] + [('all but %d' % t, 'but', t) for t in range(5)]
+
+
+@pytest.mark.parametrize('kind,t', [s[1:] for s in _SUBSETS], ids=[s[0] for s in _SUBSETS])
+def test_switched_off_terms(sess, kind, t):
+    """The null-source and null-V branches: every layer of net3d_skip_c4 alone and all but layer t, the off layers' entries of v
+    NaN.  Each weight and bias product kernel alone per layer type; the skipped s1 term of hvp_contract_kernel; V == nullptr in
+    hvp_fc_bwd_kernel; hs_on(Ra) false in hvp_wgrad_kernel for the first layer alone (no tangent reaches it)."""
+    d = case('net3d_skip_c4')
+    names = d['names']
+    assert len(names) == 5
+    chosen = [names[t]] if kind == 'only' else [nme for nme in names if nme != names[t]]
+    assert chosen in hvp_cases.subsets('net3d_skip_c4')
+    m = mk(sess, d)
+    got = _subset_call(sess, m, d, chosen, 1. / N)
+    m.close()
+    y = yard('net3d_skip_c4', chosen)
+    hold64('%s %d' % (kind, t), got, y, y['arrays'])
+
+
+@pytest.mark.parametrize('name', ['labels_c2', 'labels_c21'])
+def test_unlabelled_rows(sess, name):
+    """The zero rows of hvp_softmax64_kernel and hvp_softmax2_kernel: labels -1 and c mixed among valid ones, against the same
+    samples with the unlabelled ones removed (same loss_scale): the products within b64 of each other, each within b64 of the
+    truth, the losses equal to 1e-12 relative.  c = 2 (fused two-class head) and c = 21."""
+    d = case(name)
+    c, n = d['c'], d['n']
+    assert sorted(set(d['labels'].tolist()) - set(range(c))) == [-1, c] and n == 7
+    keep, ykeep = hvp_cases.labelled_only(name)
+    assert len(keep) == 4
+    torch = sess.torch
+    m = mk(sess, d, max_batch=hvp_cases.MAX_BATCH)
+    v = sess.to_device(np.concatenate([a.ravel() for a in d['v']]), torch.float32)
+    tx, _ = m._as_device_batch(d['x'])
+    mixed, loss_mixed = m.hess_vecp_device(tx, n, sess.to_device(d['labels'], torch.int32), v, None, 1. / n, want_loss=True)
+    tk, _ = m._as_device_batch(d['x'][keep])
+    alone, loss_alone = m.hess_vecp_device(tk, len(keep), sess.to_device(d['labels'][keep], torch.int32), v, None, 1. / n, want_loss=True)
+    a, b = m.unflatten(mixed.cpu().numpy()), m.unflatten(alone.cpu().numpy())
+    lm, la = float(loss_mixed.item()), float(loss_alone.item())
+    m.close()
+    hold64(name + ' mixed', a, yard(name), d['arrays'])
+    hold64(name + ' labelled only', b, ykeep, d['arrays'])
+    for arr, x1, x2, bar in zip(d['arrays'], a, b, bars64(ykeep)):
+        e = np.abs(x1 - x2).max()
+        print('%s %s: |mixed - labelled only| %.3e  b64 %.3e' % (name, arr, e, bar))
+        assert e <= bar, (name, arr, e, bar)
+    print('%s: loss %.17g against %.17g' % (name, lm, la))
+    assert la > 0 and abs(lm - la) <= 1e-12 * abs(la)
+
+
+def test_wgrad_slab_cap(sess):
+    """hvp_wgrad_kernel where the partial buffer's cap 2^22 / M sets the slab count: the 5x5 conv 64 -> 64 on 46 x 46, N = 5:
+    M = 102,400, cap 40 below rows / 256 = 41; 265 rows per slab against 2,116 per sample, the last slab 245 rows."""
+    prod = {p[0]: p[1:] for p in hvp_cases.conv_products('slab_cap')}
+    assert prod['conv2'] == (10580, 2116, 102400, 40, 265, 'cap') and 10580 // 256 == 41 and 10580 - 39 * 265 == 245
+    assert prod['conv1'][3:] == (41, 259, 'rows')
+    _held(sess, 'slab_cap')
+
+
+def test_one_sample(sess):
+    """N = 1, and rows < 256 in hvp_wgrad_kernel: one slab."""
+    assert hvp_cases.conv_products('one_sample') == [('conv1', 210, 210, 216, 1, 210, 'rows')] and case('one_sample')['n'] == 1
+    _held(sess, 'one_sample')
+
+
+def test_full_batch(sess):
+    """N = max_batch."""
+    assert case('full_batch')['n'] == hvp_cases.MAX_BATCH == 8
+    _held(sess, 'full_batch')
+
+
+@pytest.mark.parametrize('name', ['net3d_skip_c4', 'net3d_skip_c2', 'labels_c21'])
+def test_constant_logit_shift_is_null(sess, name):
+    """The cancellation order of hvp_softmax2_kernel.  A vector that is K on every entry of the head's bias and zero elsewhere moves
+    every logit by K, which the softmax does not see: H v = 0.  On the device Rz_nj = K exactly (every product with a zero of v is
+    a zero, 0 + K is exact), the kernel sums p_k (Rz_j - Rz_k) = p_k 0, and every array of the product is EXACTLY zero, whatever
+    K.  The other order, p_j (Rz_j - sum_k p_k Rz_k), leaves K (1 - sum_k p_k) wherever the fp64 posteriors of a sample do not add
+    up to exactly 1.  (The fp64 bar cannot see this: the truth's own evaluation carries the same K x 2^-53.)"""
+    d = case(name)
+    m = mk(sess, d, max_batch=hvp_cases.MAX_BATCH)
+    for K in (1.0, 3.0, 2.0 ** 20):
+        v = [np.zeros_like(a) for a in d['v']]
+        v[-1] = np.full_like(d['v'][-1], K)
+        hv = m.hess_vecp(d['x'], d['labels'], v)
+        for arr, a in zip(d['arrays'], hv):
+            assert np.all(a == 0.0), (name, K, arr, np.abs(a).max())
+    m.close()
+
+
+def test_accumulate_three_calls(sess):
+    """1 + 3 + 1 samples in three calls with `accumulate` against one call of 5: within 1e-12 of the array's maximum (fp64
+    rounding of the sums, as in test_batch_cuts), and the accumulated product under the fp64 bar."""
+    d = case('net3d_skip_c4')
+    m = mk(sess, d)
+    v = np.concatenate([a.ravel() for a in d['v']])
+    one = _flat_call(m, sess, d, v)
+    acc = sess.torch.zeros((len(v),), dtype=sess.torch.float64, device=sess.device)
+    for first, n in ((0, 1), (1, 3), (4, 1)):
+        cut = _flat_call(m, sess, d, v, out=acc, n=n, first=first)
+    got = m.unflatten(cut)
+    for k, (a, b) in enumerate(zip(m.unflatten(one), got)):
+        print('array %d: |one - 1 + 3 + 1| %.3e  max %.3e' % (k, np.abs(a - b).max(), np.abs(a).max()))
+        assert np.abs(a - b).max() <= 1e-12 * np.abs(a).max(), k
+    m.close()
+    hold64('1 + 3 + 1', got, yard('net3d_skip_c4'), d['arrays'])
